@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: batched env-steps/s of the AOEnv.step() hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -21,9 +21,20 @@ Workloads (BASELINE.json ``configs``; per GPU, weak scaling — the global batch
 
 Synthetic inputs: von Karman screens synthesised inside the library (Philox keyed by the GLOBAL env id = rank * batch + e, seed
 1234), actions ~ N(0, 0.5 I) for the global batch from torch seed 10 (main.py:155), sliced per rank — resident in HBM before the
-timed region.  Rank 0 prints ONE JSON line: value = total env-steps / max-over-ranks wall time, ``roofline`` (the fused kernel,
-timed live with HIP events on its own stream) and ``cpu_baseline`` (the float64 numpy restatement of the reference's literal
-dataflow, timed on this box's host cores in the three modes SURVEY.md §8d prescribes).
+timed region.  Rank 0 prints ONE JSON line: value = total env-steps / max-over-ranks wall time, ms_per_step = max-over-ranks wall
+time of one timed step.
+
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs (``--dump-outputs``), the line.  ``--full`` adds what
+else the line can carry: HIP-event timing of the kernels inside the timed region (``roofline``: the fused kernel; ``roofline_dominant``:
+the reset / extrusion / Shack-Hartmann kernels; the all-gathers' device time), ``value_pipelined`` (configs 2 and 3: a second region of
+K steps through aog_step_pipelined), ``roofline.hbm_resident_b4096`` (config 2: the fused kernel on a 4096-env working set), ``parity``
+(2 envs against the CPU oracle) and ``cpu_baseline`` (the float64 numpy restatement of the reference's literal dataflow, timed on this
+box's host cores in the three modes SURVEY.md §8d prescribes).  The ``--no-*`` switches below select within ``--full``.
+
+``--dump-outputs DIR``: after the timed steps, what the last timed step returned to its caller is written as ``DIR/<name>.npy``
+(float32, or float64 where the step returns float64; booleans and float16 widened to float32), every array indexed by env first.
+Inputs are seeded, so two builds run with the same arguments can be compared output for output.  With several ranks each writes its
+own slice as ``DIR/rank<r>_<name>.npy``.
 """
 from __future__ import annotations
 
@@ -386,6 +397,97 @@ def fused_at_b4096(env, w, device, torch, steps=120):
     return out
 
 
+def full_figures(result, args, env, w, B, world, device, torch, actions, kernel_ms, launches, other_kernels, coll_ms, coll_n,
+                 dt_pipe, kernel_ms_pipe, steps_range, prof_every, prof_block):
+    """``--full``: everything the line carries beside the headline, added to ``result`` in place (rank 0, after the timed region)."""
+    n_ap = env.tables.n_ap
+    bytes_step, flops_step, layout_step = algorithmic_per_step(w["n_pupil"], w["act_dim"], w["obs_dim"], B, n_ap)
+    if launches == 0 or kernel_ms <= 0:
+        raise SystemExit("bench.py: no fused-kernel launch was timed inside the measured region")
+    k_s = kernel_ms * 1e-3
+    traffic, pmc = None, {}
+    tfile = os.path.join(ROOT, "profiles", "traffic_latest.json")
+    if os.path.exists(tfile) and args.config == 2 and not args.batch:
+        try:
+            pmc = json.load(open(tfile))
+            traffic = pmc.get("hbm_bytes_per_launch")
+        except Exception:
+            traffic, pmc = None, {}
+    ach_gbs = bytes_step * B / k_s / 1e9
+    lay_gbs = layout_step * B / k_s / 1e9
+    # matrix work of the fused kernel as issued: split-f16 contractions, 3 products per operand pair
+    #   phase: 3 x (2 A_pad) flop per (pixel, env); tables: 2 (cos, sin) x 3 x 2 x 32 rows per (pixel, env)
+    a_pad = env.info.n_modes_padded
+    n_pix_pad = env.info.n_ap_padded
+    mfma_flops = (3 * 2 * a_pad + 2 * 3 * 2 * 32) * n_pix_pad * env.info.num_envs_padded
+    result["roofline"] = {"bound": "hbm", "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": ach_gbs / HBM_PEAK_GBS, "traffic": traffic, "kernel": "k_fused_tab" if env.info.kernel == 2 else "k_fused_valu",
+                          "kernel_ms": kernel_ms, "launches_timed": launches, "bytes_per_env_step": bytes_step,
+                          "layout_bytes_per_env_step": layout_step, "achieved_layout": lay_gbs, "frac_layout": lay_gbs / HBM_PEAK_GBS,
+                          "timed_every": prof_every, "timed_block": prof_block,
+                          "f16_mfma": {"achieved": mfma_flops / k_s / 1e12, "peak": F16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                       "frac": mfma_flops / k_s / 1e12 / F16_MFMA_PEAK_TFLOPS,
+                                       "note": "matrix flops as issued (split-f16: 3 products per operand pair, padded tiles)"},
+                          "valu_issue": None,   # filled below when the PMC citation is there
+                          "note": "achieved = algorithmic bytes (SURVEY.md 8d: 4 N^2 + ... per env-step) x envs per launch / mean HIP-event "
+                                  "duration of the fused kernel over the timed region (one block of timed_block launches in timed_every carries the two "
+                                  "event records); achieved_layout = the same with the bytes the aperture-packed layout must move (4 n_ap per "
+                                  "screen); traffic = PMC (2*FETCH_SIZE + WRITE_SIZE) per launch from profiles/traffic_latest.json; "
+                                  "6.29 TB/s is the measured copy ceiling"}
+    result["timing"].update({"collective_ms_total": coll_ms, "collectives": coll_n,
+                             "note": "rank_wall_s: every rank's own wall time of the K timed steps (value uses the maximum); collective_ms_total: "
+                                     "device time of this rank's all-gathers of episode returns inside them"})
+    if dt_pipe is not None:
+        result["value_pipelined"] = world * B * args.steps / dt_pipe
+        result["ms_per_step_pipelined"] = dt_pipe / args.steps * 1e3
+        result["pipelined_note"] = ("aog_step_pipelined over a second region of the same K steps: the next (synthetic, known) action is handed over "
+                                    "with the current one, bit-identical results, one launch less per step; NOT usable by a policy in the loop, "
+                                    "hence not `value`")
+        if kernel_ms_pipe:
+            result["roofline"]["kernel_ms_pipelined_region"] = kernel_ms_pipe
+    if pmc.get("valu_insts_per_launch") and pmc.get("trans_insts_per_launch") is not None:
+        tr_, mf_ = pmc["trans_insts_per_launch"], pmc.get("mfma_insts_per_launch", 0.0)
+        cyc = 8 * tr_ + 8 * mf_ + 4 * (pmc["valu_insts_per_launch"] - tr_ - mf_)
+        result["roofline"]["valu_issue"] = {
+            "achieved": cyc / k_s, "peak": ISSUE_CYCLES_PEAK, "unit": "SIMD issue cycles/s", "frac": cyc / k_s / ISSUE_CYCLES_PEAK,
+            "note": "issue cycles per launch = 8 x transcendental + 8 x matrix + 4 x other vector instructions (SQ_INSTS_VALU, "
+                    "SQ_INSTS_VALU_TRANS_F32, SQ_INSTS_MFMA per launch: PMC citation from profiles/traffic_latest.json, not measured in "
+                    "this run) / this run's kernel time, against 1024 SIMDs x 2.4 GHz; the binding resource of this kernel"}
+    if args.config == 2 and not args.batch and world == 1 and not args.no_b4096:
+        result["roofline"]["hbm_resident_b4096"] = fused_at_b4096(env, w, device, torch)
+    dom = roofline_dominant(env, w, other_kernels, steps_range)
+    if dom:
+        result["roofline_dominant"] = dom
+    if not args.no_parity and w["atm_type"] == "quasi_static" and not w["SH_operation"]:
+        result["parity"] = parity_check(env, w, actions[0], torch)
+    if not args.no_cpu_baseline and world == 1:
+        result["cpu_baseline"] = cpu_baseline(w)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir, prefix=""):
+    """``arrays``: {name: host tensor [B, ...]} -> ``out_dir/<prefix><name>.npy``, float64 kept, everything else as float32.  Above
+    DUMP_LIMIT_BYTES in all, a fixed sample of envs (RandomState(0), sorted) is written instead, its indices as ``env_index.npy``."""
+    import numpy as np
+
+    out = {}
+    for k, v in arrays.items():
+        a = v.numpy()
+        out[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        B = next(iter(out.values())).shape[0]
+        keep = max(1, int(DUMP_LIMIT_BYTES // (total // B + 8)))          # (8: the env's entry in env_index)
+        idx = np.sort(np.random.RandomState(0).choice(B, keep, replace=False))
+        out = {k: a[idx] for k, a in out.items()}
+        out["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, f"{prefix}{k}.npy"), np.ascontiguousarray(a))
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 def spawn_ranks(args, argv):
     """--gpus N without a launcher: start the N ranks as children (this process has not touched the GPU and never will)."""
@@ -430,6 +532,9 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=sorted(WORKLOADS))
     ap.add_argument("--kernel", default="auto", choices=["auto", "mfma", "valu"])
     ap.add_argument("--batch", type=int, default=None, help="per-GPU env batch (tests / rehearsals only; the JSON line reports it)")
+    ap.add_argument("--full", action="store_true", help="also the kernel timings, rooflines, pipelined region, B = 4096 run, parity check and "
+                                                        "CPU baseline (the --no-* switches select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-spinup", action="store_true")
@@ -447,6 +552,8 @@ def main():
         args.warmup = {2: 300, 3: 40, 4: 60, 5: 10}[args.config]
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args, sys.argv[1:]))
@@ -525,25 +632,47 @@ def main():
             buf["obs"][0].copy_(obs)
 
     def run(n_steps, pipeline=False):
+        last = None
         for i_run in range(n_steps):
             t = state["t"]
             if w["rollout"]:          # algorithm.py:242-270: policy query, env.step, transition stored (here: written in place)
                 a, _, _ = dev_actor(buf["obs"][t], 0.5, out=(buf["act"][t], buf["log_prob"][t], buf["mean"]))
                 env.step(a, out=(buf["obs"][t + 1], buf["rew"][t], buf["done"][t]))
+                last = t
             elif w["SH_operation"]:   # algorithm.py:253 + :262
                 a, _ = env.SH_step()
-                env.step(a)
+                last = (a, env.step(a))
             elif pipeline:
                 # the actions are synthetic and known ahead: the next one is handed over with the current one (aog_step_pipelined: same
                 # results bit for bit, the prologue of step t + 1 rides in the launch of step t's epilogue); an episode's last step ends the sequence
                 # (and so does the last step of this call: every timed window is a self-contained sequence)
-                env.step(actions[t], next_actions=actions[t + 1] if (t + 1 < T and i_run + 1 < n_steps) else None)
+                last = env.step(actions[t], next_actions=actions[t + 1] if (t + 1 < T and i_run + 1 < n_steps) else None)
             else:
-                env.step(actions[t])
+                last = env.step(actions[t])
             state["t"] = t + 1
             if t + 1 == T:                                        # lock-step episode end (AO_env.py:147)
                 gather.finish_episode()                           # all-gather of per-env episode returns
                 start_episode()
+        state["last"] = last
+
+    def last_outputs():
+        """What the last step of the latest run() returned to its caller, as host tensors indexed by env.  A step's outputs outlive the
+        episode's reset (reset() writes fresh tensors; the rollout buffers keep row t + 1 of obs) until the next step overwrites them."""
+        last = state["last"]
+        if harness:              # rollout(policy="shack") returns [T*E, B, ...] buffers: their last row is the last step
+            out = {"action": last["act"][-1], "log_prob": last["log_prob"][-1], "obs": last["next_obs"][-1], "reward": last["rew"][-1],
+                   "done": last["done"][-1], "ep_returns": last["ep_returns"][-1]}
+        elif w["rollout"]:
+            t = last
+            out = {"action": buf["act"][t], "log_prob": buf["log_prob"][t], "mean": buf["mean"], "obs": buf["obs"][t + 1],
+                   "reward": buf["rew"][t], "done": buf["done"][t]}
+        else:
+            sh_action, ret = last if w["SH_operation"] else (None, last)
+            obs, rew, done, trunc, info = ret
+            out = {"obs": obs, "reward": rew, "done": done, "trunc": trunc, **info}
+            if sh_action is not None:
+                out["action"] = sh_action
+        return {k: v.detach().cpu() for k, v in out.items()}
 
     # config 5 (the 'SHACK' policy, algorithm.py:252-253) runs through the rollout harness itself whenever the timed steps are whole episodes
     # (the default 40 and the driver's 20 are, T = 20): rollout(policy="shack") = reset, T x (SH_step, step), the episode's all-gather
@@ -554,7 +683,7 @@ def main():
         def run(n_steps, pipeline=False):   # (whole episodes: a warm-up that is not is rounded up)
             n_ep = (n_steps + T - 1) // T
             if n_ep:
-                rollout_harness(env, None, episodes=n_ep, policy="shack", gatherer=gather)
+                state["last"] = rollout_harness(env, None, episodes=n_ep, policy="shack", gatherer=gather)
                 state["resets"] += n_ep
             return n_ep * T
 
@@ -565,7 +694,8 @@ def main():
 
     # a window of a few dozen steps (the driver's 20) times ONE block of 2 launches: 8 timed launches of 20 held the stream for 48 us = 3.8 %
     prof_block, prof_every = (8, PROFILE_EVERY) if args.steps >= 64 else (2, max(1, args.steps // 2))   # (the library times the MIDDLE block of each period)
-    env.profile(True, every=prof_every, block=prof_block)   # switched on ahead of the warm-up: the first timed launches of a process pay ~1 ms of runtime set-up
+    if args.full:
+        env.profile(True, every=prof_every, block=prof_block)   # switched on ahead of the warm-up: the first timed launches of a process pay ~1 ms of runtime set-up
     # Device spin-up (reported as config.spinup_steps): a process's first few hundred steps run ~5 % slower than steady state (device
     # clocks).  With a caller-chosen warm-up shorter than that, the difference is run here, ahead of the W warm-up steps, so that the K
     # timed steps measure the steady state a long-running job sees.  Config 2 only (the other configs' steps are 5-100x longer).
@@ -582,8 +712,9 @@ def main():
     warm_run = run(args.warmup)
     warm_run = args.warmup if warm_run is None else warm_run
     fence()
-    env.profile_read()                       # discard the warm-up's samples; timing stays on
-    gather.time_collective(True)
+    if args.full:
+        env.profile_read()                   # discard the warm-up's samples; timing stays on
+        gather.time_collective(True)
     t_first = env.timestep                   # (python-side step counter: the extrusion's shift count of the timed region is recomputed from it)
     resets0 = state["resets"]
     t0 = time.perf_counter()
@@ -593,22 +724,24 @@ def main():
     dt_local = dt
     resets_timed = state["resets"] - resets0
     steps_range = (t_first, env.timestep)
-    kernel_ms, launches = env.profile_read()
-    other_kernels = env.profile_kernels()    # {name: (mean ms, launches)}: reset / extrusion / Shack-Hartmann kernels timed in the same region
-    coll_ms, coll_n = gather.collective_ms()
+    outputs = last_outputs() if args.dump_outputs else None   # (on the host before anything else runs on the env)
     status = env.device_status()
-    # second region, same length: the pipelined call (open-loop callers only)
     dt_pipe, kernel_ms_pipe = None, None
-    if plain_capable and not args.no_pipeline:
-        fence()
-        t0 = time.perf_counter()
-        run(args.steps, pipeline=True)
-        fence()
-        dt_pipe = time.perf_counter() - t0
-        kernel_ms_pipe, _ = env.profile_read()
-        gather.collective_ms()
-    env.profile(False)
-    status |= env.device_status()
+    if args.full:
+        kernel_ms, launches = env.profile_read()
+        other_kernels = env.profile_kernels()    # {name: (mean ms, launches)}: reset / extrusion / Shack-Hartmann kernels timed in the same region
+        coll_ms, coll_n = gather.collective_ms()
+        # second region, same length: the pipelined call (open-loop callers only)
+        if plain_capable and not args.no_pipeline:
+            fence()
+            t0 = time.perf_counter()
+            run(args.steps, pipeline=True)
+            fence()
+            dt_pipe = time.perf_counter() - t0
+            kernel_ms_pipe, _ = env.profile_read()
+            gather.collective_ms()
+        env.profile(False)
+        status |= env.device_status()
     rank_wall = [dt_local]
     if distributed:
         tmax = torch.tensor([dt, dt_pipe if dt_pipe is not None else 0.0], dtype=torch.float64, device="cpu" if share else device)
@@ -620,28 +753,10 @@ def main():
             dt_pipe = max(float(x[1]) for x in every)
     if status != 0:
         raise SystemExit(f"bench.py: device status {status} (an inter-workgroup wait timed out): results invalid")
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "")
 
     if rank == 0:
-        n_ap = env.tables.n_ap
-        bytes_step, flops_step, layout_step = algorithmic_per_step(w["n_pupil"], w["act_dim"], w["obs_dim"], B, n_ap)
-        if launches == 0 or kernel_ms <= 0:
-            raise SystemExit("bench.py: no fused-kernel launch was timed inside the measured region")
-        k_s = kernel_ms * 1e-3
-        traffic, pmc = None, {}
-        tfile = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tfile) and args.config == 2 and not args.batch:
-            try:
-                pmc = json.load(open(tfile))
-                traffic = pmc.get("hbm_bytes_per_launch")
-            except Exception:
-                traffic, pmc = None, {}
-        ach_gbs = bytes_step * B / k_s / 1e9
-        lay_gbs = layout_step * B / k_s / 1e9
-        # matrix work of the fused kernel as issued: split-f16 contractions, 3 products per operand pair
-        #   phase: 3 x (2 A_pad) flop per (pixel, env); tables: 2 (cos, sin) x 3 x 2 x 32 rows per (pixel, env)
-        a_pad = env.info.n_modes_padded
-        n_pix_pad = env.info.n_ap_padded
-        mfma_flops = (3 * 2 * a_pad + 2 * 3 * 2 * 32) * n_pix_pad * env.info.num_envs_padded
         result = {
             "metric": "env_steps_per_sec", "value": world * B * args.steps / dt, "unit": "env-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "warmup_effective": warm_run + spinup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -655,49 +770,11 @@ def main():
                        "lookahead": bool(w["rollout"] and args.lookahead),
                        "parallelism": f"envs sharded over {world} GPU(s) by global env id, no data-path collective; one all-gather of "
                                       f"episode returns per episode"},
-            "roofline": {"bound": "hbm", "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach_gbs / HBM_PEAK_GBS, "traffic": traffic, "kernel": "k_fused_tab" if env.info.kernel == 2 else "k_fused_valu",
-                         "kernel_ms": kernel_ms, "launches_timed": launches, "bytes_per_env_step": bytes_step,
-                         "layout_bytes_per_env_step": layout_step, "achieved_layout": lay_gbs, "frac_layout": lay_gbs / HBM_PEAK_GBS,
-                         "timed_every": prof_every, "timed_block": prof_block,
-                         "f16_mfma": {"achieved": mfma_flops / k_s / 1e12, "peak": F16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                      "frac": mfma_flops / k_s / 1e12 / F16_MFMA_PEAK_TFLOPS,
-                                      "note": "matrix flops as issued (split-f16: 3 products per operand pair, padded tiles)"},
-                         "valu_issue": None,   # filled below when the PMC citation is there
-                         "note": "achieved = algorithmic bytes (SURVEY.md 8d: 4 N^2 + ... per env-step) x envs per launch / mean HIP-event "
-                                 "duration of the fused kernel over the timed region (one block of timed_block launches in timed_every carries the two "
-                                 "event records); achieved_layout = the same with the bytes the aperture-packed layout must move (4 n_ap per "
-                                 "screen); traffic = PMC (2*FETCH_SIZE + WRITE_SIZE) per launch from profiles/traffic_latest.json; "
-                                 "6.29 TB/s is the measured copy ceiling"},
+            "timing": {"rank_wall_s": rank_wall, "note": "rank_wall_s: every rank's own wall time of the K timed steps (value uses the maximum)"},
         }
-        result["timing"] = {"rank_wall_s": rank_wall, "collective_ms_total": coll_ms, "collectives": coll_n,
-                            "note": "rank_wall_s: every rank's own wall time of the K timed steps (value uses the maximum); collective_ms_total: "
-                                    "device time of this rank's all-gathers of episode returns inside them"}
-        if dt_pipe is not None:
-            result["value_pipelined"] = world * B * args.steps / dt_pipe
-            result["ms_per_step_pipelined"] = dt_pipe / args.steps * 1e3
-            result["pipelined_note"] = ("aog_step_pipelined over a second region of the same K steps: the next (synthetic, known) action is handed over "
-                                        "with the current one, bit-identical results, one launch less per step; NOT usable by a policy in the loop, "
-                                        "hence not `value`")
-            if kernel_ms_pipe:
-                result["roofline"]["kernel_ms_pipelined_region"] = kernel_ms_pipe
-        if pmc.get("valu_insts_per_launch") and pmc.get("trans_insts_per_launch") is not None:
-            tr_, mf_ = pmc["trans_insts_per_launch"], pmc.get("mfma_insts_per_launch", 0.0)
-            cyc = 8 * tr_ + 8 * mf_ + 4 * (pmc["valu_insts_per_launch"] - tr_ - mf_)
-            result["roofline"]["valu_issue"] = {
-                "achieved": cyc / k_s, "peak": ISSUE_CYCLES_PEAK, "unit": "SIMD issue cycles/s", "frac": cyc / k_s / ISSUE_CYCLES_PEAK,
-                "note": "issue cycles per launch = 8 x transcendental + 8 x matrix + 4 x other vector instructions (SQ_INSTS_VALU, "
-                        "SQ_INSTS_VALU_TRANS_F32, SQ_INSTS_MFMA per launch: PMC citation from profiles/traffic_latest.json, not measured in "
-                        "this run) / this run's kernel time, against 1024 SIMDs x 2.4 GHz; the binding resource of this kernel"}
-        if args.config == 2 and not args.batch and world == 1 and not args.no_b4096:
-            result["roofline"]["hbm_resident_b4096"] = fused_at_b4096(env, w, device, torch)
-        dom = roofline_dominant(env, w, other_kernels, steps_range)
-        if dom:
-            result["roofline_dominant"] = dom
-        if not args.no_parity and w["atm_type"] == "quasi_static" and not w["SH_operation"]:
-            result["parity"] = parity_check(env, w, actions[0], torch)
-        if not args.no_cpu_baseline and world == 1:
-            result["cpu_baseline"] = cpu_baseline(w)
+        if args.full:
+            full_figures(result, args, env, w, B, world, device, torch, actions, kernel_ms, launches, other_kernels, coll_ms, coll_n,
+                         dt_pipe, kernel_ms_pipe, steps_range, prof_every, prof_block)
         print(json.dumps(result), flush=True)
     if distributed:
         dist.barrier()

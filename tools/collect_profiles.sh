@@ -11,16 +11,16 @@ OUT=$R/gpurun_out
 if [ "$2" != "summarize" ]; then
 cd /tmp && export TMPDIR=/tmp
 # 1. the bench line itself (un-profiled), then the same command under rocprofv3 --stats
-python3 $R/bench.py > $OUT/${TAG}_bench_c2.json 2> $OUT/${TAG}_bench_c2.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_c2 -- python3 $R/bench.py --no-cpu-baseline --no-parity > $OUT/${TAG}_prof_c2.log 2>&1
+python3 $R/bench.py --full > $OUT/${TAG}_bench_c2.json 2> $OUT/${TAG}_bench_c2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_c2 -- python3 $R/bench.py --full --no-cpu-baseline --no-parity > $OUT/${TAG}_prof_c2.log 2>&1
 # 2. PMC passes for the fused kernel (config-2 step loop)
 bash $R/tools/pmc_collect.sh gpurun_out/${TAG}_pmc > $OUT/${TAG}_pmc.log 2>&1
 bash $R/tools/pmc_memory.sh gpurun_out/${TAG}_pmc_mem > $OUT/${TAG}_pmc_mem.txt 2>&1
 cd /tmp
 # 3. the other configs: bench line + kernel stats
 for c in 3 4 5; do
-  python3 $R/bench.py --config $c --no-cpu-baseline > $OUT/${TAG}_bench_c$c.json 2> $OUT/${TAG}_bench_c$c.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_c$c -- python3 $R/bench.py --config $c --no-cpu-baseline --no-parity > $OUT/${TAG}_prof_c$c.log 2>&1
+  python3 $R/bench.py --config $c --full --no-cpu-baseline > $OUT/${TAG}_bench_c$c.json 2> $OUT/${TAG}_bench_c$c.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_c$c -- python3 $R/bench.py --config $c --full --no-cpu-baseline --no-parity > $OUT/${TAG}_prof_c$c.log 2>&1
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_k4 -- python3 $R/tools/k4_loop.py > $OUT/${TAG}_prof_k4.log 2>&1
 python3 $R/tools/sh_loop2.py 1024 256 64 single > $OUT/${TAG}_sh_loop.log 2>&1
@@ -29,8 +29,8 @@ python3 $R/tools/dyn_loop.py 1024 200 > $OUT/${TAG}_dyn_loop.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_sh -- python3 $R/tools/sh_loop2.py 1024 256 64 single > $OUT/${TAG}_prof_sh.log 2>&1
 python3 $R/tools/single_env_latency.py > $OUT/${TAG}_single.log 2>&1
 # 4. config-2 shape at B = 4096 (screens + tables 0.9 GB: four times the 256 MiB Infinity Cache): bench line, kernel stats, PMC of the fused kernel
-python3 $R/bench.py --batch 4096 --no-cpu-baseline --no-parity > $OUT/${TAG}_bench_c2_b4096.json 2> $OUT/${TAG}_bench_c2_b4096.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_c2_b4096 -- python3 $R/bench.py --batch 4096 --no-cpu-baseline --no-parity > $OUT/${TAG}_prof_c2_b4096.log 2>&1
+python3 $R/bench.py --batch 4096 --full --no-cpu-baseline --no-parity > $OUT/${TAG}_bench_c2_b4096.json 2> $OUT/${TAG}_bench_c2_b4096.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_c2_b4096 -- python3 $R/bench.py --batch 4096 --full --no-cpu-baseline --no-parity > $OUT/${TAG}_prof_c2_b4096.log 2>&1
 bash $R/tools/pmc_collect.sh gpurun_out/${TAG}_pmc_b4096 --B 4096 > $OUT/${TAG}_pmc_b4096.log 2>&1
 # 5. PMC of the reset kernels (semi_dynamic reset of 4096 envs: two-band synthesis + packing) and of the other rows' dominant kernels
 bash $R/tools/pmc_kernels.sh gpurun_out/${TAG}_pmc_reset $R/tools/reset_loop.py --B 4096 --episodes 1 > $OUT/${TAG}_pmc_reset.log 2>&1
@@ -78,7 +78,7 @@ PY
   echo
   for c in 3 4 5; do
     echo "## bench.py --config $c"; echo; echo '```json'; tail -1 gpurun_out/${TAG}_bench_c$c.json; echo '```'; echo
-    python3 tools/summarize_stats.py gpurun_out/${TAG}_prof_c$c "kernels of config $c" "rocprofv3 --kernel-trace --stats -- python3 bench.py --config $c --no-cpu-baseline --no-parity"
+    python3 tools/summarize_stats.py $OUT/${TAG}_prof_c$c "kernels of config $c" "rocprofv3 --kernel-trace --stats -- python3 bench.py --config $c --full --no-cpu-baseline --no-parity"
   done
   python3 tools/summarize_stats.py gpurun_out/${TAG}_prof_k4 "K4 batched focal fields (aog_focal_images, B=1024, N=256)" "rocprofv3 --kernel-trace --stats -- python3 tools/k4_loop.py"
   echo '```'; grep aog_focal_images gpurun_out/${TAG}_prof_k4.log; echo '```'; echo
