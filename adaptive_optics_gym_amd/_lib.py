@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libaogym.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 AOG_REWARD = {"strehl_ratio": 0, "smf_ssim": 1}
 AOG_PRECISION = {"fast": 0, "fp64": 1}
@@ -24,7 +24,7 @@ class AogConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "n_pupil", "n_modes", "obs_dim", "n_ap", "n_wfs_tables", "n_sci_tables",
         "n_fiber_modes", "reward_type", "sh_operation", "max_steps", "flat_mirror_start", "has_rew_threshold",
-        "precision", "kernel", "pixel_chunks", "atm_dynamic", "env_id_base", "reserved0")] + [(n, C.c_double) for n in (
+        "precision", "kernel", "pixel_chunks", "atm_dynamic", "env_id_base", "obs_separable")] + [(n, C.c_double) for n in (
         "wavelength_wfs", "wavelength_sci", "surface_rms_target", "rew_threshold", "ssim_ref_peak", "ssim_alpha")]
 
 
@@ -60,6 +60,10 @@ class AogActor(C.Structure):  # mirrors aog_actor in include/aogym.h
                 ("seed", C.c_uint64), ("call_index", C.c_uint64)]
 
 
+class AogObsMft(C.Structure):  # mirrors aog_obs_mft (ABI 20)
+    _fields_ = [("o", C.c_int32), ("reserved0", C.c_int32), ("m1", C.POINTER(C.c_double)), ("m2", C.POINTER(C.c_double))]
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -76,6 +80,7 @@ SYMBOLS = {
     "aog_destroy": (None, [C.c_void_p]),
     "aog_get_info": (C.c_int, [C.c_void_p, C.POINTER(AogInfo)]),
     "aog_upload_tables": (C.c_int, [C.c_void_p, C.POINTER(AogTables)]),
+    "aog_upload_obs_mft": (C.c_int, [C.c_void_p, C.POINTER(AogObsMft)]),
     "aog_set_screens_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aog_set_screens_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aog_upload_layer": (C.c_int, [C.c_void_p, C.POINTER(AogLayerTables)]),
@@ -145,7 +150,7 @@ def load():
         if have.split("+")[0] != want:
             raise RuntimeError(f"libaogym.so was built from other sources (build id {have}, sources {want}): run "
                                "`python -m adaptive_optics_gym_amd.build` (or __graft_entry__.build())")
-    for which, cls in enumerate((AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite)):
+    for which, cls in enumerate((AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite, AogObsMft)):
         if lib.aog_struct_size(which) != C.sizeof(cls):
             raise RuntimeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, the library's struct {lib.aog_struct_size(which)}")
     _lib = lib

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .atmosphere_host import (build_layer_tables, cn_squared_from_fried_parameter, integer_shifts, screen_numpy,
                               screens_torch)
-from .optics_host import HostTables, build_tables
+from .optics_host import HostTables, build_tables, obs_route_for
 from .params import OpticalParams, coerce_velocity
 from .spaces import make_box
 
@@ -46,6 +46,8 @@ class BatchedAOEnv:
                         below the photon noise added before the image is read) | 'double' (complex128, for comparing the noise-free
                         sensor image with a float64 oracle)
     precision           'fast' (fp32 data, float64 accumulators) | 'fp64' (validation kernel)
+                        obs_dim 1 .. 32 on both.  The observation takes the table route where it is built (fast obs_dim <= 5, fp64
+                        obs_dim <= 7) and the separable matrix Fourier transform above (``optics_host.obs_route_for``)
     extrusion           'auto' (dynamic atmosphere: the int8 matrix-core composite form, new samples good to ~1e-9 rad) | 'f64' (float64 round
                         kernels only: the validation form, bit-comparable with the oracle's recursion to 1e-12)
     kernel              'auto' | 'mfma' | 'valu'
@@ -120,8 +122,14 @@ class BatchedAOEnv:
         self.action_space = make_box(-1, 1, (self.num_modes,), np.float16)          # AO_env.py:46
 
         self.Cn_squared = cn_squared_from_fried_parameter(self.fried_parameter, self.params.wavelength_sci)
-        # (tables=: the HostTables of another instance with the same params / act_type / act_dim / obs_dim, to skip the host precompute)
-        self.tables: HostTables = tables if tables is not None else build_tables(self.params, act_type, self.num_modes, self.obs_dim)
+        if precision not in _lib.AOG_PRECISION:
+            raise ValueError("precision must be 'fast' or 'fp64'")
+        self.obs_route = obs_route_for(precision, self.obs_dim)
+        # (tables=: the HostTables of another instance with the same params / act_type / act_dim / obs_dim / route, to skip the host precompute)
+        if tables is not None and tables.obs_route != self.obs_route:
+            raise ValueError(f"tables= were built for the {tables.obs_route!r} observation route; this handle takes {self.obs_route!r}")
+        self.tables: HostTables = tables if tables is not None else build_tables(self.params, act_type, self.num_modes, self.obs_dim,
+                                                                                 obs_route=self.obs_route)
         t = self.tables
         cfg = _lib.AogConfig()
         cfg.abi_version = _lib.ABI_VERSION
@@ -143,6 +151,7 @@ class BatchedAOEnv:
         cfg.pixel_chunks = int(pixel_chunks)
         cfg.atm_dynamic = int(atm_type == "dynamic")
         cfg.env_id_base = self.global_env_offset
+        cfg.obs_separable = int(self.obs_route == "separable")
         cfg.wavelength_wfs = self.params.wavelength_wfs
         cfg.wavelength_sci = self.params.wavelength_sci
         cfg.surface_rms_target = self.params.action_rms_fraction * self.params.wavelength_sci
@@ -169,6 +178,11 @@ class BatchedAOEnv:
                               _dptr(keep["sc"], C.c_double), _dptr(keep["m1"], C.c_double), _dptr(keep["m2"], C.c_double),
                               int(t.focal_m1.shape[0]))
         _lib.check(self.lib.aog_upload_tables(self._handle, C.byref(tabs)))
+        if self.obs_route == "separable":
+            om1 = np.ascontiguousarray(np.stack([t.obs_m1.real, t.obs_m1.imag], axis=-1), dtype=np.float64)
+            om2 = np.ascontiguousarray(np.stack([t.obs_m2.real, t.obs_m2.imag], axis=-1), dtype=np.float64)
+            mft = _lib.AogObsMft(self.obs_dim, 0, _dptr(om1, C.c_double), _dptr(om2, C.c_double))
+            _lib.check(self.lib.aog_upload_obs_mft(self._handle, C.byref(mft)))
         _lib.check(self.lib.aog_set_screen_method(self._handle, _lib.AOG_SCREENS[screen_method]))
         self.info = _lib.AogInfo()
         _lib.check(self.lib.aog_get_info(self._handle, C.byref(self.info)))

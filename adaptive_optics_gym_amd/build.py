@@ -1,7 +1,7 @@
 """Build ``libaogym.so`` in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 One translation unit per kernel family, compiled in parallel: ``aogym.hip`` (C-ABI core: handle, tables, step / reset), ``atmosphere.hip``
-(dynamic atmosphere), ``screens.hip`` (screen synthesis), ``shack.hip`` (Shack-Hartmann chain), ``focal.hip`` (K4), ``actor.hip`` (policy query)
+(dynamic atmosphere), ``screens.hip`` (screen synthesis), ``shack.hip`` (Shack-Hartmann chain), ``focal.hip`` (K4 and the separable observation K11), ``actor.hip`` (policy query)
 and ``fused_inst.hip`` once per padded mode count (the fused-kernel template instantiations).
 
 The library is tied to its sources: ``source_id()`` is a SHA-256 over ``csrc/*.{h,hip}`` + ``include/aogym.h``; it is compiled into the core
@@ -30,7 +30,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-fno-s
 # headers each unit includes besides the shared ones (an edit of a family header recompiles that family only)
 SHARED = ("aogym_internal.h", "host_common.h", "k_common.h")
 FAMILY = {"aogym": ("k_pack.h", "k_step.h"), "atmosphere": ("k_pack.h", "k_extrude.h", "k_extrude_i8.h"), "screens": ("k_fft.h", "k_screens.h"),
-          "shack": ("k_fft.h", "k_shack.h"), "focal": ("k_focal.h",), "actor": ("k_actor.h",), "fused_inst": ("k_fused.h",)}
+          "shack": ("k_fft.h", "k_shack.h"), "focal": ("k_focal.h", "k_obs.h"), "actor": ("k_actor.h",), "fused_inst": ("k_fused.h",)}
 
 
 def hipcc_path() -> str:

@@ -23,6 +23,14 @@ int aog_actor_act(const aog_actor* n, int device, const void* obs_dev, int obs_i
   a.mean = mean_dev; a.action = action_dev; a.log_prob = log_prob_dev;
   a.B = n->batch; a.S = n->state_dim; a.H = n->hidden_dim; a.A = n->act_dim;
   a.kpad = round_up(std::max(n->state_dim, n->hidden_dim), 16);
+  a.kpad_b = round_up(n->hidden_dim, 16);
+  // the weight chunk takes what the activations leave of the LDS, at most kActorWFloats; it must hold one 16-row tile of the widest layer
+  // (state_dim 1024 = the 32 x 32 observation: 64 KB of observations beside the chunk)
+  const size_t act_floats = (size_t)(a.kpad + a.kpad_b) * 16 + 16;
+  a.wfloats = (int)std::min<size_t>(aog::kActorWFloats, (kLdsBytes / sizeof(float) - act_floats) / 4 * 4);
+  if (a.wfloats < 16 * a.kpad)
+    return fail(AOG_ERR_UNSUPPORTED, "aog_actor_act: state_dim %d with hidden_dim %d does not fit the LDS (activations %zu floats + one 16-row weight tile)",
+                n->state_dim, n->hidden_dim, act_floats);
   a.p_drop = n->dropout_p;
   a.keep_scale = 1.0f / (1.0f - n->dropout_p);
   a.std = std::sqrt(n->cov_var);
@@ -31,7 +39,7 @@ int aog_actor_act(const aog_actor* n, int device, const void* obs_dev, int obs_i
   a.call_lo = (uint32_t)n->call_index;
   a.call_hi = (uint32_t)(n->call_index >> 32);
   a.env_base = n->env_id_base;
-  const size_t lds = ((size_t)2 * a.kpad * 16 + 16 + (size_t)aog::kActorWFloats) * sizeof(float);
+  const size_t lds = (act_floats + (size_t)a.wfloats) * sizeof(float);
   if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_actor_act), lds, device)) return rc;
   hipLaunchKernelGGL(aog::k_actor_act, dim3((n->batch + 15) / 16), dim3(aog::kActorThreads), lds, static_cast<hipStream_t>(stream), a);
   HIP_TRY(hipGetLastError());

@@ -51,7 +51,11 @@ int ensure_dynamic_lds(const void* fn, size_t bytes, int device) {
   std::lock_guard<std::mutex> lock(mu);
   size_t& have = granted[{fn, device}];
   if (bytes > have) {
-    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    const hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (err != hipSuccess) {
+      (void)hipGetLastError();   // (a refused request is reported here; it must not surface again at the next unrelated error check)
+      return fail(AOG_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, %zu bytes) failed: %s", bytes, hipGetErrorString(err));
+    }
     have = bytes;
   }
   return AOG_OK;
@@ -122,6 +126,14 @@ int load_actuators(aog_env* e, hipStream_t s, _Float16* act_ll) {
   return AOG_OK;
 }
 
+int load_actuators_into(aog_env* e, hipStream_t s, _Float16* act16, _Float16* act_ll) {
+  const int n = e->B * e->A_pad;
+  hipLaunchKernelGGL(aog::k_load_actuators, dim3((n + 255) / 256), dim3(256), 0, s, e->act_dm, (float*)nullptr, act16, e->B, e->A, e->A_pad, e->Bp,
+                     2.0 / e->cfg.wavelength_wfs, act_ll);
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
 // New screens for the WHOLE batch make a handle whose extrusion kernel once timed out usable again (see check_poisoned).  Called by the
 // public entry points with the range of the whole call (aog_generate_screens installs large batches in several chunks).  Dynamic handles
 // drain the stream first: a timeout of a launch that is still running would otherwise poison the screens just installed.
@@ -165,11 +177,12 @@ void launch_phase_field(aog_env* e, hipStream_t s, const _Float16* act16, float*
     default: launch_phase_field_apad128(e, s, act16, fa, grid); break;
   }
 }
-void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, float* grid, size_t env_stride, int row_stride, int etile0, int n_et) {
+void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, const _Float16* act_ll, float* grid, size_t env_stride, int row_stride, int etile0,
+                       int n_et) {
   aog::PhaseFieldArgs fa{};
   fa.ap_yx = e->focal_ap_yx;
   fa.mla_rev = nullptr;
-  fa.act_ll = reinterpret_cast<const aog::f16x8*>(e->focal_act_ll) + (size_t)etile0 * (e->A_pad / 16) * 64;
+  fa.act_ll = reinterpret_cast<const aog::f16x8*>(act_ll) + (size_t)etile0 * (e->A_pad / 16) * 64;
   fa.field = reinterpret_cast<float2*>(grid);   // grid row 0 = env etile0 * 32
   fa.env_stride = env_stride;
   fa.row_stride = row_stride;
@@ -253,7 +266,9 @@ int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, flo
   p.MRS = ref ? e->MRS_used : e->MRS;
   p.MRW_used = e->MRW_used;
   p.MRS_used = e->MRS_used;
-  p.n_obs = e->n_obs;
+  p.n_obs = e->n_obs_tab;
+  p.obs_pw = e->obs_sep ? e->obs_pw : nullptr;
+  p.n_obs_sep = e->obs_sep ? e->n_obs : 0;
   p.n_fiber = e->cfg.n_fiber_modes;
   p.reward_type = e->cfg.reward_type;
   p.has_thr = e->cfg.has_rew_threshold;
@@ -358,6 +373,7 @@ int64_t aog_struct_size(int which) {
     case 4: return (int64_t)sizeof(aog_actor);
     case 5: return (int64_t)sizeof(aog_info);
     case 6: return (int64_t)sizeof(aog_layer_composite);
+    case 7: return (int64_t)sizeof(aog_obs_mft);
     default: return -1;
   }
 }
@@ -375,10 +391,23 @@ int aog_create(const aog_config* cfg, int device, aog_env** out) {
     return fail(AOG_ERR_INVALID, "aog_create: bad table counts");
   if (cfg->reward_type != AOG_REWARD_STREHL && cfg->reward_type != AOG_REWARD_SMF_SSIM)
     return fail(AOG_ERR_INVALID, "aog_create: reward_type must be 'strehl_ratio' or 'smf_ssim' (AO_env.py:476,487)");
-  if (cfg->obs_dim * cfg->obs_dim > 64) return fail(AOG_ERR_UNSUPPORTED, "aog_create: obs_dim > 8 not built");
+  if (cfg->obs_separable != 0 && cfg->obs_separable != 1) return fail(AOG_ERR_INVALID, "aog_create: obs_separable must be 0 or 1");
+  if (cfg->obs_dim > 32)
+    return fail(AOG_ERR_UNSUPPORTED, "aog_create: obs_dim %d > 32 not built (limit 32: the policy kernel aog_actor_act takes state_dim <= 1024 = 32^2)",
+                cfg->obs_dim);
+  if (!cfg->obs_separable && cfg->obs_dim * cfg->obs_dim > 64)
+    return fail(AOG_ERR_UNSUPPORTED, "aog_create: obs_dim > 8 not built on the table route (cfg.obs_separable = 1 takes obs_dim <= 32)");
   if (cfg->n_modes > 256) return fail(AOG_ERR_UNSUPPORTED, "aog_create: act_dim > 256 not built");
   if (cfg->n_wfs_tables + cfg->n_sci_tables > 80) return fail(AOG_ERR_UNSUPPORTED, "aog_create: > 80 tables");
   if (cfg->env_id_base < 0) return fail(AOG_ERR_INVALID, "aog_create: env_id_base must be >= 0");
+  if (cfg->precision == AOG_PRECISION_FP64 && !cfg->obs_separable) {
+    // the epilogue holds the coefficient matrix of every table output in LDS: at o = 8 (67 wfs tables) that is more than a CU has
+    const int n_obs = cfg->obs_dim * cfg->obs_dim;
+    const size_t lds = aog::epilogue_lds_bytes(2 * (cfg->n_wfs_tables + cfg->n_sci_tables), n_obs, cfg->n_fiber_modes, cfg->n_wfs_tables, cfg->n_sci_tables);
+    if (lds > aog_host::kLdsBytes)
+      return fail(AOG_ERR_UNSUPPORTED, "aog_create: the table route's epilogue at obs_dim %d needs %zu bytes of LDS (> %zu); use cfg.obs_separable = 1",
+                  cfg->obs_dim, lds, aog_host::kLdsBytes);
+  }
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(AOG_ERR_HIP, "aog_create: device %d not present (%d HIP devices)", device, ndev);
@@ -398,7 +427,9 @@ int aog_create(const aog_config* cfg, int device, aog_env** out) {
   e->MRW_used = cfg->n_wfs_tables;
   e->MRS_used = cfg->n_sci_tables;
   e->n_obs = cfg->obs_dim * cfg->obs_dim;
-  e->n_out = e->n_obs + cfg->n_fiber_modes;
+  e->obs_sep = cfg->obs_separable != 0;
+  e->n_obs_tab = e->obs_sep ? 0 : e->n_obs;
+  e->n_out = e->n_obs_tab + cfg->n_fiber_modes;
   // sin/cos flavour of the fast kernels: "hwraw" (default; v_sin_f32/v_cos_f32 on the revolutions, the instruction
   // reduces them itself), "hw" (same instructions after an explicit exact reduction), "poly" (degree-7/8 polynomial)
   e->sincos_hw = 2;
@@ -557,7 +588,7 @@ int aog_get_info(const aog_env* e, aog_info* out) {
   out->pixel_chunks = e->n_chunks;
   out->kernel = e->kernel;
   out->n_sums = 2 * (e->MRW + e->MRS);
-  out->reserved = e->ring_direct ? 1 : 0;
+  out->reserved = (e->ring_direct ? 1 : 0) | (e->obs_sep ? 2 : 0);
   out->device_bytes = e->dev_bytes;
   return AOG_OK;
 }
@@ -703,53 +734,17 @@ int aog_upload_tables(aog_env* e, const aog_tables* t) {
     HIP_TRY(hipMemcpy(e->focal_m2, t->focal_m2, sizeof(double) * nf * N * 2, hipMemcpyHostToDevice));
     if (e->cfg.precision == AOG_PRECISION_FAST) {   // split-f16 operand tables of the batched matrix-core path (k_focal_pass1 / k_focal_pass2)
       const int Nxp = round_up(N, 128), Nyp = round_up(N, 16), nfp = round_up(nf, 128);
-      // power-of-two scales: the largest component of a table lands in [1/2, 1)
-      auto scale_of = [](const double* v, size_t n) {
-        double mx = 0.0;
-        for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(v[i]));
-        return mx > 0.0 ? std::ldexp(1.0, -(std::ilogb(mx) + 1)) : 1.0;
-      };
-      const double s1 = scale_of(t->focal_m1, (size_t)nf * N * 2), s2 = scale_of(t->focal_m2, (size_t)nf * N * 2);
-      auto put = [](std::vector<_Float16>& tab, size_t tile, int lane, int slot, double re, double im) {
-        const double c[2] = {re, im};
-        for (int q = 0; q < 2; ++q) {
-          const _Float16 hi = (_Float16)(float)c[q];   // round to nearest, like the kernels' split8
-          tab[((tile * 4 + 2 * q) * 64 + lane) * 8 + slot] = hi;
-          tab[((tile * 4 + 2 * q + 1) * 64 + lane) * 8 + slot] = (_Float16)(float)(c[q] - (double)(float)hi);
-        }
-      };
-      // m1s [v block][k-step over y]: lane l = column v = 32 vb + (l & 31), slot j = y = 16 ks + 8 (l >> 5) + j
-      std::vector<_Float16> m1s((size_t)(nfp / 32) * (Nyp / 16) * 4 * 64 * 8, (_Float16)0.f);
-      for (int vb = 0; vb < nfp / 32; ++vb)
-        for (int ks = 0; ks < Nyp / 16; ++ks)
-          for (int l = 0; l < 64; ++l)
-            for (int j = 0; j < 8; ++j) {
-              const int v = 32 * vb + (l & 31), y = 16 * ks + 8 * (l >> 5) + j;
-              if (v < nf && y < N)
-                put(m1s, (size_t)vb * (Nyp / 16) + ks, l, j, t->focal_m1[((size_t)v * N + y) * 2] * s1, t->focal_m1[((size_t)v * N + y) * 2 + 1] * s1);
-            }
-      // m2s [u block][x tile][s]: lane l = column u = 32 ub + (l & 31), slot j = x = 32 xt + (r & 3) + 8 (r >> 2) + 4 (l >> 5), r = 8 s + j
-      // (the order in which pass 1's accumulator registers hold x)
-      std::vector<_Float16> m2s((size_t)(nfp / 32) * (Nxp / 32) * 2 * 4 * 64 * 8, (_Float16)0.f);
-      for (int ub = 0; ub < nfp / 32; ++ub)
-        for (int xt = 0; xt < Nxp / 32; ++xt)
-          for (int s2i = 0; s2i < 2; ++s2i)
-            for (int l = 0; l < 64; ++l)
-              for (int j = 0; j < 8; ++j) {
-                const int r = 8 * s2i + j, x = 32 * xt + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), u = 32 * ub + (l & 31);
-                if (u < nf && x < N)
-                  put(m2s, ((size_t)ub * (Nxp / 32) + xt) * 2 + s2i, l, j, t->focal_m2[((size_t)x * nf + u) * 2] * s2,
-                      t->focal_m2[((size_t)x * nf + u) * 2 + 1] * s2);
-              }
+      std::vector<_Float16> m1s, m2s;
+      const float unscale = mft_operand_tables(t->focal_m1, t->focal_m2, N, nf, nfp, Nxp, Nyp, m1s, m2s);
       if ((rc = dev_alloc(e, &e->focal_m1s, m1s.size(), false)) != AOG_OK) return rc;
       if ((rc = dev_alloc(e, &e->focal_m2s, m2s.size(), false)) != AOG_OK) return rc;
       HIP_TRY(hipMemcpy(e->focal_m1s, m1s.data(), sizeof(_Float16) * m1s.size(), hipMemcpyHostToDevice));
       HIP_TRY(hipMemcpy(e->focal_m2s, m2s.data(), sizeof(_Float16) * m2s.size(), hipMemcpyHostToDevice));
-      e->focal_unscale = (float)(1.0 / (s1 * s2));
+      e->focal_unscale = unscale;
       std::vector<int32_t> apidx((size_t)e->n_ap), yx((size_t)e->n_ap);
       HIP_TRY(hipMemcpy(apidx.data(), e->ap_index, sizeof(int32_t) * e->n_ap, hipMemcpyDeviceToHost));
       for (int i = 0; i < e->n_ap; ++i) yx[i] = ((apidx[i] / N) << 16) | (apidx[i] % N);
-      if ((rc = dev_alloc(e, &e->focal_ap_yx, yx.size(), false)) != AOG_OK) return rc;
+      if (!e->focal_ap_yx && (rc = dev_alloc(e, &e->focal_ap_yx, yx.size(), false)) != AOG_OK) return rc;
       HIP_TRY(hipMemcpy(e->focal_ap_yx, yx.data(), sizeof(int32_t) * yx.size(), hipMemcpyHostToDevice));
     }
     e->n_focal = nf;
@@ -985,6 +980,7 @@ int aog_set_actuators(aog_env* e, const double* act_dev, void* stream) {
 int aog_reset(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, void* stream) {
   if (!e) return fail(AOG_ERR_INVALID, "aog_reset: null handle");
   if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "aog_reset before aog_upload_tables/aog_set_screens");
+  if (e->obs_sep && !e->obs_ready) return fail(AOG_ERR_STATE, "aog_reset on a separable-observation handle before aog_upload_obs_mft");
   if (int rc = check_poisoned(e, "aog_reset")) return rc;
   if (int rc = refuse_pre_evolved(e, "aog_reset")) return rc;
   if (int rcd = x8_drop_ahead(e)) return rcd;   // (work done ahead for the next step read the state this call changes)
@@ -1002,6 +998,7 @@ int aog_reset(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, vo
   }
   int rc = launch_fused(e, s);
   if (rc != AOG_OK) return rc;
+  if ((rc = launch_obs(e, s, obs_raw, obs)) != AOG_OK) return rc;
   return launch_epilogue(e, false, obs_raw, obs, nullptr, nullptr, nullptr, nullptr, s);
 }
 
@@ -1022,6 +1019,7 @@ static int step_body(aog_env* e, const float* action, const float* action_next, 
     return fail(AOG_ERR_STATE, "aog_step: a pipelined step has already loaded the next action (continue with aog_step_pipelined)");
   if (pipelined && e->lookahead) return fail(AOG_ERR_UNSUPPORTED, "aog_step_pipelined: not together with aog_set_lookahead");
   if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "aog_step before aog_upload_tables/aog_set_screens");
+  if (e->obs_sep && !e->obs_ready) return fail(AOG_ERR_STATE, "aog_step on a separable-observation handle before aog_upload_obs_mft");
   if (int rc = check_poisoned(e, "aog_step")) return rc;
   if (e->cfg.reward_type == AOG_REWARD_SMF_SSIM && e->n_obs < 7)
     return fail(AOG_ERR_INVALID, "win_size exceeds image extent (smf_ssim needs obs_dim**2 >= 7; AO_env.py:495)");
@@ -1056,8 +1054,12 @@ static int step_body(aog_env* e, const float* action, const float* action_next, 
   if (join_ext) HIP_TRY(hipStreamWaitEvent(s, e->ev_ext_done, 0));
   int rc = launch_fused(e, s);
   if (rc != AOG_OK) return rc;
-  // lookahead: step t + 1's wind shift needs nothing from this step's outputs (AO_env.py:125 vs :132-142), only that the fused kernel
-  // has finished reading the ring.  Not on an episode's last step: reset() observes the atmosphere as this step left it (AO_env.py:84).
+  // separable observation route: its passes read this step's screens and actuators (their own operand copies), so they run here — before the
+  // extrusion of step t + 1 is released below and before the epilogue, which reads their powers and may carry the next step's prologue
+  if ((rc = launch_obs(e, s, obs_raw, obs)) != AOG_OK) return rc;
+  // lookahead: step t + 1's wind shift needs nothing from this step's outputs (AO_env.py:125 vs :132-142), only that the fused kernel (and the
+  // separable observation passes) have finished reading the screens.  Not on an episode's last step: reset() observes the atmosphere as this
+  // step left it (AO_env.py:84).
   if (e->cfg.atm_dynamic && e->lookahead && !e->next_noise && e->steps_since_reset < e->cfg.max_steps) {
     HIP_TRY(hipEventRecord(e->ev_fused_done, s));
     HIP_TRY(hipStreamWaitEvent(e->ext_stream, e->ev_fused_done, 0));

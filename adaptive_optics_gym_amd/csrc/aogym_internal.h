@@ -17,6 +17,7 @@ struct aog_env {
   int MRW = 0, MRS = 0;          // padded table counts of the fast kernels
   int MRW_used = 0, MRS_used = 0;
   int n_obs = 0, n_out = 0;
+  int n_obs_tab = 0;             // observation outputs of the table route: n_obs, or 0 on the separable route (its n_out = the fiber modes)
   int kernel = AOG_KERNEL_VALU;  // resolved
   int sincos_hw = 0;
   // launch geometry
@@ -101,6 +102,23 @@ struct aog_env {
   _Float16* focal_act_ll = nullptr;  // [n_etiles][A_pad / 16][64][8] third f16 term of the actuators (K4 phases)
   _Float16* focal_T16 = nullptr; // [focal_chunk][Nxp / 32][nfp / 32][2][4][64][8]: T' = m1' E, split, pass 2's operand order
   int focal_chunk = 0;
+  // separable observation route (cfg.obs_separable, aog_upload_obs_mft; K11, k_obs.h)
+  bool obs_sep = false;
+  bool obs_ready = false;        // aog_upload_obs_mft done
+  _Float16* obs_m1s = nullptr;   // m1 2^e1, K4's m1s layout with one v block: [Nyp / 16][4][64][8]
+  _Float16* obs_m2s = nullptr;   // m2 2^e2, K4's m2s layout with one u block: [Nxp / 32][2][4][64][8]
+  float obs_unscale = 1.f;
+  int obs_chunk = 0;             // envs per round of the phase grid / pass 1 work buffers (whole env tiles)
+  float* obs_grid = nullptr;     // [obs_chunk][Nyp][Nxp] reduced phases, kShOutside outside the aperture (Nxp = N rounded up to 32)
+  _Float16* obs_T16 = nullptr;   // [obs_chunk][Nxp / 32][2][4][64][8]
+  _Float16* obs_act16 = nullptr; // actuators of the step being observed in the phase kernel's operand layouts (hi | lo, third term):
+  _Float16* obs_act_ll = nullptr;//   their own buffers, so that nothing the fused kernel or a pipelined prologue reads is touched
+  double* obs_pw = nullptr;      // [B][o^2] float64 powers of the last observation (the SSIM reward reads them)
+  double* obs_m1d = nullptr;     // float64 handles: m1 [o][N], m2 [N][o] complex, E [N][N], T [o][N], F [B][o^2] complex
+  double* obs_m2d = nullptr;
+  double* obs_E = nullptr;
+  double* obs_T = nullptr;
+  double* obs_F = nullptr;
   // state
   float* psi_rev = nullptr;      // [n_quads][Bp][4]  (handles that run the VALU kernel only)
   double* pack_mean = nullptr;   // [B] aperture means of the screens being installed (k_screen_means -> k_pack_tiles)
@@ -213,6 +231,7 @@ int launch_fused_apad64(aog_env* e, hipStream_t s);
 int launch_fused_apad128(aog_env* e, hipStream_t s);
 // phase-only contraction u = psi + Mt a for every (pixel, env) with the actuator operands `act16`, written in the psi_tile layout
 void launch_phase(aog_env* e, hipStream_t s, const _Float16* act16, float* out_tile);
-void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, float* grid, size_t env_stride, int row_stride, int etile0, int n_et);
+void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, const _Float16* act_ll, float* grid, size_t env_stride, int row_stride, int etile0,
+                       int n_et);
 void launch_phase_field(aog_env* e, hipStream_t s, const _Float16* act16, float* field, size_t env_stride, int row_stride, bool grid);   // complex64 field, or (grid) one float of reduced phase per pixel
 }  // namespace aog_host

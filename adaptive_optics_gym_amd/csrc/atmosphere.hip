@@ -294,6 +294,23 @@ int ensure_tiles(aog_env* e, hipStream_t s) {
   return AOG_OK;
 }
 
+// The separable observation route forms its phase grid from psi_tile: on a dynamic handle it must hold the screens the step kernel of this
+// step read.  Ring-direct handles refresh it from the master screens (as ensure_tiles); the per-step repack of the other MFMA / Shack-Hartmann
+// handles writes it already; the VALU kernel's repack writes psi_rev only, so its handles convert the master screens here (aperture mean
+// removed; a global phase does not change an observation).
+int obs_tiles(aog_env* e, hipStream_t s) {
+  if (!e->cfg.atm_dynamic || e->cfg.precision != AOG_PRECISION_FAST) return AOG_OK;
+  if (e->ring_direct) return ensure_tiles(e, s);
+  if (e->kernel == AOG_KERNEL_MFMA || e->sh_ready) return AOG_OK;
+  const double inv = 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs);
+  const int N2 = e->cfg.n_pupil * e->cfg.n_pupil;
+  hipLaunchKernelGGL((aog::k_pack_screens<double>), dim3(e->B), dim3(256), 0, s, e->psi_master, e->ap_index, (float*)nullptr, e->psi_tile,
+                     (double*)nullptr, 0, N2, e->n_ap, e->n_ap_pad, e->Bp, inv, (const int32_t*)e->origin, e->cfg.n_pupil, (double*)nullptr,
+                     (double*)nullptr);
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
 int ring_from_master(aog_env* e, int first, int count, int keep_ref, hipStream_t s) {
   hipLaunchKernelGGL(aog::k_ring_from_master, dim3(count), dim3(256), 0, s, e->psi_master, e->origin, e->ap_index, e->psi_offset, e->psi_ring, first,
                      e->cfg.n_pupil, e->n_ap, 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs), keep_ref);

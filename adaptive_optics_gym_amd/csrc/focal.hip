@@ -1,10 +1,154 @@
-// K4: focal-plane field export (aog_focal_image / aog_focal_images).
+// K4: focal-plane field export (aog_focal_image / aog_focal_images); K11: the observation of the separable route (aog_upload_obs_mft, launch_obs).
 #include "host_common.h"
 #include "k_focal.h"
+#include "k_obs.h"
 
 using namespace aog_host;
 
+namespace aog_host {
+
+float mft_operand_tables(const double* m1, const double* m2, int N, int nf, int nfp, int Nxp, int Nyp, std::vector<_Float16>& m1s,
+                         std::vector<_Float16>& m2s) {
+  // power-of-two scales: the largest component of a table lands in [1/2, 1)
+  auto scale_of = [](const double* v, size_t n) {
+    double mx = 0.0;
+    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(v[i]));
+    return mx > 0.0 ? std::ldexp(1.0, -(std::ilogb(mx) + 1)) : 1.0;
+  };
+  const double s1 = scale_of(m1, (size_t)nf * N * 2), s2 = scale_of(m2, (size_t)nf * N * 2);
+  auto put = [](std::vector<_Float16>& tab, size_t tile, int lane, int slot, double re, double im) {
+    const double c[2] = {re, im};
+    for (int q = 0; q < 2; ++q) {
+      const _Float16 hi = (_Float16)(float)c[q];   // round to nearest, like the kernels' split8
+      tab[((tile * 4 + 2 * q) * 64 + lane) * 8 + slot] = hi;
+      tab[((tile * 4 + 2 * q + 1) * 64 + lane) * 8 + slot] = (_Float16)(float)(c[q] - (double)(float)hi);
+    }
+  };
+  // m1s [v block][k-step over y]: lane l = column v = 32 vb + (l & 31), slot j = y = 16 ks + 8 (l >> 5) + j
+  m1s.assign((size_t)(nfp / 32) * (Nyp / 16) * 4 * 64 * 8, (_Float16)0.f);
+  for (int vb = 0; vb < nfp / 32; ++vb)
+    for (int ks = 0; ks < Nyp / 16; ++ks)
+      for (int l = 0; l < 64; ++l)
+        for (int j = 0; j < 8; ++j) {
+          const int v = 32 * vb + (l & 31), y = 16 * ks + 8 * (l >> 5) + j;
+          if (v < nf && y < N) put(m1s, (size_t)vb * (Nyp / 16) + ks, l, j, m1[((size_t)v * N + y) * 2] * s1, m1[((size_t)v * N + y) * 2 + 1] * s1);
+        }
+  // m2s [u block][x tile][s]: lane l = column u = 32 ub + (l & 31), slot j = x = 32 xt + (r & 3) + 8 (r >> 2) + 4 (l >> 5), r = 8 s + j
+  // (the order in which pass 1's accumulator registers hold x)
+  m2s.assign((size_t)(nfp / 32) * (Nxp / 32) * 2 * 4 * 64 * 8, (_Float16)0.f);
+  for (int ub = 0; ub < nfp / 32; ++ub)
+    for (int xt = 0; xt < Nxp / 32; ++xt)
+      for (int s2i = 0; s2i < 2; ++s2i)
+        for (int l = 0; l < 64; ++l)
+          for (int j = 0; j < 8; ++j) {
+            const int r = 8 * s2i + j, x = 32 * xt + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), u = 32 * ub + (l & 31);
+            if (u < nf && x < N)
+              put(m2s, ((size_t)ub * (Nxp / 32) + xt) * 2 + s2i, l, j, m2[((size_t)x * nf + u) * 2] * s2, m2[((size_t)x * nf + u) * 2 + 1] * s2);
+          }
+  return (float)(1.0 / (s1 * s2));
+}
+
+// K11 geometry: x padded to whole 32-column tiles (one wave each), y to whole 16-row k-steps
+static int obs_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 32); }
+static int obs_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
+
+int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs) {
+  if (!e->obs_sep) return AOG_OK;
+  const int N = e->cfg.n_pupil, o = e->cfg.obs_dim, n_obs = e->n_obs;
+  if (e->cfg.precision == AOG_PRECISION_FP64) {
+    // validation form: per env, E on the pupil grid (k_focal_field writes the aperture pixels; the rest of obs_E stays 0), then the two
+    // products in float64
+    double2* E = reinterpret_cast<double2*>(e->obs_E);
+    double2* T = reinterpret_cast<double2*>(e->obs_T);
+    double2* F = reinterpret_cast<double2*>(e->obs_F);
+    for (int env = 0; env < e->B; ++env) {
+      hipLaunchKernelGGL(aog::k_focal_field, dim3((e->n_ap + 255) / 256), dim3(256), 0, s, (const float*)nullptr, e->psi64, (const float*)nullptr,
+                         e->modes64, (const float*)nullptr, e->act_dm, e->ap_index, E, env, e->n_ap, e->n_ptiles, e->A, e->A_pad, e->Bp,
+                         e->cfg.wavelength_wfs);
+      hipLaunchKernelGGL(aog::k_cgemm_small, dim3((o * N + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->obs_m1d), E, T,
+                         (float2*)nullptr, o, N, N);
+      hipLaunchKernelGGL(aog::k_cgemm_small, dim3((n_obs + 255) / 256), dim3(256), 0, s, T, reinterpret_cast<const double2*>(e->obs_m2d),
+                         F + (size_t)env * n_obs, (float2*)nullptr, o, N, o);
+    }
+    const int n = e->B * n_obs;
+    hipLaunchKernelGGL(aog::k_obs_finish64, dim3((n + 255) / 256), dim3(256), 0, s, F, n, e->obs_pw, obs_raw, obs);
+    HIP_TRY(hipGetLastError());
+    return AOG_OK;
+  }
+  if (int rc = obs_tiles(e, s)) return rc;
+  if (int rc = load_actuators_into(e, s, e->obs_act16, e->obs_act_ll)) return rc;
+  const int Nxp = obs_nxp(e), Nyp = obs_nyp(e), nxt = Nxp / 32;
+  const size_t grid_env = (size_t)Nyp * Nxp;
+  for (int env0 = 0; env0 < e->B; env0 += e->obs_chunk) {
+    const int n = std::min(e->obs_chunk, e->B - env0), n_et = (n + 31) / 32;
+    aog_host::launch_phase_grid(e, s, e->obs_act16, e->obs_act_ll, e->obs_grid, grid_env, Nxp, env0 / 32, n_et);
+    hipLaunchKernelGGL(aog::k_obs_pass1, dim3((n * nxt + 3) / 4), dim3(256), 0, s, e->obs_grid, reinterpret_cast<const aog::f16x8*>(e->obs_m1s),
+                       reinterpret_cast<aog::f16x8*>(e->obs_T16), Nxp, Nyp, n);
+    const size_t off = (size_t)env0 * n_obs;
+    hipLaunchKernelGGL(aog::k_obs_pass2, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_T16),
+                       reinterpret_cast<const aog::f16x8*>(e->obs_m2s), nxt, n, o, e->obs_unscale, e->obs_pw + off, obs_raw ? obs_raw + off : nullptr,
+                       obs ? obs + off : nullptr);
+  }
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
+}  // namespace aog_host
+
 extern "C" {
+
+int aog_upload_obs_mft(aog_env* e, const aog_obs_mft* t) {
+  if (!e || !t || !t->m1 || !t->m2) return fail(AOG_ERR_INVALID, "aog_upload_obs_mft: null argument");
+  if (!e->obs_sep) return fail(AOG_ERR_STATE, "aog_upload_obs_mft: the handle was created with cfg.obs_separable = 0 (table route)");
+  if (t->o != e->cfg.obs_dim) return fail(AOG_ERR_INVALID, "aog_upload_obs_mft: o = %d != cfg.obs_dim = %d", t->o, e->cfg.obs_dim);
+  if (!e->tables_ready) return fail(AOG_ERR_STATE, "aog_upload_obs_mft before aog_upload_tables");
+  if (e->obs_ready) return fail(AOG_ERR_STATE, "aog_upload_obs_mft: already uploaded for this handle");
+  HIP_TRY(hipSetDevice(e->device));
+  const int N = e->cfg.n_pupil, o = e->cfg.obs_dim;
+  int rc;
+  if ((rc = dev_alloc(e, &e->obs_pw, (size_t)e->B * e->n_obs)) != AOG_OK) return rc;
+  if (e->cfg.precision == AOG_PRECISION_FP64) {
+    if ((rc = dev_alloc(e, &e->obs_m1d, (size_t)o * N * 2, false)) != AOG_OK) return rc;
+    if ((rc = dev_alloc(e, &e->obs_m2d, (size_t)o * N * 2, false)) != AOG_OK) return rc;
+    if ((rc = dev_alloc(e, &e->obs_E, (size_t)N * N * 2)) != AOG_OK) return rc;
+    if ((rc = dev_alloc(e, &e->obs_T, (size_t)o * N * 2)) != AOG_OK) return rc;
+    if ((rc = dev_alloc(e, &e->obs_F, (size_t)e->B * e->n_obs * 2)) != AOG_OK) return rc;
+    HIP_TRY(hipMemcpy(e->obs_m1d, t->m1, sizeof(double) * o * N * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->obs_m2d, t->m2, sizeof(double) * o * N * 2, hipMemcpyHostToDevice));
+    e->obs_ready = true;
+    return AOG_OK;
+  }
+  const int Nxp = obs_nxp(e), Nyp = obs_nyp(e);
+  std::vector<_Float16> m1s, m2s;
+  e->obs_unscale = mft_operand_tables(t->m1, t->m2, N, o, 32, Nxp, Nyp, m1s, m2s);
+  if ((rc = dev_alloc(e, &e->obs_m1s, m1s.size(), false)) != AOG_OK) return rc;
+  if ((rc = dev_alloc(e, &e->obs_m2s, m2s.size(), false)) != AOG_OK) return rc;
+  HIP_TRY(hipMemcpy(e->obs_m1s, m1s.data(), sizeof(_Float16) * m1s.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->obs_m2s, m2s.data(), sizeof(_Float16) * m2s.size(), hipMemcpyHostToDevice));
+  if (!e->focal_ap_yx) {   // (shared with K4: where each packed aperture pixel lies on the pupil grid)
+    std::vector<int32_t> apidx((size_t)e->n_ap), yx((size_t)e->n_ap);
+    HIP_TRY(hipMemcpy(apidx.data(), e->ap_index, sizeof(int32_t) * e->n_ap, hipMemcpyDeviceToHost));
+    for (int i = 0; i < e->n_ap; ++i) yx[i] = ((apidx[i] / N) << 16) | (apidx[i] % N);
+    if ((rc = dev_alloc(e, &e->focal_ap_yx, yx.size(), false)) != AOG_OK) return rc;
+    HIP_TRY(hipMemcpy(e->focal_ap_yx, yx.data(), sizeof(int32_t) * yx.size(), hipMemcpyHostToDevice));
+  }
+  // work buffers for whole env tiles, at most ~512 MB: the phase grid (every pixel starts out as "outside the aperture": only aperture pixels
+  // are ever written) and T'
+  const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * 2 * 4 * 64 * 8;
+  const size_t cap = std::max<size_t>(32, (((size_t)512 << 20) / (grid_env * 4 + t16_env * 2)) / 32 * 32);
+  e->obs_chunk = (int)std::min<size_t>((size_t)e->n_etiles * 32, cap);
+  if ((rc = dev_alloc(e, &e->obs_grid, (size_t)e->obs_chunk * grid_env, false)) != AOG_OK) return rc;
+  if ((rc = dev_alloc(e, &e->obs_T16, (size_t)e->obs_chunk * t16_env, false)) != AOG_OK) return rc;
+  if ((rc = dev_alloc(e, &e->obs_act16, (size_t)e->n_etiles * 32 * e->A_pad * 2, true)) != AOG_OK) return rc;
+  if ((rc = dev_alloc(e, &e->obs_act_ll, (size_t)e->n_etiles * 32 * e->A_pad, true)) != AOG_OK) return rc;
+  const size_t n_fill = (size_t)e->obs_chunk * grid_env;
+  hipLaunchKernelGGL(aog::k_obs_fill, dim3((unsigned)std::min<size_t>((n_fill + 255) / 256, 4096)), dim3(256), 0, nullptr, e->obs_grid, n_fill,
+                     aog::kShOutside);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  e->obs_ready = true;
+  return AOG_OK;
+}
 
 int aog_focal_image(aog_env* e, int env_index, float* field_dev, void* stream) {
   if (!e || !field_dev) return fail(AOG_ERR_INVALID, "aog_focal_image: null argument");
@@ -65,7 +209,7 @@ int aog_focal_images(aog_env* e, int first, int count, float* field_dev, void* s
   for (int env0 = first / 32 * 32; env0 < first + count; env0 += e->focal_chunk) {
     const int env1 = std::min(first + count, env0 + e->focal_chunk);          // envs [lo, env1) of this chunk are asked for
     const int lo = std::max(first, env0), n_et = (env1 - env0 + 31) / 32;
-    aog_host::launch_phase_grid(e, s, e->act16, e->focal_grid, grid_env, Nxp, env0 / 32, n_et);
+    aog_host::launch_phase_grid(e, s, e->act16, e->focal_act_ll, e->focal_grid, grid_env, Nxp, env0 / 32, n_et);
     const size_t skip = (size_t)(lo - env0);
     hipLaunchKernelGGL(aog::k_focal_pass1, dim3(Nxp / 128, nfp / 128, env1 - lo), dim3(256), 0, s, e->focal_grid + skip * grid_env,
                        reinterpret_cast<const aog::f16x8*>(e->focal_m1s), reinterpret_cast<aog::f16x8*>(e->focal_T16), Nxp, Nyp, nfp);

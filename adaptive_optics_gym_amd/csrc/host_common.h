@@ -78,11 +78,20 @@ int clear_poison_if_whole(aog_env* e, int first, int count, hipStream_t s);
 int set_screens_f32(aog_env* e, const float* psi, int first, int count, hipStream_t s, bool means_ready = false);   // means_ready: pack_mean[0 .. count) holds the aperture means already   // device screens [count][N][N] -> internal layouts
 // act_dm -> the operand layouts of the fused kernels (act_ll: optional third f16 term of the actuators, K4)
 int load_actuators(aog_env* e, hipStream_t s, _Float16* act_ll = nullptr);
+// act_dm -> the split-f16 operand layout (and third term) in buffers of the caller's choosing; act_rev / act16 are not touched
+int load_actuators_into(aog_env* e, hipStream_t s, _Float16* act16, _Float16* act_ll);
+// focal.hip (K11): the observation of the separable route for every env — |F|^2 into obs_pw and the caller's obs_raw / obs (nullable)
+int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs);
+// split-f16 operand tables of a Fraunhofer matrix Fourier transform m1 [nf][N] . E . m2 [N][nf] (K4's layouts: m1s [nfp / 32][Nyp / 16] tiles,
+// m2s [nfp / 32][Nxp / 32][2] tiles), each matrix scaled by a power of two; returns the unscale factor 2^-(e1 + e2)
+float mft_operand_tables(const double* m1, const double* m2, int N, int nf, int nfp, int Nxp, int Nyp, std::vector<_Float16>& m1s,
+                         std::vector<_Float16>& m2s);
 // atmosphere.hip
 int pack_from_master(aog_env* e, int first, int count, hipStream_t s, bool per_step = false);
 int evolve_layer(aog_env* e, hipStream_t s, long long step_index);
 int x8_drop_ahead(aog_env* e);   // before anything the int8 extrusion's work ahead (plan, x phase of the next step) read is changed
 int ensure_tiles(aog_env* e, hipStream_t s);
+int obs_tiles(aog_env* e, hipStream_t s);   // psi_tile holding the screens this step's fused kernel read (the separable observation route)
 int ring_from_master(aog_env* e, int first, int count, int keep_ref, hipStream_t s);
 int store_master_f64(aog_env* e, const double* psi, int first, int count, hipStream_t s);
 int store_master_f32(aog_env* e, const float* psi, int first, int count, hipStream_t s);

@@ -15,6 +15,7 @@ struct ActorArgs {
   const float *w1, *b1, *w2, *b2, *w3, *b3, *wo, *bo;
   float *mean, *action, *log_prob;
   int B, S, H, A, obs_f16, kpad;
+  int kpad_b, wfloats;   // rows of the hidden-only activation buffer xb; LDS floats of a weight chunk (<= kActorWFloats)
   float p_drop, keep_scale, std, logp_const;
   unsigned long long seed;
   uint32_t call_lo, call_hi;
@@ -37,10 +38,10 @@ __device__ __forceinline__ void actor_philox(uint32_t (&c)[4], unsigned long lon
 constexpr int kActorWFloats = 24576;   // LDS floats for a weight chunk (96 KB)
 constexpr int kActorThreads = 640;     // 10 waves: one 16-unit tile each for the reference's 150 hidden units
 constexpr int kActorPre = 10;          // float4 registers per thread holding a chunk in flight (640 x 10 x 4 >= kActorWFloats)
-__device__ __forceinline__ int actor_rows_max(int K) { return max(16, ((kActorWFloats / K) >> 4) << 4); }
+__device__ __forceinline__ int actor_rows_max(int K, int wfloats) { return max(16, ((wfloats / K) >> 4) << 4); }
 // request rows [r0, r0 + rows_max) of W ([M][K], 16-byte aligned base; r0 is a multiple of 16)
-__device__ __forceinline__ void actor_issue(f32x4 (&pre)[kActorPre], const float* __restrict__ W, int K, int M, int r0) {
-  const int rc = min(actor_rows_max(K), M - r0);
+__device__ __forceinline__ void actor_issue(f32x4 (&pre)[kActorPre], const float* __restrict__ W, int K, int M, int r0, int wfloats) {
+  const int rc = min(actor_rows_max(K, wfloats), M - r0);
   const int n4 = (rc * K) >> 2;
   const f32x4* src = reinterpret_cast<const f32x4*>(W + (size_t)r0 * K);
 #pragma unroll
@@ -49,11 +50,11 @@ __device__ __forceinline__ void actor_issue(f32x4 (&pre)[kActorPre], const float
 template <int LAYER>
 __device__ __forceinline__ void actor_layer(const ActorArgs& p, const float* __restrict__ W, const float* __restrict__ bias, int K, int M,
                                             const float* xin, float* xout, float* lp_sum, float* wl, int env0, f32x4 (&pre)[kActorPre],
-                                            const float* __restrict__ Wnext, int Knext, int Mnext) {
+                                            const float* __restrict__ Wnext, int Knext, int Mnext, int kin, int kout) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int el = lane & 15, kq = lane >> 4;
   const int n_steps = (K + 3) >> 2;
-  const int rows_max = actor_rows_max(K);
+  const int rows_max = actor_rows_max(K, p.wfloats);
   for (int r0 = 0; r0 < M; r0 += rows_max) {
     const int rc = min(rows_max, M - r0);
     const int n_fl = rc * K;
@@ -67,8 +68,8 @@ __device__ __forceinline__ void actor_layer(const ActorArgs& p, const float* __r
       for (int i = (n4 << 2) + threadIdx.x; i < n_fl; i += kActorThreads) wl[i] = src[i];
     }
     __syncthreads();
-    if (r0 + rows_max < M) actor_issue(pre, W, K, M, r0 + rows_max);
-    else if (Wnext != nullptr) actor_issue(pre, Wnext, Knext, Mnext, 0);
+    if (r0 + rows_max < M) actor_issue(pre, W, K, M, r0 + rows_max, p.wfloats);
+    else if (Wnext != nullptr) actor_issue(pre, Wnext, Knext, Mnext, 0, p.wfloats);
     __builtin_amdgcn_sched_barrier(0);   // (keep the requests ahead of the matrix work)
     const int n_tiles = (rc + 15) >> 4;
     for (int tile = wave; tile < n_tiles; tile += kActorThreads / 64) {
@@ -110,7 +111,7 @@ __device__ __forceinline__ void actor_layer(const ActorArgs& p, const float* __r
         for (int u = 0; u < 8; ++u) {
           const int k = 4 * (s0 + u) + kq;
           av[u] = wrow[min(k, K - 1)] * (k < K ? row_ok : 0.f);
-          xv[u] = xin[min(k, p.kpad - 1) * 16 + el];   // rows K .. kpad-1 of xin are zero; steps past the end multiply by a = 0
+          xv[u] = xin[min(k, kin - 1) * 16 + el];   // rows K .. kin-1 of xin are zero; steps past the end multiply by a = 0
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], xv[u], acc, 0, 0, 0);
@@ -125,7 +126,7 @@ __device__ __forceinline__ void actor_layer(const ActorArgs& p, const float* __r
             const float u = (float)(c[r] >> 8) * (1.0f / 16777216.0f);   // [0, 1): keep with probability 1 - p
             v = u >= p.p_drop ? v * p.keep_scale : 0.f;
           }
-          if (m < p.kpad) xout[m * 16 + el] = v;   // units M .. are written as zero: the next layer's K padding
+          if (m < kout) xout[m * 16 + el] = v;   // units M .. are written as zero: the next layer's K padding
         }
       } else {
         float ssq = 0.f;
@@ -153,15 +154,15 @@ __device__ __forceinline__ void actor_layer(const ActorArgs& p, const float* __r
 }
 
 __global__ __launch_bounds__(kActorThreads) void k_actor_act(ActorArgs p) {
-  extern __shared__ float lds_act[];   // xa [kpad][16] | xb [kpad][16] | lp [16] | weight chunk [kActorWFloats]
-  float* xa = lds_act;
+  extern __shared__ float lds_act[];   // xa [kpad][16] | xb [kpad_b][16] | lp [16] | weight chunk [wfloats]
+  float* xa = lds_act;                 // (xa: the observations, then layer 2's output; xb: the outputs of layers 1 and 3)
   float* xb = xa + (size_t)p.kpad * 16;
-  float* lp = xb + (size_t)p.kpad * 16;
+  float* lp = xb + (size_t)p.kpad_b * 16;
   float* wt = lp + 16;
   const int env0 = blockIdx.x * 16;
   f32x4 pre[kActorPre];
-  actor_issue(pre, p.w1, p.S, p.H, 0);   // the first weight chunk travels while the observations are staged
-  for (int i = threadIdx.x; i < 2 * p.kpad * 16 + 16; i += kActorThreads) lds_act[i] = 0.f;
+  actor_issue(pre, p.w1, p.S, p.H, 0, p.wfloats);   // the first weight chunk travels while the observations are staged
+  for (int i = threadIdx.x; i < (p.kpad + p.kpad_b) * 16 + 16; i += kActorThreads) lds_act[i] = 0.f;
   __syncthreads();
   for (int i = threadIdx.x; i < p.S * 16; i += kActorThreads) {
     const int k = i >> 4, e = i & 15, env = min(env0 + e, p.B - 1);
@@ -169,13 +170,13 @@ __global__ __launch_bounds__(kActorThreads) void k_actor_act(ActorArgs p) {
                       : reinterpret_cast<const float*>(p.obs)[(size_t)env * p.S + k];
   }
   __syncthreads();
-  actor_layer<1>(p, p.w1, p.b1, p.S, p.H, xa, xb, lp, wt, env0, pre, p.w2, p.H, p.H);
+  actor_layer<1>(p, p.w1, p.b1, p.S, p.H, xa, xb, lp, wt, env0, pre, p.w2, p.H, p.H, p.kpad, p.kpad_b);
   __syncthreads();
-  actor_layer<2>(p, p.w2, p.b2, p.H, p.H, xb, xa, lp, wt, env0, pre, p.w3, p.H, p.H);
+  actor_layer<2>(p, p.w2, p.b2, p.H, p.H, xb, xa, lp, wt, env0, pre, p.w3, p.H, p.H, p.kpad_b, p.kpad);
   __syncthreads();
-  actor_layer<3>(p, p.w3, p.b3, p.H, p.H, xa, xb, lp, wt, env0, pre, p.wo, p.H, p.A);
+  actor_layer<3>(p, p.w3, p.b3, p.H, p.H, xa, xb, lp, wt, env0, pre, p.wo, p.H, p.A, p.kpad, p.kpad_b);
   __syncthreads();
-  actor_layer<4>(p, p.wo, p.bo, p.H, p.A, xb, nullptr, lp, wt, env0, pre, nullptr, 0, 0);
+  actor_layer<4>(p, p.wo, p.bo, p.H, p.A, xb, nullptr, lp, wt, env0, pre, nullptr, 0, 0, p.kpad_b, 0);
   __syncthreads();
   if (threadIdx.x < 16 && env0 + threadIdx.x < p.B && p.log_prob) p.log_prob[env0 + threadIdx.x] = -0.5f * lp[threadIdx.x] - p.logp_const;
 }

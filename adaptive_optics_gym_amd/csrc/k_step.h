@@ -102,7 +102,7 @@ __global__ void k_load_actuators(const double* __restrict__ act_dm, float* __res
   const int env = idx / A_pad, i = idx % A_pad;
   const double a64 = (i < A) ? act_dm[(size_t)env * A + i] * two_over_lambda : 0.0;
   const float ar = (float)a64;
-  act_rev[(size_t)i * Bp + env] = ar;
+  if (act_rev) act_rev[(size_t)i * Bp + env] = ar;
   store_act16(act16, env, i, A_pad, ar);
   if (act16_ll && !(A_pad & 15)) {
     const float sc = ar * 256.0f;   // (as store_act16)
@@ -182,6 +182,9 @@ struct EpilogueArgs {
   float* strehl;
   int32_t* t_render;
   float* ret_acc;   // nullable: episode-return accumulator [B] (aog_set_return_accumulator)
+  const double* obs_pw;   // separable observation route: [B][n_obs_sep] powers of k_obs_pass2 / k_obs_finish64 (the table outputs are then the
+                          // fiber modes only: n_obs = 0); nullptr on the table route
+  int n_obs_sep;
   int B, Bp, n_chunks, MRW, MRS, MRW_used, MRS_used, n_obs, n_fiber, reward_type, has_thr, max_steps, is_step;
   double thr, ssim_peak, ssim_alpha;
 };
@@ -303,7 +306,8 @@ __device__ __forceinline__ void epilogue_body(const EpilogueArgs& p, int block, 
   if (p.reward_type == 0) {
     reward = -(100.0 - strehl * 100.0);
   } else {
-    const double ssim = ssim_1d_delta_ref(pw + e, kEpiEnvs, p.n_obs, p.ssim_peak, p.n_obs / 2);
+    const double ssim = p.obs_pw ? ssim_1d_delta_ref(p.obs_pw + (size_t)env * p.n_obs_sep, 1, p.n_obs_sep, p.ssim_peak, p.n_obs_sep / 2)
+                                 : ssim_1d_delta_ref(pw + e, kEpiEnvs, p.n_obs, p.ssim_peak, p.n_obs / 2);
     reward = p.ssim_alpha * power + (1.0 - p.ssim_alpha) * ssim;
   }
   if (p.has_thr && reward < p.thr) reward = -1.0;

@@ -188,7 +188,7 @@ class HostTables:
     mode_specs: list                # (n, m) per mode — the "actuator indexing" table
     gram: np.ndarray                # [A, A]
     wfs_tables: np.ndarray          # [MRW, n_ap]
-    wfs_coef: np.ndarray            # [o^2 + n_fiber, MRW] complex
+    wfs_coef: np.ndarray            # [o^2 + n_fiber, MRW] complex (separable route: [n_fiber, MRW])
     sci_tables: np.ndarray          # [MRS, n_ap]
     sci_coef: np.ndarray            # [1, MRS] complex
     n_fiber_modes: int
@@ -198,6 +198,9 @@ class HostTables:
     lp_modes: np.ndarray = None      # [n_fiber, n_focal, n_focal]
     focal_pixel_area: float = 0.0
     strehl_focal_index: int = 0
+    obs_route: str = "tables"        # "tables": the o^2 observation kernels lead wfs_tables / wfs_coef; "separable": fiber rows only
+    obs_m1: np.ndarray = None        # separable route: [o, N] complex (obs_scale folded in), rows = y frequency
+    obs_m2: np.ndarray = None        # separable route: [N, o] complex, columns = x frequency
 
 
 def _realify(kernels: np.ndarray, tol: float = 1e-12):
@@ -231,7 +234,22 @@ def _realify(kernels: np.ndarray, tol: float = 1e-12):
     return tables / peak[:, None], coef * peak[None, :]
 
 
-def build_tables(params: OpticalParams, act_type: str, act_dim: int, obs_dim: int) -> HostTables:
+OBS_ROUTES = ("tables", "separable")
+
+
+def obs_route_for(precision: str, obs_dim: int) -> str:
+    """The observation route a handle of this precision and o takes: the table route where it is built (fast o <= 5: the fused kernels
+    take <= 28 tables; float64 o <= 7: at o = 8 the epilogue's coefficient matrix of 67 tables outgrows the LDS), the separable matrix
+    Fourier transform above."""
+    return "tables" if obs_dim <= (7 if precision == "fp64" else 5) else "separable"
+
+
+def build_tables(params: OpticalParams, act_type: str, act_dim: int, obs_dim: int, obs_route: str = "tables") -> HostTables:
+    """obs_route="tables": the observation pixels are o^2 pupil-plane kernels realified into wfs_tables ahead of the fiber modes.
+    obs_route="separable": wfs_tables / wfs_coef hold the fiber modes only; the observation is |obs_m1 (A o E) obs_m2|^2 on the pupil grid
+    (the Fraunhofer matrix Fourier transform onto the o x o grid, AO_env.py:385,391), which costs O(o N^2) and builds nothing of o^2 x n_ap."""
+    if obs_route not in OBS_ROUTES:
+        raise ValueError(f"obs_route must be one of {OBS_ROUTES}")
     N = params.num_pupil_pixels
     D = params.telescope_diameter
     ax = centred_axis(N, D)
@@ -254,10 +272,17 @@ def build_tables(params: OpticalParams, act_type: str, act_dim: int, obs_dim: in
     Xo = centred_axis(o, params.fiber_window)
     dXo = params.fiber_window / o
     obs_scale = amp * pix_area * dXo / (lam * f)
-    obs_k = np.empty((o * o, n_ap), dtype=complex)
-    for b in range(o):
-        for a in range(o):
-            obs_k[b * o + a] = obs_scale * np.exp(-1j * kappa * (Xo[a] * x_ap + Xo[b] * y_ap))
+    obs_m1 = obs_m2 = None
+    if obs_route == "tables":
+        obs_k = np.empty((o * o, n_ap), dtype=complex)
+        for b in range(o):
+            for a in range(o):
+                obs_k[b * o + a] = obs_scale * np.exp(-1j * kappa * (Xo[a] * x_ap + Xo[b] * y_ap))
+    else:
+        # obs[b][a] = |sum_{y,x} M1[b][y] (A o E)[y][x] M2[x][a]|^2 with the same axes as obs_k: flat index iy*N + ix
+        obs_k = np.empty((0, n_ap), dtype=complex)
+        obs_m1 = obs_scale * np.exp(-1j * kappa * np.outer(Xo, ax))     # [o, N(y)]
+        obs_m2 = np.exp(-1j * kappa * np.outer(ax, Xo))                 # [N(x), o]
     # fiber: LP modes on make_pupil_grid(128, 52.5 um), folded back to the pupil ("receive modes"):
     #   c_k = sum_X m_k(X) E_f(X) dA_f,  E_f(X) = 1/(i lam f) sum_x E(x) dA exp(-i kappa X.x)
     nf = params.num_focal_pixels_fiber
@@ -289,4 +314,5 @@ def build_tables(params: OpticalParams, act_type: str, act_dim: int, obs_dim: in
                       wfs_coef=wfs_coef, sci_tables=sci_tables, sci_coef=sci_coef, n_fiber_modes=int(lps.shape[0]),
                       lp_u=[lp_roots(0, V), lp_roots(1, V)], strehl_focal_index=kstar,
                       focal_m1=amp * pix_area / (1j * lam * f) * np.exp(-1j * kappa * np.outer(Xf, ax)),
-                      focal_m2=np.exp(-1j * kappa * np.outer(ax, Xf)), lp_modes=lps, focal_pixel_area=dAf)
+                      focal_m2=np.exp(-1j * kappa * np.outer(ax, Xf)), lp_modes=lps, focal_pixel_area=dAf, obs_route=obs_route,
+                      obs_m1=obs_m1, obs_m2=obs_m2)

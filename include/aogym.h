@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AOG_ABI_VERSION 19
+#define AOG_ABI_VERSION 20
 
 typedef struct aog_env aog_env;
 
@@ -65,7 +65,10 @@ typedef struct {
                                    envs [env_id_base, env_id_base + num_envs)).  Every device random stream — screen synthesis,
                                    extrusion normals, Shack-Hartmann photon noise — is keyed by the GLOBAL env id, so results do
                                    not depend on how the batch is split over handles / GPUs              */
-  int32_t reserved0;            /* = 0                                                                                          */
+  int32_t obs_separable;        /* observation route (ABI 20).  0: the o^2 observation pixels are pupil-plane kernels in wfs_tables /
+                                   wfs_coef (fast handles o <= 5, float64 handles o <= 8).  1: wfs_tables / wfs_coef describe the fiber
+                                   modes only and the observation is the separable matrix Fourier transform obs = |M1 (A o E) M2|^2
+                                   uploaded by aog_upload_obs_mft (any o <= 32; the policy kernel's state_dim <= 1024 sets the limit)    */
   double wavelength_wfs;        /* 1.5e-6 (AO_env.py:219)                                        */
   double wavelength_sci;        /* 2.2e-6 (AO_env.py:220)                                        */
   double surface_rms_target;    /* 0.1*wavelength_sci (AO_env.py:120)                            */
@@ -82,6 +85,8 @@ typedef struct {
  *   Z_j = sum_m coef[j][m] * (U_m + i V_m)
  *   obs_raw[j] = |Z_j|^2  (j < o^2);  power = sum_k |Z_{o^2+k}|^2  (k < n_fiber_modes);
  *   strehl = |Z_sci|^2.
+ * On the separable observation route (cfg.obs_separable = 1) the rows of wfs_coef are the fiber modes only (power = sum_k |Z_k|^2) and the
+ * observation comes from aog_upload_obs_mft's matrices.
  */
 typedef struct {
   const int32_t* ap_index;   /* [n_ap]  flat pupil index iy*N+ix of packed pixel p (row-major order) */
@@ -102,7 +107,8 @@ typedef struct {
 
 typedef struct {
   int32_t abi_version, num_envs, num_envs_padded, n_ap, n_ap_padded, n_modes_padded;
-  int32_t pixel_chunks, kernel, n_sums, reserved;
+  int32_t pixel_chunks, kernel, n_sums;
+  int32_t reserved;          /* flags: bit 0 = the dynamic atmosphere is read ring-direct, bit 1 = separable observation route */
   int64_t device_bytes;      /* bytes of HBM the handle owns */
 } aog_info;
 
@@ -113,8 +119,8 @@ int aog_abi_version(void);
 const char* aog_build_id(void);
 const char* aog_last_error(void);
 /* sizeof() of the structs of this header as the library was compiled, so that a binding in another language can verify its own
- * declarations at load time: which = 0 aog_config, 1 aog_tables, 2 aog_layer_tables, 3 aog_sh_tables, 4 aog_actor, 5 aog_info, 6 aog_layer_composite;
- * -1 for any other value. */
+ * declarations at load time: which = 0 aog_config, 1 aog_tables, 2 aog_layer_tables, 3 aog_sh_tables, 4 aog_actor, 5 aog_info, 6 aog_layer_composite,
+ * 7 aog_obs_mft; -1 for any other value. */
 int64_t aog_struct_size(int which);
 
 /* AOEnv.__init__ (AO_env.py:17-71): allocate the handle and its state on `device`. */
@@ -125,6 +131,19 @@ int aog_get_info(const aog_env* env, aog_info* out);
 /* The part of AOEnv.__init__ that goes through hcipy (pupil_simulation, incoming_wavefront,
  * DM_function, fiber_coupling; AO_env.py:50-64). */
 int aog_upload_tables(aog_env* env, const aog_tables* tables);
+
+/* Separable observation route (cfg.obs_separable = 1; ABI 20): the two matrices of the Fraunhofer matrix Fourier transform onto the o x o
+ * observation grid (propagator_fiber_subsample, AO_env.py:385,391), the observation scale folded into m1:
+ *   obs_raw[v * o + u] = |sum_{y,x} m1[v][y] A[y][x] E[y][x] m2[x][u]|^2,   E = exp(i phi) on the pupil grid, A = aperture.
+ * HOST pointers, float64, interleaved (re, im); converted once into the operand tables of the kernels.  aog_reset / aog_step on a separable
+ * handle before this call return AOG_ERR_STATE. */
+typedef struct {
+  int32_t o;                 /* = cfg.obs_dim                                                        */
+  int32_t reserved0;         /* = 0                                                                  */
+  const double* m1;          /* [o][N][2]                                                            */
+  const double* m2;          /* [N][o][2]                                                            */
+} aog_obs_mft;
+int aog_upload_obs_mft(aog_env* env, const aog_obs_mft* mft);
 
 /* layer._achromatic_screen for envs [first, first+count) (hcipy InfiniteAtmosphericLayer state created at
  * AO_env.py:370 / regenerated at AO_env.py:77).  psi_dev: [count][N][N] achromatic screens (phase * lambda,
