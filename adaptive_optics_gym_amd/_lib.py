@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libaogym.so")
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 AOG_REWARD = {"strehl_ratio": 0, "smf_ssim": 1}
 AOG_PRECISION = {"fast": 0, "fp64": 1}
@@ -101,6 +101,8 @@ SYMBOLS = {
     "aog_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "aog_get_phase_screen": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "aog_actor_act": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_reset_act": (C.c_int, [C.c_void_p, C.POINTER(AogActor)] + [C.c_void_p] * 6),
+    "aog_step_act": (C.c_int, [C.c_void_p, C.POINTER(AogActor)] + [C.c_void_p] * 10 + [C.POINTER(C.c_int), C.c_void_p]),
     "aog_device_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "aog_set_return_accumulator": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_get_actuators": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -504,12 +504,9 @@ class BatchedAOEnv:
         {"power": [B] float32, "obs_raw": [B, o^2] float32, "strehl": [B] float32}).
         ``out`` (optional): (obs float16 [B, o^2], reward float32 [B], done bool/uint8 [B]) contiguous device tensors to write
         into — a rollout hands in slices of its transition buffers, so nothing is copied afterwards."""
-        torch = self._torch
         a = self._as_actions(actions)
         if self.atm_type == "dynamic" and self._host_rng:
             self._host_extrusion_noise()
-        n = self.obs_dim ** 2
-        B = self.num_envs
         if self._persistent_out and out is None and self._step_cache is not None:
             # persistent outputs: the views of the block and their addresses are made once (a step's host cost drops from ~22 to ~10 us, which
             # matters right after a synchronisation, when the first launches of a burst cost the host twice their steady-state time)
@@ -518,6 +515,19 @@ class BatchedAOEnv:
             self.timestep += 1
             self.last_obs_raw = ret[4]["obs_raw"]
             return ret
+        ret, ptrs, obs_raw = self._step_outputs(out)
+        self._launch_step(a, next_actions, ptrs)
+        self.timestep += 1
+        self.last_obs_raw = obs_raw
+        if self._persistent_out and out is None:
+            self._step_cache = (ret, ptrs)
+        return ret
+
+    def _step_outputs(self, out):
+        """The tensors a step writes and returns: (step tuple, their addresses in aog_step's order, obs_raw)."""
+        torch = self._torch
+        n = self.obs_dim ** 2
+        B = self.num_envs
         # ONE allocation per step: fp32 block (obs_raw | reward | power | strehl), fp16 obs, uint8 done — or none at all when the
         # caller asked for a persistent block (``persistent_outputs``: the single-env wrapper copies it to the host in one transfer)
         nb32, nb16 = 4 * B * (n + 3), 2 * B * n
@@ -544,15 +554,82 @@ class BatchedAOEnv:
                 raise ValueError("step(out=...): expected contiguous (float16 [B, o^2], float32 [B], bool/uint8 [B]) device tensors")
         base = f32.data_ptr()
         ptrs = (base, obs.data_ptr(), reward.data_ptr(), done.data_ptr(), base + 4 * B * (n + 1), base + 4 * B * (n + 2))
-        self._launch_step(a, next_actions, ptrs)
-        self.timestep += 1
-        self.last_obs_raw = obs_raw
         if self._trunc is None:
             self._trunc = torch.zeros((B,), dtype=torch.bool, device=self.device)
         ret = (obs, reward, done if done.dtype == torch.bool else done.view(torch.bool), self._trunc, {"power": power, "obs_raw": obs_raw, "strehl": strehl})
-        if self._persistent_out and out is None:
-            self._step_cache = (ret, ptrs)
-        return ret
+        return ret, ptrs, obs_raw
+
+    # ------------------------------------------------------------------------------------------------
+    # causal policy stepping: the rollout's actor.get_action(obs) -> env.step(action) (algorithm.py:256-262) with the policy attached
+    def _policy_net(self, policy, cov_var, policy_out):
+        """(aog_actor of the policy's next query, (action, log_prob, mean) output tensors) for the fused tail (aog_reset_act / aog_step_act)."""
+        torch = self._torch
+        if int(policy.env_id_base) != self.global_env_offset:
+            raise ValueError(f"policy.env_id_base ({policy.env_id_base}) != env.global_env_offset ({self.global_env_offset}): the policy's random "
+                             "streams are keyed by the global env id of row 0")
+        layers = policy.layers()
+        S, A = layers[0].weight.shape[1], layers[3].weight.shape[0]
+        if S != self.obs_dim ** 2 or A != self.num_modes:
+            raise ValueError(f"the actor maps {S} -> {A}; this env observes obs_dim^2 = {self.obs_dim ** 2} and takes num_modes = {self.num_modes}")
+        B = self.num_envs
+        if policy_out is None:
+            action = torch.empty((B, A), dtype=torch.float32, device=self.device)
+            log_prob = torch.empty((B,), dtype=torch.float32, device=self.device)
+            mean = torch.empty((B, A), dtype=torch.float32, device=self.device)
+        else:
+            action, log_prob, mean = policy_out
+        for t, shape, required in ((action, (B, A), True), (log_prob, (B,), True), (mean, (B, A), False)):
+            if (t is None and required) or (t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()
+                                                               or t.device != self.device)):
+                raise ValueError("policy_out: expected contiguous float32 (action [B, A], log_prob [B], mean [B, A] or None) tensors on the env's device")
+        return policy.net(B, cov_var, layers), (action, log_prob, mean)
+
+    def reset_with_policy(self, policy, cov_var=0.5, policy_out=None, mask=None):
+        """``reset()`` of the whole batch with ``policy`` (a ``rollout.DeviceActor``) attached (``aog_reset_act``): the reset's last launch
+        also queries the policy on the reset observation and loads the resulting action into the mirror, so the next ``step_with_policy``
+        steps it (pass no ``action`` there).  Returns ``((obs, info), (action, log_prob, mean))``; the query consumes one of the policy's call
+        indices, exactly like ``policy(obs)``.  ``policy_out``: (action [B, A], log_prob [B], mean [B, A] or None) float32 tensors to write
+        into.  Masked resets are not fused (the query covers the whole batch): use ``reset(mask)`` and pass the first action."""
+        if mask is not None:
+            raise ValueError("reset_with_policy resets the whole batch; reset some envs with reset(mask) and step with an explicit action")
+        torch = self._torch
+        net, (action, log_prob, mean) = self._policy_net(policy, cov_var, policy_out)
+        if self.atm_type == "semi_dynamic":
+            self._generate_screens(mask=None)  # layer.reset() (AO_env.py:76-77)
+        n = self.obs_dim ** 2
+        obs = torch.empty((self.num_envs, n), dtype=torch.float16, device=self.device)
+        obs_raw = torch.empty((self.num_envs, n), dtype=torch.float32, device=self.device)
+        p = C.c_void_p
+        _lib.check(self.lib.aog_reset_act(self._handle, C.byref(net), p(obs_raw.data_ptr()), p(obs.data_ptr()), p(action.data_ptr()),
+                                          p(log_prob.data_ptr()), p(mean.data_ptr() if mean is not None else None), self._stream()))
+        policy.calls += 1
+        self.last_obs_raw = obs_raw
+        return (obs, {}), (action, log_prob, mean)
+
+    def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None):
+        """``step()`` with ``policy`` (a ``rollout.DeviceActor``) attached (``aog_step_act``): steps the action left pending by
+        ``reset_with_policy`` or the previous call (``action=None``), or ``action`` (first step after a plain ``reset``; an error while one
+        is pending).  Unless this is the episode's last step, the step's last launch also queries the policy on the new observation and
+        loads that action into the mirror for the next call: one launch where ``step`` + ``policy(obs)`` + the next ``step``'s prologue take
+        three.  Bit-identical to that unfused loop.  Returns ``(step tuple, (action, log_prob, mean))``, or ``(step tuple, None)`` on the
+        episode's last step (no query, no call index consumed, ``policy_out`` untouched).  ``out`` as in ``step``; ``policy_out`` as in
+        ``reset_with_policy``."""
+        a = self._as_actions(action) if action is not None else None
+        net, pol = self._policy_net(policy, cov_var, policy_out)
+        if self.atm_type == "dynamic" and self._host_rng:
+            self._host_extrusion_noise()
+        ret, ptrs, obs_raw = self._step_outputs(out)
+        p = C.c_void_p
+        queried = C.c_int(0)
+        _lib.check(self.lib.aog_step_act(self._handle, C.byref(net), p(a.data_ptr() if a is not None else None), p(ptrs[0]), p(ptrs[1]), p(ptrs[2]),
+                                         p(ptrs[3]), p(ptrs[4]), p(ptrs[5]), p(pol[0].data_ptr()), p(pol[1].data_ptr()),
+                                         p(pol[2].data_ptr() if pol[2] is not None else None), C.byref(queried), self._stream()))
+        self.timestep += 1
+        self.last_obs_raw = obs_raw
+        if not queried.value:
+            return ret, None
+        policy.calls += 1
+        return ret, pol
 
     def _as_actions(self, actions):
         """[B, A] float32 contiguous device tensor (as is when it already is one)."""

@@ -3,6 +3,7 @@
 #include "host_common.h"
 #include "k_pack.h"
 #include "k_step.h"
+#include "k_step_act.h"
 
 #include <hipfft/hipfft.h>
 
@@ -244,9 +245,39 @@ int launch_fused(aog_env* e, hipStream_t s) {
   return AOG_OK;
 }
 
+size_t epilogue_lds(const aog_env* e) {
+  const bool ref = e->cfg.precision == AOG_PRECISION_FP64;
+  const int NS = 2 * (ref ? e->MRW_used + e->MRS_used : e->MRW + e->MRS);
+  return aog::epilogue_lds_bytes(NS, e->n_obs_tab, e->cfg.n_fiber_modes, e->MRW_used, e->MRS_used);
+}
+
+// the policy attached to aog_reset_act / aog_step_act: its arguments (actor_args, checked before the call changes anything) and outputs
+struct ActTail {
+  aog::ActorArgs a;
+  size_t lds = 0;   // the query's own dynamic LDS
+};
+
+// the prologue of the next step from `action` (k_epilogue_prologue, k_epilogue_act_prologue)
+aog::PrologueArgs prologue_args(const aog_env* e, const float* action) {
+  aog::PrologueArgs q{};
+  const bool mfma_fast = e->kernel == AOG_KERNEL_MFMA && e->cfg.precision == AOG_PRECISION_FAST && !e->sh_ready;
+  q.action = action;
+  q.gram = e->gram;
+  q.act_dm = e->act_dm;
+  q.act_rev = mfma_fast ? nullptr : e->act_rev;
+  q.act16 = e->act16;
+  q.B = e->B; q.A = e->A; q.A_pad = e->A_pad; q.Bp = e->Bp;
+  q.sh_operation = e->cfg.sh_operation;
+  q.target = e->cfg.surface_rms_target;
+  q.two_over_lambda = 2.0 / e->cfg.wavelength_wfs;
+  return q;
+}
+
 // action_next (aog_step_pipelined): the prologue of the NEXT step rides in the same launch (k_epilogue_prologue)
+// tail (aog_reset_act / aog_step_act): the policy query on this epilogue's observation and the prologue of the next step from its action ride in
+// the same launch, per workgroup of 16 envs (k_epilogue_act_prologue)
 int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
-                    float* strehl, hipStream_t s, const float* action_next = nullptr) {
+                    float* strehl, hipStream_t s, const float* action_next = nullptr, const ActTail* tail = nullptr) {
   aog::EpilogueArgs p{};
   p.partials = e->partials;
   p.wfs_coef = e->wfs_coef;
@@ -278,21 +309,19 @@ int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, flo
   p.thr = e->cfg.rew_threshold;
   p.ssim_peak = e->cfg.ssim_ref_peak;
   p.ssim_alpha = e->cfg.ssim_alpha;
-  const int NS = 2 * (p.MRW + p.MRS);
-  const size_t lds = aog::epilogue_lds_bytes(NS, p.n_obs, p.n_fiber, p.MRW_used, p.MRS_used);
+  const size_t lds = epilogue_lds(e);
   const int n_epi = (e->Bp + aog::kEpiEnvs - 1) / aog::kEpiEnvs;
-  if (action_next) {
-    aog::PrologueArgs q{};
-    const bool mfma_fast = e->kernel == AOG_KERNEL_MFMA && e->cfg.precision == AOG_PRECISION_FAST && !e->sh_ready;
-    q.action = action_next;
-    q.gram = e->gram;
-    q.act_dm = e->act_dm;
-    q.act_rev = mfma_fast ? nullptr : e->act_rev;
-    q.act16 = e->act16;
-    q.B = e->B; q.A = e->A; q.A_pad = e->A_pad; q.Bp = e->Bp;
-    q.sh_operation = e->cfg.sh_operation;
-    q.target = e->cfg.surface_rms_target;
-    q.two_over_lambda = 2.0 / e->cfg.wavelength_wfs;
+  if (tail) {
+    aog::ActorArgs a = tail->a;
+    aog::PrologueArgs q = prologue_args(e, a.action);
+    const int obs_from_lds = e->obs_sep ? 0 : 1;
+    a.obs = obs;
+    a.obs_f16 = 1;
+    const size_t lds_all = aog::step_act_lds_bytes(lds, tail->lds);   // (<= kLdsBytes: checked by step_act_tail)
+    if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue_act_prologue), lds_all, e->device)) return rc;
+    hipLaunchKernelGGL(aog::k_epilogue_act_prologue, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, a, q, obs_from_lds);
+  } else if (action_next) {
+    const aog::PrologueArgs q = prologue_args(e, action_next);
     if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue_prologue), lds, e->device)) return rc;
     hipLaunchKernelGGL(aog::k_epilogue_prologue, dim3(n_epi + (e->B + aog::kEpiProEnvs - 1) / aog::kEpiProEnvs), dim3(1024), lds, s, p, q, n_epi);
   } else {
@@ -977,7 +1006,31 @@ int aog_set_actuators(aog_env* e, const double* act_dev, void* stream) {
   return AOG_OK;
 }
 
-int aog_reset(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, void* stream) {
+}  // extern "C"
+
+namespace {
+// the checks of aog_reset_act / aog_step_act that concern the policy, made before the call changes anything; fills the tail's arguments
+int step_act_tail(const aog_env* e, const aog_actor* net, const char* who, uint16_t* obs, float* action_out, float* log_prob_out, float* mean_out,
+                  ActTail* t) {
+  if (!e || !net || !obs || !action_out || !log_prob_out) return fail(AOG_ERR_INVALID, "%s: null argument", who);
+  if (net->batch != e->B || net->state_dim != e->n_obs || net->act_dim != e->A)
+    return fail(AOG_ERR_INVALID, "%s: the actor (batch %d, state_dim %d, act_dim %d) does not fit the handle (batch %d, obs_dim^2 %d, n_modes %d)", who,
+                net->batch, net->state_dim, net->act_dim, e->B, e->n_obs, e->A);
+  if (int rc = actor_args(net, who, &t->a, &t->lds)) return rc;
+  t->a.action = action_out;
+  t->a.log_prob = log_prob_out;
+  t->a.mean = mean_out;
+  // the table route stages the observation from the epilogue's LDS, one element per thread
+  if (!e->obs_sep && e->n_obs * aog::kEpiEnvs > aog::kStepActThreads)
+    return fail(AOG_ERR_UNSUPPORTED, "%s: %d table-route observations per env exceed the tail's %d staging threads / 16", who, e->n_obs, aog::kStepActThreads);
+  const size_t epi = epilogue_lds(e), lds = aog::step_act_lds_bytes(epi, t->lds);
+  if (lds > kLdsBytes)
+    return fail(AOG_ERR_UNSUPPORTED, "%s: the fused tail needs %zu bytes of LDS (epilogue %zu, policy query %zu, prologue %zu) > %zu", who, lds, epi, t->lds,
+                (size_t)aog::kStepActProDoubles * sizeof(double), kLdsBytes);
+  return AOG_OK;
+}
+
+int reset_impl(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, void* stream, const ActTail* tail) {
   if (!e) return fail(AOG_ERR_INVALID, "aog_reset: null handle");
   if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "aog_reset before aog_upload_tables/aog_set_screens");
   if (e->obs_sep && !e->obs_ready) return fail(AOG_ERR_STATE, "aog_reset on a separable-observation handle before aog_upload_obs_mft");
@@ -999,11 +1052,27 @@ int aog_reset(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, vo
   int rc = launch_fused(e, s);
   if (rc != AOG_OK) return rc;
   if ((rc = launch_obs(e, s, obs_raw, obs)) != AOG_OK) return rc;
-  return launch_epilogue(e, false, obs_raw, obs, nullptr, nullptr, nullptr, nullptr, s);
+  rc = launch_epilogue(e, false, obs_raw, obs, nullptr, nullptr, nullptr, nullptr, s, nullptr, tail);
+  if (rc == AOG_OK && tail) e->pro_pending = true;   // (the mirror holds the first action: aog_step_act(action = NULL) steps it)
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int aog_reset(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, void* stream) { return reset_impl(e, mask, obs_raw, obs, stream, nullptr); }
+
+int aog_reset_act(aog_env* e, const aog_actor* net, float* obs_raw, uint16_t* obs, float* action_out, float* log_prob_out, float* mean_out,
+                  void* stream) {
+  if (!e) return fail(AOG_ERR_INVALID, "aog_reset_act: null handle");
+  if (int rc = refuse_pre_evolved(e, "aog_reset_act")) return rc;
+  ActTail t{};
+  if (int rc = step_act_tail(e, net, "aog_reset_act", obs, action_out, log_prob_out, mean_out, &t)) return rc;
+  return reset_impl(e, nullptr, obs_raw, obs, stream, &t);
 }
 
 static int step_impl(aog_env* e, const float* action, const float* action_next, bool pipelined, float* obs_raw, uint16_t* obs, float* reward,
-                     uint8_t* done, float* power, float* strehl, void* stream);
+                     uint8_t* done, float* power, float* strehl, void* stream, const ActTail* tail = nullptr, int* queried = nullptr);
 int aog_step(aog_env* e, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
              float* strehl, void* stream) {
   return step_impl(e, action, nullptr, false, obs_raw, obs, reward, done, power, strehl, stream);
@@ -1012,10 +1081,22 @@ int aog_step_pipelined(aog_env* e, const float* action, const float* action_next
                        float* power, float* strehl, void* stream) {
   return step_impl(e, action, action_next, true, obs_raw, obs, reward, done, power, strehl, stream);
 }
+int aog_step_act(aog_env* e, const aog_actor* net, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
+                 float* strehl, float* action_out, float* log_prob_out, float* mean_out, int* queried, void* stream) {
+  if (queried) *queried = 0;
+  if (!e) return fail(AOG_ERR_INVALID, "aog_step_act: null handle");
+  if (!action && !e->pro_pending)
+    return fail(AOG_ERR_INVALID, "aog_step_act: action = NULL but no action is pending (the first step after a plain aog_reset needs its action)");
+  if (action && e->pro_pending)
+    return fail(AOG_ERR_INVALID, "aog_step_act: an action is pending (from aog_reset_act / aog_step_act / aog_step_pipelined): pass action = NULL");
+  ActTail t{};
+  if (int rc = step_act_tail(e, net, "aog_step_act", obs, action_out, log_prob_out, mean_out, &t)) return rc;
+  return step_impl(e, action, nullptr, false, obs_raw, obs, reward, done, power, strehl, stream, &t, queried);
+}
 static int step_body(aog_env* e, const float* action, const float* action_next, bool pipelined, float* obs_raw, uint16_t* obs, float* reward,
-                     uint8_t* done, float* power, float* strehl, void* stream, bool* mutated) {
-  if (!e || !action) return fail(AOG_ERR_INVALID, "aog_step: null argument");
-  if (!pipelined && e->pro_pending)
+                     uint8_t* done, float* power, float* strehl, void* stream, bool* mutated, const ActTail* tail, int* queried) {
+  if (!e || (!action && !(tail && e->pro_pending))) return fail(AOG_ERR_INVALID, "aog_step: null argument");
+  if (!pipelined && !tail && e->pro_pending)
     return fail(AOG_ERR_STATE, "aog_step: a pipelined step has already loaded the next action (continue with aog_step_pipelined)");
   if (pipelined && e->lookahead) return fail(AOG_ERR_UNSUPPORTED, "aog_step_pipelined: not together with aog_set_lookahead");
   if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "aog_step before aog_upload_tables/aog_set_screens");
@@ -1067,15 +1148,18 @@ static int step_body(aog_env* e, const float* action, const float* action_next, 
     HIP_TRY(hipEventRecord(e->ev_ext_done, e->ext_stream));
     e->pre_evolved = true;
   }
-  const int rce = launch_epilogue(e, true, obs_raw, obs, reward, done, power, strehl, s, pipelined ? action_next : nullptr);
-  if (rce == AOG_OK && pipelined && action_next) e->pro_pending = true;
+  // aog_step_act: the policy rides with the epilogue unless this is the episode's last step (the next one begins with a reset)
+  const bool query = tail && e->steps_since_reset < e->cfg.max_steps;
+  const int rce = launch_epilogue(e, true, obs_raw, obs, reward, done, power, strehl, s, pipelined ? action_next : nullptr, query ? tail : nullptr);
+  if (rce == AOG_OK && ((pipelined && action_next) || query)) e->pro_pending = true;
+  if (rce == AOG_OK && query && queried) *queried = 1;
   return rce;
 }
 
 static int step_impl(aog_env* e, const float* action, const float* action_next, bool pipelined, float* obs_raw, uint16_t* obs, float* reward,
-                     uint8_t* done, float* power, float* strehl, void* stream) {
+                     uint8_t* done, float* power, float* strehl, void* stream, const ActTail* tail, int* queried) {
   bool mutated = false;
-  const int rc = step_body(e, action, action_next, pipelined, obs_raw, obs, reward, done, power, strehl, stream, &mutated);
+  const int rc = step_body(e, action, action_next, pipelined, obs_raw, obs, reward, done, power, strehl, stream, &mutated, tail, queried);
   // A launch or a dynamic-LDS request that fails AFTER the step counters moved (and perhaps after the next extrusion was queued) leaves the
   // handle's counters, screens and mirror inconsistent: mark it unusable (bit 1 of the status word; cleared like a barrier timeout, by
   // installing screens for the whole batch or restoring a saved state) instead of letting later steps run on it.

@@ -9,6 +9,10 @@
 #include <cstring>
 #include <vector>
 
+namespace aog {
+struct ActorArgs;
+}
+
 namespace aog_host {
 
 // sets aog_last_error() of the calling thread and returns `code`
@@ -96,5 +100,8 @@ int ring_from_master(aog_env* e, int first, int count, int keep_ref, hipStream_t
 int store_master_f64(aog_env* e, const double* psi, int first, int count, hipStream_t s);
 int store_master_f32(aog_env* e, const float* psi, int first, int count, hipStream_t s);
 int unroll_master(aog_env* e, double* psi_dev, int first, int count, hipStream_t s);
+// actor.hip: the checks and arguments of a policy query (aog_actor_act, aog_step_act): all but the observations and outputs; *lds = the query's
+// dynamic LDS (activations + weight chunk).  AOG_ERR_UNSUPPORTED (naming the sizes) when they do not fit.
+int actor_args(const aog_actor* net, const char* who, aog::ActorArgs* out, size_t* lds);
 
 }  // namespace aog_host

@@ -1,4 +1,4 @@
-// R1: policy query of the rollout as one kernel.
+// R1: policy query of the rollout: the device building blocks (kernel k_actor_act in actor.hip, the fused step tail in k_step_act.h).
 #pragma once
 #include "k_common.h"
 
@@ -38,18 +38,22 @@ __device__ __forceinline__ void actor_philox(uint32_t (&c)[4], unsigned long lon
 constexpr int kActorWFloats = 24576;   // LDS floats for a weight chunk (96 KB)
 constexpr int kActorThreads = 640;     // 10 waves: one 16-unit tile each for the reference's 150 hidden units
 constexpr int kActorPre = 10;          // float4 registers per thread holding a chunk in flight (640 x 10 x 4 >= kActorWFloats)
+// THREADS (a multiple of 64) threads share a layer's tiles and PRE float4 registers each hold the chunk in flight (THREADS x PRE x 4 >= the
+// chunk's floats): k_actor_act runs <kActorThreads, kActorPre>, the fused step tail (k_step_act.h) its own 1024-thread shape.  A tile's
+// accumulation chain is the same whichever wave runs it.
 __device__ __forceinline__ int actor_rows_max(int K, int wfloats) { return max(16, ((wfloats / K) >> 4) << 4); }
 // request rows [r0, r0 + rows_max) of W ([M][K], 16-byte aligned base; r0 is a multiple of 16)
-__device__ __forceinline__ void actor_issue(f32x4 (&pre)[kActorPre], const float* __restrict__ W, int K, int M, int r0, int wfloats) {
+template <int THREADS, int PRE>
+__device__ __forceinline__ void actor_issue(f32x4 (&pre)[PRE], const float* __restrict__ W, int K, int M, int r0, int wfloats) {
   const int rc = min(actor_rows_max(K, wfloats), M - r0);
   const int n4 = (rc * K) >> 2;
   const f32x4* src = reinterpret_cast<const f32x4*>(W + (size_t)r0 * K);
 #pragma unroll
-  for (int u = 0; u < kActorPre; ++u) pre[u] = src[min((int)threadIdx.x + kActorThreads * u, max(n4 - 1, 0))];
+  for (int u = 0; u < PRE; ++u) pre[u] = src[min((int)threadIdx.x + THREADS * u, max(n4 - 1, 0))];
 }
-template <int LAYER>
+template <int LAYER, int THREADS, int PRE>
 __device__ __forceinline__ void actor_layer(const ActorArgs& p, const float* __restrict__ W, const float* __restrict__ bias, int K, int M,
-                                            const float* xin, float* xout, float* lp_sum, float* wl, int env0, f32x4 (&pre)[kActorPre],
+                                            const float* xin, float* xout, float* lp_sum, float* wl, int env0, f32x4 (&pre)[PRE],
                                             const float* __restrict__ Wnext, int Knext, int Mnext, int kin, int kout) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int el = lane & 15, kq = lane >> 4;
@@ -63,16 +67,16 @@ __device__ __forceinline__ void actor_layer(const ActorArgs& p, const float* __r
       // `pre` holds this chunk (requested during the previous chunk's matrix work, or at kernel start)
       const int n4 = n_fl >> 2;
 #pragma unroll
-      for (int u = 0; u < kActorPre; ++u)
-        if ((int)threadIdx.x + kActorThreads * u < n4) reinterpret_cast<f32x4*>(wl)[threadIdx.x + kActorThreads * u] = pre[u];
-      for (int i = (n4 << 2) + threadIdx.x; i < n_fl; i += kActorThreads) wl[i] = src[i];
+      for (int u = 0; u < PRE; ++u)
+        if ((int)threadIdx.x + THREADS * u < n4) reinterpret_cast<f32x4*>(wl)[threadIdx.x + THREADS * u] = pre[u];
+      for (int i = (n4 << 2) + threadIdx.x; i < n_fl; i += THREADS) wl[i] = src[i];
     }
     __syncthreads();
-    if (r0 + rows_max < M) actor_issue(pre, W, K, M, r0 + rows_max, p.wfloats);
-    else if (Wnext != nullptr) actor_issue(pre, Wnext, Knext, Mnext, 0, p.wfloats);
+    if (r0 + rows_max < M) actor_issue<THREADS, PRE>(pre, W, K, M, r0 + rows_max, p.wfloats);
+    else if (Wnext != nullptr) actor_issue<THREADS, PRE>(pre, Wnext, Knext, Mnext, 0, p.wfloats);
     __builtin_amdgcn_sched_barrier(0);   // (keep the requests ahead of the matrix work)
     const int n_tiles = (rc + 15) >> 4;
-    for (int tile = wave; tile < n_tiles; tile += kActorThreads / 64) {
+    for (int tile = wave; tile < n_tiles; tile += THREADS / 64) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       const int lrow = tile * 16 + el;                 // row inside the chunk
       const float row_ok = lrow < rc ? 1.f : 0.f;
@@ -153,32 +157,27 @@ __device__ __forceinline__ void actor_layer(const ActorArgs& p, const float* __r
   }
 }
 
-__global__ __launch_bounds__(kActorThreads) void k_actor_act(ActorArgs p) {
-  extern __shared__ float lds_act[];   // xa [kpad][16] | xb [kpad_b][16] | lp [16] | weight chunk [wfloats]
-  float* xa = lds_act;                 // (xa: the observations, then layer 2's output; xb: the outputs of layers 1 and 3)
+// LDS of a policy query: xa [kpad][16] | xb [kpad_b][16] | lp [16] | weight chunk [wfloats] (xa: the observations, then layer 2's output;
+// xb: the outputs of layers 1 and 3).  actor_act_floats = the floats before the chunk.
+__host__ __device__ inline size_t actor_act_floats(int kpad, int kpad_b) { return (size_t)(kpad + kpad_b) * 16 + 16; }
+// The four layers and the log-probability of this workgroup's 16 envs (env0 ..), the observations staged in xa, the first weight chunk of
+// layer 1 in flight in `pre`.  Ends with a barrier: the LDS is free afterwards.
+template <int THREADS, int PRE>
+__device__ __forceinline__ void actor_mlp(const ActorArgs& p, float* lds_act, int env0, f32x4 (&pre)[PRE]) {
+  float* xa = lds_act;
   float* xb = xa + (size_t)p.kpad * 16;
   float* lp = xb + (size_t)p.kpad_b * 16;
   float* wt = lp + 16;
-  const int env0 = blockIdx.x * 16;
-  f32x4 pre[kActorPre];
-  actor_issue(pre, p.w1, p.S, p.H, 0, p.wfloats);   // the first weight chunk travels while the observations are staged
-  for (int i = threadIdx.x; i < (p.kpad + p.kpad_b) * 16 + 16; i += kActorThreads) lds_act[i] = 0.f;
+  actor_layer<1, THREADS, PRE>(p, p.w1, p.b1, p.S, p.H, xa, xb, lp, wt, env0, pre, p.w2, p.H, p.H, p.kpad, p.kpad_b);
   __syncthreads();
-  for (int i = threadIdx.x; i < p.S * 16; i += kActorThreads) {
-    const int k = i >> 4, e = i & 15, env = min(env0 + e, p.B - 1);
-    xa[i] = p.obs_f16 ? (float)reinterpret_cast<const _Float16*>(p.obs)[(size_t)env * p.S + k]
-                      : reinterpret_cast<const float*>(p.obs)[(size_t)env * p.S + k];
-  }
+  actor_layer<2, THREADS, PRE>(p, p.w2, p.b2, p.H, p.H, xb, xa, lp, wt, env0, pre, p.w3, p.H, p.H, p.kpad_b, p.kpad);
   __syncthreads();
-  actor_layer<1>(p, p.w1, p.b1, p.S, p.H, xa, xb, lp, wt, env0, pre, p.w2, p.H, p.H, p.kpad, p.kpad_b);
+  actor_layer<3, THREADS, PRE>(p, p.w3, p.b3, p.H, p.H, xa, xb, lp, wt, env0, pre, p.wo, p.H, p.A, p.kpad, p.kpad_b);
   __syncthreads();
-  actor_layer<2>(p, p.w2, p.b2, p.H, p.H, xb, xa, lp, wt, env0, pre, p.w3, p.H, p.H, p.kpad_b, p.kpad);
-  __syncthreads();
-  actor_layer<3>(p, p.w3, p.b3, p.H, p.H, xa, xb, lp, wt, env0, pre, p.wo, p.H, p.A, p.kpad, p.kpad_b);
-  __syncthreads();
-  actor_layer<4>(p, p.wo, p.bo, p.H, p.A, xb, nullptr, lp, wt, env0, pre, nullptr, 0, 0, p.kpad_b, 0);
+  actor_layer<4, THREADS, PRE>(p, p.wo, p.bo, p.H, p.A, xb, nullptr, lp, wt, env0, pre, nullptr, 0, 0, p.kpad_b, 0);
   __syncthreads();
   if (threadIdx.x < 16 && env0 + threadIdx.x < p.B && p.log_prob) p.log_prob[env0 + threadIdx.x] = -0.5f * lp[threadIdx.x] - p.logp_const;
+  __syncthreads();
 }
 
 }  // namespace aog

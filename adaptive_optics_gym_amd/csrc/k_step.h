@@ -16,17 +16,20 @@ constexpr int kProEnvs = 4;   // envs (= waves) per workgroup: they share one co
 // SHARED_GRAM = false: the Gram matrix is read through the caches instead of a 32 KB LDS copy — same arithmetic in the same order (bit-
 // identical), 1 us slower, but the workgroup then fits beside a resident extrusion workgroup (146 KB of a CU's 160 KB LDS): the form
 // aog_step uses while the next step's extrusion runs on the library's stream (aog_set_lookahead)
+// Gs: SHARED_GRAM ? 64 * 64 : 0 doubles of LDS, aps: ENVS * 256 (prologue_lds_doubles): static in the kernels below, the caller's dynamic LDS in
+// the fused step tail (k_step_act.h)
 template <bool SHARED_GRAM, int ENVS>
-__device__ __forceinline__ void prologue_body(const float* __restrict__ action, const double* __restrict__ gram,
-                                              double* __restrict__ act_dm, float* __restrict__ act_rev,
-                                              _Float16* __restrict__ act16, int B, int A, int A_pad, int Bp,
-                                              int sh_operation, double target, double two_over_lambda, int block) {
+__host__ __device__ constexpr int prologue_lds_doubles() { return (SHARED_GRAM ? 64 * 64 : 0) + ENVS * 256; }
+template <bool SHARED_GRAM, int ENVS>
+__device__ __forceinline__ void prologue_body_lds(const float* __restrict__ action, const double* __restrict__ gram,
+                                                  double* __restrict__ act_dm, float* __restrict__ act_rev,
+                                                  _Float16* __restrict__ act16, int B, int A, int A_pad, int Bp,
+                                                  int sh_operation, double target, double two_over_lambda, int block, double* Gs, double* aps) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int env = block * ENVS + wave;
   const bool live = env < B;
-  __shared__ double Gs[SHARED_GRAM ? 64 * 64 : 1];   // G[j][i] at j * 64 + i (A <= 64); lane i then reads a conflict-free row per j
-  __shared__ double aps[ENVS][256];
-  double* ap = aps[wave];
+  // Gs: G[j][i] at j * 64 + i (A <= 64); lane i then reads a conflict-free row per j
+  double* ap = aps + wave * 256;
   // A <= 64 (every fast-path config of the reference): the Gram matrix crosses L2 -> LDS ONCE per workgroup, every load of it in
   // flight together with the action loads: one memory round trip in front of the arithmetic (4 K multiply-adds per env).  Round 1
   // had every env pull its own 32 KB copy through L2 (33 MB per step at B = 1024).
@@ -82,6 +85,15 @@ __device__ __forceinline__ void prologue_body(const float* __restrict__ action, 
     if (act_rev) act_rev[(size_t)i * Bp + env] = ar;
     store_act16(act16, env, i, A_pad, ar);
   }
+}
+template <bool SHARED_GRAM, int ENVS>
+__device__ __forceinline__ void prologue_body(const float* __restrict__ action, const double* __restrict__ gram,
+                                              double* __restrict__ act_dm, float* __restrict__ act_rev,
+                                              _Float16* __restrict__ act16, int B, int A, int A_pad, int Bp,
+                                              int sh_operation, double target, double two_over_lambda, int block) {
+  __shared__ double Gs[SHARED_GRAM ? 64 * 64 : 1];
+  __shared__ double aps[ENVS * 256];
+  prologue_body_lds<SHARED_GRAM, ENVS>(action, gram, act_dm, act_rev, act16, B, A, A_pad, Bp, sh_operation, target, two_over_lambda, block, Gs, aps);
 }
 template <bool SHARED_GRAM>
 __global__ __launch_bounds__(64 * kProEnvs) void k_prologue(const float* __restrict__ action, const double* __restrict__ gram,
@@ -222,6 +234,8 @@ __host__ __device__ inline size_t epilogue_lds_bytes(int NS, int n_obs, int n_fi
   return ((size_t)kEpiGroups * NS * kEpiEnvs + (size_t)NS * kEpiEnvs + (size_t)(n_obs + n_fiber + 1) * kEpiEnvs +
           (size_t)(n_obs + n_fiber) * MRW_used * 2 + (size_t)MRS_used * 2) * sizeof(double);
 }
+// offset (doubles) of the epilogue's output powers pw [n_out + 1][kEpiEnvs] in its LDS: the observation of env e is pw[j * kEpiEnvs + e], j < n_obs
+__host__ __device__ inline size_t epilogue_pw_offset(int NS) { return (size_t)kEpiGroups * NS * kEpiEnvs + (size_t)NS * kEpiEnvs; }
 __device__ __forceinline__ void epilogue_body(const EpilogueArgs& p, int block, double* __restrict__ sm) {
   const int e = threadIdx.x & (kEpiEnvs - 1);
   const int q = (threadIdx.x / kEpiEnvs) & 15;            // sum slot
@@ -233,7 +247,7 @@ __device__ __forceinline__ void epilogue_body(const EpilogueArgs& p, int block, 
   const size_t cstride = (size_t)NS * p.Bp;
   double* part = sm;                                              // [group][NS][4]
   double* U = part + (size_t)kEpiGroups * NS * kEpiEnvs;          // [NS][4]: U_m = U[(2m) * 4 + e], V_m = U[(2m + 1) * 4 + e]
-  double* pw = U + (size_t)NS * kEpiEnvs;                         // [n_out + 1][4]: powers of the outputs, then Strehl
+  double* pw = sm + epilogue_pw_offset(NS);                       // [n_out + 1][4]: powers of the outputs, then Strehl
   double* cfs = pw + (size_t)(n_out + 1) * kEpiEnvs;              // [n_out][MRW_used][2] then [MRS_used][2]
   double* cfsci = cfs + (size_t)n_out * p.MRW_used * 2;
   // the per-env state the last phase updates is requested now (it would otherwise be one more memory round trip at the very end)

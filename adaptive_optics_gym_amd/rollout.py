@@ -138,15 +138,31 @@ class DeviceActor:
             raise RuntimeError("DeviceActor: the actor module it was built for has been garbage-collected")
         return a
 
+    def layers(self):
+        """The four ``nn.Linear`` of the module, checked: contiguous float32 CUDA weights (ValueError otherwise)."""
+        import torch
+
+        layers = actor_layers(self.actor)
+        for layer in layers:
+            if layer.weight.dtype != torch.float32 or not layer.weight.is_contiguous() or not layer.weight.is_cuda:
+                raise ValueError("DeviceActor needs contiguous float32 CUDA weights")
+        return layers
+
+    def net(self, batch: int, cov_var: float = 0.5, layers=None):
+        """The ``aog_actor`` of the NEXT query (call index ``self.calls``) for ``batch`` observation rows.  Does not advance the counter: a
+        caller whose launch makes the query (``__call__``, ``BatchedAOEnv.step_with_policy``) adds one, so every query draws fresh streams."""
+        layers = self.layers() if layers is None else layers
+        S, H, A = layers[0].weight.shape[1], layers[0].weight.shape[0], layers[3].weight.shape[0]
+        C, _lib = self._C, self._lib_mod
+        return _lib.AogActor(int(batch), S, H, A, self.env_id_base, 0, *[C.c_void_p(t.data_ptr()) for layer in layers for t in (layer.weight, layer.bias)],
+                             self.dropout_p, float(cov_var), self.seed, self.calls)
+
     def __call__(self, obs, cov_var: float = 0.5, out=None):
         """obs [B, S] float16 or float32 on the GPU -> (action [B, A] float32, log_prob [B] float32, mean [B, A])."""
         import torch
 
         C, _lib = self._C, self._lib_mod
-        layers = actor_layers(self.actor)
-        for layer in layers:
-            if layer.weight.dtype != torch.float32 or not layer.weight.is_contiguous() or not layer.weight.is_cuda:
-                raise ValueError("DeviceActor needs contiguous float32 CUDA weights")
+        layers = self.layers()
         if obs.dtype not in (torch.float16, torch.float32) or not obs.is_contiguous():
             raise ValueError("obs must be a contiguous float16 or float32 tensor")
         B, S = obs.shape
@@ -159,8 +175,7 @@ class DeviceActor:
             mean = torch.empty((B, A), dtype=torch.float32, device=obs.device)
         else:
             action, log_prob, mean = out
-        net = _lib.AogActor(B, S, H, A, self.env_id_base, 0, *[C.c_void_p(t.data_ptr()) for layer in layers for t in (layer.weight, layer.bias)],
-                            self.dropout_p, float(cov_var), self.seed, self.calls)
+        net = self.net(B, cov_var, layers)
         self.calls += 1
         _lib.check(self.lib.aog_actor_act(C.byref(net), obs.device.index or 0, C.c_void_p(obs.data_ptr()), int(obs.dtype == torch.float16),
                                           C.c_void_p(mean.data_ptr()), C.c_void_p(action.data_ptr()), C.c_void_p(log_prob.data_ptr()),
@@ -169,7 +184,7 @@ class DeviceActor:
 
 
 def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, generator=None, actor_impl: str = "auto", seed: int = 0,
-            dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None):
+            dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None, fused_policy: bool = False):
     """Collect ``episodes`` lock-step episodes from ``env`` (a ``BatchedAOEnv``).
 
     ``actor_impl``: "hip" = the fused policy-query kernel (``DeviceActor``), "torch" = the module's own forward +
@@ -184,7 +199,12 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     ``policy="shack"`` (``algorithm.py:252-253``, the 'SHACK' algorithm): the action of every step comes from ``env.SH_step()`` (the
     Shack-Hartmann integrator on the device; needs an env built with ``SH_operation=True``), ``actor`` may be None and ``log_prob`` holds the
     reference's constant 1.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
-    action before the env sees it (and before it is stored, like the reference's in-place ``action +=``)."""
+    action before the env sees it (and before it is stored, like the reference's in-place ``action +=``).
+
+    ``fused_policy=True``: the policy query rides with the env step (``env.reset_with_policy`` / ``env.step_with_policy``, one launch where
+    the epilogue of step t, the query on its observation and the prologue of step t + 1 take three): needs ``policy="actor"`` resolved to
+    ``actor_impl="hip"`` and no ``ou_noise`` (the noise would have to be added between the query and the prologue); ValueError otherwise.
+    Returns the same dict, bit for bit, as the unfused loop with the same ``DeviceActor`` (seed and call counter)."""
     import numpy as np
     import torch
 
@@ -211,6 +231,13 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         if dev_actor is None or dev_actor.seed != int(seed) or dev_actor.env_id_base != base or dev_actor.actor is not actor:
             dev_actor = DeviceActor(actor, seed=seed, env_id_base=base)
             _DEVICE_ACTORS[actor] = dev_actor
+    if fused_policy:
+        if shack:
+            raise ValueError("fused_policy=True needs policy='actor' (the Shack-Hartmann integrator is not a policy query)")
+        if dev_actor is None:
+            raise ValueError("fused_policy=True needs the HIP policy query (actor_impl='hip': a make_actor / reference Actor module with CUDA weights)")
+        if ou_noise is not None:
+            raise ValueError("fused_policy=True cannot add ou_noise: the noise would have to enter between the policy query and the prologue")
     import inspect
 
     step_takes_out = "out" in inspect.signature(env.step).parameters
@@ -222,51 +249,55 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     n = T * episodes
     out = None
     ep_returns = []
-    with torch.no_grad():
-        i = 0
-        for _ in range(episodes):
-            obs, _ = env.reset()
-            gatherer.start_episode()
-            i0 = i
-            for _t in range(T):
-                if out is None:   # buffers are laid out once the shapes are known: [T*E, B, ...], written in place
-                    S = obs.shape[1]
-                    A = int(env.num_modes) if shack else int(list(actor.parameters())[-1].shape[0])   # width of the output layer's bias
-                    dev = obs.device
-                    out = {"obs": torch.empty((n, B, S), dtype=obs.dtype, device=dev), "act": torch.empty((n, B, A), dtype=torch.float32, device=dev),
-                           "log_prob": torch.empty((n, B), dtype=torch.float32, device=dev), "rew": torch.empty((n, B), dtype=torch.float32, device=dev),
-                           "next_obs": torch.empty((n, B, S), dtype=obs.dtype, device=dev), "done": torch.empty((n, B), dtype=torch.bool, device=dev)}
-                    mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
-                if shack:
-                    sh_act, _ = env.SH_step()                       # (actuators [B, A] float64, the reference's constant log-probability 1)
-                    out["act"][i].copy_(sh_act)
-                    out["log_prob"][i].fill_(1.0)
-                    action = out["act"][i]
-                elif dev_actor is not None:
-                    action, _, _ = dev_actor(obs, cov_var, out=(out["act"][i], out["log_prob"][i], mean_buf))
-                else:
-                    action, log_prob = sample_action(actor(obs), cov_var, generator)
-                    out["act"][i].copy_(action)
-                    out["log_prob"][i].copy_(log_prob)
-                if ou_noise is not None:
-                    out["act"][i].add_(ou_noise.sample())           # algorithm.py:258-259
-                    action = out["act"][i]
-                if step_takes_out:   # the env writes the transition straight into this step's slices
-                    next_obs = env.step(action, out=(out["next_obs"][i], out["rew"][i], out["done"][i]))[0]
-                else:
-                    next_obs, rew, done, _, _ = env.step(action)
-                    out["rew"][i].copy_(rew)
-                    out["next_obs"][i].copy_(next_obs)
-                    out["done"][i].copy_(done)
-                if _t == 0:
-                    out["obs"][i].copy_(obs)
-                obs = next_obs
-                i += 1
-                # lock-step: done is identical for every env (AO_env.py:147), so no host sync is needed to break
-            if T > 1:
-                out["obs"][i0 + 1:i0 + T].copy_(out["next_obs"][i0:i0 + T - 1])   # obs of step t+1 = next_obs of step t
-            gatherer.add(out["rew"][i0:i0 + T].sum(0))
-            ep_returns.append(gatherer.finish_episode().clone())
+    if fused_policy:
+        with torch.no_grad():
+            out = _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns)
+    else:
+        with torch.no_grad():
+            i = 0
+            for _ in range(episodes):
+                obs, _ = env.reset()
+                gatherer.start_episode()
+                i0 = i
+                for _t in range(T):
+                    if out is None:   # buffers are laid out once the shapes are known: [T*E, B, ...], written in place
+                        S = obs.shape[1]
+                        A = int(env.num_modes) if shack else int(list(actor.parameters())[-1].shape[0])   # width of the output layer's bias
+                        dev = obs.device
+                        out = {"obs": torch.empty((n, B, S), dtype=obs.dtype, device=dev), "act": torch.empty((n, B, A), dtype=torch.float32, device=dev),
+                               "log_prob": torch.empty((n, B), dtype=torch.float32, device=dev), "rew": torch.empty((n, B), dtype=torch.float32, device=dev),
+                               "next_obs": torch.empty((n, B, S), dtype=obs.dtype, device=dev), "done": torch.empty((n, B), dtype=torch.bool, device=dev)}
+                        mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
+                    if shack:
+                        sh_act, _ = env.SH_step()                       # (actuators [B, A] float64, the reference's constant log-probability 1)
+                        out["act"][i].copy_(sh_act)
+                        out["log_prob"][i].fill_(1.0)
+                        action = out["act"][i]
+                    elif dev_actor is not None:
+                        action, _, _ = dev_actor(obs, cov_var, out=(out["act"][i], out["log_prob"][i], mean_buf))
+                    else:
+                        action, log_prob = sample_action(actor(obs), cov_var, generator)
+                        out["act"][i].copy_(action)
+                        out["log_prob"][i].copy_(log_prob)
+                    if ou_noise is not None:
+                        out["act"][i].add_(ou_noise.sample())           # algorithm.py:258-259
+                        action = out["act"][i]
+                    if step_takes_out:   # the env writes the transition straight into this step's slices
+                        next_obs = env.step(action, out=(out["next_obs"][i], out["rew"][i], out["done"][i]))[0]
+                    else:
+                        next_obs, rew, done, _, _ = env.step(action)
+                        out["rew"][i].copy_(rew)
+                        out["next_obs"][i].copy_(next_obs)
+                        out["done"][i].copy_(done)
+                    if _t == 0:
+                        out["obs"][i].copy_(obs)
+                    obs = next_obs
+                    i += 1
+                    # lock-step: done is identical for every env (AO_env.py:147), so no host sync is needed to break
+                if T > 1:
+                    out["obs"][i0 + 1:i0 + T].copy_(out["next_obs"][i0:i0 + T - 1])   # obs of step t+1 = next_obs of step t
+                gatherer.add(out["rew"][i0:i0 + T].sum(0))
+                ep_returns.append(gatherer.finish_episode().clone())
     if looking_ahead:
         env.lookahead(False)
     out["ep_returns"] = torch.stack(ep_returns)
@@ -274,6 +305,36 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     lens = np.zeros(n)
     lens[:episodes] = T
     out["batch_lens"] = lens
+    return out
+
+
+def _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns):
+    """rollout(fused_policy=True)'s loop: reset_with_policy writes row i0's action, step i the action of row i + 1 (none on the last step)."""
+    import torch
+
+    B, S, A, dev = env.num_envs, int(env.obs_dim) ** 2, int(env.num_modes), env.device
+    n = T * episodes
+    out = {"obs": torch.empty((n, B, S), dtype=torch.float16, device=dev), "act": torch.empty((n, B, A), dtype=torch.float32, device=dev),
+           "log_prob": torch.empty((n, B), dtype=torch.float32, device=dev), "rew": torch.empty((n, B), dtype=torch.float32, device=dev),
+           "next_obs": torch.empty((n, B, S), dtype=torch.float16, device=dev), "done": torch.empty((n, B), dtype=torch.bool, device=dev)}
+    mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
+    for e in range(episodes):
+        i0 = e * T
+        (obs, _), _ = env.reset_with_policy(dev_actor, cov_var, policy_out=(out["act"][i0], out["log_prob"][i0], mean_buf))
+        gatherer.start_episode()
+        out["obs"][i0].copy_(obs)
+        for t in range(T):
+            i = i0 + t
+            last = t == T - 1
+            pol_out = None if last else (out["act"][i + 1], out["log_prob"][i + 1], mean_buf)
+            _, pol = env.step_with_policy(dev_actor, cov_var, out=(out["next_obs"][i], out["rew"][i], out["done"][i]), policy_out=pol_out)
+            if (pol is None) != last:
+                raise RuntimeError(f"step_with_policy {'did not query' if pol is None else 'queried'} the policy at step {t + 1} of {T}: the env's "
+                                   "episode length differs from timesteps_per_episode")
+        if T > 1:
+            out["obs"][i0 + 1:i0 + T].copy_(out["next_obs"][i0:i0 + T - 1])   # obs of step t+1 = next_obs of step t
+        gatherer.add(out["rew"][i0:i0 + T].sum(0))
+        ep_returns.append(gatherer.finish_episode().clone())
     return out
 
 

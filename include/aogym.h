@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AOG_ABI_VERSION 20
+#define AOG_ABI_VERSION 21
 
 typedef struct aog_env aog_env;
 
@@ -359,6 +359,34 @@ typedef struct aog_actor {
 /* obs: [batch][state_dim], float16 bits (obs_is_f16 = 1: what aog_step writes) or float32; outputs may be NULL. */
 int aog_actor_act(const aog_actor* net, int device, const void* obs_dev, int obs_is_f16, float* mean_dev /* [batch][act] */,
                   float* action_dev /* [batch][act] */, float* log_prob_dev /* [batch] */, void* stream);
+
+/* ---- causal policy stepping (ABI 21): the rollout's actor.get_action(obs) -> env.step(action) (algorithm.py:256-262) with the policy
+ * attached to the env.  The epilogue of step t, the policy query (aog_actor_act's arithmetic) on its float16 observation and the
+ * action -> actuator prologue of step t + 1 run as ONE launch, 16 envs per workgroup: results bit-identical to aog_step + aog_actor_act
+ * (obs_is_f16 = 1) + the next aog_step's prologue, log_prob up to the summation order aog_actor_act itself leaves open.
+ *   net          batch = B, state_dim = obs_dim^2, act_dim = n_modes, and every check of aog_actor_act; else AOG_ERR_INVALID.  What does not fit
+ *                the LDS beside the epilogue and prologue (state_dim 1024 fits up to hidden_dim 150 at least) is AOG_ERR_UNSUPPORTED, naming the sizes.
+ *                net->call_index keys the query's random streams exactly as in aog_actor_act (a query consumes one index).
+ *   obs          required (the query reads it); obs_raw nullable.
+ *   action_out [B][A], log_prob_out [B] float32 required; mean_out [B][A] float32 nullable.
+ * Between a call that leaves an action pending and the next aog_step_act the mirror already holds that action: aog_reset, aog_step,
+ * aog_get_state, aog_get_actuators, aog_focal_image(s), aog_sh_* ... fail with AOG_ERR_STATE, as after aog_step_pipelined; aog_set_actuators
+ * / aog_set_state replace the mirror and drop the pending action.  Works with aog_set_lookahead (the tail reads no screens; the next step's
+ * extrusion is released before the epilogue as in aog_step).  A failure after the step counters moved makes the handle unusable, as in
+ * aog_step.
+ *
+ * aog_reset with the policy attached: aog_reset of the whole batch (a masked reset goes through aog_reset), then the policy query on the reset
+ * observation and the prologue of step 1 in the same launch as the reset's epilogue.  Leaves the first action pending. */
+int aog_reset_act(aog_env* env, const aog_actor* net, float* obs_raw_dev, uint16_t* obs_dev, float* action_out, float* log_prob_out,
+                  float* mean_out /* nullable */, void* stream);
+/* Step t with the policy attached.  action = NULL: step the pending action (from aog_reset_act or the previous aog_step_act);
+ * non-NULL: no action may be pending (the first step after a plain aog_reset); AOG_ERR_INVALID otherwise.  Unless this is the episode's
+ * last step (cfg.max_steps steps after the last whole-batch reset), the tail queries the policy on obs_t, writes action / log_prob / mean of
+ * step t + 1 and loads that action into the mirror (pending), *queried = 1; on the last step it is a plain epilogue, the policy outputs are
+ * untouched and *queried = 0.  Other arguments as aog_step. */
+int aog_step_act(aog_env* env, const aog_actor* net, const float* action_dev, float* obs_raw_dev, uint16_t* obs_dev, float* reward_dev,
+                 uint8_t* done_dev, float* power_dev, float* strehl_dev, float* action_out, float* log_prob_out, float* mean_out,
+                 int* queried /* host int, nullable */, void* stream);
 
 /* Self-test hook: sin(2 pi u), cos(2 pi u) for n float32 revolutions u_dev with the fused kernels' device code.
  * flavour 0 = polynomial, 1 = v_sin_f32/v_cos_f32 after the exact reduction, 2 = v_sin_f32/v_cos_f32 on raw input. */
