@@ -245,11 +245,9 @@ int launch_fused(aog_env* e, hipStream_t s) {
   return AOG_OK;
 }
 
-size_t epilogue_lds(const aog_env* e) {
-  const bool ref = e->cfg.precision == AOG_PRECISION_FP64;
-  const int NS = 2 * (ref ? e->MRW_used + e->MRS_used : e->MRW + e->MRS);
-  return aog::epilogue_lds_bytes(NS, e->n_obs_tab, e->cfg.n_fiber_modes, e->MRW_used, e->MRS_used);
-}
+// The epilogue's dynamic LDS.  e->MRW / e->MRS are the table counts the partial slabs hold: the padded counts of the fast kernels, and the
+// counts in use on float64 validation handles (aog_create sets them so), whose single slab k_fused_ref writes.
+size_t epilogue_lds(const aog_env* e) { return aog::EpilogueLds(e->MRW, e->MRS, e->n_out, e->MRW_used, e->MRS_used).bytes(); }
 
 // the policy attached to aog_reset_act / aog_step_act: its arguments (actor_args, checked before the call changes anything) and outputs
 struct ActTail {
@@ -257,9 +255,10 @@ struct ActTail {
   size_t lds = 0;   // the query's own dynamic LDS
 };
 
-// the prologue of the next step from `action` (k_epilogue_prologue, k_epilogue_act_prologue)
+// the prologue of a step from `action` (k_prologue, k_epilogue_prologue, k_epilogue_act_prologue)
 aog::PrologueArgs prologue_args(const aog_env* e, const float* action) {
   aog::PrologueArgs q{};
+  // each fused kernel reads one operand layout: write only that one (the float64 device kernel and the VALU kernel read act_rev)
   const bool mfma_fast = e->kernel == AOG_KERNEL_MFMA && e->cfg.precision == AOG_PRECISION_FAST && !e->sh_ready;
   q.action = action;
   q.gram = e->gram;
@@ -291,10 +290,9 @@ int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, flo
   p.t_render = e->t_render;
   p.B = e->B;
   p.Bp = e->Bp;
-  const bool ref = e->cfg.precision == AOG_PRECISION_FP64;
-  p.n_chunks = ref ? 1 : e->n_chunks;
-  p.MRW = ref ? e->MRW_used : e->MRW;
-  p.MRS = ref ? e->MRS_used : e->MRS;
+  p.n_chunks = e->geom.n_chunks;
+  p.MRW = e->MRW;   // (see epilogue_lds)
+  p.MRS = e->MRS;
   p.MRW_used = e->MRW_used;
   p.MRS_used = e->MRS_used;
   p.n_obs = e->n_obs_tab;
@@ -432,7 +430,7 @@ int aog_create(const aog_config* cfg, int device, aog_env** out) {
   if (cfg->precision == AOG_PRECISION_FP64 && !cfg->obs_separable) {
     // the epilogue holds the coefficient matrix of every table output in LDS: at o = 8 (67 wfs tables) that is more than a CU has
     const int n_obs = cfg->obs_dim * cfg->obs_dim;
-    const size_t lds = aog::epilogue_lds_bytes(2 * (cfg->n_wfs_tables + cfg->n_sci_tables), n_obs, cfg->n_fiber_modes, cfg->n_wfs_tables, cfg->n_sci_tables);
+    const size_t lds = aog::EpilogueLds(cfg->n_wfs_tables, cfg->n_sci_tables, n_obs + cfg->n_fiber_modes, cfg->n_wfs_tables, cfg->n_sci_tables).bytes();
     if (lds > aog_host::kLdsBytes)
       return fail(AOG_ERR_UNSUPPORTED, "aog_create: the table route's epilogue at obs_dim %d needs %zu bytes of LDS (> %zu); use cfg.obs_separable = 1",
                   cfg->obs_dim, lds, aog_host::kLdsBytes);
@@ -475,47 +473,19 @@ int aog_create(const aog_config* cfg, int device, aog_env** out) {
                   "use AOG_PRECISION_FP64 for this shape");
     }
     e->kernel = cfg->kernel == AOG_KERNEL_AUTO ? AOG_KERNEL_MFMA : cfg->kernel;
-    // launch geometry: aim at ~3 (VALU) / ~2 (MFMA) waves per SIMD over 256 CUs
-    const int n_groups = e->Bp / 64;
-    int P = cfg->pixel_chunks > 0 ? cfg->pixel_chunks : std::max(1, (256 * 4 * 3 + n_groups - 1) / n_groups);
-    int qpc = round_up((e->n_quads + P - 1) / P, 8);
-    e->valu_qpc = qpc;
-    e->valu_chunks = (e->n_quads + qpc - 1) / qpc;
-    e->mfma_we = e->n_etiles >= 4 ? 4 : (e->n_etiles >= 2 ? 2 : 1);
-    // Asymmetric wave pairs (see k_fused_tab): the float64-flush variant with at least 4 env tiles runs 8-wave workgroups, one per
-    // CU, whose two pixel sub-chunks split a chunk about 2 : 1 with the priority on the larger share; the many-table variants keep the
-    // 4-wave interleaved form (their chunks are short and come in many rounds, which balances itself).
-    // (every table count since round 4: the many-table variants keep their float64 sums in LDS and run chunks as long as o = 2's; eight waves
-    // of them need 8 x 2 LIVE x 512 B of LDS — 128 KB at o = 5 — beside the chunk's science rows: one workgroup per CU, which is what this form runs)
-    const bool asym = e->kernel == AOG_KERNEL_MFMA && e->n_etiles >= 4 && !getenv("AOG_FUSED_4WAVE");
-    e->mfma_waves = asym ? 8 : 4;
-    e->mfma_heavy = asym ? 672 : 0;
-    const int wp = e->mfma_waves / e->mfma_we;
-    const int wg_y = (e->n_etiles + e->mfma_we - 1) / e->mfma_we;
-    // P pixel chunks (proportional split of the tiles), 8 waves per CU when the batch allows
-    int Pm = cfg->pixel_chunks > 0 ? cfg->pixel_chunks : std::max(1, (asym ? 256 : 256 * 2) / wg_y);
-    // (every variant keeps float64 sums now — registers for o = 2, an LDS plane per wave beyond — so a chunk may be long: as long as its
-    // science rows (128 B a tile) fit in the LDS beside that plane and the actuator operands; fused_inst.hip lays the same areas out)
-    const int live = e->MRW <= 8 ? 0 : (e->MRW <= 16 ? 8 : (e->MRW <= 24 ? 12 : 16));
-    const size_t lds_fixed = (size_t)e->mfma_waves * 2 * live * 64 * sizeof(double) +
-                             ((e->A_pad > 64 || cfg->atm_dynamic) ? (size_t)e->mfma_waves * (e->A_pad / 16) * 2 * 64 * 16 + (size_t)e->mfma_waves * 32 * 36 * 4 : 0) + 64;
-    const int max_tpc = std::min(4096, (int)((aog_host::kLdsBytes - lds_fixed) / 128));
-    Pm = std::max(Pm, (e->n_ptiles + max_tpc - 1) / max_tpc);
-    Pm = std::min(Pm, e->n_ptiles);
-    e->mfma_chunks_x = Pm;
-    e->mfma_tpc = (e->n_ptiles + Pm - 1) / Pm;  // max tiles of any chunk: ceil(n/P)
-    e->n_chunks = e->kernel == AOG_KERNEL_MFMA ? e->mfma_chunks_x * wp : e->valu_chunks;
+    e->geom = aog::fused_geometry(e->Bp, e->n_ap_pad, e->A_pad, e->MRW, e->kernel == AOG_KERNEL_MFMA, cfg->atm_dynamic != 0, cfg->pixel_chunks,
+                                  getenv("AOG_FUSED_4WAVE") != nullptr);
   } else {
     e->A_pad = round_up(e->A, 8);
     e->MRW = e->MRW_used;
     e->MRS = e->MRS_used;
     e->kernel = 0;
-    e->n_chunks = 1;
+    e->geom.n_chunks = 1;
   }
 
   int rc = AOG_OK;
   const size_t NS = 2 * (size_t)(e->MRW + e->MRS);
-  e->partial_elems = (size_t)e->n_chunks * NS * e->Bp;
+  e->partial_elems = (size_t)e->geom.n_chunks * NS * e->Bp;
 #define TRY_ALLOC(x) if ((rc = (x)) != AOG_OK) { aog_destroy(e); return rc; }
   TRY_ALLOC(dev_alloc(e, &e->ap_index, e->n_ap));
   TRY_ALLOC(dev_alloc(e, &e->gram, (size_t)e->A * e->A));
@@ -620,7 +590,7 @@ int aog_get_info(const aog_env* e, aog_info* out) {
   out->n_ap = e->n_ap;
   out->n_ap_padded = e->n_ap_pad;
   out->n_modes_padded = e->A_pad;
-  out->pixel_chunks = e->n_chunks;
+  out->pixel_chunks = e->geom.n_chunks;
   out->kernel = e->kernel;
   out->n_sums = 2 * (e->MRW + e->MRS);
   out->reserved = (e->ring_direct ? 1 : 0) | (e->obs_sep ? 2 : 0);
@@ -1062,45 +1032,9 @@ int reset_impl(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, v
   if (rc == AOG_OK && tail) e->pro_pending = true;   // (the mirror holds the first action: aog_step_act(action = NULL) steps it)
   return rc;
 }
-}  // namespace
 
-extern "C" {
-
-int aog_reset(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, void* stream) { return reset_impl(e, mask, obs_raw, obs, stream, nullptr); }
-
-int aog_reset_act(aog_env* e, const aog_actor* net, float* obs_raw, uint16_t* obs, float* action_out, float* log_prob_out, float* mean_out,
-                  void* stream) {
-  if (!e) return fail(AOG_ERR_INVALID, "aog_reset_act: null handle");
-  if (int rc = refuse_pre_evolved(e, "aog_reset_act")) return rc;
-  ActTail t{};
-  if (int rc = step_act_tail(e, net, "aog_reset_act", obs, action_out, log_prob_out, mean_out, &t)) return rc;
-  return reset_impl(e, nullptr, obs_raw, obs, stream, &t);
-}
-
-static int step_impl(aog_env* e, const float* action, const float* action_next, bool pipelined, float* obs_raw, uint16_t* obs, float* reward,
-                     uint8_t* done, float* power, float* strehl, void* stream, const ActTail* tail = nullptr, int* queried = nullptr);
-int aog_step(aog_env* e, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
-             float* strehl, void* stream) {
-  return step_impl(e, action, nullptr, false, obs_raw, obs, reward, done, power, strehl, stream);
-}
-int aog_step_pipelined(aog_env* e, const float* action, const float* action_next, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done,
-                       float* power, float* strehl, void* stream) {
-  return step_impl(e, action, action_next, true, obs_raw, obs, reward, done, power, strehl, stream);
-}
-int aog_step_act(aog_env* e, const aog_actor* net, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
-                 float* strehl, float* action_out, float* log_prob_out, float* mean_out, int* queried, void* stream) {
-  if (queried) *queried = 0;
-  if (!e) return fail(AOG_ERR_INVALID, "aog_step_act: null handle");
-  if (!action && !e->pro_pending)
-    return fail(AOG_ERR_INVALID, "aog_step_act: action = NULL but no action is pending (the first step after a plain aog_reset needs its action)");
-  if (action && e->pro_pending)
-    return fail(AOG_ERR_INVALID, "aog_step_act: an action is pending (from aog_reset_act / aog_step_act / aog_step_pipelined): pass action = NULL");
-  ActTail t{};
-  if (int rc = step_act_tail(e, net, "aog_step_act", obs, action_out, log_prob_out, mean_out, &t)) return rc;
-  return step_impl(e, action, nullptr, false, obs_raw, obs, reward, done, power, strehl, stream, &t, queried);
-}
-static int step_body(aog_env* e, const float* action, const float* action_next, bool pipelined, float* obs_raw, uint16_t* obs, float* reward,
-                     uint8_t* done, float* power, float* strehl, void* stream, bool* mutated, const ActTail* tail, int* queried) {
+int step_body(aog_env* e, const float* action, const float* action_next, bool pipelined, float* obs_raw, uint16_t* obs, float* reward,
+              uint8_t* done, float* power, float* strehl, void* stream, bool* mutated, const ActTail* tail, int* queried) {
   if (!e || (!action && !(tail && e->pro_pending))) return fail(AOG_ERR_INVALID, "aog_step: null argument");
   if (!pipelined && !tail && e->pro_pending)
     return fail(AOG_ERR_STATE, "aog_step: a pipelined step has already loaded the next action (continue with aog_step_pipelined)");
@@ -1129,12 +1063,9 @@ static int step_body(aog_env* e, const float* action, const float* action_next, 
       if (rce != AOG_OK) return rce;
     }
   }
-  // each fused kernel reads one operand layout: write only that one (the float64 device kernel and the VALU kernel read act_rev)
-  const bool mfma_fast = e->kernel == AOG_KERNEL_MFMA && e->cfg.precision == AOG_PRECISION_FAST && !e->sh_ready;
   if (!e->pro_pending) {   // (pipelined: the previous call's last launch already turned this step's action into actuators)
-    hipLaunchKernelGGL(join_ext ? aog::k_prologue<false> : aog::k_prologue<true>, dim3((e->B + aog::kProEnvs - 1) / aog::kProEnvs), dim3(64 * aog::kProEnvs), 0, s, action, e->gram, e->act_dm,
-                       mfma_fast ? nullptr : e->act_rev, e->act16, e->B, e->A,
-                       e->A_pad, e->Bp, e->cfg.sh_operation, e->cfg.surface_rms_target, 2.0 / e->cfg.wavelength_wfs);
+    hipLaunchKernelGGL(join_ext ? aog::k_prologue<false> : aog::k_prologue<true>, dim3((e->B + aog::kProEnvs - 1) / aog::kProEnvs), dim3(64 * aog::kProEnvs), 0, s,
+                       prologue_args(e, action));
     HIP_TRY(hipGetLastError());
   }
   e->pro_pending = false;
@@ -1162,8 +1093,8 @@ static int step_body(aog_env* e, const float* action, const float* action_next, 
   return rce;
 }
 
-static int step_impl(aog_env* e, const float* action, const float* action_next, bool pipelined, float* obs_raw, uint16_t* obs, float* reward,
-                     uint8_t* done, float* power, float* strehl, void* stream, const ActTail* tail, int* queried) {
+int step_impl(aog_env* e, const float* action, const float* action_next, bool pipelined, float* obs_raw, uint16_t* obs, float* reward,
+              uint8_t* done, float* power, float* strehl, void* stream, const ActTail* tail = nullptr, int* queried = nullptr) {
   bool mutated = false;
   const int rc = step_body(e, action, action_next, pipelined, obs_raw, obs, reward, done, power, strehl, stream, &mutated, tail, queried);
   // A launch or a dynamic-LDS request that fails AFTER the step counters moved (and perhaps after the next extrusion was queued) leaves the
@@ -1172,7 +1103,41 @@ static int step_impl(aog_env* e, const float* action, const float* action_next, 
   if (rc != AOG_OK && mutated && e && e->host_flag) *static_cast<volatile int*>(e->host_flag) |= 2;
   return rc;
 }
+}  // namespace
 
+extern "C" {
+
+int aog_reset(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, void* stream) { return reset_impl(e, mask, obs_raw, obs, stream, nullptr); }
+
+int aog_reset_act(aog_env* e, const aog_actor* net, float* obs_raw, uint16_t* obs, float* action_out, float* log_prob_out, float* mean_out,
+                  void* stream) {
+  if (!e) return fail(AOG_ERR_INVALID, "aog_reset_act: null handle");
+  if (int rc = refuse_pre_evolved(e, "aog_reset_act")) return rc;
+  ActTail t{};
+  if (int rc = step_act_tail(e, net, "aog_reset_act", obs, action_out, log_prob_out, mean_out, &t)) return rc;
+  return reset_impl(e, nullptr, obs_raw, obs, stream, &t);
+}
+
+int aog_step(aog_env* e, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
+             float* strehl, void* stream) {
+  return step_impl(e, action, nullptr, false, obs_raw, obs, reward, done, power, strehl, stream);
+}
+int aog_step_pipelined(aog_env* e, const float* action, const float* action_next, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done,
+                       float* power, float* strehl, void* stream) {
+  return step_impl(e, action, action_next, true, obs_raw, obs, reward, done, power, strehl, stream);
+}
+int aog_step_act(aog_env* e, const aog_actor* net, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
+                 float* strehl, float* action_out, float* log_prob_out, float* mean_out, int* queried, void* stream) {
+  if (queried) *queried = 0;
+  if (!e) return fail(AOG_ERR_INVALID, "aog_step_act: null handle");
+  if (!action && !e->pro_pending)
+    return fail(AOG_ERR_INVALID, "aog_step_act: action = NULL but no action is pending (the first step after a plain aog_reset needs its action)");
+  if (action && e->pro_pending)
+    return fail(AOG_ERR_INVALID, "aog_step_act: an action is pending (from aog_reset_act / aog_step_act / aog_step_pipelined): pass action = NULL");
+  ActTail t{};
+  if (int rc = step_act_tail(e, net, "aog_step_act", obs, action_out, log_prob_out, mean_out, &t)) return rc;
+  return step_impl(e, action, nullptr, false, obs_raw, obs, reward, done, power, strehl, stream, &t, queried);
+}
 int aog_selftest_sincos(const float* u_dev, float* sin_dev, float* cos_dev, int n, int flavour, void* stream) {
   if (!u_dev || !sin_dev || !cos_dev || n < 0 || flavour < 0 || flavour > 2) return fail(AOG_ERR_INVALID, "aog_selftest_sincos: bad argument");
   if (n == 0) return AOG_OK;

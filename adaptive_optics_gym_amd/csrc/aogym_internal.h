@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/aogym.h"
+#include "fused_layout.h"
 
 struct aog_env {
   aog_config cfg{};
@@ -20,12 +21,7 @@ struct aog_env {
   int n_obs_tab = 0;             // observation outputs of the table route: n_obs, or 0 on the separable route (its n_out = the fiber modes)
   int kernel = AOG_KERNEL_VALU;  // resolved
   int sincos_hw = 0;
-  // launch geometry
-  int valu_chunks = 0, valu_qpc = 0;
-  int mfma_we = 1, mfma_chunks_x = 0, mfma_tpc = 0;
-  int mfma_waves = 4;            // waves per workgroup of k_fused_tab (8 with asymmetric pairs)
-  int mfma_heavy = 0;            // asymmetric wave pairs: share (x / 1024) of a chunk's tiles that the prioritised sub-chunk takes; 0 = off
-  int n_chunks = 0;              // partial slabs the epilogue sums
+  aog::FusedGeom geom;           // launch geometry of the fused kernels (float64 validation handles: n_chunks = 1, the rest unused)
   int64_t dev_bytes = 0;
   // constant tables
   int32_t* ap_index = nullptr;

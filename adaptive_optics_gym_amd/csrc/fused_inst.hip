@@ -12,28 +12,29 @@ using aog_host::round_up;
 template <int A_PAD, int MRW, int SC>
 int launch_valu(aog_env* e, hipStream_t s) {
   const int n_groups = e->Bp / 64;
-  dim3 grid(e->valu_chunks, (n_groups + 3) / 4);
+  dim3 grid(e->geom.valu_chunks, (n_groups + 3) / 4);
   const float ratio = (float)(e->cfg.wavelength_wfs / e->cfg.wavelength_sci);
   hipLaunchKernelGGL((aog::k_fused_valu<A_PAD, MRW, 1, SC>), grid, dim3(256), 0, s, e->modes_f32, e->tabs_f32,
                      reinterpret_cast<const float4*>(e->psi_rev), e->act_rev, e->partials, e->n_quads, e->Bp, n_groups,
-                     e->valu_qpc, ratio);
+                     e->geom.valu_qpc, ratio);
   return 0;
 }
 
 template <int A_PAD, int MRW>
 int launch_tab(aog_env* e, hipStream_t s) {
+  const aog::FusedGeom& fg = e->geom;
   aog::MfmaGeom g;
   g.n_ptiles = e->n_ptiles;
   g.n_etiles = e->n_etiles;
   g.Bp = e->Bp;
-  g.P = e->mfma_chunks_x;
-  g.we = e->mfma_we;
-  g.wg_y = (e->n_etiles + e->mfma_we - 1) / e->mfma_we;
-  g.max_tiles = e->mfma_tpc;
+  g.P = fg.chunks_x;
+  g.we = fg.we;
+  g.wg_y = fg.wg_y;
+  g.max_tiles = fg.tpc;
   g.skew = aog::kSkewNops;
-  g.heavy = e->mfma_heavy;
-  const int threads = 64 * e->mfma_waves;
-  g.pair = (e->mfma_waves == 4 && g.wg_y % 2 == 0 && 64 % g.wg_y == 0 && g.wg_y >= 2) ? 1 : 0;
+  g.heavy = fg.heavy;
+  const int threads = 64 * fg.waves;
+  g.pair = fg.pair;
   g.dev = 0;
   g.timeline = nullptr;
 #ifdef AOG_DEV
@@ -52,11 +53,7 @@ int launch_tab(aog_env* e, hipStream_t s) {
   const int wgs_per_xcd = g.pair ? round_up(chunks_per_xcd, 64 / g.wg_y) * g.wg_y : chunks_per_xcd * g.wg_y;
   dim3 grid(8 * wgs_per_xcd);
   const float ratio = (float)(e->cfg.wavelength_wfs / e->cfg.wavelength_sci);
-  const size_t lds_0 = (size_t)e->mfma_tpc * 8 * 16 + ((A_PAD > 64 || e->ring_direct) ? (size_t)e->mfma_waves * (A_PAD / 16) * 2 * 64 * 16 : 0) +   // science rows (+ actuator operands)
-                       (e->ring_direct ? (size_t)e->mfma_waves * 32 * 36 * 4 : 0);                                             // (+ ring-direct transpose tiles)
-  g.acc_off = (int)((lds_0 + 15) / 16 * 16);
-  // many-table variants: float64 table sums per wave, [2 LIVE][64 lanes]
-  const size_t lds_t = g.acc_off + (aog::TabGeom<MRW>::kF64 ? 0 : (size_t)e->mfma_waves * 2 * aog::TabGeom<MRW>::kLiveRegs * 64 * sizeof(double));
+  const size_t lds_t = (size_t)aog::FusedLds(fg.tpc, fg.waves, A_PAD, MRW, e->ring_direct).total;   // (a total beyond the CU's LDS is refused by ensure_dynamic_lds)
   aog::DynPsi dyn{};
   if (e->ring_direct) {   // dynamic atmosphere: the screens come straight from the fp32 ring copy of the master screens
     dyn.ring = e->psi_ring;

@@ -25,7 +25,7 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
       return ::aog_host::fail(AOG_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
   } while (0)
 
-constexpr size_t kLdsBytes = 160 * 1024;   // LDS per CU on gfx950
+using aog::kLdsBytes;
 
 int dev_alloc_bytes(aog_env* e, void** out, size_t bytes, bool zero);
 void dev_release_ptr(aog_env* e, void** ptr);

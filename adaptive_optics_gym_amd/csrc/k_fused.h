@@ -1,5 +1,6 @@
 // The fused pupil pass (VALU form, f16 matrix-core form) and the phase-only contraction.
 #pragma once
+#include "fused_layout.h"
 #include "k_common.h"
 
 namespace aog {
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void k_fused_valu(const float* __restrict__ mo
 //   modes16    [pixel tile][s][hi|lo][lane][8 halfs]: lane (pixel i = l&31, h = l>>5), element e <-> mode 16 s + 8 h + e
 //   act16      [env tile][s][hi|lo][lane][8 halfs]:   lane (env j = l&31, h),          element e <-> mode 16 s + 8 h + e
 // ------------------------------------------------------------------------------------------------
-// Launch geometry of k_fused_tab (host side fills it; see aog_create):
+// Launch geometry of k_fused_tab (the host side fills it from fused_geometry, fused_layout.h):
 //   1-D grid of 8 * ceil(P/8) * wg_y workgroups.  Workgroup L runs on XCD L % 8 (round-robin dispatch, speed only):
 //   xcd = L & 7, j = L >> 3, env group = j % wg_y, pixel chunk c = (j / wg_y) * 8 + xcd, so the wg_y workgroups that
 //   share a pixel chunk (= the same mode-matrix and table tiles) sit on ONE XCD back to back and each XCD's L2 only ever
@@ -101,7 +102,6 @@ struct MfmaGeom {
   int skew;   // start-up skew of every second workgroup, x 16 cycles
   int pair;   // 1: the two workgroups that share a CU walk the SAME pixel chunk (different env groups), see fused_wg_map
   int heavy;  // > 0: asymmetric wave pairs, sub-chunk 0 takes heavy / 1024 of a chunk's tiles (see k_fused_tab); 0: interleaved
-  int acc_off;   // many-table variants: byte offset of the float64 table-sum accumulators in the workgroup's dynamic LDS (behind everything else)
   int dev;    // developer experiments (AOG_DEV builds only; 0 in the product)
   long long* timeline;   // AOG_DEV builds: per-wave time stamps (wall_clock64, 10 ns ticks) [wave][8], or null
 };
@@ -156,11 +156,6 @@ struct DynPsi {
 };
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
-template <int MRW>
-struct TabGeom {
-  static constexpr int kLiveRegs = MRW <= 8 ? 4 : (MRW <= 16 ? 8 : (MRW <= 24 ? 12 : 16));   // accumulator registers a < kLiveRegs hold real tables
-  static constexpr bool kF64 = MRW <= 8;
-};
 __device__ __forceinline__ uint32_t pk_f16(float a, float b) {   // (half(a), half(b)) in one register; callers pass values exact in f16
   return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
 }
@@ -170,10 +165,12 @@ __global__ __launch_bounds__(512, 2) void k_fused_tab(const f16x8* __restrict__ 
                                                       const f16x8* __restrict__ act16, double* __restrict__ partials, MfmaGeom geo, float ratio,
                                                       DynPsi dyn) {
   constexpr int NSTEP = A_PAD / 16, NM = 3 * NSTEP, NS = 2 * (MRW + 1);
-  constexpr int LIVE = TabGeom<MRW>::kLiveRegs;
-  constexpr bool F64 = TabGeom<MRW>::kF64;
-  extern __shared__ f32x4 lds_sci[];   // [tile in chunk][h][4] float4 = the science table in accumulator order
+  constexpr int LIVE = tab_live_regs(MRW);
+  constexpr bool F64 = tab_f64_in_regs(MRW);
+  extern __shared__ f32x4 lds_sci[];   // the workgroup's dynamic LDS (FusedLds); it starts with the science rows
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const FusedLds lay(geo.max_tiles, (int)(blockDim.x >> 6), A_PAD, MRW, DYN);
+  char* const lds = reinterpret_cast<char*>(lds_sci);
   const int L = blockIdx.x, j = L >> 3;
 #ifdef AOG_DEV
   long long tl[5] = {geo.timeline ? (long long)wall_clock64() : 0, 0, 0, 0, 0};
@@ -211,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void k_fused_tab(const f16x8* __restrict__ 
   // The float64-flush variant (few tables) and the 128-mode variants are short of registers: their actuator operands live in LDS (this
   // wave's own 2 NSTEP KB, behind the science rows) and are read back right before each phase MFMA.
   constexpr bool BLDS = A_PAD > 64 || DYN;   // (the ring-direct variant needs its registers for addresses)
-  f16x8* lds_b = reinterpret_cast<f16x8*>(lds_sci + (size_t)geo.max_tiles * 8) + (size_t)wave * NSTEP * 2 * 64 + lane;
+  f16x8* lds_b = reinterpret_cast<f16x8*>(lds + lay.op_off + wave * lay.op_wave) + lane;
   if constexpr (BLDS) {
 #pragma unroll
     for (int s = 0; s < NSTEP; ++s) {
@@ -224,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void k_fused_tab(const f16x8* __restrict__ 
   // envs 8 i .. 8 i + 7 with EIGHT LANES PER LINE: lane l fetches the 16-byte piece l & 7 (register group g = piece >> 1 of half-wave
   // piece & 1) of env 8 i + (l >> 3), so an instruction touches 8 lines (per-lane loads in the accumulator layout touched 32 and ran
   // the launch at 100 us against 51).  The pieces reach the accumulator layout (lane = env, 16 pixels) through this wave's private
-  // [32][36] float tile in LDS right before the tile is reduced.
+  // [32][kXpRow] float tile in LDS right before the tile is reduced.
   const float* ring_env[4] = {nullptr, nullptr, nullptr, nullptr};
   int dyn_ox[4] = {0, 0, 0, 0}, dyn_oy[4] = {0, 0, 0, 0};
   float* dyn_x = nullptr;
@@ -237,7 +234,7 @@ __global__ __launch_bounds__(512, 2) void k_fused_tab(const f16x8* __restrict__ 
       dyn_ox[i] = dyn.origin[2 * env];
       dyn_oy[i] = dyn.origin[2 * env + 1];
     }
-    dyn_x = reinterpret_cast<float*>(lds_b - lane + (size_t)((int)(blockDim.x >> 6) - wave) * NSTEP * 2 * 64) + (size_t)wave * 32 * 36;
+    dyn_x = reinterpret_cast<float*>(lds + lay.xp_off + wave * FusedLds::kXpWave);
   }
   auto load_modes = [&](f16x8 (&mh)[NSTEP], f16x8 (&ml)[NSTEP], int t) {
 #ifdef AOG_DEV
@@ -295,13 +292,13 @@ __global__ __launch_bounds__(512, 2) void k_fused_tab(const f16x8* __restrict__ 
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         f32x4 v = {d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]};
-        *reinterpret_cast<f32x4*>(dyn_x + (size_t)(8 * i + (lane >> 3)) * 36 + 4 * dyn_piece) = v;
+        *reinterpret_cast<f32x4*>(dyn_x + (size_t)(8 * i + (lane >> 3)) * FusedLds::kXpRow + 4 * dyn_piece) = v;
       }
       __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the tile is private to this wave
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(dyn_x + (size_t)(lane & 31) * 36 + 8 * g + 4 * h);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(dyn_x + (size_t)(lane & 31) * FusedLds::kXpRow + 8 * g + 4 * h);
         d[4 * g] = v[0]; d[4 * g + 1] = v[1]; d[4 * g + 2] = v[2]; d[4 * g + 3] = v[3];
       }
       __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -324,8 +321,8 @@ __global__ __launch_bounds__(512, 2) void k_fused_tab(const f16x8* __restrict__ 
   load_tab(ta, first);
   __builtin_amdgcn_sched_barrier(0);
   {
-    const int n4 = (t1 - t0) * 8;
-    const f32x4* src = sci_tile + (size_t)t0 * 8;
+    const int n4 = (t1 - t0) * FusedLds::kSciVecs;
+    const f32x4* src = sci_tile + (size_t)t0 * FusedLds::kSciVecs;
     for (int i = threadIdx.x; i < n4; i += blockDim.x) lds_sci[i] = src[i];
   }
   __syncthreads();
@@ -347,7 +344,7 @@ __global__ __launch_bounds__(512, 2) void k_fused_tab(const f16x8* __restrict__ 
   // sums live in this wave's own plane of LDS, [2 LIVE][64 lanes], and the fp32 registers are folded into it every kTabF32Tiles tiles (the fp32
   // run length the tolerances were set for).  Round 3 instead cut the pixel range into chunks of <= 13 tiles per wave and wrote a float slab
   // per chunk (124+ slabs, a fold kernel, and every wave's 5 us of set-up amortised over 13 tiles: 267 us per 4096 envs at o = 5 against 4 x 52).
-  double* lds_acc = reinterpret_cast<double*>(reinterpret_cast<char*>(lds_sci) + geo.acc_off) + (size_t)wave * 2 * LIVE * 64 + lane;
+  double* lds_acc = reinterpret_cast<double*>(lds + lay.acc_off + wave * lay.acc_wave) + lane;
   if constexpr (!F64) {
 #pragma unroll
     for (int a = 0; a < 2 * LIVE; ++a) lds_acc[a * 64] = 0.0;
@@ -461,7 +458,7 @@ __global__ __launch_bounds__(512, 2) void k_fused_tab(const f16x8* __restrict__ 
       constexpr bool PREV = decltype(prevc)::v != 0, NEXT = decltype(nextc)::v != 0;
       constexpr int NQ0 = (NEXT ? NM : 0) + (PREV ? 6 : 0);   // matrix ops dealt over the 8 pixels of step 0
       dyn_transpose(P);
-      const f32x4* gs = lds_sci + (size_t)(t - t0) * 8 + h * 4;
+      const f32x4* gs = lds_sci + (size_t)(t - t0) * FusedLds::kSciVecs + h * 4;
       {
         const f32x4 g0 = gs[0], g1 = gs[1];
         static_for<8>([&](auto ec) {

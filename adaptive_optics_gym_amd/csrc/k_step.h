@@ -20,11 +20,24 @@ constexpr int kProEnvs = 4;   // envs (= waves) per workgroup: they share one co
 // the fused step tail (k_step_act.h)
 template <bool SHARED_GRAM, int ENVS>
 __host__ __device__ constexpr int prologue_lds_doubles() { return (SHARED_GRAM ? 64 * 64 : 0) + ENVS * 256; }
+struct PrologueArgs {
+  const float* action;
+  const double* gram;
+  double* act_dm;
+  float* act_rev;   // nullable: written only for the handles whose kernels read this layout
+  _Float16* act16;
+  int B, A, A_pad, Bp, sh_operation;
+  double target, two_over_lambda;
+};
 template <bool SHARED_GRAM, int ENVS>
-__device__ __forceinline__ void prologue_body_lds(const float* __restrict__ action, const double* __restrict__ gram,
-                                                  double* __restrict__ act_dm, float* __restrict__ act_rev,
-                                                  _Float16* __restrict__ act16, int B, int A, int A_pad, int Bp,
-                                                  int sh_operation, double target, double two_over_lambda, int block, double* Gs, double* aps) {
+__device__ __forceinline__ void prologue_body_lds(const PrologueArgs& q, int block, double* Gs, double* aps) {
+  const float* __restrict__ action = q.action;
+  const double* __restrict__ gram = q.gram;
+  double* __restrict__ act_dm = q.act_dm;
+  float* __restrict__ act_rev = q.act_rev;
+  _Float16* __restrict__ act16 = q.act16;
+  const int B = q.B, A = q.A, A_pad = q.A_pad, Bp = q.Bp, sh_operation = q.sh_operation;
+  const double target = q.target, two_over_lambda = q.two_over_lambda;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int env = block * ENVS + wave;
   const bool live = env < B;
@@ -87,20 +100,14 @@ __device__ __forceinline__ void prologue_body_lds(const float* __restrict__ acti
   }
 }
 template <bool SHARED_GRAM, int ENVS>
-__device__ __forceinline__ void prologue_body(const float* __restrict__ action, const double* __restrict__ gram,
-                                              double* __restrict__ act_dm, float* __restrict__ act_rev,
-                                              _Float16* __restrict__ act16, int B, int A, int A_pad, int Bp,
-                                              int sh_operation, double target, double two_over_lambda, int block) {
+__device__ __forceinline__ void prologue_body(const PrologueArgs& q, int block) {
   __shared__ double Gs[SHARED_GRAM ? 64 * 64 : 1];
   __shared__ double aps[ENVS * 256];
-  prologue_body_lds<SHARED_GRAM, ENVS>(action, gram, act_dm, act_rev, act16, B, A, A_pad, Bp, sh_operation, target, two_over_lambda, block, Gs, aps);
+  prologue_body_lds<SHARED_GRAM, ENVS>(q, block, Gs, aps);
 }
 template <bool SHARED_GRAM>
-__global__ __launch_bounds__(64 * kProEnvs) void k_prologue(const float* __restrict__ action, const double* __restrict__ gram,
-                                                            double* __restrict__ act_dm, float* __restrict__ act_rev,
-                                                            _Float16* __restrict__ act16, int B, int A, int A_pad, int Bp,
-                                                            int sh_operation, double target, double two_over_lambda) {
-  prologue_body<SHARED_GRAM, kProEnvs>(action, gram, act_dm, act_rev, act16, B, A, A_pad, Bp, sh_operation, target, two_over_lambda, (int)blockIdx.x);
+__global__ __launch_bounds__(64 * kProEnvs) void k_prologue(PrologueArgs q) {
+  prologue_body<SHARED_GRAM, kProEnvs>(q, (int)blockIdx.x);
 }
 
 // actuators (metres, float64) -> the two fp32 operand layouts (used by reset / set_actuators)
@@ -226,16 +233,30 @@ __device__ inline double ssim_1d_delta_ref(const double* x, int stride, int n, d
 // block = 16 envs x 16 sum slots x 4 chunk groups (1024 threads, grid = Bp / 16: 64 workgroups at B = 1024):
 // thread (e, q, cq) adds sums s = q, q + 16, ... over chunks cq, cq + 16, ... (independent loads in flight); the chunk groups meet
 // in LDS; then one thread per (env, output) forms |coef . sums|^2, and one thread per env finishes reward / done / power.
-// dynamic LDS: see epilogue_lds_bytes().
+// dynamic LDS: EpilogueLds.
 constexpr int kEpiEnvs = 16;     // 16 envs x 8 B = one 128-byte line of a slab row per (chunk, sum): round 1's 4 envs fetched 32-byte pieces
 constexpr int kEpiGroups = 4;
 constexpr int kEpiOutSlots = 16;   // threads per env in the output phase
-__host__ __device__ inline size_t epilogue_lds_bytes(int NS, int n_obs, int n_fiber, int MRW_used, int MRS_used) {
-  return ((size_t)kEpiGroups * NS * kEpiEnvs + (size_t)NS * kEpiEnvs + (size_t)(n_obs + n_fiber + 1) * kEpiEnvs +
-          (size_t)(n_obs + n_fiber) * MRW_used * 2 + (size_t)MRS_used * 2) * sizeof(double);
-}
-// offset (doubles) of the epilogue's output powers pw [n_out + 1][kEpiEnvs] in its LDS: the observation of env e is pw[j * kEpiEnvs + e], j < n_obs
-__host__ __device__ inline size_t epilogue_pw_offset(int NS) { return (size_t)kEpiGroups * NS * kEpiEnvs + (size_t)NS * kEpiEnvs; }
+// The epilogue's dynamic LDS: offsets and total in doubles.  MRW / MRS: the table counts the partial slabs hold (NS = 2 (MRW + MRS) sums per
+// env: the padded counts of the fast kernels; float64 validation handles carry the counts in use there), n_out = n_obs + n_fiber.
+//   part  [kEpiGroups][NS][kEpiEnvs]   sums of each chunk group
+//   U     [NS][kEpiEnvs]               their totals: U_m = U[(2 m) * kEpiEnvs + e], V_m = U[(2 m + 1) * kEpiEnvs + e]
+//   pw    [n_out + 1][kEpiEnvs]        powers of the outputs, then Strehl: the observation of env e is pw[j * kEpiEnvs + e], j < n_obs
+//   cfs   [n_out][MRW_used][2]         coefficient matrices of the outputs
+//   cfsci [MRS_used][2]                and of the science amplitude
+struct EpilogueLds {
+  size_t part = 0, U, pw, cfs, cfsci, total;
+  __host__ __device__ EpilogueLds(int MRW, int MRS, int n_out, int MRW_used, int MRS_used) {
+    const size_t NS = 2 * (size_t)(MRW + MRS);
+    U = part + kEpiGroups * NS * kEpiEnvs;
+    pw = U + NS * kEpiEnvs;
+    cfs = pw + (size_t)(n_out + 1) * kEpiEnvs;
+    cfsci = cfs + (size_t)n_out * MRW_used * 2;
+    total = cfsci + (size_t)MRS_used * 2;
+  }
+  __host__ __device__ explicit EpilogueLds(const EpilogueArgs& p) : EpilogueLds(p.MRW, p.MRS, p.n_obs + p.n_fiber, p.MRW_used, p.MRS_used) {}
+  __host__ __device__ size_t bytes() const { return total * sizeof(double); }
+};
 __device__ __forceinline__ void epilogue_body(const EpilogueArgs& p, int block, double* __restrict__ sm) {
   const int e = threadIdx.x & (kEpiEnvs - 1);
   const int q = (threadIdx.x / kEpiEnvs) & 15;            // sum slot
@@ -245,11 +266,8 @@ __device__ __forceinline__ void epilogue_body(const EpilogueArgs& p, int block, 
   const int NS = 2 * MR;
   const int n_out = p.n_obs + p.n_fiber;
   const size_t cstride = (size_t)NS * p.Bp;
-  double* part = sm;                                              // [group][NS][4]
-  double* U = part + (size_t)kEpiGroups * NS * kEpiEnvs;          // [NS][4]: U_m = U[(2m) * 4 + e], V_m = U[(2m + 1) * 4 + e]
-  double* pw = sm + epilogue_pw_offset(NS);                       // [n_out + 1][4]: powers of the outputs, then Strehl
-  double* cfs = pw + (size_t)(n_out + 1) * kEpiEnvs;              // [n_out][MRW_used][2] then [MRS_used][2]
-  double* cfsci = cfs + (size_t)n_out * p.MRW_used * 2;
+  const EpilogueLds lay(p);
+  double *part = sm + lay.part, *U = sm + lay.U, *pw = sm + lay.pw, *cfs = sm + lay.cfs, *cfsci = sm + lay.cfsci;
   // the per-env state the last phase updates is requested now (it would otherwise be one more memory round trip at the very end)
   int tr_prev = 0;
   float ret_prev = 0.f;
@@ -341,23 +359,13 @@ __global__ __launch_bounds__(1024) void k_epilogue(EpilogueArgs p) {
 // workgroups [0, n_epi) run the epilogue, the rest the prologue with one env per wave, 16 per workgroup (same arithmetic in the same order
 // as the standalone kernel's four: bit-identical).  One launch and one dispatch gap less per step.
 constexpr int kEpiProEnvs = 16;
-struct PrologueArgs {
-  const float* action;
-  const double* gram;
-  double* act_dm;
-  float* act_rev;
-  _Float16* act16;
-  int B, A, A_pad, Bp, sh_operation;
-  double target, two_over_lambda;
-};
 __global__ __launch_bounds__(1024) void k_epilogue_prologue(EpilogueArgs p, PrologueArgs q, int n_epi) {
   extern __shared__ double sm[];
   if ((int)blockIdx.x < n_epi) {
     epilogue_body(p, (int)blockIdx.x, sm);
     return;
   }
-  prologue_body<true, kEpiProEnvs>(q.action, q.gram, q.act_dm, q.act_rev, q.act16, q.B, q.A, q.A_pad, q.Bp, q.sh_operation, q.target, q.two_over_lambda,
-                                   (int)blockIdx.x - n_epi);
+  prologue_body<true, kEpiProEnvs>(q, (int)blockIdx.x - n_epi);
 }
 
 // Zero-fill on the caller's stream as a kernel of the library (the per-step paths zero a few KB .. MB: barrier tickets, lenslet sums,

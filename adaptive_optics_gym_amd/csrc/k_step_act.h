@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kStepActThreads) void k_epilogue_act_prologue(Epilo
   float ov = 0.f;
   const int i = threadIdx.x;
   if (obs_from_lds && i < a.S * 16) {
-    const double w = sm[epilogue_pw_offset(2 * (p.MRW + p.MRS)) + i];
+    const double w = sm[EpilogueLds(p).pw + i];
     ov = (float)(_Float16)w;
   }
   __syncthreads();
@@ -65,8 +65,7 @@ __global__ __launch_bounds__(kStepActThreads) void k_epilogue_act_prologue(Epilo
   }
   __syncthreads();
   actor_mlp<kStepActThreads, kStepActPre>(a, lds_act, env0, pre);   // (ends with a barrier: the actions are written and the LDS is free)
-  prologue_body_lds<true, kEpiEnvs>(q.action, q.gram, q.act_dm, q.act_rev, q.act16, q.B, q.A, q.A_pad, q.Bp, q.sh_operation, q.target, q.two_over_lambda,
-                                    block, sm, sm + 64 * 64);
+  prologue_body_lds<true, kEpiEnvs>(q, block, sm, sm + 64 * 64);
 }
 
 }  // namespace aog
