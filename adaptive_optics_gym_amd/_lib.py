@@ -60,6 +60,14 @@ class AogActor(C.Structure):  # mirrors aog_actor in include/aogym.h
                 ("seed", C.c_uint64), ("call_index", C.c_uint64)]
 
 
+class AogActionNoise(C.Structure):  # mirrors aog_action_noise (action form of a policy query: mode, optional OU state)
+    _fields_ = [("mode", C.c_int32), ("reserved0", C.c_int32), ("ou_state", C.c_void_p), ("ou_mu", C.c_double), ("ou_theta", C.c_double),
+                ("ou_sigma", C.c_double)]
+
+
+AOG_ACTION_MODE = {"sample": 0, "mean": 1}
+
+
 class AogObsMft(C.Structure):  # mirrors aog_obs_mft (ABI 20)
     _fields_ = [("o", C.c_int32), ("reserved0", C.c_int32), ("m1", C.POINTER(C.c_double)), ("m2", C.POINTER(C.c_double))]
 
@@ -104,8 +112,13 @@ SYMBOLS = {
     "aog_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "aog_get_phase_screen": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "aog_actor_act": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_actor_act_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AogActionNoise),
+                                      C.c_void_p]),
     "aog_reset_act": (C.c_int, [C.c_void_p, C.POINTER(AogActor)] + [C.c_void_p] * 6),
+    "aog_reset_act_noise": (C.c_int, [C.c_void_p, C.POINTER(AogActor)] + [C.c_void_p] * 5 + [C.POINTER(AogActionNoise), C.c_void_p]),
     "aog_step_act": (C.c_int, [C.c_void_p, C.POINTER(AogActor)] + [C.c_void_p] * 10 + [C.POINTER(C.c_int), C.c_void_p]),
+    "aog_step_act_noise": (C.c_int, [C.c_void_p, C.POINTER(AogActor)] + [C.c_void_p] * 10 + [C.POINTER(C.c_int), C.POINTER(AogActionNoise),
+                                                                                            C.c_void_p]),
     "aog_device_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "aog_set_return_accumulator": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_get_actuators": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -155,7 +168,7 @@ def load():
         if have.split("+")[0] != want:
             raise RuntimeError(f"libaogym.so was built from other sources (build id {have}, sources {want}): run "
                                "`python -m adaptive_optics_gym_amd.build` (or __graft_entry__.build())")
-    for which, cls in enumerate((AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite, AogObsMft)):
+    for which, cls in enumerate((AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite, AogObsMft, AogActionNoise)):
         if lib.aog_struct_size(which) != C.sizeof(cls):
             raise RuntimeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, the library's struct {lib.aog_struct_size(which)}")
     _lib = lib

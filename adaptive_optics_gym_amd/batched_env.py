@@ -661,9 +661,15 @@ class BatchedAOEnv:
 
     # ------------------------------------------------------------------------------------------------
     # causal policy stepping: the rollout's actor.get_action(obs) -> env.step(action) (algorithm.py:256-262) with the policy attached
-    def _policy_net(self, policy, cov_var, policy_out):
-        """(aog_actor of the policy's next query, (action, log_prob, mean) output tensors) for the fused tail (aog_reset_act / aog_step_act)."""
+    def _policy_net(self, policy, cov_var, policy_out, ou_noise=None, action_mode="sample"):
+        """(aog_actor of the policy's next query, (action, log_prob, mean) output tensors, aog_action_noise or None) for the fused tail
+        (aog_reset_act / aog_step_act, their _noise forms when ``ou_noise`` or ``action_mode`` differ from the defaults)."""
+        from .rollout import action_noise
+
         torch = self._torch
+        noise = action_noise(ou_noise, action_mode)
+        if ou_noise is not None:
+            ou_noise.check(self.num_envs, self.num_modes, self.device)
         if int(policy.env_id_base) != self.global_env_offset:
             raise ValueError(f"policy.env_id_base ({policy.env_id_base}) != env.global_env_offset ({self.global_env_offset}): the policy's random "
                              "streams are keyed by the global env id of row 0")
@@ -682,48 +688,58 @@ class BatchedAOEnv:
             if (t is None and required) or (t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()
                                                                or t.device != self.device)):
                 raise ValueError("policy_out: expected contiguous float32 (action [B, A], log_prob [B], mean [B, A] or None) tensors on the env's device")
-        return policy.net(B, cov_var, layers), (action, log_prob, mean)
+        return policy.net(B, cov_var, layers), (action, log_prob, mean), noise
 
-    def reset_with_policy(self, policy, cov_var=0.5, policy_out=None, mask=None):
+    def reset_with_policy(self, policy, cov_var=0.5, policy_out=None, mask=None, ou_noise=None, action_mode="sample"):
         """``reset()`` of the whole batch with ``policy`` (a ``rollout.DeviceActor``) attached (``aog_reset_act``): the reset's last launch
         also queries the policy on the reset observation and loads the resulting action into the mirror, so the next ``step_with_policy``
         steps it (pass no ``action`` there).  Returns ``((obs, info), (action, log_prob, mean))``; the query consumes one of the policy's call
         indices, exactly like ``policy(obs)``.  ``policy_out``: (action [B, A], log_prob [B], mean [B, A] or None) float32 tensors to write
-        into.  Masked resets are not fused (the query covers the whole batch): use ``reset(mask)`` and pass the first action."""
+        into.  Masked resets are not fused (the query covers the whole batch): use ``reset(mask)`` and pass the first action.
+        ``ou_noise`` (a ``rollout.DeviceOUNoise`` of [B, A]) / ``action_mode="mean"``: the query's action form, as in ``DeviceActor.__call__``
+        (``aog_reset_act_noise``)."""
         if mask is not None:
             raise ValueError("reset_with_policy resets the whole batch; reset some envs with reset(mask) and step with an explicit action")
         torch = self._torch
-        net, (action, log_prob, mean) = self._policy_net(policy, cov_var, policy_out)
+        net, (action, log_prob, mean), noise = self._policy_net(policy, cov_var, policy_out, ou_noise, action_mode)
         if self.atm_type == "semi_dynamic":
             self._generate_screens(mask=None)  # layer.reset() (AO_env.py:76-77)
         n = self.obs_dim ** 2
         obs = torch.empty((self.num_envs, n), dtype=torch.float16, device=self.device)
         obs_raw = torch.empty((self.num_envs, n), dtype=torch.float32, device=self.device)
         p = C.c_void_p
-        _lib.check(self.lib.aog_reset_act(self._handle, C.byref(net), p(obs_raw.data_ptr()), p(obs.data_ptr()), p(action.data_ptr()),
-                                          p(log_prob.data_ptr()), p(mean.data_ptr() if mean is not None else None), self._stream()))
+        args = (self._handle, C.byref(net), p(obs_raw.data_ptr()), p(obs.data_ptr()), p(action.data_ptr()), p(log_prob.data_ptr()),
+                p(mean.data_ptr() if mean is not None else None))
+        if noise is None:
+            _lib.check(self.lib.aog_reset_act(*args, self._stream()))
+        else:
+            _lib.check(self.lib.aog_reset_act_noise(*args, C.byref(noise), self._stream()))
         policy.calls += 1
         self.last_obs_raw = obs_raw
         return (obs, {}), (action, log_prob, mean)
 
-    def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None):
+    def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None, ou_noise=None, action_mode="sample"):
         """``step()`` with ``policy`` (a ``rollout.DeviceActor``) attached (``aog_step_act``): steps the action left pending by
         ``reset_with_policy`` or the previous call (``action=None``), or ``action`` (first step after a plain ``reset``; an error while one
         is pending).  Unless this is the episode's last step, the step's last launch also queries the policy on the new observation and
         loads that action into the mirror for the next call: one launch where ``step`` + ``policy(obs)`` + the next ``step``'s prologue take
         three.  Bit-identical to that unfused loop.  Returns ``(step tuple, (action, log_prob, mean))``, or ``(step tuple, None)`` on the
         episode's last step (no query, no call index consumed, ``policy_out`` untouched).  ``out`` as in ``step``; ``policy_out`` as in
-        ``reset_with_policy``."""
+        ``reset_with_policy``; ``ou_noise`` / ``action_mode`` as there (``aog_step_act_noise``: the OU state advances only when the policy is
+        queried)."""
         a = self._as_actions(action) if action is not None else None
-        net, pol = self._policy_net(policy, cov_var, policy_out)
+        net, pol, noise = self._policy_net(policy, cov_var, policy_out, ou_noise, action_mode)
         if self.atm_type == "dynamic" and self._host_rng:
             self._host_extrusion_noise()
         ret, ptrs, obs_raw = self._step_outputs(out)
         p = C.c_void_p
         queried = C.c_int(0)
-        _lib.check(self.lib.aog_step_act(self._handle, C.byref(net), p(a.data_ptr() if a is not None else None), p(ptrs[0]), p(ptrs[1]), p(ptrs[2]),
-                                         p(ptrs[3]), p(ptrs[4]), p(ptrs[5]), p(pol[0].data_ptr()), p(pol[1].data_ptr()),
-                                         p(pol[2].data_ptr() if pol[2] is not None else None), C.byref(queried), self._stream()))
+        args = (self._handle, C.byref(net), p(a.data_ptr() if a is not None else None), p(ptrs[0]), p(ptrs[1]), p(ptrs[2]), p(ptrs[3]), p(ptrs[4]),
+                p(ptrs[5]), p(pol[0].data_ptr()), p(pol[1].data_ptr()), p(pol[2].data_ptr() if pol[2] is not None else None), C.byref(queried))
+        if noise is None:
+            _lib.check(self.lib.aog_step_act(*args, self._stream()))
+        else:
+            _lib.check(self.lib.aog_step_act_noise(*args, C.byref(noise), self._stream()))
         self.timestep += 1
         self.last_obs_raw = obs_raw
         if not queried.value:

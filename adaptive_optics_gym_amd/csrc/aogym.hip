@@ -252,7 +252,9 @@ size_t epilogue_lds(const aog_env* e) { return aog::EpilogueLds(e->MRW, e->MRS, 
 // the policy attached to aog_reset_act / aog_step_act: its arguments (actor_args, checked before the call changes anything) and outputs
 struct ActTail {
   aog::ActorArgs a;
-  size_t lds = 0;   // the query's own dynamic LDS
+  size_t lds = 0;      // the query's own dynamic LDS
+  aog::ActorNoise nz{};
+  bool noisy = false;  // nz needs k_epilogue_act_prologue_noise (aog_action_noise: mean mode / OU term)
 };
 
 // the prologue of a step from `action` (k_prologue, k_epilogue_prologue, k_epilogue_act_prologue)
@@ -316,8 +318,14 @@ int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, flo
     a.obs = obs;
     a.obs_f16 = 1;
     const size_t lds_all = aog::step_act_lds_bytes(lds, tail->lds);   // (<= kLdsBytes: checked by step_act_tail)
-    if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue_act_prologue), lds_all, e->device)) return rc;
-    hipLaunchKernelGGL(aog::k_epilogue_act_prologue, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, a, q, obs_from_lds);
+    const void* kernel = tail->noisy ? reinterpret_cast<const void*>(aog::k_epilogue_act_prologue_noise)
+                                     : reinterpret_cast<const void*>(aog::k_epilogue_act_prologue);
+    if (int rc = aog_host::ensure_dynamic_lds(kernel, lds_all, e->device)) return rc;
+    if (tail->noisy)
+      hipLaunchKernelGGL(aog::k_epilogue_act_prologue_noise, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, aog::ActorNoiseArgs{a, tail->nz}, q,
+                         obs_from_lds);
+    else
+      hipLaunchKernelGGL(aog::k_epilogue_act_prologue, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, a, q, obs_from_lds);
   } else if (action_next) {
     const aog::PrologueArgs q = prologue_args(e, action_next);
     if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue_prologue), lds, e->device)) return rc;
@@ -401,6 +409,7 @@ int64_t aog_struct_size(int which) {
     case 5: return (int64_t)sizeof(aog_info);
     case 6: return (int64_t)sizeof(aog_layer_composite);
     case 7: return (int64_t)sizeof(aog_obs_mft);
+    case 8: return (int64_t)sizeof(aog_action_noise);
     default: return -1;
   }
 }
@@ -987,8 +996,9 @@ int aog_set_actuators(aog_env* e, const double* act_dev, void* stream) {
 namespace {
 // the checks of aog_reset_act / aog_step_act that concern the policy, made before the call changes anything; fills the tail's arguments
 int step_act_tail(const aog_env* e, const aog_actor* net, const char* who, uint16_t* obs, float* action_out, float* log_prob_out, float* mean_out,
-                  ActTail* t) {
+                  const aog_action_noise* noise, ActTail* t) {
   if (!e || !net || !obs || !action_out || !log_prob_out) return fail(AOG_ERR_INVALID, "%s: null argument", who);
+  if (int rc = action_noise_args(noise, who, &t->nz, &t->noisy)) return rc;
   if (net->batch != e->B || net->state_dim != e->n_obs || net->act_dim != e->A)
     return fail(AOG_ERR_INVALID, "%s: the actor (batch %d, state_dim %d, act_dim %d) does not fit the handle (batch %d, obs_dim^2 %d, n_modes %d)", who,
                 net->batch, net->state_dim, net->act_dim, e->B, e->n_obs, e->A);
@@ -1109,13 +1119,17 @@ extern "C" {
 
 int aog_reset(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, void* stream) { return reset_impl(e, mask, obs_raw, obs, stream, nullptr); }
 
-int aog_reset_act(aog_env* e, const aog_actor* net, float* obs_raw, uint16_t* obs, float* action_out, float* log_prob_out, float* mean_out,
-                  void* stream) {
+int aog_reset_act_noise(aog_env* e, const aog_actor* net, float* obs_raw, uint16_t* obs, float* action_out, float* log_prob_out, float* mean_out,
+                        const aog_action_noise* noise, void* stream) {
   if (!e) return fail(AOG_ERR_INVALID, "aog_reset_act: null handle");
   if (int rc = refuse_pre_evolved(e, "aog_reset_act")) return rc;
   ActTail t{};
-  if (int rc = step_act_tail(e, net, "aog_reset_act", obs, action_out, log_prob_out, mean_out, &t)) return rc;
+  if (int rc = step_act_tail(e, net, "aog_reset_act", obs, action_out, log_prob_out, mean_out, noise, &t)) return rc;
   return reset_impl(e, nullptr, obs_raw, obs, stream, &t);
+}
+int aog_reset_act(aog_env* e, const aog_actor* net, float* obs_raw, uint16_t* obs, float* action_out, float* log_prob_out, float* mean_out,
+                  void* stream) {
+  return aog_reset_act_noise(e, net, obs_raw, obs, action_out, log_prob_out, mean_out, nullptr, stream);
 }
 
 int aog_step(aog_env* e, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
@@ -1126,8 +1140,9 @@ int aog_step_pipelined(aog_env* e, const float* action, const float* action_next
                        float* power, float* strehl, void* stream) {
   return step_impl(e, action, action_next, true, obs_raw, obs, reward, done, power, strehl, stream);
 }
-int aog_step_act(aog_env* e, const aog_actor* net, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
-                 float* strehl, float* action_out, float* log_prob_out, float* mean_out, int* queried, void* stream) {
+int aog_step_act_noise(aog_env* e, const aog_actor* net, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done,
+                       float* power, float* strehl, float* action_out, float* log_prob_out, float* mean_out, int* queried,
+                       const aog_action_noise* noise, void* stream) {
   if (queried) *queried = 0;
   if (!e) return fail(AOG_ERR_INVALID, "aog_step_act: null handle");
   if (!action && !e->pro_pending)
@@ -1135,8 +1150,12 @@ int aog_step_act(aog_env* e, const aog_actor* net, const float* action, float* o
   if (action && e->pro_pending)
     return fail(AOG_ERR_INVALID, "aog_step_act: an action is pending (from aog_reset_act / aog_step_act / aog_step_pipelined): pass action = NULL");
   ActTail t{};
-  if (int rc = step_act_tail(e, net, "aog_step_act", obs, action_out, log_prob_out, mean_out, &t)) return rc;
+  if (int rc = step_act_tail(e, net, "aog_step_act", obs, action_out, log_prob_out, mean_out, noise, &t)) return rc;
   return step_impl(e, action, nullptr, false, obs_raw, obs, reward, done, power, strehl, stream, &t, queried);
+}
+int aog_step_act(aog_env* e, const aog_actor* net, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
+                 float* strehl, float* action_out, float* log_prob_out, float* mean_out, int* queried, void* stream) {
+  return aog_step_act_noise(e, net, action, obs_raw, obs, reward, done, power, strehl, action_out, log_prob_out, mean_out, queried, nullptr, stream);
 }
 int aog_selftest_sincos(const float* u_dev, float* sin_dev, float* cos_dev, int n, int flavour, void* stream) {
   if (!u_dev || !sin_dev || !cos_dev || n < 0 || flavour < 0 || flavour > 2) return fail(AOG_ERR_INVALID, "aog_selftest_sincos: bad argument");

@@ -11,6 +11,7 @@
 
 namespace aog {
 struct ActorArgs;
+struct ActorNoise;
 }
 
 namespace aog_host {
@@ -108,5 +109,7 @@ int unroll_master(aog_env* e, double* psi_dev, int first, int count, hipStream_t
 // actor.hip: the checks and arguments of a policy query (aog_actor_act, aog_step_act): all but the observations and outputs; *lds = the query's
 // dynamic LDS (activations + weight chunk).  AOG_ERR_UNSUPPORTED (naming the sizes) when they do not fit.
 int actor_args(const aog_actor* net, const char* who, aog::ActorArgs* out, size_t* lds);
+// actor.hip: the checks of an aog_action_noise (NULL: none, AOG_OK) and its kernel form; *noisy = the query runs the NOISE instantiation.
+int action_noise_args(const aog_action_noise* nz, const char* who, aog::ActorNoise* out, bool* noisy);
 
 }  // namespace aog_host

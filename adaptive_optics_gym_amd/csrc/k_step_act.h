@@ -68,4 +68,44 @@ __global__ __launch_bounds__(kStepActThreads) void k_epilogue_act_prologue(Epilo
   prologue_body_lds<true, kEpiEnvs>(q, block, sm, sm + 64 * 64);
 }
 
+// k_epilogue_act_prologue with the query's action form a.nz (aog_reset_act_noise / aog_step_act_noise: mean mode and / or an OU term), as in
+// k_actor_act_noise.  A kernel of its own, the body above repeated: the plain kernel keeps its arguments and code (a shared body changes its
+// register allocation; see profiles/action_noise.md).
+__global__ __launch_bounds__(kStepActThreads) void k_epilogue_act_prologue_noise(EpilogueArgs p, ActorNoiseArgs a, PrologueArgs q, int obs_from_lds) {
+  extern __shared__ double sm[];
+  const int block = (int)blockIdx.x;
+  const int env0 = block * kEpiEnvs;
+  const bool act = env0 < a.B;   // (uniform per workgroup: the padding past B runs the epilogue only)
+  f32x4 pre[kStepActPre];
+  if (act) actor_issue<kStepActThreads, kStepActPre>(pre, a.w1, a.S, a.H, 0, a.wfloats);
+  epilogue_body(p, block, sm);
+  __syncthreads();
+  if (!act) return;
+  // table route: this thread's element of the staged observations (k = i / 16, env e = i % 16; S * 16 <= 49 * 16 < 1024) out of the
+  // epilogue's LDS before the activations overwrite it, rounded to float16 exactly as the epilogue stored it
+  float ov = 0.f;
+  const int i = threadIdx.x;
+  if (obs_from_lds && i < a.S * 16) {
+    const double w = sm[EpilogueLds(p).pw + i];
+    ov = (float)(_Float16)w;
+  }
+  __syncthreads();
+  float* lds_act = reinterpret_cast<float*>(sm);
+  float* xa = lds_act;
+  for (int j = threadIdx.x; j < (int)actor_act_floats(a.kpad, a.kpad_b); j += kStepActThreads) lds_act[j] = 0.f;
+  __syncthreads();
+  if (obs_from_lds) {
+    if (i < a.S * 16) xa[i] = ov;
+  } else {
+    const _Float16* obs = reinterpret_cast<const _Float16*>(a.obs);
+    for (int j = threadIdx.x; j < a.S * 16; j += kStepActThreads) {
+      const int k = j >> 4, e = j & 15, env = min(env0 + e, a.B - 1);
+      xa[j] = (float)obs[(size_t)env * a.S + k];
+    }
+  }
+  __syncthreads();
+  actor_mlp<kStepActThreads, kStepActPre, true, ActorNoiseArgs>(a, lds_act, env0, pre);   // (ends with a barrier: the actions are written and the LDS is free)
+  prologue_body_lds<true, kEpiEnvs>(q, block, sm, sm + 64 * 64);
+}
+
 }  // namespace aog

@@ -100,6 +100,65 @@ class OrnsteinUhlenbeckNoise:
         return self.state
 
 
+class DeviceOUNoise:
+    """DDPG's exploration noise (``network.py:259-274``, ``algorithm.py:258-259``) advanced INSIDE the HIP policy query (``aog_action_noise``):
+    a float64 state ``[num_envs, action_dim]`` on the device, like the reference's ``np.ones(...) * mu``, that every query it is passed to
+    (``DeviceActor(..., ou_noise=)``, ``BatchedAOEnv.reset_with_policy`` / ``step_with_policy(..., ou_noise=)``, ``rollout(..., ou_noise=)``)
+    advances once: ``s = s + (theta (mu - s) + sigma n)`` in float64, then ``action = float32(float64(action) + s)``.  The normals come from
+    the query's Philox streams keyed by the GLOBAL env id, so a split batch reproduces the whole one; torch's generator plays no part.
+    ``reset(mask)`` puts the masked envs (all of them without a mask) back to ``mu``; like the reference's, ``rollout`` never resets it."""
+
+    def __init__(self, num_envs: int, action_dim: int, mu: float = 0.0, theta: float = 0.3, sigma: float = 0.05, device=None):
+        import torch
+
+        num_envs, action_dim = int(num_envs), int(action_dim)
+        if num_envs < 1 or action_dim < 1:
+            raise ValueError(f"DeviceOUNoise: num_envs ({num_envs}) and action_dim ({action_dim}) must be >= 1")
+        self.mu, self.theta, self.sigma = float(mu), float(theta), float(sigma)
+        if not all(math.isfinite(v) for v in (self.mu, self.theta, self.sigma)) or self.sigma < 0:
+            raise ValueError(f"DeviceOUNoise: mu, theta, sigma must be finite and sigma >= 0 (got {self.mu}, {self.theta}, {self.sigma})")
+        device = torch.device(device if device is not None else "cuda")
+        if device.type != "cuda":
+            raise ValueError(f"DeviceOUNoise: the state lives on the GPU, not on {device}")
+        self.state = torch.full((num_envs, action_dim), self.mu, dtype=torch.float64, device=device)
+
+    def reset(self, mask=None):
+        import torch
+
+        if mask is None:
+            self.state.fill_(self.mu)
+            return
+        m = torch.as_tensor(mask, device=self.state.device)
+        if m.dtype != torch.bool or tuple(m.shape) != (self.state.shape[0],):
+            raise ValueError(f"DeviceOUNoise.reset: mask must be a bool vector of {self.state.shape[0]} entries")
+        self.state[m] = self.mu
+
+    def check(self, batch: int, action_dim: int, device):
+        """ValueError unless the state fits a query of ``batch`` rows and ``action_dim`` units on ``device``."""
+        import torch
+
+        st = self.state
+        if (not isinstance(st, torch.Tensor) or st.dtype != torch.float64 or not st.is_contiguous() or tuple(st.shape) != (int(batch), int(action_dim))
+                or st.device != torch.device(device)):
+            raise ValueError(f"ou_noise: the state must be a contiguous float64 [{batch}, {action_dim}] tensor on {device} "
+                             f"(got {getattr(st, 'dtype', type(st))} {tuple(getattr(st, 'shape', ()))} on {getattr(st, 'device', None)})")
+
+
+def action_noise(ou_noise=None, action_mode: str = "sample"):
+    """The ``aog_action_noise`` of a HIP query, or None when both are the defaults (the plain entry points run).  ValueError for an unknown
+    mode or an ``ou_noise`` that is not a ``DeviceOUNoise``."""
+    from . import _lib
+
+    if action_mode not in _lib.AOG_ACTION_MODE:
+        raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
+    if ou_noise is not None and not isinstance(ou_noise, DeviceOUNoise):
+        raise ValueError("ou_noise of a HIP policy query must be a DeviceOUNoise (the torch OrnsteinUhlenbeckNoise is added outside the query)")
+    if ou_noise is None and action_mode == "sample":
+        return None
+    ptr, mu, theta, sigma = (None, 0.0, 0.0, 0.0) if ou_noise is None else (ou_noise.state.data_ptr(), ou_noise.mu, ou_noise.theta, ou_noise.sigma)
+    return _lib.AogActionNoise(_lib.AOG_ACTION_MODE[action_mode], 0, ptr, mu, theta, sigma)
+
+
 # rollout()'s DeviceActor per actor module.  Kept here, NOT on the module: a DeviceActor holds the ctypes library handle, which can be
 # neither deep-copied (target networks) nor pickled (torch.save of the module).  Weak keys, and DeviceActor only holds a weak
 # reference back to its module, so neither keeps the other alive.
@@ -157,8 +216,10 @@ class DeviceActor:
         return _lib.AogActor(int(batch), S, H, A, self.env_id_base, 0, *[C.c_void_p(t.data_ptr()) for layer in layers for t in (layer.weight, layer.bias)],
                              self.dropout_p, float(cov_var), self.seed, self.calls)
 
-    def __call__(self, obs, cov_var: float = 0.5, out=None):
-        """obs [B, S] float16 or float32 on the GPU -> (action [B, A] float32, log_prob [B] float32, mean [B, A])."""
+    def __call__(self, obs, cov_var: float = 0.5, out=None, ou_noise=None, action_mode: str = "sample"):
+        """obs [B, S] float16 or float32 on the GPU -> (action [B, A] float32, log_prob [B] float32, mean [B, A]).  ``action_mode="mean"``:
+        the action is the mean (dropout still active) and log_prob the density there; ``ou_noise`` (a ``DeviceOUNoise`` of [B, A]): its
+        state advances once and is added to the action (``aog_actor_act_noise``)."""
         import torch
 
         C, _lib = self._C, self._lib_mod
@@ -175,16 +236,23 @@ class DeviceActor:
             mean = torch.empty((B, A), dtype=torch.float32, device=obs.device)
         else:
             action, log_prob, mean = out
+        noise = action_noise(ou_noise, action_mode)
+        if ou_noise is not None:
+            ou_noise.check(B, A, obs.device)
         net = self.net(B, cov_var, layers)
         self.calls += 1
-        _lib.check(self.lib.aog_actor_act(C.byref(net), obs.device.index or 0, C.c_void_p(obs.data_ptr()), int(obs.dtype == torch.float16),
-                                          C.c_void_p(mean.data_ptr()), C.c_void_p(action.data_ptr()), C.c_void_p(log_prob.data_ptr()),
-                                          C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)))
+        args = (C.byref(net), obs.device.index or 0, C.c_void_p(obs.data_ptr()), int(obs.dtype == torch.float16), C.c_void_p(mean.data_ptr()),
+                C.c_void_p(action.data_ptr()), C.c_void_p(log_prob.data_ptr()))
+        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        if noise is None:
+            _lib.check(self.lib.aog_actor_act(*args, stream))
+        else:
+            _lib.check(self.lib.aog_actor_act_noise(*args, C.byref(noise), stream))
         return action, log_prob, mean
 
 
 def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, generator=None, actor_impl: str = "auto", seed: int = 0,
-            dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None, fused_policy: bool = False):
+            dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None, fused_policy: bool = False, action_mode: str = "sample"):
     """Collect ``episodes`` lock-step episodes from ``env`` (a ``BatchedAOEnv``).
 
     ``actor_impl``: "hip" = the fused policy-query kernel (``DeviceActor``), "torch" = the module's own forward +
@@ -199,12 +267,19 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     ``policy="shack"`` (``algorithm.py:252-253``, the 'SHACK' algorithm): the action of every step comes from ``env.SH_step()`` (the
     Shack-Hartmann integrator on the device; needs an env built with ``SH_operation=True``), ``actor`` may be None and ``log_prob`` holds the
     reference's constant 1.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
-    action before the env sees it (and before it is stored, like the reference's in-place ``action +=``).
+    action before the env sees it (and before it is stored, like the reference's in-place ``action +=``), or a ``DeviceOUNoise``
+    (``main.py:218-220``: mu 0, theta 0.3, sigma 0.05), which the HIP policy query advances and adds itself: float64 state, Philox normals keyed
+    by the global env id (a split batch reproduces the whole one), no extra launch.  Neither is reset here, as in the reference.
+
+    ``action_mode="mean"`` (evaluation, ``eval_policy.py:31``): the action is the policy's mean with dropout still active, ``log_prob`` the
+    density of ``N(mean, cov_var I)`` there; with ``actor_impl="torch"`` the action is ``actor(obs)``.  A ``DeviceOUNoise`` needs the HIP
+    query, and neither a ``DeviceOUNoise`` nor ``action_mode="mean"`` goes with ``policy="shack"``: ValueError.
 
     ``fused_policy=True``: the policy query rides with the env step (``env.reset_with_policy`` / ``env.step_with_policy``, one launch where
     the epilogue of step t, the query on its observation and the prologue of step t + 1 take three): needs ``policy="actor"`` resolved to
-    ``actor_impl="hip"`` and no ``ou_noise`` (the noise would have to be added between the query and the prologue); ValueError otherwise.
-    Returns the same dict, bit for bit, as the unfused loop with the same ``DeviceActor`` (seed and call counter)."""
+    ``actor_impl="hip"``, and takes a ``DeviceOUNoise`` and ``action_mode`` but not the torch ``OrnsteinUhlenbeckNoise`` (that noise would have
+    to be added between the query and the prologue); ValueError otherwise.  Returns the same dict, bit for bit, as the unfused loop with the
+    same ``DeviceActor`` (seed and call counter) and, if any, an OU state equal to the unfused loop's."""
     import numpy as np
     import torch
 
@@ -216,7 +291,12 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         gatherer = EpisodeReturnGatherer(B, env.device, False)
     if policy not in ("actor", "shack"):
         raise ValueError("policy must be 'actor' or 'shack'")
+    if action_mode not in ("sample", "mean"):
+        raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
     shack = policy == "shack"
+    dev_ou = isinstance(ou_noise, DeviceOUNoise)
+    if shack and (dev_ou or action_mode != "sample"):
+        raise ValueError("policy='shack' takes neither a DeviceOUNoise nor action_mode='mean' (the Shack-Hartmann integrator is not a policy query)")
     if shack:
         if not getattr(env, "SH_operation", False):
             raise ValueError("policy='shack' needs an env created with SH_operation=True (AO_env.py:115-116, 254)")
@@ -231,13 +311,22 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         if dev_actor is None or dev_actor.seed != int(seed) or dev_actor.env_id_base != base or dev_actor.actor is not actor:
             dev_actor = DeviceActor(actor, seed=seed, env_id_base=base)
             _DEVICE_ACTORS[actor] = dev_actor
+    if dev_ou and not shack and dev_actor is None:
+        raise ValueError("a DeviceOUNoise is advanced by the HIP policy query (actor_impl='hip'); the torch query takes an OrnsteinUhlenbeckNoise")
+    # the query's action-form keywords, passed only when they differ from the defaults
+    pkw = {}
+    if dev_ou:
+        pkw["ou_noise"] = ou_noise
+    if action_mode != "sample":
+        pkw["action_mode"] = action_mode
     if fused_policy:
         if shack:
             raise ValueError("fused_policy=True needs policy='actor' (the Shack-Hartmann integrator is not a policy query)")
         if dev_actor is None:
             raise ValueError("fused_policy=True needs the HIP policy query (actor_impl='hip': a make_actor / reference Actor module with CUDA weights)")
-        if ou_noise is not None:
-            raise ValueError("fused_policy=True cannot add ou_noise: the noise would have to enter between the policy query and the prologue")
+        if ou_noise is not None and not dev_ou:
+            raise ValueError("fused_policy=True cannot add the torch ou_noise: the noise would have to enter between the policy query and the "
+                             "prologue (a DeviceOUNoise is added inside the query)")
     import inspect
 
     step_takes_out = "out" in inspect.signature(env.step).parameters
@@ -251,7 +340,7 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     ep_returns = []
     if fused_policy:
         with torch.no_grad():
-            out = _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns)
+            out = _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns, pkw)
     else:
         with torch.no_grad():
             i = 0
@@ -274,12 +363,16 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                         out["log_prob"][i].fill_(1.0)
                         action = out["act"][i]
                     elif dev_actor is not None:
-                        action, _, _ = dev_actor(obs, cov_var, out=(out["act"][i], out["log_prob"][i], mean_buf))
+                        action, _, _ = dev_actor(obs, cov_var, out=(out["act"][i], out["log_prob"][i], mean_buf), **pkw)
+                    elif action_mode == "mean":   # eval_policy.py:31: the mean, dropout still active; log_prob = the density at the mean
+                        out["act"][i].copy_(actor(obs))
+                        out["log_prob"][i].fill_(-0.5 * A * math.log(2 * math.pi * cov_var))
+                        action = out["act"][i]
                     else:
                         action, log_prob = sample_action(actor(obs), cov_var, generator)
                         out["act"][i].copy_(action)
                         out["log_prob"][i].copy_(log_prob)
-                    if ou_noise is not None:
+                    if ou_noise is not None and not dev_ou:
                         out["act"][i].add_(ou_noise.sample())           # algorithm.py:258-259
                         action = out["act"][i]
                     if step_takes_out:   # the env writes the transition straight into this step's slices
@@ -308,8 +401,9 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     return out
 
 
-def _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns):
-    """rollout(fused_policy=True)'s loop: reset_with_policy writes row i0's action, step i the action of row i + 1 (none on the last step)."""
+def _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns, pkw):
+    """rollout(fused_policy=True)'s loop: reset_with_policy writes row i0's action, step i the action of row i + 1 (none on the last step).
+    ``pkw``: the query's action-form keywords (ou_noise, action_mode) that differ from the defaults."""
     import torch
 
     B, S, A, dev = env.num_envs, int(env.obs_dim) ** 2, int(env.num_modes), env.device
@@ -320,14 +414,14 @@ def _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns):
     mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
     for e in range(episodes):
         i0 = e * T
-        (obs, _), _ = env.reset_with_policy(dev_actor, cov_var, policy_out=(out["act"][i0], out["log_prob"][i0], mean_buf))
+        (obs, _), _ = env.reset_with_policy(dev_actor, cov_var, policy_out=(out["act"][i0], out["log_prob"][i0], mean_buf), **pkw)
         gatherer.start_episode()
         out["obs"][i0].copy_(obs)
         for t in range(T):
             i = i0 + t
             last = t == T - 1
             pol_out = None if last else (out["act"][i + 1], out["log_prob"][i + 1], mean_buf)
-            _, pol = env.step_with_policy(dev_actor, cov_var, out=(out["next_obs"][i], out["rew"][i], out["done"][i]), policy_out=pol_out)
+            _, pol = env.step_with_policy(dev_actor, cov_var, out=(out["next_obs"][i], out["rew"][i], out["done"][i]), policy_out=pol_out, **pkw)
             if (pol is None) != last:
                 raise RuntimeError(f"step_with_policy {'did not query' if pol is None else 'queried'} the policy at step {t + 1} of {T}: the env's "
                                    "episode length differs from timesteps_per_episode")

@@ -120,7 +120,7 @@ const char* aog_build_id(void);
 const char* aog_last_error(void);
 /* sizeof() of the structs of this header as the library was compiled, so that a binding in another language can verify its own
  * declarations at load time: which = 0 aog_config, 1 aog_tables, 2 aog_layer_tables, 3 aog_sh_tables, 4 aog_actor, 5 aog_info, 6 aog_layer_composite,
- * 7 aog_obs_mft; -1 for any other value. */
+ * 7 aog_obs_mft, 8 aog_action_noise; -1 for any other value. */
 int64_t aog_struct_size(int which);
 
 /* AOEnv.__init__ (AO_env.py:17-71): allocate the handle and its state on `device`. */
@@ -377,6 +377,29 @@ typedef struct aog_actor {
 int aog_actor_act(const aog_actor* net, int device, const void* obs_dev, int obs_is_f16, float* mean_dev /* [batch][act] */,
                   float* action_dev /* [batch][act] */, float* log_prob_dev /* [batch] */, void* stream);
 
+/* ---- action forms of the policy query: evaluation (the mean) and DDPG's exploration noise (algorithm.py:258-259, network.py:259-274) ----
+ * For each (env < batch, unit) let g = the float32 action of aog_actor_act (mean + sqrt(cov_var) eps).
+ *   mode  AOG_ACTION_SAMPLE: g as is.  AOG_ACTION_MEAN: g = mean (the same float as mean_dev), dropout as net->dropout_p says, no eps;
+ *         log_prob = the density of N(mean, cov_var I) at the mean = -0.5 act_dim log(2 pi cov_var).
+ *   ou_state  NULL: no OU term.  Otherwise the caller's Ornstein-Uhlenbeck state [batch][act] float64 on the device, advanced once per query
+ *         in the reference's order, float64, no fused multiply-add: s = s + (ou_theta (ou_mu - s) + ou_sigma n); then
+ *         action = (float)((double)g + s) (numpy's float32 += float64).  mean and log_prob do not change.  The normals n ~ N(0, 1) come from
+ *         Philox4x32-10 keyed by (seed, call_index, GLOBAL env id, unit) under a stream tag of their own (independent of the dropout masks
+ *         and eps), so a split batch reproduces the whole batch bit for bit, whichever entry point runs the query.  Rows >= batch (ragged
+ *         workgroups, padding) are not touched.
+ * AOG_ERR_INVALID for a mode other than 0 / 1, a nonzero reserved0, a non-finite ou_mu / ou_theta / ou_sigma or ou_sigma < 0 (checked
+ * before any device work).  The _noise entry points with noise = NULL are the plain ones; the plain ones forward to them with NULL. */
+#define AOG_ACTION_SAMPLE 0
+#define AOG_ACTION_MEAN 1
+typedef struct aog_action_noise {
+  int32_t mode;                         /* AOG_ACTION_SAMPLE or AOG_ACTION_MEAN */
+  int32_t reserved0;                    /* = 0 */
+  double* ou_state;                     /* [batch][act] float64 device pointer, nullable */
+  double ou_mu, ou_theta, ou_sigma;     /* main.py:218-220: 0, 0.3, 0.05 */
+} aog_action_noise;
+int aog_actor_act_noise(const aog_actor* net, int device, const void* obs_dev, int obs_is_f16, float* mean_dev, float* action_dev, float* log_prob_dev,
+                        const aog_action_noise* noise /* nullable */, void* stream);
+
 /* ---- causal policy stepping (ABI 21): the rollout's actor.get_action(obs) -> env.step(action) (algorithm.py:256-262) with the policy
  * attached to the env.  The epilogue of step t, the policy query (aog_actor_act's arithmetic) on its float16 observation and the
  * action -> actuator prologue of step t + 1 run as ONE launch, 16 envs per workgroup: results bit-identical to aog_step + aog_actor_act
@@ -404,6 +427,14 @@ int aog_reset_act(aog_env* env, const aog_actor* net, float* obs_raw_dev, uint16
 int aog_step_act(aog_env* env, const aog_actor* net, const float* action_dev, float* obs_raw_dev, uint16_t* obs_dev, float* reward_dev,
                  uint8_t* done_dev, float* power_dev, float* strehl_dev, float* action_out, float* log_prob_out, float* mean_out,
                  int* queried /* host int, nullable */, void* stream);
+/* aog_reset_act / aog_step_act with an action form (aog_action_noise above; NULL = the plain calls).  The fused tail applies it exactly as
+ * aog_actor_act_noise does: the action it writes and loads into the mirror is the noisy / mean one, and the OU state advances once per query
+ * (not on an episode's last step, which queries nothing). */
+int aog_reset_act_noise(aog_env* env, const aog_actor* net, float* obs_raw_dev, uint16_t* obs_dev, float* action_out, float* log_prob_out,
+                        float* mean_out /* nullable */, const aog_action_noise* noise /* nullable */, void* stream);
+int aog_step_act_noise(aog_env* env, const aog_actor* net, const float* action_dev, float* obs_raw_dev, uint16_t* obs_dev, float* reward_dev,
+                       uint8_t* done_dev, float* power_dev, float* strehl_dev, float* action_out, float* log_prob_out, float* mean_out,
+                       int* queried /* host int, nullable */, const aog_action_noise* noise /* nullable */, void* stream);
 
 /* Self-test hook: sin(2 pi u), cos(2 pi u) for n float32 revolutions u_dev with the fused kernels' device code.
  * flavour 0 = polynomial, 1 = v_sin_f32/v_cos_f32 after the exact reduction, 2 = v_sin_f32/v_cos_f32 on raw input. */
