@@ -1,4 +1,4 @@
-// libaogym.so — C-ABI (include/aogym.h) over the gfx950 kernels in aogym_kernels.h.
+// libaogym.so — C-ABI (include/aogym.h) over the gfx950 kernels in the k_*.h headers.
 // Host side only: argument checking, table conversion/upload, launch geometry, stream-ordered launches.
 #include "host_common.h"
 #include "k_pack.h"
@@ -19,6 +19,15 @@
 #include <type_traits>
 #include <vector>
 
+#ifdef AOG_DEV
+namespace aog_host { long long* dev_timeline = nullptr; }
+extern "C" int aog_dev_read_timeline(void* dst, size_t nbytes) {   // developer builds only: not in include/aogym.h
+  if (!aog_host::dev_timeline) return -1;
+  if (hipDeviceSynchronize() != hipSuccess) return -2;
+  return hipMemcpy(dst, aog_host::dev_timeline, nbytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
+}
+#endif
+
 namespace aog_host {
 
 thread_local std::string g_last_error;
@@ -32,19 +41,7 @@ int fail(int code, const char* fmt, ...) {
   g_last_error = buf;
   return code;
 }
-}  // namespace aog_host
-using namespace aog_host;
 
-
-#ifdef AOG_DEV
-namespace aog_host { long long* dev_timeline = nullptr; }
-extern "C" int aog_dev_read_timeline(void* dst, size_t nbytes) {   // developer builds only: not in include/aogym.h
-  if (!aog_host::dev_timeline) return -1;
-  if (hipDeviceSynchronize() != hipSuccess) return -2;
-  return hipMemcpy(dst, aog_host::dev_timeline, nbytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
-}
-#endif
-namespace aog_host {
 int ensure_dynamic_lds(const void* fn, size_t bytes, int device) {
   if (bytes <= 64 * 1024) return AOG_OK;   // the default limit
   static std::mutex mu;
@@ -61,8 +58,6 @@ int ensure_dynamic_lds(const void* fn, size_t bytes, int device) {
   }
   return AOG_OK;
 }
-}  // namespace aog_host
-namespace aog_host {
 
 int dev_alloc_bytes(aog_env* e, void** out, size_t bytes, bool zero) {
   void* p = nullptr;
@@ -75,6 +70,8 @@ int dev_alloc_bytes(aog_env* e, void** out, size_t bytes, bool zero) {
   return AOG_OK;
 }
 
+// give a work buffer of the handle back (workspaces that are re-sized when the caller changes the synthesis method or oversampling:
+// without this every change would keep the old gigabytes until aog_destroy)
 void dev_release_ptr(aog_env* e, void** ptr) {
   if (!*ptr) return;
   for (size_t i = 0; i < e->allocs.size(); ++i)
@@ -94,19 +91,29 @@ void zero_words(void* p, size_t n_words, hipStream_t s) {
   if (n_words) hipLaunchKernelGGL(aog::k_zero_words, dim3(blocks), dim3(256), 0, s, static_cast<uint32_t*>(p), n_words);
 }
 
-// A bounded inter-workgroup wait of an earlier launch timed out (k_extrude16_split): every screen that launch touched is suspect.
-// The flag lives in pinned host memory, so this costs one load and no synchronisation; it is seen at the latest by the call after
-// the one whose launch tripped it.  Installing fresh screens for the whole batch (aog_set_screens / aog_set_state) clears it.
-int check_poisoned(const aog_env* e, const char* who) {
-  if (e->host_flag && *static_cast<volatile const int*>(e->host_flag) != 0)
-    return fail(AOG_ERR_STATE, "%s: %s; the screens of this handle are invalid (install new screens for the whole batch or restore a saved state)", who,
-                (*static_cast<volatile const int*>(e->host_flag) & 2) ? "an earlier aog_step failed after its counters had moved"
-                                                                     : "an inter-workgroup wait of the dynamic-atmosphere kernel timed out in an earlier step");
+int poisoned(const aog_env* e) { return e->host_flag ? *static_cast<volatile const int*>(e->host_flag) : 0; }
+
+void poison(aog_env* e, int bits) {
+  if (e->host_flag) *static_cast<volatile int*>(e->host_flag) |= bits;
+}
+
+int clear_poison(aog_env* e) {
+  HIP_TRY(hipMemset(e->dev_status, 0, sizeof(int)));
+  *static_cast<volatile int*>(e->host_flag) = 0;
   return AOG_OK;
 }
 
-// give a work buffer of the handle back (workspaces that are re-sized when the caller changes the synthesis method or oversampling:
-// without this every change would keep the old gigabytes until aog_destroy)
+// A bounded inter-workgroup wait of an earlier launch timed out (k_extrude16_split): every screen that launch touched is suspect.
+// The status word is seen at the latest by the call after the one whose launch tripped it.  Installing fresh screens for the whole batch
+// (aog_set_screens / aog_set_state) clears it.
+int check_poisoned(const aog_env* e, const char* who) {
+  if (const int bits = poisoned(e))
+    return fail(AOG_ERR_STATE, "%s: %s; the screens of this handle are invalid (install new screens for the whole batch or restore a saved state)", who,
+                (bits & 2) ? "an earlier aog_step failed after its counters had moved"
+                           : "an inter-workgroup wait of the dynamic-atmosphere kernel timed out in an earlier step");
+  return AOG_OK;
+}
+
 // With lookahead on, between aog_step(t) and aog_step(t + 1) the screens already stand at step t + 1: anything that reads or replaces
 // them then would see (or break) a state the env is not in.  Episode boundaries are safe: the last step of an episode does not look ahead.
 int refuse_pre_evolved(const aog_env* e, const char* who) {
@@ -119,45 +126,49 @@ int refuse_pre_evolved(const aog_env* e, const char* who) {
   return AOG_OK;
 }
 
-int load_actuators(aog_env* e, hipStream_t s, _Float16* act_ll) {
+int check_env_range(const char* who, int first, int count, int B) {
+  if (first < 0 || count < 0 || first + count > B) return fail(AOG_ERR_INVALID, "%s: env range [%d,%d) outside [0,%d)", who, first, first + count, B);
+  return AOG_OK;
+}
+
+int load_actuators(aog_env* e, hipStream_t s, ActTargets to) {
   const int n = e->B * e->A_pad;
-  hipLaunchKernelGGL(aog::k_load_actuators, dim3((n + 255) / 256), dim3(256), 0, s, e->act_dm, e->act_rev, e->act16, e->B, e->A, e->A_pad, e->Bp,
-                     2.0 / e->cfg.wavelength_wfs, act_ll);
+  hipLaunchKernelGGL(aog::k_load_actuators, dim3((n + 255) / 256), dim3(256), 0, s, e->act_dm, to.act_rev, to.act16, e->B, e->A, e->A_pad, e->Bp,
+                     2.0 / e->cfg.wavelength_wfs, to.act_ll);
   HIP_TRY(hipGetLastError());
   return AOG_OK;
 }
 
-int load_actuators_into(aog_env* e, hipStream_t s, _Float16* act16, _Float16* act_ll) {
-  const int n = e->B * e->A_pad;
-  hipLaunchKernelGGL(aog::k_load_actuators, dim3((n + 255) / 256), dim3(256), 0, s, e->act_dm, (float*)nullptr, act16, e->B, e->A, e->A_pad, e->Bp,
-                     2.0 / e->cfg.wavelength_wfs, act_ll);
-  HIP_TRY(hipGetLastError());
-  return AOG_OK;
+std::vector<int32_t> ap_yx_table(const aog_env* e) {
+  const int N = e->cfg.n_pupil;
+  std::vector<int32_t> yx(e->ap_index_host.size());
+  for (size_t i = 0; i < yx.size(); ++i) yx[i] = ((e->ap_index_host[i] / N) << 16) | (e->ap_index_host[i] % N);
+  return yx;
 }
 
 // New screens for the WHOLE batch make a handle whose extrusion kernel once timed out usable again (see check_poisoned).  Called by the
 // public entry points with the range of the whole call (aog_generate_screens installs large batches in several chunks).  Dynamic handles
 // drain the stream first: a timeout of a launch that is still running would otherwise poison the screens just installed.
 int clear_poison_if_whole(aog_env* e, int first, int count, hipStream_t s) {
-  if (first != 0 || count != e->B || !e->host_flag) return AOG_OK;
+  if (first != 0 || count != e->B) return AOG_OK;
   if (e->cfg.atm_dynamic) HIP_TRY(hipStreamSynchronize(s));
-  if (*static_cast<volatile int*>(e->host_flag)) {
+  if (poisoned(e)) {
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemset(e->dev_status, 0, sizeof(int)));
-    *static_cast<volatile int*>(e->host_flag) = 0;
+    return clear_poison(e);
   }
   return AOG_OK;
 }
-}  // namespace aog_host
 
+// "anything else takes the 128 launchers": float64 validation handles (A_pad a multiple of 8) never launch through them
+const ApadLaunchers& launchers_for(int A_pad) {
+  switch (A_pad) {
+    case 16: return apad_launchers<16>();
+    case 32: return apad_launchers<32>();
+    case 64: return apad_launchers<64>();
+    default: return apad_launchers<128>();
+  }
+}
 
-namespace aog_host {
-#define AOG_PHASE_DECL(A)                                                                                                          \
-  int launch_phase_apad##A(aog_env* e, hipStream_t s, const _Float16* act16, float* out_tile);                                     \
-  int launch_phase_field_apad##A(aog_env* e, hipStream_t s, const _Float16* act16, const aog::PhaseFieldArgs& fa, bool grid);      \
-  int launch_phase_grid_apad##A(aog_env* e, hipStream_t s, const _Float16* act16, const aog::PhaseFieldArgs& fa, int etile0, int n_et);
-AOG_PHASE_DECL(16) AOG_PHASE_DECL(32) AOG_PHASE_DECL(64) AOG_PHASE_DECL(128)
-#undef AOG_PHASE_DECL
 // grid = true: one float per pixel (reduced phase) instead of the complex field: see k_phase_mfma<.., GRID>
 void launch_phase_field(aog_env* e, hipStream_t s, const _Float16* act16, float* field, size_t env_stride, int row_stride, bool grid) {
   aog::PhaseFieldArgs fa{};
@@ -171,12 +182,7 @@ void launch_phase_field(aog_env* e, hipStream_t s, const _Float16* act16, float*
   fa.B = e->B;
   fa.N = e->cfg.n_pupil;
   fa.amplitude = (float)e->sh_amp;
-  switch (e->A_pad) {
-    case 16: launch_phase_field_apad16(e, s, act16, fa, grid); break;
-    case 32: launch_phase_field_apad32(e, s, act16, fa, grid); break;
-    case 64: launch_phase_field_apad64(e, s, act16, fa, grid); break;
-    default: launch_phase_field_apad128(e, s, act16, fa, grid); break;
-  }
+  launchers_for(e->A_pad).phase_field(e, s, act16, fa, grid);
 }
 void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, const _Float16* act_ll, float* grid, size_t env_stride, int row_stride, int etile0,
                        int n_et) {
@@ -190,22 +196,11 @@ void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, const _
   fa.n_ap = e->n_ap;
   fa.B = e->B - etile0 * 32;
   fa.N = e->cfg.n_pupil;
-  switch (e->A_pad) {
-    case 16: launch_phase_grid_apad16(e, s, act16, fa, etile0, n_et); break;
-    case 32: launch_phase_grid_apad32(e, s, act16, fa, etile0, n_et); break;
-    case 64: launch_phase_grid_apad64(e, s, act16, fa, etile0, n_et); break;
-    default: launch_phase_grid_apad128(e, s, act16, fa, etile0, n_et); break;
-  }
+  launchers_for(e->A_pad).phase_grid(e, s, act16, fa, etile0, n_et);
 }
-void launch_phase(aog_env* e, hipStream_t s, const _Float16* act16, float* out_tile) {
-  switch (e->A_pad) {
-    case 16: launch_phase_apad16(e, s, act16, out_tile); break;
-    case 32: launch_phase_apad32(e, s, act16, out_tile); break;
-    case 64: launch_phase_apad64(e, s, act16, out_tile); break;
-    default: launch_phase_apad128(e, s, act16, out_tile); break;
-  }
-}
+void launch_phase(aog_env* e, hipStream_t s, const _Float16* act16, float* out_tile) { launchers_for(e->A_pad).phase(e, s, act16, out_tile); }
 }  // namespace aog_host
+using namespace aog_host;
 
 namespace {
 
@@ -218,27 +213,14 @@ int pick_pad(int v, const int* opts, int n) {
 const int kApadOpts[] = {16, 32, 64, 128};
 const int kMrwOpts[] = {7, 12, 20, 28};
 
-int launch_fast(aog_env* e, hipStream_t s) {
-  switch (e->A_pad) {
-    case 16: return aog_host::launch_fused_apad16(e, s);
-    case 32: return aog_host::launch_fused_apad32(e, s);
-    case 64: return aog_host::launch_fused_apad64(e, s);
-    default: return aog_host::launch_fused_apad128(e, s);
-  }
-}
-
 int launch_fused(aog_env* e, hipStream_t s) {
-  // event timing of one launch block in profile_every: the two records cost ~3 us each on the stream, so a throughput measurement that
-  // also wants the kernel's duration samples instead of timing every launch
-  // (blocks of 8 consecutive launches, one block in profile_every: a timed launch mostly sees the same neighbours as with every launch timed)
-  // (the MIDDLE block of each period of profile_every blocks: a short window's first launches come right after a synchronisation and are its slowest)
-  const bool timed = e->profile && ((e->profile_phase++ / (unsigned)e->profile_block) % (unsigned)e->profile_every) == (unsigned)e->profile_every / 2;
+  const bool timed = e->profile && profile_sampled(e, e->profile_phase++);   // (this launch advances the counter: evolve_layer only reads it)
   TimedRegion tr(e, s, AOG_PROF_FUSED, timed);
   if (e->cfg.precision == AOG_PRECISION_FP64) {
     hipLaunchKernelGGL(aog::k_fused_ref, dim3(e->B), dim3(256), 0, s, e->modes64, e->tabs64, e->psi64, e->act_dm,
                        e->partials, e->n_ap, e->A, e->MRW_used, e->MRS_used, e->Bp, e->cfg.wavelength_wfs,
                        e->cfg.wavelength_sci);
-  } else if (int rc = launch_fast(e, s)) {
+  } else if (int rc = launchers_for(e->A_pad).fused(e, s)) {
     return rc;   // (the dynamic-LDS request of this shape was refused: the message names the size)
   }
   HIP_TRY(hipGetLastError());
@@ -342,13 +324,12 @@ template <typename T>
 int set_screens(aog_env* e, const T* psi, int first, int count, hipStream_t s, bool means_ready = false) {
   if (!e || !psi) return fail(AOG_ERR_INVALID, "aog_set_screens: null argument");
   if (!e->tables_ready) return fail(AOG_ERR_STATE, "aog_set_screens before aog_upload_tables");
-  if (first < 0 || count < 0 || first + count > e->B)
-    return fail(AOG_ERR_INVALID, "aog_set_screens: env range [%d,%d) outside [0,%d)", first, first + count, e->B);
+  if (int rc = check_env_range("aog_set_screens", first, count, e->B)) return rc;
   if (int rc = refuse_pre_evolved(e, "aog_set_screens")) return rc;
   if (int rcd = x8_drop_ahead(e)) return rcd;   // (work done ahead for the next step read the state this call changes)
   if (count == 0) return AOG_OK;
   HIP_TRY(hipSetDevice(e->device));
-  const double inv = 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs);
+  const double inv = rev_per_metre(e);
   const int N2 = e->cfg.n_pupil * e->cfg.n_pupil;
   if (e->cfg.atm_dynamic) {
     if (int rcs = std::is_same<T, double>::value ? store_master_f64(e, reinterpret_cast<const double*>(psi), first, count, s)
@@ -525,15 +506,9 @@ int aog_create(const aog_config* cfg, int device, aog_env** out) {
     TRY_ALLOC(dev_alloc(e, &e->origin, (size_t)e->B * 2));
     e->n_ext_groups = (e->B + aog::kExt16G - 1) / aog::kExt16G;
     TRY_ALLOC(dev_alloc(e, &e->ext_bar, (size_t)2 * round_up(e->n_ext_groups, 8)));   // two ticket sets (see evolve_layer)
-    TRY_ALLOC(dev_alloc(e, &e->ext_perm, (size_t)e->n_ext_groups * aog::kExt16G));
-    {
-      std::vector<int32_t> ident((size_t)e->n_ext_groups * aog::kExt16G, -1);
-      for (int i = 0; i < e->B; ++i) ident[i] = i;
-      if (hipMemcpy(e->ext_perm, ident.data(), sizeof(int32_t) * ident.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        aog_destroy(e);
-        return fail(AOG_ERR_HIP, "aog_create: hipMemcpy failed");
-      }
-    }
+    std::vector<int32_t> ident((size_t)e->n_ext_groups * aog::kExt16G, -1);
+    for (int i = 0; i < e->B; ++i) ident[i] = i;
+    TRY_ALLOC(upload(e, &e->ext_perm, ident));
     TRY_ALLOC(dev_alloc(e, &e->ext_counter, (size_t)e->B));
     TRY_ALLOC(dev_alloc(e, &e->velocity, (size_t)e->B * 2));
     TRY_ALLOC(dev_alloc(e, &e->psi_offset, (size_t)e->B));
@@ -618,6 +593,7 @@ int aog_upload_tables(aog_env* e, const aog_tables* t) {
     if (p && t->ap_index[p] <= t->ap_index[p - 1]) return fail(AOG_ERR_INVALID, "aog_upload_tables: ap_index must be strictly increasing");
   }
   HIP_TRY(hipMemcpy(e->ap_index, t->ap_index, sizeof(int32_t) * n_ap, hipMemcpyHostToDevice));
+  e->ap_index_host.assign(t->ap_index, t->ap_index + n_ap);
   {
     const int Nw = (e->cfg.n_pupil + 31) / 32;
     std::vector<uint32_t> bits((size_t)e->cfg.n_pupil * Nw, 0u);
@@ -625,11 +601,7 @@ int aog_upload_tables(aog_env* e, const aog_tables* t) {
       const int f = t->ap_index[p], iy = f / e->cfg.n_pupil, ix = f % e->cfg.n_pupil;
       bits[(size_t)iy * Nw + (ix >> 5)] |= 1u << (ix & 31);
     }
-    if (!e->ap_bits) {
-      const int rcb = dev_alloc(e, &e->ap_bits, bits.size(), false);
-      if (rcb != AOG_OK) return rcb;
-    }
-    HIP_TRY(hipMemcpy(e->ap_bits, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice));
+    if (int rc = upload(e, &e->ap_bits, bits, true)) return rc;
   }
   HIP_TRY(hipMemcpy(e->gram, t->gram, sizeof(double) * A * A, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->wfs_coef, t->wfs_coef, sizeof(double) * e->n_out * e->MRW_used * 2, hipMemcpyHostToDevice));
@@ -729,37 +701,26 @@ int aog_upload_tables(aog_env* e, const aog_tables* t) {
       }
     if (ok) {
       int rc;
-      if ((rc = dev_alloc(e, &e->quad_desc, desc.size(), false)) != AOG_OK) return rc;
-      if ((rc = dev_alloc(e, &e->quad_cont, cont.size(), false)) != AOG_OK) return rc;
+      if ((rc = upload(e, &e->quad_desc, desc)) != AOG_OK) return rc;
+      if ((rc = upload(e, &e->quad_cont, cont)) != AOG_OK) return rc;
       if ((rc = dev_alloc(e, &e->psi_ring, (size_t)e->B * N * (N + 4), true)) != AOG_OK) return rc;
-      HIP_TRY(hipMemcpy(e->quad_desc, desc.data(), sizeof(uint32_t) * desc.size(), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(e->quad_cont, cont.data(), sizeof(uint32_t) * cont.size(), hipMemcpyHostToDevice));
       e->ring_direct = true;
     }
   }
   if (t->focal_m1 && t->focal_m2 && t->n_focal > 0 && !e->focal_m1) {
     const int N = e->cfg.n_pupil, nf = t->n_focal;
     int rc;
-    if ((rc = dev_alloc(e, &e->focal_m1, (size_t)nf * N * 2, false)) != AOG_OK) return rc;
-    if ((rc = dev_alloc(e, &e->focal_m2, (size_t)nf * N * 2, false)) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->focal_m1, t->focal_m1, (size_t)nf * N * 2)) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->focal_m2, t->focal_m2, (size_t)nf * N * 2)) != AOG_OK) return rc;
     if ((rc = dev_alloc(e, &e->focal_E, (size_t)N * N * 2)) != AOG_OK) return rc;
     if ((rc = dev_alloc(e, &e->focal_T, (size_t)nf * N * 2)) != AOG_OK) return rc;
-    HIP_TRY(hipMemcpy(e->focal_m1, t->focal_m1, sizeof(double) * nf * N * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->focal_m2, t->focal_m2, sizeof(double) * nf * N * 2, hipMemcpyHostToDevice));
     if (e->cfg.precision == AOG_PRECISION_FAST) {   // split-f16 operand tables of the batched matrix-core path (k_focal_pass1 / k_focal_pass2)
       const int Nxp = round_up(N, 128), Nyp = round_up(N, 16), nfp = round_up(nf, 128);
       std::vector<_Float16> m1s, m2s;
-      const float unscale = mft_operand_tables(t->focal_m1, t->focal_m2, N, nf, nfp, Nxp, Nyp, m1s, m2s);
-      if ((rc = dev_alloc(e, &e->focal_m1s, m1s.size(), false)) != AOG_OK) return rc;
-      if ((rc = dev_alloc(e, &e->focal_m2s, m2s.size(), false)) != AOG_OK) return rc;
-      HIP_TRY(hipMemcpy(e->focal_m1s, m1s.data(), sizeof(_Float16) * m1s.size(), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(e->focal_m2s, m2s.data(), sizeof(_Float16) * m2s.size(), hipMemcpyHostToDevice));
-      e->focal_unscale = unscale;
-      std::vector<int32_t> apidx((size_t)e->n_ap), yx((size_t)e->n_ap);
-      HIP_TRY(hipMemcpy(apidx.data(), e->ap_index, sizeof(int32_t) * e->n_ap, hipMemcpyDeviceToHost));
-      for (int i = 0; i < e->n_ap; ++i) yx[i] = ((apidx[i] / N) << 16) | (apidx[i] % N);
-      if (!e->focal_ap_yx && (rc = dev_alloc(e, &e->focal_ap_yx, yx.size(), false)) != AOG_OK) return rc;
-      HIP_TRY(hipMemcpy(e->focal_ap_yx, yx.data(), sizeof(int32_t) * yx.size(), hipMemcpyHostToDevice));
+      e->focal_unscale = mft_operand_tables(t->focal_m1, t->focal_m2, N, nf, nfp, Nxp, Nyp, m1s, m2s);
+      if ((rc = upload(e, &e->focal_m1s, m1s)) != AOG_OK) return rc;
+      if ((rc = upload(e, &e->focal_m2s, m2s)) != AOG_OK) return rc;
+      if ((rc = upload(e, &e->focal_ap_yx, ap_yx_table(e), true)) != AOG_OK) return rc;
     }
     e->n_focal = nf;
   }
@@ -789,7 +750,7 @@ int aog_get_screens_f64(aog_env* e, double* psi_dev, int first, int count, void*
   if (!e || !psi_dev) return fail(AOG_ERR_INVALID, "aog_get_screens_f64: null argument");
   if (!e->screens_ready) return fail(AOG_ERR_STATE, "aog_get_screens_f64 before any screen was installed");
   if (int rc = refuse_pre_evolved(e, "aog_get_screens_f64")) return rc;
-  if (first < 0 || count < 0 || first + count > e->B) return fail(AOG_ERR_INVALID, "aog_get_screens_f64: env range outside [0,%d)", e->B);
+  if (int rc = check_env_range("aog_get_screens_f64", first, count, e->B)) return rc;
   if (count == 0) return AOG_OK;
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -896,19 +857,13 @@ int aog_set_state(aog_env* e, const void* blob_dev, int64_t timestep, void* stre
   e->sh_calls = tail.sh_calls;
   e->steps_since_reset = tail.steps_since_reset;
   e->sh_sums_ready = false;
-  if (e->host_flag && *static_cast<volatile int*>(e->host_flag)) {   // a restored state replaces every screen: the handle is usable again
-    HIP_TRY(hipMemset(e->dev_status, 0, sizeof(int)));
-    *static_cast<volatile int*>(e->host_flag) = 0;
-  }
+  if (poisoned(e))   // a restored state replaces every screen: the handle is usable again
+    if (int rc = clear_poison(e)) return rc;
   if (e->ring_direct) {
     int rc = ring_from_master(e, 0, e->B, 1, s);
     if (rc != AOG_OK) return rc;
   }
-  // derived operand layouts follow the restored actuators
-  const int n = e->B * e->A_pad;
-  hipLaunchKernelGGL(aog::k_load_actuators, dim3((n + 255) / 256), dim3(256), 0, s, e->act_dm, e->act_rev, e->act16, e->B, e->A, e->A_pad, e->Bp,
-                     2.0 / e->cfg.wavelength_wfs);
-  HIP_TRY(hipGetLastError());
+  if (int rc = load_actuators(e, s, {e->act_rev, e->act16, nullptr})) return rc;   // derived operand layouts follow the restored actuators
   e->screens_ready = true;
   return AOG_OK;
 }
@@ -917,7 +872,7 @@ int aog_get_phase_screen(aog_env* e, int env_index, float* phase_dev, void* stre
   if (!e || !phase_dev) return fail(AOG_ERR_INVALID, "aog_get_phase_screen: null argument");
   if (!e->screens_ready) return fail(AOG_ERR_STATE, "aog_get_phase_screen before aog_set_screens");
   if (e->cfg.precision != AOG_PRECISION_FAST) return fail(AOG_ERR_UNSUPPORTED, "aog_get_phase_screen: fast precision handles only");
-  if (env_index < 0 || env_index >= e->B) return fail(AOG_ERR_INVALID, "aog_get_phase_screen: env %d outside [0,%d)", env_index, e->B);
+  if (int rc = check_env_range("aog_get_phase_screen", env_index, 1, e->B)) return rc;
   if (int rcp = refuse_pre_evolved(e, "aog_get_phase_screen")) return rcp;
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -942,7 +897,7 @@ int aog_device_status(aog_env* e, int32_t* status_out) {
   HIP_TRY(hipDeviceSynchronize());
   int v[16];
   HIP_TRY(hipMemcpy(v, e->dev_status, sizeof v, hipMemcpyDeviceToHost));
-  *status_out = v[0] | *static_cast<volatile int*>(e->host_flag);
+  *status_out = v[0] | poisoned(e);
 #ifdef AOG_DEV
   if (getenv("AOG_X8_DEV") && (atoi(getenv("AOG_X8_DEV")) & 1024)) {
     fprintf(stderr, "[aogym] k_x8_product: cycles per step max %d min %d, most steps %d, workgroups %d; 10 ns ticks from the first workgroup's start: last start %d, last loop end %d, last end %d; mean start-to-loop-end %d\n", v[8], v[9], v[10], v[11], v[3] - v[2], v[4] - v[2], v[5] - v[2], v[11] ? v[6] / v[11] : 0);
@@ -984,11 +939,7 @@ int aog_set_actuators(aog_env* e, const double* act_dev, void* stream) {
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(hipMemcpyAsync(e->act_dm, act_dev, sizeof(double) * e->B * e->A, hipMemcpyDeviceToDevice, s));
-  const int n = e->B * e->A_pad;
-  hipLaunchKernelGGL(aog::k_load_actuators, dim3((n + 255) / 256), dim3(256), 0, s, e->act_dm, e->act_rev, e->act16,
-                     e->B, e->A, e->A_pad, e->Bp, 2.0 / e->cfg.wavelength_wfs);
-  HIP_TRY(hipGetLastError());
-  return AOG_OK;
+  return load_actuators(e, s, {e->act_rev, e->act16, nullptr});
 }
 
 }  // extern "C"
@@ -1026,17 +977,10 @@ int reset_impl(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, v
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (!mask) e->steps_since_reset = 0;
-  {
-    const int n = e->B * e->A;
-    hipLaunchKernelGGL(aog::k_reset_state, dim3((n + 255) / 256), dim3(256), 0, s, mask, e->act_dm, e->t_render, e->B, e->A,
-                       e->cfg.flat_mirror_start);
-    const int n2 = e->B * e->A_pad;
-    hipLaunchKernelGGL(aog::k_load_actuators, dim3((n2 + 255) / 256), dim3(256), 0, s, e->act_dm, e->act_rev, e->act16,
-                       e->B, e->A, e->A_pad, e->Bp, 2.0 / e->cfg.wavelength_wfs);
-    HIP_TRY(hipGetLastError());
-  }
-  int rc = launch_fused(e, s);
-  if (rc != AOG_OK) return rc;
+  const int n = e->B * e->A;
+  hipLaunchKernelGGL(aog::k_reset_state, dim3((n + 255) / 256), dim3(256), 0, s, mask, e->act_dm, e->t_render, e->B, e->A, e->cfg.flat_mirror_start);
+  int rc = load_actuators(e, s, {e->act_rev, e->act16, nullptr});
+  if (rc != AOG_OK || (rc = launch_fused(e, s)) != AOG_OK) return rc;
   if ((rc = launch_obs(e, s, obs_raw, obs)) != AOG_OK) return rc;
   rc = launch_epilogue(e, false, obs_raw, obs, nullptr, nullptr, nullptr, nullptr, s, nullptr, tail);
   if (rc == AOG_OK && tail) e->pro_pending = true;   // (the mirror holds the first action: aog_step_act(action = NULL) steps it)
@@ -1110,7 +1054,7 @@ int step_impl(aog_env* e, const float* action, const float* action_next, bool pi
   // A launch or a dynamic-LDS request that fails AFTER the step counters moved (and perhaps after the next extrusion was queued) leaves the
   // handle's counters, screens and mirror inconsistent: mark it unusable (bit 1 of the status word; cleared like a barrier timeout, by
   // installing screens for the whole batch or restoring a saved state) instead of letting later steps run on it.
-  if (rc != AOG_OK && mutated && e && e->host_flag) *static_cast<volatile int*>(e->host_flag) |= 2;
+  if (rc != AOG_OK && mutated && e) poison(e, 2);
   return rc;
 }
 }  // namespace

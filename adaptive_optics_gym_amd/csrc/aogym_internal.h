@@ -9,6 +9,10 @@
 #include "../../include/aogym.h"
 #include "fused_layout.h"
 
+namespace aog {
+struct X8Table;
+}
+
 struct aog_env {
   aog_config cfg{};
   int device = 0;
@@ -25,6 +29,7 @@ struct aog_env {
   int64_t dev_bytes = 0;
   // constant tables
   int32_t* ap_index = nullptr;
+  std::vector<int32_t> ap_index_host;   // host copy (aog_upload_tables): ap_yx_table, the micro-lens table of aog_upload_sh
   uint32_t* ap_bits = nullptr;   // [N][ceil(N / 32)] the aperture as a bit mask (bit x & 31 of word x >> 5 of row y): k_screen2_cols' aperture sums
   double* syn_part = nullptr;    // [synthesis batch][column tiles] aperture sums of the screens just drawn, per column tile (k_screen2_cols -> k_mean_from_parts)
   size_t syn_part_elems = 0;
@@ -172,7 +177,7 @@ struct aog_env {
   int nz_v = 0, nz_h = 0;
   // int8 composite extrusion (aog_upload_layer_composite; kernels in k_extrude_i8.h).  x8_host: host copies of the operator tables (opaque here)
   void* x8_host = nullptr;
-  void* x8_tables_dev = nullptr;   // aog::X8Table [2][kX8MaxK + 1]
+  aog::X8Table* x8_tables_dev = nullptr;   // [2][kX8MaxK + 1]
   int x8_kmax[2] = {0, 0};         // k_max uploaded per axis (0 = none)
   int ext_mode = 0;                // AOG_EXTRUDE_*
   int32_t* x8_dxy = nullptr;
@@ -230,15 +235,4 @@ int ensure_dynamic_lds(const void* fn, size_t bytes, int device);
 #ifdef AOG_DEV
 extern long long* dev_timeline;   // per-wave time stamps of the last fused launch (AOG_DEV_TIMELINE=1)
 #endif
-// Fused-kernel launchers, one translation unit per padded mode count so the build parallelises
-// (fused_inst.hip compiled with -DAOG_INST_APAD=16|32|64|128).  Return 0 or the aog_status of a failed dynamic-LDS request.
-int launch_fused_apad16(aog_env* e, hipStream_t s);
-int launch_fused_apad32(aog_env* e, hipStream_t s);
-int launch_fused_apad64(aog_env* e, hipStream_t s);
-int launch_fused_apad128(aog_env* e, hipStream_t s);
-// phase-only contraction u = psi + Mt a for every (pixel, env) with the actuator operands `act16`, written in the psi_tile layout
-void launch_phase(aog_env* e, hipStream_t s, const _Float16* act16, float* out_tile);
-void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, const _Float16* act_ll, float* grid, size_t env_stride, int row_stride, int etile0,
-                       int n_et);
-void launch_phase_field(aog_env* e, hipStream_t s, const _Float16* act16, float* field, size_t env_stride, int row_stride, bool grid);   // complex64 field, or (grid) one float of reduced phase per pixel
 }  // namespace aog_host

@@ -62,11 +62,11 @@ int x8_ensure_buffers(aog_env* e) {
 int x8_evolve(aog_env* e, hipStream_t s, long long step_index) {
   if (int rc = x8_ensure_buffers(e)) return rc;
   aog::X8Args p{};
-  p.tables = static_cast<const aog::X8Table*>(e->x8_tables_dev);
+  p.tables = e->x8_tables_dev;
   p.master = e->psi_master;
   p.ring = e->ring_direct ? e->psi_ring : nullptr;
   p.ring_ref = e->psi_offset;
-  p.ring_inv = 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs);
+  p.ring_inv = rev_per_metre(e);
   p.origin = e->origin;
   p.ext_counter = e->ext_counter;
   p.velocity = e->velocity;
@@ -156,7 +156,7 @@ int aog_host::x8_drop_ahead(aog_env* e) {
 namespace aog_host {
 // float64 ring-buffer master screens of envs [first, first+count) -> the fused kernels' fp32 layouts
 int pack_from_master(aog_env* e, int first, int count, hipStream_t s, bool per_step) {
-  const double inv = 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs);
+  const double inv = rev_per_metre(e);
   const int N2 = e->cfg.n_pupil * e->cfg.n_pupil;
   if (per_step && e->kernel == AOG_KERNEL_MFMA && e->cfg.precision == AOG_PRECISION_FAST && first == 0 && count == e->B) {
     // fast path: offsets = means measured by the previous repack, whole-row writes
@@ -222,9 +222,8 @@ int evolve_layer(aog_env* e, hipStream_t s, long long step_index) {
   p.env_base = e->cfg.env_id_base;
   p.ring = e->ring_direct ? e->psi_ring : nullptr;
   p.ring_ref = e->psi_offset;
-  p.ring_inv = 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs);
-  // (sampled like the fused kernel's launches — blocks of 8 steps, one block in profile_every: two event records cost ~6 us of a 250 us step)
-  TimedRegion tr_ext(e, s, AOG_PROF_EXTRUDE, ((e->profile_phase / (unsigned)e->profile_block) % (unsigned)e->profile_every) == (unsigned)e->profile_every / 2);
+  p.ring_inv = rev_per_metre(e);
+  TimedRegion tr_ext(e, s, AOG_PROF_EXTRUDE, profile_sampled(e, e->profile_phase));   // (the step's fused launch advances the counter)
   if (x8_usable(e)) {
     // int8 matrix-core form: the step's x shifts, then its y shifts, each as one exact fixed-point product (k_extrude_i8.h)
     if (int rc = x8_evolve(e, s, step_index)) return rc;
@@ -247,7 +246,6 @@ int evolve_layer(aog_env* e, hipStream_t s, long long step_index) {
       e->ext_resident = std::max(1, per_cu > 1 ? per_cu - 1 : 1) * cus;
       if (const char* v = getenv("AOG_EXTRUDE_RESIDENT")) e->ext_resident = std::max(8 * aog::kExtParts, atoi(v));   // (tests: force several launches)
     }
-    p.origin = e->origin;
     const int groups8 = round_up(e->n_ext_groups, 8);
     // two ticket sets alternate between steps: this step's launches poll `bar` and zero `bar_next` (both start zeroed at creation)
     unsigned* bar = e->ext_bar + (size_t)(e->ext_bar_phase & 1) * groups8;
@@ -262,15 +260,13 @@ int evolve_layer(aog_env* e, hipStream_t s, long long step_index) {
     HIP_TRY(hipGetLastError());
   } else if (!getenv("AOG_EXTRUDE_SIMPLE") && ext16_lds(e) <= kLdsBytes) {
     // default: float64 matrix-core form, 16 envs per workgroup (a workgroup owns whole envs: no cross-workgroup hazard)
-    const size_t lds = (size_t)aog::kExt16G * ((std::max(e->nz_v, e->nz_h) | 1) + (e->cfg.n_pupil | 1)) * sizeof(double);
+    const size_t lds = ext16_lds(e);
     if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_extrude16), lds, e->device)) return rc;
-    p.origin = e->origin;
     hipLaunchKernelGGL(aog::k_extrude16, dim3((e->B + aog::kExt16G - 1) / aog::kExt16G), dim3(512), lds, s, p, e->B);
     HIP_TRY(hipGetLastError());
   } else {
     const size_t lds = (size_t)aog::kExtG * (std::max(e->nz_v, e->nz_h) + 2 * e->cfg.n_pupil) * sizeof(double);
     if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_extrude), lds, e->device)) return rc;
-    p.origin = e->origin;
     hipLaunchKernelGGL(aog::k_extrude, dim3((e->B + aog::kExtG - 1) / aog::kExtG), dim3(aog::kExtThreads), lds, s, p, e->B);
     HIP_TRY(hipGetLastError());
   }
@@ -283,15 +279,19 @@ int evolve_layer(aog_env* e, hipStream_t s, long long step_index) {
   return pack_from_master(e, 0, e->B, s, true);
 }
 
+// the master screens of every env -> psi_tile alone (aperture mean removed; neither psi_rev nor the repack's offsets and sums are touched)
+static int tiles_from_master(aog_env* e, hipStream_t s) {
+  hipLaunchKernelGGL((aog::k_pack_screens<double>), dim3(e->B), dim3(256), 0, s, e->psi_master, e->ap_index, (float*)nullptr, e->psi_tile,
+                     (double*)nullptr, 0, e->cfg.n_pupil * e->cfg.n_pupil, e->n_ap, e->n_ap_pad, e->Bp, rev_per_metre(e), (const int32_t*)e->origin,
+                     e->cfg.n_pupil, (double*)nullptr, (double*)nullptr);
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
 // psi_tile of a ring-direct handle is only refreshed when something other than the step kernel needs it
 int ensure_tiles(aog_env* e, hipStream_t s) {
   if (!e->ring_direct || !e->tiles_stale) return AOG_OK;
-  const double inv = 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs);
-  const int N2 = e->cfg.n_pupil * e->cfg.n_pupil;
-  hipLaunchKernelGGL((aog::k_pack_screens<double>), dim3(e->B), dim3(256), 0, s, e->psi_master, e->ap_index, (float*)nullptr, e->psi_tile,
-                     (double*)nullptr, 0, N2, e->n_ap, e->n_ap_pad, e->Bp, inv, (const int32_t*)e->origin, e->cfg.n_pupil, (double*)nullptr,
-                     (double*)nullptr);
-  HIP_TRY(hipGetLastError());
+  if (int rc = tiles_from_master(e, s)) return rc;
   e->tiles_stale = false;
   return AOG_OK;
 }
@@ -304,18 +304,12 @@ int obs_tiles(aog_env* e, hipStream_t s) {
   if (!e->cfg.atm_dynamic || e->cfg.precision != AOG_PRECISION_FAST) return AOG_OK;
   if (e->ring_direct) return ensure_tiles(e, s);
   if (e->kernel == AOG_KERNEL_MFMA || e->sh_ready) return AOG_OK;
-  const double inv = 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs);
-  const int N2 = e->cfg.n_pupil * e->cfg.n_pupil;
-  hipLaunchKernelGGL((aog::k_pack_screens<double>), dim3(e->B), dim3(256), 0, s, e->psi_master, e->ap_index, (float*)nullptr, e->psi_tile,
-                     (double*)nullptr, 0, N2, e->n_ap, e->n_ap_pad, e->Bp, inv, (const int32_t*)e->origin, e->cfg.n_pupil, (double*)nullptr,
-                     (double*)nullptr);
-  HIP_TRY(hipGetLastError());
-  return AOG_OK;
+  return tiles_from_master(e, s);
 }
 
 int ring_from_master(aog_env* e, int first, int count, int keep_ref, hipStream_t s) {
   hipLaunchKernelGGL(aog::k_ring_from_master, dim3(count), dim3(256), 0, s, e->psi_master, e->origin, e->ap_index, e->psi_offset, e->psi_ring, first,
-                     e->cfg.n_pupil, e->n_ap, 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs), keep_ref);
+                     e->cfg.n_pupil, e->n_ap, rev_per_metre(e), keep_ref);
   HIP_TRY(hipGetLastError());
   e->tiles_stale = true;
   return AOG_OK;
@@ -378,9 +372,7 @@ int aog_upload_layer(aog_env* e, const aog_layer_tables* t) {
     std::vector<double> tr((size_t)rows * cols);
     for (int r = 0; r < rows; ++r)
       for (int c = 0; c < cols; ++c) tr[(size_t)c * rows + r] = src[(size_t)r * cols + c];
-    if (!*dst && (rc = dev_alloc(e, dst, tr.size(), false)) != AOG_OK) return rc;
-    HIP_TRY(hipMemcpy(*dst, tr.data(), sizeof(double) * tr.size(), hipMemcpyHostToDevice));
-    return AOG_OK;
+    return upload(e, dst, tr, true);
   };
   // src [rows][cols] -> [row block][k / 8][lane = (k % 4) * 16 + row % 16][(k / 4) % 2], zero padded: one 16-B load per lane
   // feeds the A operands of two consecutive v_mfma_f64_16x16x4 k-steps
@@ -392,9 +384,7 @@ int aog_upload_layer(aog_env* e, const aog_layer_tables* t) {
         const int lane = (c & 3) * 16 + (r & 15);
         blk[(((size_t)(r >> 4) * k8 + (c >> 3)) * 64 + lane) * 2 + ((c >> 2) & 1)] = src[(size_t)r * cols + c];
       }
-    if (!*dst && (rc = dev_alloc(e, dst, blk.size(), false)) != AOG_OK) return rc;
-    HIP_TRY(hipMemcpy(*dst, blk.data(), sizeof(double) * blk.size(), hipMemcpyHostToDevice));
-    return AOG_OK;
+    return upload(e, dst, blk, true);
   };
   if (e->layer_ready) return fail(AOG_ERR_STATE, "aog_upload_layer: already uploaded");
   if (int rcp = refuse_pre_evolved(e, "aog_upload_layer")) return rcp;
@@ -432,18 +422,14 @@ int aog_upload_layer(aog_env* e, const aog_layer_tables* t) {
   if ((rc = upload_t(t->B_vertical, N, N, &e->Bt_v)) != AOG_OK) return rc;
   if ((rc = upload_t(Ap_h.data(), N, e->nz_h, &e->At_h)) != AOG_OK) return rc;
   if ((rc = upload_t(t->B_horizontal, N, N, &e->Bt_h)) != AOG_OK) return rc;
-  if ((rc = dev_alloc(e, &e->stencil_v, e->nz_v, false)) != AOG_OK) return rc;
-  if ((rc = dev_alloc(e, &e->stencil_h, e->nz_h, false)) != AOG_OK) return rc;
-  HIP_TRY(hipMemcpy(e->stencil_v, st_v.data(), sizeof(int32_t) * e->nz_v, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->stencil_h, st_h.data(), sizeof(int32_t) * e->nz_h, hipMemcpyHostToDevice));
+  if ((rc = upload(e, &e->stencil_v, st_v)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->stencil_h, st_h)) != AOG_OK) return rc;
   {
     std::vector<int32_t> pv(e->nz_v), ph(e->nz_h);
     for (int k = 0; k < e->nz_v; ++k) pv[k] = (int32_t)(((uint32_t)(st_v[k] / N) << 16) | (uint32_t)(st_v[k] % N));
     for (int k = 0; k < e->nz_h; ++k) ph[k] = (int32_t)(((uint32_t)(st_h[k] / N) << 16) | (uint32_t)(st_h[k] % N));
-    if ((rc = dev_alloc(e, &e->stencil_v_yx, e->nz_v, false)) != AOG_OK) return rc;
-    if ((rc = dev_alloc(e, &e->stencil_h_yx, e->nz_h, false)) != AOG_OK) return rc;
-    HIP_TRY(hipMemcpy(e->stencil_v_yx, pv.data(), sizeof(int32_t) * e->nz_v, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->stencil_h_yx, ph.data(), sizeof(int32_t) * e->nz_h, hipMemcpyHostToDevice));
+    if ((rc = upload(e, &e->stencil_v_yx, pv)) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->stencil_h_yx, ph)) != AOG_OK) return rc;
   }
   e->layer_ready = true;
   if (!e->turb_cn2.empty()) {   // the int8 noise scales are relative to the layer's sqrt(Cn^2)
@@ -490,11 +476,6 @@ int aog_upload_layer_composite(aog_env* e, const aog_layer_composite* t) {
   const int UK = Uk[K];
   if (Uk[1] < 2) return fail(AOG_ERR_INVALID, "aog_upload_layer_composite: the first shift reads %d columns", Uk[1]);
   int rc;
-  auto up = [&](auto** dst, const auto* src, size_t count) -> int {
-    if ((rc = dev_alloc(e, dst, count, false)) != AOG_OK) return rc;
-    HIP_TRY(hipMemcpy(*dst, src, sizeof(**dst) * count, hipMemcpyHostToDevice));
-    return AOG_OK;
-  };
   // ONE table per axis: the rows of shift j of the K-shift operator are the rows of shift j of every k-shift operator, k >= j (slice j depends
   // on the old screen and on the normals of shifts 1 .. j only), so envs of every shift count share it
   const int KsAK = (UK + 31) / 32, KsBK = K * Np / 32, RT = K * Np / 32, KsT = KsAK + KsBK + aog::kX8PadSteps;
@@ -545,10 +526,10 @@ int aog_upload_layer_composite(aog_env* e, const aog_layer_composite* t) {
   int32_t* d_yx = nullptr;
   int8_t* d_T8 = nullptr;
   double *d_r1 = nullptr, *d_r2 = nullptr;
-  if ((rc = up(&d_yx, yx.data(), yx.size())) != AOG_OK) return rc;
-  if ((rc = up(&d_T8, T8.data(), T8.size())) != AOG_OK) return rc;
-  if ((rc = up(&d_r1, r1.data(), r1.size())) != AOG_OK) return rc;
-  if ((rc = up(&d_r2, r2.data(), r2.size())) != AOG_OK) return rc;
+  if ((rc = upload(e, &d_yx, yx)) != AOG_OK) return rc;
+  if ((rc = upload(e, &d_T8, T8)) != AOG_OK) return rc;
+  if ((rc = upload(e, &d_r1, r1)) != AOG_OK) return rc;
+  if ((rc = upload(e, &d_r2, r2)) != AOG_OK) return rc;
   double sx = 0.0, sxx = 0.0;
   for (int k = 1, cc = 0; k <= K; ++k) {   // per shift count: how much of the table an env of that count (prepare) or a row of that shift (product) uses
     for (; cc < Uk[k]; ++cc) {
@@ -566,13 +547,7 @@ int aog_upload_layer_composite(aog_env* e, const aog_layer_composite* t) {
     tb.sxx = sxx;
   }
   e->x8_kmax[t->axis] = K;
-  if (!e->x8_tables_dev) {
-    void* dp = nullptr;
-    if ((rc = dev_alloc_bytes(e, &dp, sizeof h->tab, true)) != AOG_OK) return rc;
-    e->x8_tables_dev = dp;
-  }
-  HIP_TRY(hipMemcpy(e->x8_tables_dev, h->tab, sizeof h->tab, hipMemcpyHostToDevice));
-  return AOG_OK;
+  return upload(e, &e->x8_tables_dev, &h->tab[0][0], sizeof h->tab / sizeof h->tab[0][0], true);
 }
 
 int aog_set_extrusion_mode(aog_env* e, int mode) {

@@ -76,7 +76,7 @@ int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs) {
     return AOG_OK;
   }
   if (int rc = obs_tiles(e, s)) return rc;
-  if (int rc = load_actuators_into(e, s, e->obs_act16, e->obs_act_ll)) return rc;
+  if (int rc = load_actuators(e, s, {nullptr, e->obs_act16, e->obs_act_ll})) return rc;   // (own copies: act_rev / act16 are not touched)
   const int Nxp = obs_nxp(e), Nyp = obs_nyp(e), nxt = Nxp / 32;
   const size_t grid_env = (size_t)Nyp * Nxp;
   for (int env0 = 0; env0 < e->B; env0 += e->obs_chunk) {
@@ -108,30 +108,21 @@ int aog_upload_obs_mft(aog_env* e, const aog_obs_mft* t) {
   int rc;
   if ((rc = dev_alloc(e, &e->obs_pw, (size_t)e->B * e->n_obs)) != AOG_OK) return rc;
   if (e->cfg.precision == AOG_PRECISION_FP64) {
-    if ((rc = dev_alloc(e, &e->obs_m1d, (size_t)o * N * 2, false)) != AOG_OK) return rc;
-    if ((rc = dev_alloc(e, &e->obs_m2d, (size_t)o * N * 2, false)) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->obs_m1d, t->m1, (size_t)o * N * 2)) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->obs_m2d, t->m2, (size_t)o * N * 2)) != AOG_OK) return rc;
     if ((rc = dev_alloc(e, &e->obs_E, (size_t)N * N * 2)) != AOG_OK) return rc;
     if ((rc = dev_alloc(e, &e->obs_T, (size_t)o * N * 2)) != AOG_OK) return rc;
     if ((rc = dev_alloc(e, &e->obs_F, (size_t)e->B * e->n_obs * 2)) != AOG_OK) return rc;
-    HIP_TRY(hipMemcpy(e->obs_m1d, t->m1, sizeof(double) * o * N * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->obs_m2d, t->m2, sizeof(double) * o * N * 2, hipMemcpyHostToDevice));
     e->obs_ready = true;
     return AOG_OK;
   }
   const int Nxp = obs_nxp(e), Nyp = obs_nyp(e);
   std::vector<_Float16> m1s, m2s;
   e->obs_unscale = mft_operand_tables(t->m1, t->m2, N, o, 32, Nxp, Nyp, m1s, m2s);
-  if ((rc = dev_alloc(e, &e->obs_m1s, m1s.size(), false)) != AOG_OK) return rc;
-  if ((rc = dev_alloc(e, &e->obs_m2s, m2s.size(), false)) != AOG_OK) return rc;
-  HIP_TRY(hipMemcpy(e->obs_m1s, m1s.data(), sizeof(_Float16) * m1s.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->obs_m2s, m2s.data(), sizeof(_Float16) * m2s.size(), hipMemcpyHostToDevice));
-  if (!e->focal_ap_yx) {   // (shared with K4: where each packed aperture pixel lies on the pupil grid)
-    std::vector<int32_t> apidx((size_t)e->n_ap), yx((size_t)e->n_ap);
-    HIP_TRY(hipMemcpy(apidx.data(), e->ap_index, sizeof(int32_t) * e->n_ap, hipMemcpyDeviceToHost));
-    for (int i = 0; i < e->n_ap; ++i) yx[i] = ((apidx[i] / N) << 16) | (apidx[i] % N);
-    if ((rc = dev_alloc(e, &e->focal_ap_yx, yx.size(), false)) != AOG_OK) return rc;
-    HIP_TRY(hipMemcpy(e->focal_ap_yx, yx.data(), sizeof(int32_t) * yx.size(), hipMemcpyHostToDevice));
-  }
+  if ((rc = upload(e, &e->obs_m1s, m1s)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->obs_m2s, m2s)) != AOG_OK) return rc;
+  // (shared with K4: where each packed aperture pixel lies on the pupil grid)
+  if (!e->focal_ap_yx && (rc = upload(e, &e->focal_ap_yx, ap_yx_table(e))) != AOG_OK) return rc;
   // work buffers for whole env tiles, at most ~512 MB: the phase grid (every pixel starts out as "outside the aperture": only aperture pixels
   // are ever written) and T'
   const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * 2 * 4 * 64 * 8;
@@ -154,7 +145,7 @@ int aog_focal_image(aog_env* e, int env_index, float* field_dev, void* stream) {
   if (!e || !field_dev) return fail(AOG_ERR_INVALID, "aog_focal_image: null argument");
   if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "aog_focal_image before aog_upload_tables/aog_set_screens");
   if (!e->n_focal) return fail(AOG_ERR_STATE, "aog_focal_image: focal_m1/focal_m2 were not uploaded");
-  if (env_index < 0 || env_index >= e->B) return fail(AOG_ERR_INVALID, "aog_focal_image: env %d outside [0,%d)", env_index, e->B);
+  if (int rc = check_env_range("aog_focal_image", env_index, 1, e->B)) return rc;
   if (int rcp = refuse_pre_evolved(e, "aog_focal_image")) return rcp;
   const bool fast = e->cfg.precision == AOG_PRECISION_FAST;
   if (fast && e->focal_m1s) return aog_focal_images(e, env_index, 1, field_dev, stream);   // the batched matrix-core path
@@ -177,7 +168,7 @@ int aog_focal_images(aog_env* e, int first, int count, float* field_dev, void* s
   if (!e || !field_dev) return fail(AOG_ERR_INVALID, "aog_focal_images: null argument");
   if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "aog_focal_images before aog_upload_tables/aog_set_screens");
   if (!e->n_focal) return fail(AOG_ERR_STATE, "aog_focal_images: focal_m1/focal_m2 were not uploaded");
-  if (first < 0 || count < 0 || first + count > e->B) return fail(AOG_ERR_INVALID, "aog_focal_images: env range outside [0,%d)", e->B);
+  if (int rc = check_env_range("aog_focal_images", first, count, e->B)) return rc;
   if (e->cfg.precision != AOG_PRECISION_FAST || !e->focal_m1s)
     return fail(AOG_ERR_UNSUPPORTED, "aog_focal_images: fast-precision handles only (use aog_focal_image on a float64 validation handle)");
   if (int rcp = refuse_pre_evolved(e, "aog_focal_images")) return rcp;
@@ -205,7 +196,7 @@ int aog_focal_images(aog_env* e, int first, int count, float* field_dev, void* s
   if ((rc = ensure_tiles(e, s)) != AOG_OK) return rc;
   if (e->cfg.atm_dynamic && !e->ring_direct && e->kernel != AOG_KERNEL_MFMA && (rc = pack_from_master(e, 0, e->B, s)) != AOG_OK) return rc;
   // u = psi + Mt a with the CURRENT mirror state of every env (act16 is rewritten from act_dm: the VALU step kernel does not keep it)
-  if ((rc = load_actuators(e, s, e->focal_act_ll)) != AOG_OK) return rc;
+  if ((rc = load_actuators(e, s, {e->act_rev, e->act16, e->focal_act_ll})) != AOG_OK) return rc;
   for (int env0 = first / 32 * 32; env0 < first + count; env0 += e->focal_chunk) {
     const int env1 = std::min(first + count, env0 + e->focal_chunk);          // envs [lo, env1) of this chunk are asked for
     const int lo = std::max(first, env0), n_et = (env1 - env0 + 31) / 32;

@@ -12,6 +12,7 @@
 namespace aog {
 struct ActorArgs;
 struct ActorNoise;
+struct PhaseFieldArgs;
 }
 
 namespace aog_host {
@@ -46,6 +47,20 @@ void dev_release(aog_env* e, T** ptr) {
   *ptr = nullptr;
 }
 
+// host table -> a device buffer of the handle: allocate `count` elements at *dst and copy them from src (blocking).  keep: a buffer
+// that is already there is written again in place (a table uploaded twice has the same size)
+template <typename T>
+int upload(aog_env* e, T** dst, const T* src, size_t count, bool keep = false) {
+  if (!(keep && *dst))
+    if (int rc = dev_alloc(e, dst, count, false)) return rc;
+  HIP_TRY(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
+  return AOG_OK;
+}
+template <typename T>
+int upload(aog_env* e, T** dst, const std::vector<T>& src, bool keep = false) {
+  return upload(e, dst, src.data(), src.size(), keep);
+}
+
 // zero `n_words` 32-bit words at p on stream s with a kernel of the library (see k_zero_words for why not hipMemsetAsync)
 void zero_words(void* p, size_t n_words, hipStream_t s);
 
@@ -77,14 +92,49 @@ struct TimedRegion {
   TimedRegion& operator=(const TimedRegion&) = delete;
 };
 
+// The handle's status word (bit 0: a bounded inter-workgroup wait of k_extrude16_split timed out, bit 1: a step failed after its counters
+// had moved).  It lives in pinned, device-mapped host memory: reading it costs one load and no synchronisation.  Only these three touch it.
+int poisoned(const aog_env* e);
+void poison(aog_env* e, int bits);
+int clear_poison(aog_env* e);   // the host word and the device-side sticky word (the caller has drained the streams that could set them)
 int check_poisoned(const aog_env* e, const char* who);
 int refuse_pre_evolved(const aog_env* e, const char* who);
 int clear_poison_if_whole(aog_env* e, int first, int count, hipStream_t s);
+// AOG_ERR_INVALID unless envs [first, first + count) lie inside [0, B)
+int check_env_range(const char* who, int first, int count, int B);
+// metres of optical path -> revolutions of the wavefront sensor's wavelength
+inline double rev_per_metre(const aog_env* e) { return 1.0 / (2.0 * M_PI * e->cfg.wavelength_wfs); }
+// Event timing samples launch number `phase` of a handle: blocks of profile_block consecutive launches, the MIDDLE block of each period
+// of profile_every blocks (a short window's first launches come right after a synchronisation and are its slowest; two event records cost
+// ~6 us on the stream, so a throughput measurement that also wants kernel durations does not time every launch)
+inline bool profile_sampled(const aog_env* e, unsigned phase) {
+  return ((phase / (unsigned)e->profile_block) % (unsigned)e->profile_every) == (unsigned)e->profile_every / 2;
+}
 int set_screens_f32(aog_env* e, const float* psi, int first, int count, hipStream_t s, bool means_ready = false);   // means_ready: pack_mean[0 .. count) holds the aperture means already   // device screens [count][N][N] -> internal layouts
-// act_dm -> the operand layouts of the fused kernels (act_ll: optional third f16 term of the actuators, K4)
-int load_actuators(aog_env* e, hipStream_t s, _Float16* act_ll = nullptr);
-// act_dm -> the split-f16 operand layout (and third term) in buffers of the caller's choosing; act_rev / act16 are not touched
-int load_actuators_into(aog_env* e, hipStream_t s, _Float16* act16, _Float16* act_ll);
+// act_dm -> the operand layouts of the fused and phase kernels, in buffers of the caller's choosing
+struct ActTargets {
+  float* act_rev;     // [A_pad][Bp] fp32 (nullable)
+  _Float16* act16;    // split-f16 B operands
+  _Float16* act_ll;   // nullable third f16 term of the actuators (K4, K11)
+};
+int load_actuators(aog_env* e, hipStream_t s, ActTargets to);
+// iy << 16 | ix of every aperture pixel, from the host copy of ap_index
+std::vector<int32_t> ap_yx_table(const aog_env* e);
+// Launchers of the kernels instantiated per padded mode count, one translation unit each so the build parallelises (fused_inst.hip compiled
+// with -DAOG_INST_APAD=16|32|64|128 defines apad_launchers<that count>).  Each returns 0 or the aog_status of a failed dynamic-LDS request.
+struct ApadLaunchers {
+  int (*fused)(aog_env* e, hipStream_t s);
+  int (*phase)(aog_env* e, hipStream_t s, const _Float16* act16, float* out_tile);
+  int (*phase_field)(aog_env* e, hipStream_t s, const _Float16* act16, const aog::PhaseFieldArgs& fa, bool grid);
+  int (*phase_grid)(aog_env* e, hipStream_t s, const _Float16* act16, const aog::PhaseFieldArgs& fa, int etile0, int n_et);
+};
+template <int A_PAD>
+const ApadLaunchers& apad_launchers();
+// phase-only contraction u = psi + Mt a for every (pixel, env) with the actuator operands `act16`, written in the psi_tile layout
+void launch_phase(aog_env* e, hipStream_t s, const _Float16* act16, float* out_tile);
+void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, const _Float16* act_ll, float* grid, size_t env_stride, int row_stride, int etile0,
+                       int n_et);
+void launch_phase_field(aog_env* e, hipStream_t s, const _Float16* act16, float* field, size_t env_stride, int row_stride, bool grid);   // complex64 field, or (grid) one float of reduced phase per pixel
 // focal.hip (K11): the observation of the separable route for every env — |F|^2 into obs_pw and the caller's obs_raw / obs (nullable)
 int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs);
 // split-f16 operand tables of a Fraunhofer matrix Fourier transform m1 [nf][N] . E . m2 [N][nf] (K4's layouts: m1s [nfp / 32][Nyp / 16] tiles,

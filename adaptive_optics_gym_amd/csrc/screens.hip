@@ -288,7 +288,7 @@ int aog_generate_screens(aog_env* e, int first, int count, int oversampling, dou
                          void* stream) {
   if (!e) return fail(AOG_ERR_INVALID, "aog_generate_screens: null handle");
   if (!e->tables_ready) return fail(AOG_ERR_STATE, "aog_generate_screens before aog_upload_tables");
-  if (first < 0 || count < 0 || first + count > e->B) return fail(AOG_ERR_INVALID, "aog_generate_screens: env range outside [0,%d)", e->B);
+  if (int rc = check_env_range("aog_generate_screens", first, count, e->B)) return rc;
   if (oversampling < 1 || oversampling > 32 || !(cn_squared > 0) || !(outer_scale > 0) || !(pixel_pitch > 0))
     return fail(AOG_ERR_INVALID, "aog_generate_screens: bad parameter");
   if (count == 0) return AOG_OK;

@@ -20,19 +20,14 @@ int aog_upload_sh(aog_env* e, const aog_sh_tables* t) {
     if (t->sub_slot[i] < -1 || t->sub_slot[i] >= t->n_sub) return fail(AOG_ERR_INVALID, "aog_upload_sh: sub_slot out of range");
   HIP_TRY(hipSetDevice(e->device));
   int rc;
-  auto up = [&](auto** dst, const auto* src, size_t count) -> int {
-    if ((rc = dev_alloc(e, dst, count, false)) != AOG_OK) return rc;
-    HIP_TRY(hipMemcpy(*dst, src, sizeof(**dst) * count, hipMemcpyHostToDevice));
-    return AOG_OK;
-  };
   e->sh_n_sub = t->n_sub;
-  if ((rc = up(&e->sh_slot, t->sub_slot, N2)) != AOG_OK) return rc;
-  if ((rc = up(&e->sh_centres, t->centres, (size_t)t->n_sub * 2)) != AOG_OK) return rc;
-  if ((rc = up(&e->sh_ref, t->slopes_ref, (size_t)t->n_sub * 2)) != AOG_OK) return rc;
-  if ((rc = up(&e->sh_recon, t->reconstruction, (size_t)e->A * t->n_sub * 2)) != AOG_OK) return rc;
-  if ((rc = up(&e->sh_mla, t->mla_phase, N2 * 2)) != AOG_OK) return rc;
-  if ((rc = up(&e->sh_tf, t->transfer, N2 * 4 * 2)) != AOG_OK) return rc;
-  if ((rc = up(&e->sh_xdet, t->x_det, (size_t)N)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->sh_slot, t->sub_slot, N2)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->sh_centres, t->centres, (size_t)t->n_sub * 2)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->sh_ref, t->slopes_ref, (size_t)t->n_sub * 2)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->sh_recon, t->reconstruction, (size_t)e->A * t->n_sub * 2)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->sh_mla, t->mla_phase, N2 * 2)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->sh_tf, t->transfer, N2 * 4 * 2)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->sh_xdet, t->x_det, (size_t)N)) != AOG_OK) return rc;
   if ((rc = dev_alloc(e, &e->sh_act, (size_t)e->B * e->A)) != AOG_OK) return rc;
   if ((rc = dev_alloc(e, &e->sh_act16, (size_t)e->n_etiles * e->A_pad * 32 * 2)) != AOG_OK) return rc;
   if ((rc = dev_alloc(e, &e->sh_phase, (size_t)e->n_etiles * e->n_ptiles * 1024)) != AOG_OK) return rc;
@@ -59,8 +54,8 @@ int aog_upload_sh(aog_env* e, const aog_sh_tables* t) {
           tfq[dst] = (float)t->transfer[src];
           tfq[dst + 1] = (float)t->transfer[src + 1];
         }
-    if ((rc = up(&e->sh_tw, tw.data(), tw.size())) != AOG_OK) return rc;
-    if ((rc = up(&e->sh_tfq, tfq.data(), tfq.size())) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->sh_tw, tw)) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->sh_tfq, tfq)) != AOG_OK) return rc;
     {
       // Does the transfer function factorise, H[ky][kx] = hx[kx] hy[ky] (the paraxial Fresnel one does)?  hx = H[0][.], hy = H[.][0] / H[0][0];
       // checked on every element in float64.  If so the propagation runs as the separable two-pass form (k_sh_rows_sep / k_sh_cols_sep).
@@ -106,24 +101,22 @@ int aog_upload_sh(aog_env* e, const aog_sh_tables* t) {
             hyq[((size_t)r * 64 + lane) * 2] = (float)hy[2 * ky];
             hyq[((size_t)r * 64 + lane) * 2 + 1] = (float)hy[2 * ky + 1];
           }
-        if ((rc = up(&e->sh_hxq, hxq.data(), hxq.size())) != AOG_OK) return rc;
-        if ((rc = up(&e->sh_hyq, hyq.data(), hyq.size())) != AOG_OK) return rc;
+        if ((rc = upload(e, &e->sh_hxq, hxq)) != AOG_OK) return rc;
+        if ((rc = upload(e, &e->sh_hyq, hyq)) != AOG_OK) return rc;
       }
     }
     if ((rc = dev_alloc(e, &e->sh_sums, (size_t)e->B * t->n_sub * 3)) != AOG_OK) return rc;
-    std::vector<int32_t> apidx((size_t)e->n_ap), yx((size_t)e->n_ap);
-    HIP_TRY(hipMemcpy(apidx.data(), e->ap_index, sizeof(int32_t) * e->n_ap, hipMemcpyDeviceToHost));
-    for (int i = 0; i < e->n_ap; ++i) yx[i] = ((apidx[i] / N) << 16) | (apidx[i] % N);
+    const std::vector<int32_t>& apidx = e->ap_index_host;
     std::vector<float> mla32(N2 * 2);
     for (size_t i = 0; i < N2 * 2; ++i) mla32[i] = (float)t->mla_phase[i];
-    if ((rc = up(&e->sh_ap_yx, yx.data(), yx.size())) != AOG_OK) return rc;
-    if ((rc = up(&e->sh_mla32, mla32.data(), mla32.size())) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->sh_ap_yx, ap_yx_table(e))) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->sh_mla32, mla32)) != AOG_OK) return rc;
     // the micro-lens factor's argument in revolutions per packed aperture pixel: added to the phase by k_phase_mfma<.., GRID>; the phase
     // grid the first pass reads starts out as "outside the aperture" everywhere (only aperture pixels are ever written)
     std::vector<float> mrev((size_t)e->n_ap);
     for (int i = 0; i < e->n_ap; ++i)
       mrev[i] = (float)(atan2(t->mla_phase[(size_t)apidx[i] * 2 + 1], t->mla_phase[(size_t)apidx[i] * 2]) / (2.0 * M_PI));
-    if ((rc = up(&e->sh_ftab, mrev.data(), mrev.size())) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->sh_ftab, mrev)) != AOG_OK) return rc;
     {
       std::vector<float> fill((size_t)N2, aog::kShOutside);
       for (int b = 0; b < e->B; ++b)
@@ -143,7 +136,7 @@ int aog_upload_sh(aog_env* e, const aog_sh_tables* t) {
   if (!e->sh_double && !e->sh_pruned) {
     std::vector<float> tf32(N2 * 4 * 2);
     for (size_t i = 0; i < tf32.size(); ++i) tf32[i] = (float)t->transfer[i];
-    if ((rc = up(&e->sh_tf32, tf32.data(), tf32.size())) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->sh_tf32, tf32)) != AOG_OK) return rc;
   }
   if ((rc = dev_alloc(e, &e->sh_image, (size_t)e->B * N2, false)) != AOG_OK) return rc;
   if ((rc = dev_alloc(e, &e->sh_noisy, (size_t)e->B * N2, false)) != AOG_OK) return rc;
