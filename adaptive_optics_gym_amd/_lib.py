@@ -101,6 +101,7 @@ SYMBOLS = {
     "aog_get_screens_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aog_generate_screens": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "aog_set_turbulence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_set_detector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_turbulence_factors": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     "aog_set_screen_method": (C.c_int, [C.c_void_p, C.c_int]),

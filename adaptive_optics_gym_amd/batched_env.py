@@ -16,7 +16,7 @@ from . import _lib
 from .atmosphere_host import (build_layer_tables, cn_squared_from_fried_parameter, integer_shifts, screen_numpy,
                               screens_torch)
 from .optics_host import HostTables, build_tables, obs_route_for
-from .params import OpticalParams, resolve_per_env, resolve_turbulence
+from .params import OpticalParams, resolve_detector, resolve_per_env, resolve_turbulence
 from .spaces import make_box
 
 
@@ -59,6 +59,15 @@ class BatchedAOEnv:
     and evolves exactly what a uniform instance at (r0_e, v_e) would (dynamic int8 extrusion: bit for bit for the envs at the batch's
     largest Cn^2, the tables' value; to ~1e-9 rad per new sample for the others, like the int8 form against the float64 one).
     ``set_turbulence`` changes r0 per episode (domain randomisation); per-env speed is fixed at construction (it sets k_max).
+
+    ``obs_photons`` (default None: the exact focal-plane powers, as the reference) switches the photodetector model on: expected
+    photo-electrons per frame of the whole unit-power beam, with ``obs_read_noise`` (electrons rms per pixel and frame) and
+    ``obs_background`` (electrons per pixel and frame, subtracted again); each a scalar, ``num_envs`` or ``total_envs`` values like
+    ``atm_fried``.  Pixel j of env e then reads (Poisson(F_e c_j + b_e) + sigma_e g_j - b_e) / F_e around its clean value c_j
+    (``aog_set_detector``).  Only the observation is noisy: reward, power, Strehl, done, screens and mirror are those of the same env without
+    a detector, bit for bit — the reward is the training signal of the true state.  The noise is drawn inside the step kernels from a
+    Philox stream keyed by (seed, global env id, pixel, frame), so split batches reproduce whole ones and ``get_state`` / ``set_state``
+    resume it.  ``set_detector`` changes the values per episode; ``detector_parameters`` shows them.
     """
 
     def __init__(self, num_envs=1, device=None, atm_type="quasi_static", atm_vel=0, atm_fried=0.15,
@@ -66,7 +75,8 @@ class BatchedAOEnv:
                  timesteps_per_episode=20, flat_mirror_start_per_episode=True, SH_operation=False, *,
                  num_pupil_pixels=240, seed=None, screen_source="device", screen_oversampling=16, screens=None,
                  precision="fast", kernel="auto", pixel_chunks=0, rng=None, verbose=True, params=None,
-                 global_env_offset=0, total_envs=None, sh_fft_precision="single", screen_method="twoband", tables=None, extrusion="auto"):
+                 global_env_offset=0, total_envs=None, sh_fft_precision="single", screen_method="twoband", tables=None, extrusion="auto",
+                 obs_photons=None, obs_read_noise=0.0, obs_background=0.0):
         import torch
 
         self._torch = torch
@@ -97,6 +107,9 @@ class BatchedAOEnv:
             raise ValueError("sh_fft_precision must be 'single' or 'double'")
         self.sh_fft_precision = sh_fft_precision
         turb = resolve_turbulence(atm_type, atm_fried, atm_vel, self.num_envs, self.total_envs, self.global_env_offset, verbose)
+        self._detector = resolve_detector(obs_photons, obs_read_noise, obs_background, self.num_envs, self.total_envs, self.global_env_offset)
+        self._last_obs = None
+        self.observation_frames = 0   # observations written so far (every reset / step adds one): the frame of the detector's random stream
         fried, self._fried_all, vel_scalar = turb["fried"], turb["fried_all"], turb["vel_scalar"]
         self.velocity, self._wind_speeds = turb["velocity"], turb["speeds"]
         self.fried_parameter = atm_fried if turb["fried_scalar"] else fried.copy()
@@ -174,6 +187,9 @@ class BatchedAOEnv:
         self._handle = C.c_void_p()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _lib.check(self.lib.aog_create(C.byref(cfg), dev_index, C.byref(self._handle)))
+        self._host_rng = self._rng is not None or screen_source == "numpy"
+        self._lib_seeded = False
+        self._seed_library(draw=False)
 
         keep = dict(
             ap=np.ascontiguousarray(t.ap_index, dtype=np.int32),
@@ -245,6 +261,7 @@ class BatchedAOEnv:
             self._generate_screens(first_call=True)
         if self.SH_operation:
             self._upload_shack_hartmann()
+        self._push_detector()   # (last: in host-RNG mode without a seed it draws the handle's seed after the reference's own draws)
 
     # ------------------------------------------------------------------------------------------------
     # per-env turbulence
@@ -328,6 +345,95 @@ class BatchedAOEnv:
         self.fried_parameter = float(self._fried[0]) if bool(np.all(self._fried == self._fried[0])) else self._fried.copy()
         self._set_cn2(self._fried)
         self._push_turbulence()
+
+    # ------------------------------------------------------------------------------------------------
+    # photodetector model of the observations
+    @property
+    def detector_parameters(self):
+        """None without a detector, else {"photons", "read_noise", "background"}: [B] float64 read-only views of what each env runs at."""
+        if self._detector is None:
+            return None
+        out = {}
+        for k, a in self._detector.items():
+            v = a.view()
+            v.flags.writeable = False
+            out[k] = v
+        return out
+
+    def _seed_library(self, draw):
+        """The handle's 64-bit rng_seed, set once.  Device random streams: ``seed`` (1234 when None), whatever else the constructor does
+        (screens= on a static atmosphere seeds no stream otherwise).  Host-RNG mode with a ``seed`` and no ``rng``: that seed too (the
+        same on every slice of a split batch).  Otherwise (``rng=`` or the process-global numpy stream: the single-env wrapper) there is
+        no number to take, so — only when a detector needs one (``draw``) — 62 bits are drawn from that stream: two instances then
+        draw different detector noise, and seeding the stream reproduces it.  Envs without a detector never consume host draws here."""
+        if self._lib_seeded:
+            return
+        if not self._host_rng or (self._rng is None and self.seed is not None):
+            value = 1234 if self.seed is None else int(self.seed)
+        elif draw:
+            r = self._env_rng(0)
+            value = (int(r.randint(0, 2 ** 31)) << 31) | int(r.randint(0, 2 ** 31))
+        else:
+            return
+        _lib.check(self.lib.aog_set_rng_seed(self._handle, C.c_uint64(value)))
+        self._lib_seeded = True
+
+    def _push_detector(self):
+        """Hand the per-env detector values to the library (aog_set_detector), or NULL without a detector."""
+        d = self._detector
+        if d is None:
+            if getattr(self, "_lib_detector", False):
+                _lib.check(self.lib.aog_set_detector(self._handle, None, None, None, self._stream()))
+            self._lib_detector = False
+            return
+        self._seed_library(draw=True)
+        ptr = [d[k].ctypes.data_as(C.c_void_p) for k in ("photons", "read_noise", "background")]
+        _lib.check(self.lib.aog_set_detector(self._handle, *ptr, self._stream()))   # (the library copies the values before it returns)
+        self._lib_detector = True
+
+    def set_detector(self, photons, read_noise=None, background=None, mask=None):
+        """New detector values for the envs selected by ``mask`` (default all), from the next observation on: per-episode randomisation
+        of the light level.  Each argument as ``obs_photons`` / ``obs_read_noise`` / ``obs_background``; ``read_noise`` / ``background`` =
+        None keep the current values (0 when there was no detector).  ``photons=None`` switches the detector off for every env (``mask``
+        must be None then): the env is again the noise-free one, bit for bit."""
+        if photons is None:
+            if mask is not None:
+                raise ValueError("set_detector(None) switches the detector off for the whole batch; mask must be None")
+            self._detector = None
+            self._push_detector()
+            return
+        cur = self._detector
+        new = resolve_detector(photons, 0.0 if read_noise is None else read_noise, 0.0 if background is None else background,
+                               self.num_envs, self.total_envs, self.global_env_offset)
+        if cur is not None:
+            if read_noise is None:
+                new["read_noise"] = cur["read_noise"].copy()
+            if background is None:
+                new["background"] = cur["background"].copy()
+        if mask is not None:
+            sel = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask).astype(bool).reshape(-1)
+            if sel.size != self.num_envs:
+                raise ValueError("set_detector: mask must have num_envs entries")
+            if cur is None and not sel.all():
+                raise ValueError("set_detector: the env has no detector yet; the first call must cover every env")
+            if cur is not None:
+                for k in new:
+                    new[k] = np.where(sel, new[k], cur[k])
+        self._detector = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in new.items()}
+        self._push_detector()
+
+    def _obs_buffers(self, masked):
+        """Fresh (obs float16, obs_raw float32) [B, o^2] for a reset.  A masked reset of an env with a detector draws for the masked envs
+        only and leaves the other rows as they are: those start as copies of the last observation."""
+        torch = self._torch
+        n = self.obs_dim ** 2
+        if masked and self._detector is not None and self._last_obs is not None:
+            return self._last_obs.clone(), self.last_obs_raw.clone()
+        if masked and self._detector is not None:
+            return (torch.zeros((self.num_envs, n), dtype=torch.float16, device=self.device),
+                    torch.zeros((self.num_envs, n), dtype=torch.float32, device=self.device))
+        return (torch.empty((self.num_envs, n), dtype=torch.float16, device=self.device),
+                torch.empty((self.num_envs, n), dtype=torch.float32, device=self.device))
 
     # ------------------------------------------------------------------------------------------------
     def _stream(self):
@@ -583,12 +689,12 @@ class BatchedAOEnv:
             m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
         if self.atm_type == "semi_dynamic":
             self._generate_screens(mask=m)  # layer.reset() (AO_env.py:76-77)
-        n = self.obs_dim ** 2
-        obs = torch.empty((self.num_envs, n), dtype=torch.float16, device=self.device)
-        obs_raw = torch.empty((self.num_envs, n), dtype=torch.float32, device=self.device)
+        obs, obs_raw = self._obs_buffers(m is not None)
         _lib.check(self.lib.aog_reset(self._handle, C.c_void_p(m.data_ptr()) if m is not None else None,
                                       C.c_void_p(obs_raw.data_ptr()), C.c_void_p(obs.data_ptr()), self._stream()))
         self.last_obs_raw = obs_raw
+        self._last_obs = obs
+        self.observation_frames += 1
         return obs, {}
 
     _PIPELINE_END = object()
@@ -614,11 +720,15 @@ class BatchedAOEnv:
             self._launch_step(a, next_actions, ptrs)
             self.timestep += 1
             self.last_obs_raw = ret[4]["obs_raw"]
+            self._last_obs = ret[0]
+            self.observation_frames += 1
             return ret
         ret, ptrs, obs_raw = self._step_outputs(out)
         self._launch_step(a, next_actions, ptrs)
         self.timestep += 1
         self.last_obs_raw = obs_raw
+        self._last_obs = ret[0]
+        self.observation_frames += 1
         if self._persistent_out and out is None:
             self._step_cache = (ret, ptrs)
         return ret
@@ -716,6 +826,8 @@ class BatchedAOEnv:
             _lib.check(self.lib.aog_reset_act_noise(*args, C.byref(noise), self._stream()))
         policy.calls += 1
         self.last_obs_raw = obs_raw
+        self._last_obs = obs
+        self.observation_frames += 1
         return (obs, {}), (action, log_prob, mean)
 
     def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None, ou_noise=None, action_mode="sample"):
@@ -742,6 +854,8 @@ class BatchedAOEnv:
             _lib.check(self.lib.aog_step_act_noise(*args, C.byref(noise), self._stream()))
         self.timestep += 1
         self.last_obs_raw = obs_raw
+        self._last_obs = ret[0]
+        self.observation_frames += 1
         if not queried.value:
             return ret, None
         policy.calls += 1
@@ -845,10 +959,18 @@ class BatchedAOEnv:
         torch.cuda.current_stream(self.device).synchronize()
         rng = [self._env_rng(e).get_state() for e in range(self.num_envs)] if self._host_rng else None
         return {"blob": blob, "lib_timestep": int(ts.value), "timestep": self.timestep, "episode_no": self.episode_no, "rng": rng,
-                "fried_parameters": self._fried.copy()}
+                "fried_parameters": self._fried.copy(),
+                "observation_frames": self.observation_frames,
+                "detector": None if self._detector is None else {k: v.copy() for k, v in self._detector.items()}}
 
     def set_state(self, state):
         torch = self._torch
+        det = state.get("detector")
+        if (det is None) != (self._detector is None):
+            raise ValueError("set_state: the state was saved " + ("without" if det is None else "with") + " a detector and this environment was built "
+                             + ("with" if det is None else "without") + " one (obs_photons)")
+        if det is not None and any(np.asarray(det[k]).shape != (self.num_envs,) for k in ("photons", "read_noise", "background")):
+            raise ValueError("state's detector values do not match this environment's num_envs")
         blob = state["blob"].to(self.device).contiguous()
         if blob.numel() != int(self.lib.aog_state_bytes(self._handle)):
             raise ValueError("state blob does not match this environment's configuration")
@@ -856,6 +978,7 @@ class BatchedAOEnv:
         torch.cuda.current_stream(self.device).synchronize()
         self.timestep = int(state["timestep"])
         self.episode_no = int(state["episode_no"])
+        self.observation_frames = int(state.get("observation_frames", 0))   # (the library's own count came with the blob)
         if state.get("rng") is not None:
             for e, st in enumerate(state["rng"]):
                 self._env_rng(e).set_state(st)
@@ -864,6 +987,9 @@ class BatchedAOEnv:
             if np.asarray(fried).shape != (self.num_envs,):
                 raise ValueError("state's fried_parameters do not match this environment's num_envs")
             self._apply_fried(fried)   # (the values only: the screens came with the blob)
+        if det is not None:
+            self._detector = {k: np.ascontiguousarray(det[k], dtype=np.float64).copy() for k in ("photons", "read_noise", "background")}
+            self._push_detector()   # (the frame count came with the blob)
 
     def accumulate_returns(self, returns=None):
         """Have every ``step`` add its rewards into ``returns`` ([B] float32 contiguous device tensor; the caller zeroes it at

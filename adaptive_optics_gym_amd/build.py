@@ -29,8 +29,9 @@ UNITS = ("aogym", "atmosphere", "screens", "shack", "focal", "actor")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-fno-slp-vectorize"]
 # headers each unit includes besides the shared ones (an edit of a family header recompiles that family only)
 SHARED = ("aogym_internal.h", "host_common.h", "k_common.h", "fused_layout.h")
-FAMILY = {"aogym": ("k_pack.h", "k_step.h", "k_actor.h", "k_step_act.h"), "atmosphere": ("k_pack.h", "k_extrude.h", "k_extrude_i8.h"), "screens": ("k_fft.h", "k_screens.h"),
-          "shack": ("k_fft.h", "k_shack.h"), "focal": ("k_focal.h", "k_obs.h"), "actor": ("k_actor.h",), "fused_inst": ("k_fused.h",)}
+DETECTOR = ("k_poisson.h", "k_detector.h")
+FAMILY = {"aogym": ("k_pack.h", "k_step.h", "k_actor.h", "k_step_act.h") + DETECTOR, "atmosphere": ("k_pack.h", "k_extrude.h", "k_extrude_i8.h"), "screens": ("k_fft.h", "k_screens.h"),
+          "shack": ("k_fft.h", "k_shack.h", "k_poisson.h"), "focal": ("k_focal.h", "k_obs.h") + DETECTOR, "actor": ("k_actor.h",), "fused_inst": ("k_fused.h",)}
 
 
 def hipcc_path() -> str:

@@ -199,6 +199,18 @@ void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, const _
   launchers_for(e->A_pad).phase_grid(e, s, act16, fa, etile0, n_et);
 }
 void launch_phase(aog_env* e, hipStream_t s, const _Float16* act16, float* out_tile) { launchers_for(e->A_pad).phase(e, s, act16, out_tile); }
+
+aog::DetectorArgs detector_args(const aog_env* e, const uint8_t* mask) {
+  aog::DetectorArgs d{};
+  d.par = e->det_par;
+  d.mask = mask;
+  d.seed = e->rng_seed;
+  d.frame_lo = (uint32_t)e->obs_frame;
+  d.frame_hi = (uint32_t)(e->obs_frame >> 32);
+  d.env_base = e->cfg.env_id_base;
+  d.B = e->B;
+  return d;
+}
 }  // namespace aog_host
 using namespace aog_host;
 
@@ -229,7 +241,11 @@ int launch_fused(aog_env* e, hipStream_t s) {
 
 // The epilogue's dynamic LDS.  e->MRW / e->MRS are the table counts the partial slabs hold: the padded counts of the fast kernels, and the
 // counts in use on float64 validation handles (aog_create sets them so), whose single slab k_fused_ref writes.
-size_t epilogue_lds(const aog_env* e) { return aog::EpilogueLds(e->MRW, e->MRS, e->n_out, e->MRW_used, e->MRS_used).bytes(); }
+// Handles with a detector add the plane of noisy observations (table route: n_obs_tab x 16 doubles).
+size_t epilogue_lds(const aog_env* e, bool detector) {
+  return aog::EpilogueLds(e->MRW, e->MRS, e->n_out, e->MRW_used, e->MRS_used, detector ? e->n_obs_tab : 0).bytes();
+}
+size_t epilogue_lds(const aog_env* e) { return epilogue_lds(e, e->det_on); }
 
 // the policy attached to aog_reset_act / aog_step_act: its arguments (actor_args, checked before the call changes anything) and outputs
 struct ActTail {
@@ -259,8 +275,9 @@ aog::PrologueArgs prologue_args(const aog_env* e, const float* action) {
 // action_next (aog_step_pipelined): the prologue of the NEXT step rides in the same launch (k_epilogue_prologue)
 // tail (aog_reset_act / aog_step_act): the policy query on this epilogue's observation and the prologue of the next step from its action ride in
 // the same launch, per workgroup of 16 envs (k_epilogue_act_prologue)
+// mask (masked aog_reset): handles with a detector draw for the masked envs only
 int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
-                    float* strehl, hipStream_t s, const float* action_next = nullptr, const ActTail* tail = nullptr) {
+                    float* strehl, hipStream_t s, const float* action_next = nullptr, const ActTail* tail = nullptr, const uint8_t* mask = nullptr) {
   aog::EpilogueArgs p{};
   p.partials = e->partials;
   p.wfs_coef = e->wfs_coef;
@@ -293,7 +310,32 @@ int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, flo
   p.ssim_alpha = e->cfg.ssim_alpha;
   const size_t lds = epilogue_lds(e);
   const int n_epi = (e->Bp + aog::kEpiEnvs - 1) / aog::kEpiEnvs;
-  if (tail) {
+  if (e->det_on) {   // the same three launch forms through the kernels that draw the detector's noise
+    const aog::DetectorArgs d = detector_args(e, mask);
+    if (tail) {
+      aog::ActorArgs a = tail->a;
+      aog::PrologueArgs q = prologue_args(e, a.action);
+      const int obs_from_lds = e->obs_sep ? 0 : 1;
+      a.obs = obs;
+      a.obs_f16 = 1;
+      const size_t lds_all = aog::step_act_lds_bytes(lds, tail->lds);   // (<= kLdsBytes: checked by step_act_tail)
+      const void* kernel = tail->noisy ? reinterpret_cast<const void*>(aog::k_epilogue_act_prologue_noise_det)
+                                       : reinterpret_cast<const void*>(aog::k_epilogue_act_prologue_det);
+      if (int rc = aog_host::ensure_dynamic_lds(kernel, lds_all, e->device)) return rc;
+      if (tail->noisy)
+        hipLaunchKernelGGL(aog::k_epilogue_act_prologue_noise_det, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, aog::ActorNoiseArgs{a, tail->nz},
+                           q, obs_from_lds, d);
+      else
+        hipLaunchKernelGGL(aog::k_epilogue_act_prologue_det, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, a, q, obs_from_lds, d);
+    } else if (action_next) {
+      const aog::PrologueArgs q = prologue_args(e, action_next);
+      if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue_prologue_det), lds, e->device)) return rc;
+      hipLaunchKernelGGL(aog::k_epilogue_prologue_det, dim3(n_epi + (e->B + aog::kEpiProEnvs - 1) / aog::kEpiProEnvs), dim3(1024), lds, s, p, q, n_epi, d);
+    } else {
+      if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue_det), lds, e->device)) return rc;
+      hipLaunchKernelGGL(aog::k_epilogue_det, dim3(n_epi), dim3(1024), lds, s, p, d);
+    }
+  } else if (tail) {
     aog::ActorArgs a = tail->a;
     aog::PrologueArgs q = prologue_args(e, a.action);
     const int obs_from_lds = e->obs_sep ? 0 : 1;
@@ -544,6 +586,9 @@ void aog_destroy(aog_env* e) {
   if (e->turb_stage32) (void)hipHostFree(e->turb_stage32);
   if (e->turb_ev64) (void)hipEventDestroy(e->turb_ev64);
   if (e->turb_ev32) (void)hipEventDestroy(e->turb_ev32);
+  if (e->det_ev) (void)hipEventSynchronize(e->det_ev);
+  if (e->det_stage) (void)hipHostFree(e->det_stage);
+  if (e->det_ev) (void)hipEventDestroy(e->det_ev);
   if (e->x8_plan_stream) {
     (void)hipStreamSynchronize(e->x8_plan_stream);
     (void)hipStreamDestroy(e->x8_plan_stream);
@@ -746,6 +791,43 @@ int aog_set_rng_seed(aog_env* e, uint64_t seed) {
   return AOG_OK;
 }
 
+int aog_set_detector(aog_env* e, const double* photons_host, const double* read_noise_host, const double* background_host, void* stream) {
+  if (!e) return fail(AOG_ERR_INVALID, "aog_set_detector: null handle");
+  if (!photons_host) {   // back to the noise-free kernels: today's code, today's bits
+    e->det_on = false;
+    return AOG_OK;
+  }
+  if (!read_noise_host || !background_host) return fail(AOG_ERR_INVALID, "aog_set_detector: read_noise / background are NULL beside photons");
+  for (int b = 0; b < e->B; ++b) {
+    if (!(photons_host[b] > 0) || !std::isfinite(photons_host[b]))
+      return fail(AOG_ERR_INVALID, "aog_set_detector: photons[%d] = %g is not finite and > 0", b, photons_host[b]);
+    if (!(read_noise_host[b] >= 0) || !std::isfinite(read_noise_host[b]))
+      return fail(AOG_ERR_INVALID, "aog_set_detector: read_noise[%d] = %g is not finite and >= 0", b, read_noise_host[b]);
+    if (!(background_host[b] >= 0) || !std::isfinite(background_host[b]))
+      return fail(AOG_ERR_INVALID, "aog_set_detector: background[%d] = %g is not finite and >= 0", b, background_host[b]);
+  }
+  // the table route's epilogue keeps the noisy observation in a second LDS plane beside the clean powers
+  const size_t lds = epilogue_lds(e, true);
+  if (lds > kLdsBytes)
+    return fail(AOG_ERR_UNSUPPORTED, "aog_set_detector: the epilogue would need %zu bytes of LDS (%zu without a detector + %zu for the noisy plane of %d "
+                "observations x %d envs) > %zu", lds, epilogue_lds(e, false), lds - epilogue_lds(e, false), e->n_obs_tab, aog::kEpiEnvs, kLdsBytes);
+  HIP_TRY(hipSetDevice(e->device));
+  // (each piece on its own: a call that failed half way leaves nothing the next one would take for complete)
+  if (!e->det_par)
+    if (int rc = dev_alloc(e, &e->det_par, (size_t)3 * e->B)) return rc;
+  if (!e->det_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->det_stage), sizeof(double) * 3 * e->B, hipHostMallocDefault));
+  if (!e->det_ev) HIP_TRY(hipEventCreateWithFlags(&e->det_ev, hipEventDisableTiming));
+  HIP_TRY(hipEventSynchronize(e->det_ev));   // (the previous copy out of the staging buffer; long done in practice)
+  const size_t B = (size_t)e->B;
+  std::copy(photons_host, photons_host + B, e->det_stage);
+  std::copy(read_noise_host, read_noise_host + B, e->det_stage + B);
+  std::copy(background_host, background_host + B, e->det_stage + 2 * B);
+  HIP_TRY(hipMemcpyAsync(e->det_par, e->det_stage, sizeof(double) * 3 * B, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
+  HIP_TRY(hipEventRecord(e->det_ev, static_cast<hipStream_t>(stream)));
+  e->det_on = true;
+  return AOG_OK;
+}
+
 int aog_get_screens_f64(aog_env* e, double* psi_dev, int first, int count, void* stream) {
   if (!e || !psi_dev) return fail(AOG_ERR_INVALID, "aog_get_screens_f64: null argument");
   if (!e->screens_ready) return fail(AOG_ERR_STATE, "aog_get_screens_f64 before any screen was installed");
@@ -807,7 +889,10 @@ struct StateTail {  // host-side counters that steer the device RNG streams; sto
   int64_t timestep;
   uint64_t rng_seed;
   uint32_t sh_calls, steps_since_reset;
+  uint64_t obs_frame;   // (blobs written before the detector existed left these bytes unwritten: such a blob restores an arbitrary frame count,
+                        // which only matters once a detector is switched on — the stream then starts wherever the count stands)
 };
+static_assert(sizeof(StateTail) <= 256, "the state blob reserves 256 bytes for the tail");
 }  // namespace
 
 int64_t aog_state_bytes(const aog_env* e) {
@@ -826,9 +911,14 @@ int aog_get_state(aog_env* e, void* blob_dev, int64_t* timestep_out, void* strea
     HIP_TRY(hipMemcpyAsync(static_cast<char*>(blob_dev) + off, p.ptr, p.bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     off += (p.bytes + 255) / 256 * 256;
   }
-  StateTail tail{e->timestep, e->rng_seed, e->sh_calls, (uint32_t)e->steps_since_reset};
+  union {   // the whole reserved tail is written: fields added later read zero from blobs of today
+    StateTail tail;
+    char bytes[256];
+  } t{};
+  memset(t.bytes, 0, sizeof t.bytes);
+  t.tail = StateTail{e->timestep, e->rng_seed, e->sh_calls, (uint32_t)e->steps_since_reset, e->obs_frame};
   HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-  HIP_TRY(hipMemcpy(static_cast<char*>(blob_dev) + off, &tail, sizeof tail, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(static_cast<char*>(blob_dev) + off, t.bytes, sizeof t.bytes, hipMemcpyHostToDevice));
   if (timestep_out) *timestep_out = e->timestep;
   return AOG_OK;
 }
@@ -856,6 +946,7 @@ int aog_set_state(aog_env* e, const void* blob_dev, int64_t timestep, void* stre
   e->rng_seed = tail.rng_seed;
   e->sh_calls = tail.sh_calls;
   e->steps_since_reset = tail.steps_since_reset;
+  e->obs_frame = tail.obs_frame;
   e->sh_sums_ready = false;
   if (poisoned(e))   // a restored state replaces every screen: the handle is usable again
     if (int rc = clear_poison(e)) return rc;
@@ -962,8 +1053,8 @@ int step_act_tail(const aog_env* e, const aog_actor* net, const char* who, uint1
     return fail(AOG_ERR_UNSUPPORTED, "%s: %d table-route observations per env exceed the tail's %d staging threads / 16", who, e->n_obs, aog::kStepActThreads);
   const size_t epi = epilogue_lds(e), lds = aog::step_act_lds_bytes(epi, t->lds);
   if (lds > kLdsBytes)
-    return fail(AOG_ERR_UNSUPPORTED, "%s: the fused tail needs %zu bytes of LDS (epilogue %zu, policy query %zu, prologue %zu) > %zu", who, lds, epi, t->lds,
-                (size_t)aog::kStepActProDoubles * sizeof(double), kLdsBytes);
+    return fail(AOG_ERR_UNSUPPORTED, "%s: the fused tail needs %zu bytes of LDS (epilogue %zu, of which the detector's noisy plane %zu; policy query %zu, "
+                "prologue %zu) > %zu", who, lds, epi, epi - epilogue_lds(e, false), t->lds, (size_t)aog::kStepActProDoubles * sizeof(double), kLdsBytes);
   return AOG_OK;
 }
 
@@ -981,9 +1072,10 @@ int reset_impl(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, v
   hipLaunchKernelGGL(aog::k_reset_state, dim3((n + 255) / 256), dim3(256), 0, s, mask, e->act_dm, e->t_render, e->B, e->A, e->cfg.flat_mirror_start);
   int rc = load_actuators(e, s, {e->act_rev, e->act16, nullptr});
   if (rc != AOG_OK || (rc = launch_fused(e, s)) != AOG_OK) return rc;
-  if ((rc = launch_obs(e, s, obs_raw, obs)) != AOG_OK) return rc;
-  rc = launch_epilogue(e, false, obs_raw, obs, nullptr, nullptr, nullptr, nullptr, s, nullptr, tail);
+  if ((rc = launch_obs(e, s, obs_raw, obs, mask)) != AOG_OK) return rc;
+  rc = launch_epilogue(e, false, obs_raw, obs, nullptr, nullptr, nullptr, nullptr, s, nullptr, tail, mask);
   if (rc == AOG_OK && tail) e->pro_pending = true;   // (the mirror holds the first action: aog_step_act(action = NULL) steps it)
+  if (rc == AOG_OK) e->obs_frame += 1;
   return rc;
 }
 
@@ -1044,6 +1136,7 @@ int step_body(aog_env* e, const float* action, const float* action_next, bool pi
   const int rce = launch_epilogue(e, true, obs_raw, obs, reward, done, power, strehl, s, pipelined ? action_next : nullptr, query ? tail : nullptr);
   if (rce == AOG_OK && ((pipelined && action_next) || query)) e->pro_pending = true;
   if (rce == AOG_OK && query && queried) *queried = 1;
+  if (rce == AOG_OK) e->obs_frame += 1;
   return rce;
 }
 

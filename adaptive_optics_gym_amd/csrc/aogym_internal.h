@@ -206,6 +206,12 @@ struct aog_env {
   hipEvent_t turb_ev64 = nullptr, turb_ev32 = nullptr;   // recorded after the last copy out of each staging buffer
   long long turb_version = 0;    // bumped by every aog_set_turbulence with values
   long long turb_amp_key[3] = {-1, 0, 0};   // (version, oversampling, pixel pitch bits) turb_f32 was made for
+  // photodetector model of the observations (aog_set_detector).  det_on = false: the noise-free kernels with their arguments, as before
+  bool det_on = false;
+  double* det_par = nullptr;     // [3][B] device: photons per frame, read noise, background
+  double* det_stage = nullptr;   // pinned [3][B]
+  hipEvent_t det_ev = nullptr;   // recorded after the last copy out of the staging buffer
+  uint64_t obs_frame = 0;        // observations written so far (each aog_reset* / aog_step* call adds one): the frame of the detector's counter
   const double* next_noise = nullptr;
   int next_noise_max_ext = 0;
   unsigned long long rng_seed = 1234;

@@ -52,7 +52,7 @@ float mft_operand_tables(const double* m1, const double* m2, int N, int nf, int 
 static int obs_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 32); }
 static int obs_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
 
-int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs) {
+int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const uint8_t* mask) {
   if (!e->obs_sep) return AOG_OK;
   const int N = e->cfg.n_pupil, o = e->cfg.obs_dim, n_obs = e->n_obs;
   if (e->cfg.precision == AOG_PRECISION_FP64) {
@@ -71,7 +71,10 @@ int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs) {
                          F + (size_t)env * n_obs, (float2*)nullptr, o, N, o);
     }
     const int n = e->B * n_obs;
-    hipLaunchKernelGGL(aog::k_obs_finish64, dim3((n + 255) / 256), dim3(256), 0, s, F, n, e->obs_pw, obs_raw, obs);
+    if (e->det_on)
+      hipLaunchKernelGGL(aog::k_obs_finish64_det, dim3((n + 255) / 256), dim3(256), 0, s, F, n, n_obs, e->obs_pw, obs_raw, obs, detector_args(e, mask));
+    else
+      hipLaunchKernelGGL(aog::k_obs_finish64, dim3((n + 255) / 256), dim3(256), 0, s, F, n, e->obs_pw, obs_raw, obs);
     HIP_TRY(hipGetLastError());
     return AOG_OK;
   }
@@ -85,9 +88,14 @@ int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs) {
     hipLaunchKernelGGL(aog::k_obs_pass1, dim3((n * nxt + 3) / 4), dim3(256), 0, s, e->obs_grid, reinterpret_cast<const aog::f16x8*>(e->obs_m1s),
                        reinterpret_cast<aog::f16x8*>(e->obs_T16), Nxp, Nyp, n);
     const size_t off = (size_t)env0 * n_obs;
-    hipLaunchKernelGGL(aog::k_obs_pass2, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_T16),
-                       reinterpret_cast<const aog::f16x8*>(e->obs_m2s), nxt, n, o, e->obs_unscale, e->obs_pw + off, obs_raw ? obs_raw + off : nullptr,
-                       obs ? obs + off : nullptr);
+    if (e->det_on)
+      hipLaunchKernelGGL(aog::k_obs_pass2_det, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_T16),
+                         reinterpret_cast<const aog::f16x8*>(e->obs_m2s), nxt, n, o, e->obs_unscale, e->obs_pw + off, obs_raw ? obs_raw + off : nullptr,
+                         obs ? obs + off : nullptr, detector_args(e, mask), env0);
+    else
+      hipLaunchKernelGGL(aog::k_obs_pass2, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_T16),
+                         reinterpret_cast<const aog::f16x8*>(e->obs_m2s), nxt, n, o, e->obs_unscale, e->obs_pw + off, obs_raw ? obs_raw + off : nullptr,
+                         obs ? obs + off : nullptr);
   }
   HIP_TRY(hipGetLastError());
   return AOG_OK;

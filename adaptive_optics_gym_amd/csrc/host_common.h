@@ -13,6 +13,7 @@ namespace aog {
 struct ActorArgs;
 struct ActorNoise;
 struct PhaseFieldArgs;
+struct DetectorArgs;
 }
 
 namespace aog_host {
@@ -136,7 +137,10 @@ void launch_phase_grid(aog_env* e, hipStream_t s, const _Float16* act16, const _
                        int n_et);
 void launch_phase_field(aog_env* e, hipStream_t s, const _Float16* act16, float* field, size_t env_stride, int row_stride, bool grid);   // complex64 field, or (grid) one float of reduced phase per pixel
 // focal.hip (K11): the observation of the separable route for every env — |F|^2 into obs_pw and the caller's obs_raw / obs (nullable)
-int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs);
+// (mask: the masked reset's; handles with a detector draw for the masked envs only)
+int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const uint8_t* mask = nullptr);
+// the detector's kernel arguments for the observation this call writes (e->det_on): frame = e->obs_frame
+aog::DetectorArgs detector_args(const aog_env* e, const uint8_t* mask);
 // split-f16 operand tables of a Fraunhofer matrix Fourier transform m1 [nf][N] . E . m2 [N][nf] (K4's layouts: m1s [nfp / 32][Nyp / 16] tiles,
 // m2s [nfp / 32][Nxp / 32][2] tiles), each matrix scaled by a power of two; returns the unscale factor 2^-(e1 + e2)
 float mft_operand_tables(const double* m1, const double* m2, int N, int nf, int nfp, int Nxp, int Nyp, std::vector<_Float16>& m1s,

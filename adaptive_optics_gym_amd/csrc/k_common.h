@@ -165,4 +165,14 @@ __device__ inline double philox_normal(unsigned long long seed, uint32_t env, ui
   return (idx & 1) ? b : a;
 }
 
+// The cosine branch of one Box-Muller pair exactly as philox_normal4 forms it (radius from the top 24 bits of word_r, angle in revolutions from
+// those of word_a), for callers that hold the Philox words already.  (philox_normal4 keeps its own text: the extrusion kernels' code is
+// sensitive to how it is inlined.)
+__device__ __forceinline__ double box_muller24_cos(uint32_t word_r, uint32_t word_a) {
+  const float u1 = ((float)(word_r >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
+  const float u2 = (float)(word_a >> 8) * (1.0f / 16777216.0f);            // [0, 1) revolutions
+  const float r = sqrtf(-2.0f * __logf(u1));
+  return (double)(r * __builtin_amdgcn_cosf(u2));
+}
+
 }  // namespace aog

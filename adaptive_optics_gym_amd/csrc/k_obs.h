@@ -7,6 +7,7 @@
 // waves sharing a 128-row span through LDS would spend 3/4 of its matrix work on padding.  Here a wave owns one (env, 32-column x tile)
 // and forms its A operand in registers — no LDS, no barrier — and pass 2 is one wave per env.
 #pragma once
+#include "k_detector.h"
 #include "k_focal.h"
 
 namespace aog {
@@ -149,6 +150,55 @@ __global__ __launch_bounds__(256) void k_obs_pass2(const f16x8* __restrict__ T16
   }
 }
 
+// k_obs_pass2 for handles with a detector (env0 = the handle's index of env 0 of this launch): pw keeps the clean power, obs_raw / obs take the
+// noisy value.  A kernel of its own, the sums above repeated (the plain kernel keeps its arguments and code: as a shared body its loads were
+// scheduled differently); every lane of the wave walks the store loop, so that the sampler is called by whole waves.
+__global__ __launch_bounds__(256) void k_obs_pass2_det(const f16x8* __restrict__ T16, const f16x8* __restrict__ m2s, int nxt, int n_env, int o, float unscale,
+                                                       double* __restrict__ pw, float* __restrict__ obs_raw, uint16_t* __restrict__ obs, DetectorArgs d,
+                                                       int env0) {
+  const int lane = threadIdx.x & 63;
+  const int env = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (env >= n_env) return;
+  const int nk = 2 * nxt;
+  const f16x8* __restrict__ asrc = T16 + (size_t)env * nk * kFocalTile + lane;
+  const f16x8* __restrict__ bsrc = m2s + lane;
+  double dr[16], di[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { dr[r] = 0.0; di[r] = 0.0; }
+  f16x8 a[4], b[4], an[4], bn[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { a[q] = asrc[q * 64]; b[q] = bsrc[q * 64]; }
+  for (int ks = 0; ks < nk; ++ks) {
+    const size_t nxt_off = (size_t)min(ks + 1, nk - 1) * kFocalTile;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { an[q] = asrc[nxt_off + q * 64]; bn[q] = bsrc[nxt_off + q * 64]; }
+    __builtin_amdgcn_sched_barrier(0);
+    f32x16 cr, ci;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { cr[r] = 0.f; ci[r] = 0.f; }
+    obs_mma(a, b, cr, ci);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dr[r] += (double)cr[r]; di[r] += (double)ci[r]; }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { a[q] = an[q]; b[q] = bn[q]; }
+  }
+  const int u = lane & 31, n_obs = o * o;
+  const double us = (double)unscale;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    if ((r & 3) + 8 * (r >> 2) >= o) break;   // (wave-uniform: no lane has a row in this register or a later one)
+    const int v = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const bool have = u < o && v < o, draw = have && (d.mask == nullptr || d.mask[env0 + env] != 0);
+    const double fr = dr[r] * us, fi = di[r] * us;
+    const double w = fr * fr + fi * fi;
+    const size_t i = (size_t)env * n_obs + v * o + u;
+    const double y = det_noisy_value(d, w, env0 + env, v * o + u, draw);
+    if (have) pw[i] = w;
+    if (draw) det_store(y, i, obs_raw, obs);
+  }
+}
+
 // work-buffer initialisation: n floats of value v
 __global__ void k_obs_fill(float* __restrict__ p, size_t n, float v) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
@@ -160,6 +210,19 @@ __global__ void k_obs_finish64(const double2* __restrict__ F, int n, double* __r
   if (i >= n) return;
   const double2 f = F[i];
   obs_store(f.x * f.x + f.y * f.y, (size_t)i, pw, obs_raw, obs);
+}
+// the same for handles with a detector: whole waves enter (n rounded up by the caller's grid), element i = (env i / n_obs, pixel i % n_obs)
+__global__ void k_obs_finish64_det(const double2* __restrict__ F, int n, int n_obs, double* __restrict__ pw, float* __restrict__ obs_raw,
+                                   uint16_t* __restrict__ obs, DetectorArgs d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool have = i < n;
+  const int env = have ? i / n_obs : 0, j = have ? i - env * n_obs : 0;
+  const double2 f = F[have ? i : 0];
+  const double w = f.x * f.x + f.y * f.y;
+  const bool draw = have && (d.mask == nullptr || d.mask[env] != 0);
+  const double y = det_noisy_value(d, w, env, j, draw);
+  if (have) pw[i] = w;
+  if (draw) det_store(y, (size_t)i, obs_raw, obs);
 }
 
 }  // namespace aog

@@ -1,6 +1,7 @@
 // Per-step kernels around the fused pupil pass: prologue (action -> actuators), float64 validation pass, epilogue, small state kernels.
 #pragma once
 #include "k_common.h"
+#include "k_detector.h"
 
 namespace aog {
 
@@ -244,20 +245,28 @@ constexpr int kEpiOutSlots = 16;   // threads per env in the output phase
 //   pw    [n_out + 1][kEpiEnvs]        powers of the outputs, then Strehl: the observation of env e is pw[j * kEpiEnvs + e], j < n_obs
 //   cfs   [n_out][MRW_used][2]         coefficient matrices of the outputs
 //   cfsci [MRS_used][2]                and of the science amplitude
+//   pwn   [n_noisy][kEpiEnvs]          handles with a detector (n_noisy = n_obs, else 0): the noisy observation beside the clean powers, which
+//                                      the SSIM reward keeps reading; the fused step tail stages the actor's input from it
 struct EpilogueLds {
-  size_t part = 0, U, pw, cfs, cfsci, total;
-  __host__ __device__ EpilogueLds(int MRW, int MRS, int n_out, int MRW_used, int MRS_used) {
+  size_t part = 0, U, pw, cfs, cfsci, pwn, total;
+  __host__ __device__ EpilogueLds(int MRW, int MRS, int n_out, int MRW_used, int MRS_used, int n_noisy = 0) {
     const size_t NS = 2 * (size_t)(MRW + MRS);
     U = part + kEpiGroups * NS * kEpiEnvs;
     pw = U + NS * kEpiEnvs;
     cfs = pw + (size_t)(n_out + 1) * kEpiEnvs;
     cfsci = cfs + (size_t)n_out * MRW_used * 2;
-    total = cfsci + (size_t)MRS_used * 2;
+    pwn = cfsci + (size_t)MRS_used * 2;
+    total = pwn + (size_t)n_noisy * kEpiEnvs;
   }
-  __host__ __device__ explicit EpilogueLds(const EpilogueArgs& p) : EpilogueLds(p.MRW, p.MRS, p.n_obs + p.n_fiber, p.MRW_used, p.MRS_used) {}
+  __host__ __device__ explicit EpilogueLds(const EpilogueArgs& p, bool detector = false)
+      : EpilogueLds(p.MRW, p.MRS, p.n_obs + p.n_fiber, p.MRW_used, p.MRS_used, detector ? p.n_obs : 0) {}
   __host__ __device__ size_t bytes() const { return total * sizeof(double); }
 };
-__device__ __forceinline__ void epilogue_body(const EpilogueArgs& p, int block, double* __restrict__ sm) {
+// DET (handles with a detector, the k_*_det kernels): the output phase keeps the clean powers in pw and stores nothing; a phase of its own,
+// entered by every wave of the workgroup in full (the sampler's inversion is a loop a wave walks together), then draws the noisy value of
+// each (pixel, env), stores obs_raw / obs and leaves it in pwn.  It needs no barrier of its own towards the last phase, which reads pw only.
+template <bool DET = false>
+__device__ __forceinline__ void epilogue_body(const EpilogueArgs& p, int block, double* __restrict__ sm, const DetectorArgs* det = nullptr) {
   const int e = threadIdx.x & (kEpiEnvs - 1);
   const int q = (threadIdx.x / kEpiEnvs) & 15;            // sum slot
   const int cq = threadIdx.x / (kEpiEnvs * 16);           // chunk group (= wave index)
@@ -266,7 +275,7 @@ __device__ __forceinline__ void epilogue_body(const EpilogueArgs& p, int block, 
   const int NS = 2 * MR;
   const int n_out = p.n_obs + p.n_fiber;
   const size_t cstride = (size_t)NS * p.Bp;
-  const EpilogueLds lay(p);
+  const EpilogueLds lay(p, DET);
   double *part = sm + lay.part, *U = sm + lay.U, *pw = sm + lay.pw, *cfs = sm + lay.cfs, *cfsci = sm + lay.cfsci;
   // the per-env state the last phase updates is requested now (it would otherwise be one more memory round trip at the very end)
   int tr_prev = 0;
@@ -320,16 +329,30 @@ __device__ __forceinline__ void epilogue_body(const EpilogueArgs& p, int block, 
       }
       const double w = zr * zr + zi * zi;
       pw[(size_t)j * kEpiEnvs + oe] = w;
-      if (j < p.n_obs && oenv < p.B) {
-        if (p.obs_raw) p.obs_raw[(size_t)oenv * p.n_obs + j] = (float)w;
-        if (p.obs) {
-          const _Float16 hv = (_Float16)w;  // round-to-nearest-even from float64, like np.array(x, float16)
-          p.obs[(size_t)oenv * p.n_obs + j] = *reinterpret_cast<const uint16_t*>(&hv);
+      if constexpr (!DET) {
+        if (j < p.n_obs && oenv < p.B) {
+          if (p.obs_raw) p.obs_raw[(size_t)oenv * p.n_obs + j] = (float)w;
+          if (p.obs) {
+            const _Float16 hv = (_Float16)w;  // round-to-nearest-even from float64, like np.array(x, float16)
+            p.obs[(size_t)oenv * p.n_obs + j] = *reinterpret_cast<const uint16_t*>(&hv);
+          }
         }
       }
     }
   }
   __syncthreads();
+  if constexpr (DET) {
+    double* pwn = sm + lay.pwn;
+    const int n_el = p.n_obs * kEpiEnvs;   // element i = (pixel i / kEpiEnvs, env i % kEpiEnvs), pw's order
+    for (int base = 0; base < n_el; base += (int)blockDim.x) {   // (trip count uniform over the workgroup)
+      const int i = base + (int)threadIdx.x, j = i / kEpiEnvs, oenv = block * kEpiEnvs + (i & (kEpiEnvs - 1));
+      const bool have = i < n_el;
+      const bool draw = have && oenv < p.B && (det->mask == nullptr || det->mask[oenv] != 0);
+      const double y = det_noisy_value(*det, have ? pw[i] : 0.0, oenv, j, draw);
+      if (have) pwn[i] = y;
+      if (draw) det_store(y, (size_t)oenv * p.n_obs + j, p.obs_raw, p.obs);
+    }
+  }
   if (threadIdx.x >= kEpiEnvs || env >= p.B || !p.is_step) return;
   double power = 0;
   for (int j = p.n_obs; j < n_out; ++j) power += pw[(size_t)j * kEpiEnvs + e];
@@ -355,6 +378,10 @@ __global__ __launch_bounds__(1024) void k_epilogue(EpilogueArgs p) {
   extern __shared__ double sm[];
   epilogue_body(p, (int)blockIdx.x, sm);
 }
+__global__ __launch_bounds__(1024) void k_epilogue_det(EpilogueArgs p, DetectorArgs d) {
+  extern __shared__ double sm[];
+  epilogue_body<true>(p, (int)blockIdx.x, sm, &d);
+}
 // Pipelined stepping (aog_step_pipelined): the epilogue of step t and the prologue of step t + 1 — which share nothing — in ONE launch:
 // workgroups [0, n_epi) run the epilogue, the rest the prologue with one env per wave, 16 per workgroup (same arithmetic in the same order
 // as the standalone kernel's four: bit-identical).  One launch and one dispatch gap less per step.
@@ -363,6 +390,14 @@ __global__ __launch_bounds__(1024) void k_epilogue_prologue(EpilogueArgs p, Prol
   extern __shared__ double sm[];
   if ((int)blockIdx.x < n_epi) {
     epilogue_body(p, (int)blockIdx.x, sm);
+    return;
+  }
+  prologue_body<true, kEpiProEnvs>(q, (int)blockIdx.x - n_epi);
+}
+__global__ __launch_bounds__(1024) void k_epilogue_prologue_det(EpilogueArgs p, PrologueArgs q, int n_epi, DetectorArgs d) {
+  extern __shared__ double sm[];
+  if ((int)blockIdx.x < n_epi) {
+    epilogue_body<true>(p, (int)blockIdx.x, sm, &d);
     return;
   }
   prologue_body<true, kEpiProEnvs>(q, (int)blockIdx.x - n_epi);

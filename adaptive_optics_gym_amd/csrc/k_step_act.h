@@ -108,4 +108,53 @@ __global__ __launch_bounds__(kStepActThreads) void k_epilogue_act_prologue_noise
   prologue_body_lds<true, kEpiEnvs>(q, block, sm, sm + 64 * 64);
 }
 
+// The two kernels above for handles with a detector (aog_set_detector): epilogue_body<true> draws the noisy observation, and the table route
+// stages the actor's input from the noisy plane pwn — the float16 that was stored.  Kernels of their own, so that the plain ones keep their
+// arguments and code.
+template <bool NOISE, class A>
+__device__ __forceinline__ void step_act_det_body(const EpilogueArgs& p, const A& a, const PrologueArgs& q, int obs_from_lds, const DetectorArgs& d,
+                                                  double* sm) {
+  const int block = (int)blockIdx.x;
+  const int env0 = block * kEpiEnvs;
+  const bool act = env0 < a.B;   // (uniform per workgroup: the padding past B runs the epilogue only)
+  f32x4 pre[kStepActPre];
+  if (act) actor_issue<kStepActThreads, kStepActPre>(pre, a.w1, a.S, a.H, 0, a.wfloats);
+  epilogue_body<true>(p, block, sm, &d);
+  __syncthreads();
+  if (!act) return;
+  float ov = 0.f;
+  const int i = threadIdx.x;
+  if (obs_from_lds && i < a.S * 16) {
+    const double y = sm[EpilogueLds(p, true).pwn + i];
+    ov = (float)(_Float16)y;
+  }
+  __syncthreads();
+  float* lds_act = reinterpret_cast<float*>(sm);
+  float* xa = lds_act;
+  for (int j = threadIdx.x; j < (int)actor_act_floats(a.kpad, a.kpad_b); j += kStepActThreads) lds_act[j] = 0.f;
+  __syncthreads();
+  if (obs_from_lds) {
+    if (i < a.S * 16) xa[i] = ov;
+  } else {
+    const _Float16* obs = reinterpret_cast<const _Float16*>(a.obs);
+    for (int j = threadIdx.x; j < a.S * 16; j += kStepActThreads) {
+      const int k = j >> 4, e = j & 15, env = min(env0 + e, a.B - 1);
+      xa[j] = (float)obs[(size_t)env * a.S + k];
+    }
+  }
+  __syncthreads();
+  actor_mlp<kStepActThreads, kStepActPre, NOISE, A>(a, lds_act, env0, pre);   // (ends with a barrier: the actions are written and the LDS is free)
+  prologue_body_lds<true, kEpiEnvs>(q, block, sm, sm + 64 * 64);
+}
+__global__ __launch_bounds__(kStepActThreads) void k_epilogue_act_prologue_det(EpilogueArgs p, ActorArgs a, PrologueArgs q, int obs_from_lds,
+                                                                               DetectorArgs d) {
+  extern __shared__ double sm[];
+  step_act_det_body<false, ActorArgs>(p, a, q, obs_from_lds, d, sm);
+}
+__global__ __launch_bounds__(kStepActThreads) void k_epilogue_act_prologue_noise_det(EpilogueArgs p, ActorNoiseArgs a, PrologueArgs q, int obs_from_lds,
+                                                                                     DetectorArgs d) {
+  extern __shared__ double sm[];
+  step_act_det_body<true, ActorNoiseArgs>(p, a, q, obs_from_lds, d, sm);
+}
+
 }  // namespace aog

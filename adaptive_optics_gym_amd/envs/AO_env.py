@@ -21,12 +21,14 @@ class AOEnv(env_base()):
     def __init__(self, atm_type="quasi_static", atm_vel=0, atm_fried=0.15, act_type="num_actuators", act_dim=64,
                  obs_dim=2, rew_type="strehl_ratio", rew_threshold=None, timesteps_per_episode=20,
                  flat_mirror_start_per_episode=True, SH_operation=False, *, num_pupil_pixels=240, device=None,
-                 screens=None, precision="fast", kernel="auto", rng=np.random, verbose=True):
+                 screens=None, precision="fast", kernel="auto", rng=np.random, verbose=True, obs_photons=None, obs_read_noise=0.0,
+                 obs_background=0.0):
         super().__init__()
         self._env = BatchedAOEnv(1, device, atm_type, atm_vel, atm_fried, act_type, act_dim, obs_dim, rew_type,
                                  rew_threshold, timesteps_per_episode, flat_mirror_start_per_episode, SH_operation,
                                  num_pupil_pixels=num_pupil_pixels, screen_source="numpy", screens=screens,
-                                 precision=precision, kernel=kernel, rng=rng, verbose=verbose)
+                                 precision=precision, kernel=kernel, rng=rng, verbose=verbose, obs_photons=obs_photons,
+                                 obs_read_noise=obs_read_noise, obs_background=obs_background)
         e = self._env
         self.atm_type, self.rew_type, self.act_type = e.atm_type, e.rew_type, e.act_type
         self.flat_mirror_start_per_episode = e.flat_mirror_start_per_episode

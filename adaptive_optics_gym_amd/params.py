@@ -84,6 +84,26 @@ def resolve_per_env(name: str, value, num_envs: int, total_envs: int, global_env
     return whole[global_env_offset:global_env_offset + num_envs].copy(), whole, False
 
 
+def resolve_detector(photons, read_noise, background, num_envs: int, total_envs: int, global_env_offset: int):
+    """The photodetector arguments (``obs_photons``, ``obs_read_noise``, ``obs_background``), each a scalar, ``num_envs`` or ``total_envs``
+    values like ``atm_fried`` (``resolve_per_env``), checked: ``None`` when ``photons`` is None (no detector: the noise-free observation),
+    else dict(photons, read_noise, background), [num_envs] float64 arrays.  ``ValueError`` for non-finite values, photons <= 0, negative
+    read noise or background, wrong lengths; ``None`` for read_noise / background means 0."""
+    if photons is None:
+        return None
+    out = {}
+    for key, name, value in (("photons", "obs_photons", photons), ("read_noise", "obs_read_noise", read_noise),
+                             ("background", "obs_background", background)):
+        local, whole, _ = resolve_per_env(name, 0.0 if value is None else value, num_envs, total_envs, global_env_offset)
+        if key == "photons":
+            if np.any(whole <= 0):
+                raise ValueError("obs_photons: photo-electrons per frame must be > 0")
+        elif np.any(whole < 0):
+            raise ValueError(f"{name} must be >= 0")
+        out[key] = np.ascontiguousarray(local, dtype=np.float64)
+    return out
+
+
 def coerce_velocities(atm_type: str, speeds, verbose: bool = True):
     """``coerce_velocity`` applied to every entry of a [B] float64 array of wind speeds (AO_env.py:200-208).  Each message the reference
     prints is printed once when at least one entry was changed."""

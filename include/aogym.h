@@ -242,6 +242,25 @@ int aog_generate_screens(aog_env* env, int first, int count, int oversampling, d
  * NULL returns the handle to the handle-wide value (today's code and bits).  Drops the int8 extrusion's work ahead; AOG_ERR_STATE between
  * two steps of a lookahead episode. */
 int aog_set_turbulence(aog_env* env, const double* cn_squared_host, void* stream);
+
+/* Photodetector model of the observations: shot noise, read noise and a calibrated background, per env ([B] float64 HOST arrays, copied
+ * through pinned staging on `stream`).  With c_j = double(float(w_j)) the value a handle without a detector writes to obs_raw for pixel j,
+ *   lam_j = photons_e c_j + background_e,   n_j = large_poisson(lam_j),   y_j = (n_j + read_noise_e g_j - background_e) / photons_e,
+ *   obs_raw = float(y_j), obs = half(y_j)       (float64, no fused multiply-add; g_j standard normal)
+ * photons: expected photo-electrons per frame of the whole unit-power beam (finite, > 0); read_noise: electrons rms per pixel and frame
+ * (>= 0); background: electrons per pixel and frame (>= 0), subtracted again as a calibrated detector does.  AOG_ERR_INVALID otherwise.
+ * ONLY THE OBSERVATION IS NOISY: reward (Strehl, and the SSIM term, which keeps reading the clean float64 powers), power, Strehl, done,
+ * the return accumulator, screens and mirror are those of the handle without a detector bit for bit — the reward is the training signal of
+ * the true state.  The fused tail (aog_reset_act / aog_step_act) feeds the policy the float16 that was stored.
+ * Random stream: one Philox4x32-10 call per (global env, pixel, frame), key = the handle's rng_seed, counter = {j | 6 << 24,
+ * env_id_base + e, frame & 0xFFFFFFFF, (frame >> 32) ^ 0xDE7EC7}; word 0 the Poisson uniform (radius of the rounded-normal branch above
+ * lam = 12), word 1 that branch's angle, words 2, 3 the read-noise normal.  frame = the number of observations the handle has written so
+ * far: every aog_reset* / aog_step* call adds one, with or without a detector; a masked aog_reset counts as one frame, draws for the masked
+ * envs only and leaves the other rows of obs_raw / obs untouched.  The count travels in the state blob.  Nothing else enters (route, launch
+ * shape, fused or separate launches, batch split).
+ * photons_host = NULL switches the detector off: the handle then launches the kernels it launched before, with the same arguments.
+ * AOG_ERR_UNSUPPORTED (naming the sizes) when the table route's epilogue cannot hold the noisy plane in LDS beside the clean powers. */
+int aog_set_detector(aog_env* env, const double* photons_host, const double* read_noise_host, const double* background_host, void* stream);
 /* The per-env values aog_set_turbulence derives, for `count` Cn^2 values (pure host function, no handle or device): two-band sample
  * amplitudes (high / low band), literal-route crop scale, sqrt(Cn^2), int8 noise scale sqrt(Cn^2) / table_sqrt_cn_squared.  Null outputs
  * are skipped. */
