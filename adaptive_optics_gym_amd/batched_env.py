@@ -24,6 +24,17 @@ def _dptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
 
 
+def _mask_array(mask, num_envs, who):
+    """A ``mask`` argument (None: every env; numpy, torch on any device, or a list) as a boolean [num_envs] numpy array; ``who`` names the
+    caller in the error."""
+    if mask is None:
+        return np.ones(num_envs, dtype=bool)
+    sel = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask).astype(bool).reshape(-1)
+    if sel.size != num_envs:
+        raise ValueError(f"{who}: mask must have num_envs entries")
+    return sel
+
+
 class BatchedAOEnv:
     """Constructor keywords = AOEnv's (AO_env.py:17-29) plus:
 
@@ -79,6 +90,8 @@ class BatchedAOEnv:
                  obs_photons=None, obs_read_noise=0.0, obs_background=0.0):
         import torch
 
+        self._handle = None   # (first: close() and accumulate_returns() read it on an env whose construction failed below)
+        self._returns_ref = None
         self._torch = torch
         self.lib = _lib.load()  # raises if the HIP extension is missing — no CPU fallback
         if not torch.cuda.is_available():
@@ -108,7 +121,7 @@ class BatchedAOEnv:
         self.sh_fft_precision = sh_fft_precision
         turb = resolve_turbulence(atm_type, atm_fried, atm_vel, self.num_envs, self.total_envs, self.global_env_offset, verbose)
         self._detector = resolve_detector(obs_photons, obs_read_noise, obs_background, self.num_envs, self.total_envs, self.global_env_offset)
-        self._last_obs = None
+        self._last_obs = self.last_obs_raw = None
         self.observation_frames = 0   # observations written so far (every reset / step adds one): the frame of the detector's random stream
         fried, self._fried_all, vel_scalar = turb["fried"], turb["fried_all"], turb["vel_scalar"]
         self.velocity, self._wind_speeds = turb["velocity"], turb["speeds"]
@@ -135,12 +148,18 @@ class BatchedAOEnv:
             raise ValueError("extrusion must be 'auto' or 'f64'")
         self._extrusion = extrusion
         self._rng = rng
-        self._episode_returns = None
+        self._rngs = {}                # screen_source='numpy' with a seed: env -> its RandomState (_env_rng)
+        self._gen = None               # screen_source='torch': the instance's torch.Generator (_generate_screens)
+        self._host_rng = self._rng is not None or screen_source == "numpy"
+        self._lib_seeded = False       # see _seed_library()
+        self._lib_per_env = False      # the library holds per-env Cn^2 (_push_turbulence)
+        self._lib_detector = False     # the library holds detector values (_push_detector)
+        # host arrays / device tensors a library call reads: kept alive here
+        self._cn2_keep = self._layer = self._noise_dev = self._next_actions_keepalive = None
         self._trunc = None
         self._persistent_out = False   # see persistent_outputs()
         self._step_cache = None        # (views of the persistent block + their addresses)
         self._pack = None
-
 
         self.observation_space = make_box(-1, 1, (self.obs_dim ** 2,), np.float16)  # AO_env.py:45
         self.action_space = make_box(-1, 1, (self.num_modes,), np.float16)          # AO_env.py:46
@@ -156,6 +175,25 @@ class BatchedAOEnv:
             raise ValueError(f"tables= were built for the {tables.obs_route!r} observation route; this handle takes {self.obs_route!r}")
         self.tables: HostTables = tables if tables is not None else build_tables(self.params, act_type, self.num_modes, self.obs_dim,
                                                                                  obs_route=self.obs_route)
+        self._create_handle(precision, kernel, pixel_chunks)
+        self._upload_tables()
+        layer = self._draw_wind_and_stencils()
+        theta = self.wind_u * 2 * np.pi
+        speed = float(self.velocity) if vel_scalar else self._wind_speeds[:, None]
+        self.velocity_vectors = speed * np.stack([np.cos(theta), np.sin(theta)], axis=1)  # [B, 2] m/s
+        if self.atm_type == "dynamic":
+            self._upload_layer(layer)
+        self._push_turbulence()
+        if screens is not None:
+            self.set_screens(screens)
+        else:
+            self._generate_screens()
+        if self.SH_operation:
+            self._upload_shack_hartmann()
+        self._push_detector()   # (last: in host-RNG mode without a seed it draws the handle's seed after the reference's own draws)
+
+    def _create_handle(self, precision, kernel, pixel_chunks):
+        """Fill the library's aog_config from this instance, create the handle on the env's device and give it its seed."""
         t = self.tables
         cfg = _lib.AogConfig()
         cfg.abi_version = _lib.ABI_VERSION
@@ -167,30 +205,31 @@ class BatchedAOEnv:
         cfg.n_wfs_tables = t.wfs_tables.shape[0]
         cfg.n_sci_tables = t.sci_tables.shape[0]
         cfg.n_fiber_modes = t.n_fiber_modes
-        cfg.reward_type = _lib.AOG_REWARD[rew_type]
+        cfg.reward_type = _lib.AOG_REWARD[self.rew_type]
         cfg.sh_operation = int(self.SH_operation)
-        cfg.max_steps = int(timesteps_per_episode)
+        cfg.max_steps = int(self.max_steps)
         cfg.flat_mirror_start = int(self.flat_mirror_start_per_episode)
-        cfg.has_rew_threshold = int(rew_threshold is not None)
+        cfg.has_rew_threshold = int(self.rew_threshold is not None)
         cfg.precision = _lib.AOG_PRECISION[precision]
         cfg.kernel = _lib.AOG_KERNEL[kernel]
         cfg.pixel_chunks = int(pixel_chunks)
-        cfg.atm_dynamic = int(atm_type == "dynamic")
+        cfg.atm_dynamic = int(self.atm_type == "dynamic")
         cfg.env_id_base = self.global_env_offset
         cfg.obs_separable = int(self.obs_route == "separable")
         cfg.wavelength_wfs = self.params.wavelength_wfs
         cfg.wavelength_sci = self.params.wavelength_sci
         cfg.surface_rms_target = self.params.action_rms_fraction * self.params.wavelength_sci
-        cfg.rew_threshold = float(rew_threshold) if rew_threshold is not None else 0.0
+        cfg.rew_threshold = float(self.rew_threshold) if self.rew_threshold is not None else 0.0
         cfg.ssim_ref_peak = self.params.ssim_ref_peak
         cfg.ssim_alpha = self.params.ssim_alpha
         self._handle = C.c_void_p()
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        dev_index = self.device.index if self.device.index is not None else self._torch.cuda.current_device()
         _lib.check(self.lib.aog_create(C.byref(cfg), dev_index, C.byref(self._handle)))
-        self._host_rng = self._rng is not None or screen_source == "numpy"
-        self._lib_seeded = False
         self._seed_library(draw=False)
 
+    def _upload_tables(self):
+        """The host tables (and, separable route, the observation's transform matrices) to the handle; then its screen method and ``info``."""
+        t = self.tables
         keep = dict(
             ap=np.ascontiguousarray(t.ap_index, dtype=np.int32),
             modes=np.ascontiguousarray(t.modes, dtype=np.float64),
@@ -212,15 +251,16 @@ class BatchedAOEnv:
             om2 = np.ascontiguousarray(np.stack([t.obs_m2.real, t.obs_m2.imag], axis=-1), dtype=np.float64)
             mft = _lib.AogObsMft(self.obs_dim, 0, _dptr(om1, C.c_double), _dptr(om2, C.c_double))
             _lib.check(self.lib.aog_upload_obs_mft(self._handle, C.byref(mft)))
-        _lib.check(self.lib.aog_set_screen_method(self._handle, _lib.AOG_SCREENS[screen_method]))
+        _lib.check(self.lib.aog_set_screen_method(self._handle, _lib.AOG_SCREENS[self.screen_method]))
         self.info = _lib.AogInfo()
         _lib.check(self.lib.aog_get_info(self._handle, C.byref(self.info)))
 
-        # atmosphere (AO_env.py:361-370)
+    def _draw_wind_and_stencils(self):
+        """atmosphere (AO_env.py:361-370): set ``wind_u`` (every env's wind direction / 2 pi) and return the dynamic atmosphere's layer
+        tables (None otherwise)."""
         # hcipy's construction order (SURVEY.md A.9): wind direction (rand), the two stencil draws (geometric x2), then
         # the screen normals.  Host-RNG mode consumes the numpy stream in that order; env 0's draws define the stencils /
         # AR matrices shared by the whole batch (for B = 1 this is exactly the reference's layer).
-        self._host_rng = self._rng is not None or screen_source == "numpy"
         N = self.num_pupil_pixels
         wind_u = np.zeros(self.num_envs)   # hcipy draws theta = rand() * 2 pi per layer
         layer = None
@@ -239,7 +279,7 @@ class BatchedAOEnv:
                     r.geometric(0.5, N)
                     r.geometric(0.5, N)
         else:
-            base_seed = 1234 if seed is None else int(seed)
+            base_seed = self._base_seed
             trng = np.random.RandomState(base_seed)
             wind_u = trng.rand(self.total_envs)[self.global_env_offset:self.global_env_offset + self.num_envs]
             if self.atm_type == "dynamic":
@@ -247,21 +287,7 @@ class BatchedAOEnv:
                 # and instances holding different slices of one batch must share the AR matrices whatever total_envs they were given
                 layer = build_layer_tables(N, self.params.pupil_pixel, self.params.outer_scale, np.random.RandomState([base_seed & 0xFFFFFFFF, 0x57E9C11]))
         self.wind_u = np.array(wind_u, dtype=np.float64)
-        theta = self.wind_u * 2 * np.pi
-        if vel_scalar:
-            self.velocity_vectors = float(self.velocity) * np.stack([np.cos(theta), np.sin(theta)], axis=1)  # [B, 2] m/s
-        else:
-            self.velocity_vectors = self._wind_speeds[:, None] * np.stack([np.cos(theta), np.sin(theta)], axis=1)
-        if self.atm_type == "dynamic":
-            self._upload_layer(layer)
-        self._push_turbulence()
-        if screens is not None:
-            self.set_screens(screens)
-        else:
-            self._generate_screens(first_call=True)
-        if self.SH_operation:
-            self._upload_shack_hartmann()
-        self._push_detector()   # (last: in host-RNG mode without a seed it draws the handle's seed after the reference's own draws)
+        return layer
 
     # ------------------------------------------------------------------------------------------------
     # per-env turbulence
@@ -301,7 +327,7 @@ class BatchedAOEnv:
             self._cn2_keep = np.ascontiguousarray(self._cn2, dtype=np.float64)
             _lib.check(self.lib.aog_set_turbulence(self._handle, self._cn2_keep.ctypes.data_as(C.c_void_p), self._stream()))
             self._lib_per_env = True
-        elif getattr(self, "_lib_per_env", False):
+        elif self._lib_per_env:
             _lib.check(self.lib.aog_set_turbulence(self._handle, None, self._stream()))
             self._lib_per_env = False
 
@@ -316,21 +342,15 @@ class BatchedAOEnv:
         values were passed — and each env's normals are scaled by sqrt(Cn^2_e / Cn^2_table) <= 1, so an r0 below that smallest one raises
         ``ValueError`` (the library refuses it too): build the env with the smallest r0 the randomisation will draw among its ``atm_fried``.
         Per-env wind speed stays what the constructor was given."""
-        torch = self._torch
         fried, _, _ = resolve_per_env("fried", fried, self.num_envs, self.total_envs, self.global_env_offset)
         if np.any(fried <= 0):
             raise ValueError("set_turbulence: Fried parameters must be > 0")
-        if mask is None:
-            sel = np.ones(self.num_envs, dtype=bool)
-        else:
-            sel = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask).astype(bool).reshape(-1)
-            if sel.size != self.num_envs:
-                raise ValueError("set_turbulence: mask must have num_envs entries")
+        sel = _mask_array(mask, self.num_envs, "set_turbulence")
         new = self._fried.copy()
         new[sel] = fried[sel]
         self._apply_fried(new)
         if self.atm_type != "semi_dynamic" and sel.any():
-            self._generate_screens(mask=None if sel.all() else torch.as_tensor(sel.astype(np.uint8), device=self.device))
+            self._generate_screens(mask=None if sel.all() else sel)
 
     def _apply_fried(self, new):
         new = np.asarray(new, dtype=np.float64).copy()
@@ -360,29 +380,39 @@ class BatchedAOEnv:
             out[k] = v
         return out
 
-    def _seed_library(self, draw):
+    @property
+    def _base_seed(self):
+        """The number the instance's seeded streams start from: ``seed``, or 1234 when it is None."""
+        return 1234 if self.seed is None else int(self.seed)
+
+    def _seed_library(self, draw, provisional=False):
         """The handle's 64-bit rng_seed, set once.  Device random streams: ``seed`` (1234 when None), whatever else the constructor does
         (screens= on a static atmosphere seeds no stream otherwise).  Host-RNG mode with a ``seed`` and no ``rng``: that seed too (the
         same on every slice of a split batch).  Otherwise (``rng=`` or the process-global numpy stream: the single-env wrapper) there is
         no number to take, so — only when a detector needs one (``draw``) — 62 bits are drawn from that stream: two instances then
-        draw different detector noise, and seeding the stream reproduces it.  Envs without a detector never consume host draws here."""
+        draw different detector noise, and seeding the stream reproduces it.  Envs without a detector never consume host draws here.
+        ``provisional`` (``_upload_layer``): that last case on a dynamic atmosphere meanwhile runs at the base seed, which the handle's
+        state blob records and ``sh_update(None)`` draws from; a detector's draw still replaces it."""
         if self._lib_seeded:
             return
+        final = True
         if not self._host_rng or (self._rng is None and self.seed is not None):
-            value = 1234 if self.seed is None else int(self.seed)
+            value = self._base_seed
         elif draw:
             r = self._env_rng(0)
             value = (int(r.randint(0, 2 ** 31)) << 31) | int(r.randint(0, 2 ** 31))
+        elif provisional:
+            value, final = self._base_seed, False
         else:
             return
         _lib.check(self.lib.aog_set_rng_seed(self._handle, C.c_uint64(value)))
-        self._lib_seeded = True
+        self._lib_seeded = final
 
     def _push_detector(self):
         """Hand the per-env detector values to the library (aog_set_detector), or NULL without a detector."""
         d = self._detector
         if d is None:
-            if getattr(self, "_lib_detector", False):
+            if self._lib_detector:
                 _lib.check(self.lib.aog_set_detector(self._handle, None, None, None, self._stream()))
             self._lib_detector = False
             return
@@ -410,15 +440,11 @@ class BatchedAOEnv:
                 new["read_noise"] = cur["read_noise"].copy()
             if background is None:
                 new["background"] = cur["background"].copy()
-        if mask is not None:
-            sel = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask).astype(bool).reshape(-1)
-            if sel.size != self.num_envs:
-                raise ValueError("set_detector: mask must have num_envs entries")
-            if cur is None and not sel.all():
-                raise ValueError("set_detector: the env has no detector yet; the first call must cover every env")
-            if cur is not None:
-                for k in new:
-                    new[k] = np.where(sel, new[k], cur[k])
+        sel = _mask_array(mask, self.num_envs, "set_detector")
+        if cur is None and not sel.all():
+            raise ValueError("set_detector: the env has no detector yet; the first call must cover every env")
+        if cur is not None and not sel.all():
+            new = {k: np.where(sel, v, cur[k]) for k, v in new.items()}
         self._detector = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in new.items()}
         self._push_detector()
 
@@ -429,11 +455,8 @@ class BatchedAOEnv:
         n = self.obs_dim ** 2
         if masked and self._detector is not None and self._last_obs is not None:
             return self._last_obs.clone(), self.last_obs_raw.clone()
-        if masked and self._detector is not None:
-            return (torch.zeros((self.num_envs, n), dtype=torch.float16, device=self.device),
-                    torch.zeros((self.num_envs, n), dtype=torch.float32, device=self.device))
-        return (torch.empty((self.num_envs, n), dtype=torch.float16, device=self.device),
-                torch.empty((self.num_envs, n), dtype=torch.float32, device=self.device))
+        new = torch.zeros if masked and self._detector is not None else torch.empty
+        return (new((self.num_envs, n), dtype=torch.float16, device=self.device), new((self.num_envs, n), dtype=torch.float32, device=self.device))
 
     # ------------------------------------------------------------------------------------------------
     def _stream(self):
@@ -444,44 +467,37 @@ class BatchedAOEnv:
             return self._rng
         if self.seed is None:
             return np.random
-        if not hasattr(self, "_rngs"):
-            self._rngs = {}
         if e not in self._rngs:
             self._rngs[e] = np.random.RandomState(self.seed + self.global_env_offset + e)   # seed + GLOBAL env id
         return self._rngs[e]
 
-    def _generate_screens(self, first_call=False, mask=None):
+    def _generate_screens(self, mask=None):
+        """New screens from ``screen_source`` for every env, or for those ``mask`` selects."""
         torch = self._torch
         p = self.params
-        if self._rng is not None or self.screen_source == "numpy":
-            for e in range(self.num_envs):
-                if mask is not None and not bool(mask[e]):
-                    continue
-                psi = screen_numpy(p.num_pupil_pixels, p.pupil_pixel, float(self._cn2[e]), p.outer_scale, self._env_rng(e),
+        sel = _mask_array(mask, self.num_envs, "reset")   # (set_turbulence has checked its own)
+        if self._host_rng:
+            for e in np.flatnonzero(sel):
+                psi = screen_numpy(p.num_pupil_pixels, p.pupil_pixel, float(self._cn2[e]), p.outer_scale, self._env_rng(int(e)),
                                    self.screen_oversampling)
-                self.set_screens(psi[None], first=e)
+                self.set_screens(psi[None], first=int(e))
         elif self.screen_source == "device":
-            _lib.check(self.lib.aog_set_rng_seed(self._handle, C.c_uint64(1234 if self.seed is None else int(self.seed))))
             args = (int(self.screen_oversampling), self._screen_cn2(), float(p.outer_scale), float(p.pupil_pixel), self._stream())
-            if mask is None:
-                _lib.check(self.lib.aog_generate_screens(self._handle, 0, self.num_envs, *args))
-            else:
-                idx = np.flatnonzero(np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask))
-                runs = np.split(idx, np.flatnonzero(np.diff(idx) != 1) + 1) if idx.size else []
-                for r in runs:
-                    _lib.check(self.lib.aog_generate_screens(self._handle, int(r[0]), int(r.size), *args))
+            idx = np.flatnonzero(sel)   # one call per run of consecutive envs (no mask: the whole batch)
+            for r in np.split(idx, np.flatnonzero(np.diff(idx) != 1) + 1) if idx.size else []:
+                _lib.check(self.lib.aog_generate_screens(self._handle, int(r[0]), int(r.size), *args))
         else:
-            if not hasattr(self, "_gen"):
+            if self._gen is None:
                 self._gen = torch.Generator(device=self.device)
                 # (one torch stream per instance, offset by the instance's first global env id: distinct atmospheres on every rank,
                 # but — unlike 'device' and 'numpy' — not invariant to how the batch is split)
-                self._gen.manual_seed((1234 if self.seed is None else int(self.seed)) + self.global_env_offset)
+                self._gen.manual_seed(self._base_seed + self.global_env_offset)
             psi = screens_torch(self.num_envs, p.num_pupil_pixels, p.pupil_pixel, self.Cn_squared, p.outer_scale,
                                 self.device, self._gen, self.screen_oversampling)   # (Cn_squared: scalar, or [B] per env)
             if mask is None:
                 self.set_screens(psi)
             else:
-                for e in np.flatnonzero(np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask)):
+                for e in np.flatnonzero(sel):
                     self.set_screens(psi[e:e + 1], first=int(e))
 
     def _upload_layer(self, layer):
@@ -496,7 +512,7 @@ class BatchedAOEnv:
         _lib.check(self.lib.aog_upload_layer(self._handle, C.byref(lt)))
         v = torch.from_numpy(np.ascontiguousarray(self.velocity_vectors)).to(self.device)
         _lib.check(self.lib.aog_set_wind(self._handle, C.c_void_p(v.data_ptr()), float(np.abs(self.velocity_vectors).max()), self._stream()))
-        _lib.check(self.lib.aog_set_rng_seed(self._handle, C.c_uint64(1234 if self.seed is None else int(self.seed))))
+        self._seed_library(draw=False, provisional=True)
         torch.cuda.current_stream(self.device).synchronize()
         self._upload_composite(layer)
 
@@ -558,9 +574,7 @@ class BatchedAOEnv:
         B, N = self.num_envs, self.num_pupil_pixels
         action = torch.empty((B, self.num_modes), dtype=torch.float64, device=self.device)
         if self._host_rng:
-            img = torch.empty((B, N * N), dtype=torch.float64, device=self.device)
-            _lib.check(self.lib.aog_sh_image(self._handle, C.c_void_p(img.data_ptr()), self._stream()))
-            lam = img.cpu().numpy()
+            lam = self.sh_image().cpu().numpy()
             noisy = np.empty_like(lam)
             for e in range(B):
                 r = self._env_rng(e)
@@ -601,7 +615,6 @@ class BatchedAOEnv:
     def _host_extrusion_noise(self):
         """Host-RNG (parity) mode: draw the normals of the coming step's extrusions from each env's numpy stream in hcipy's
         order (all x shifts, then all y shifts; ``normal(0, 1, N)`` per extrusion) and hand them to the library."""
-        torch = self._torch
         N = self.num_pupil_pixels
         t_prev, t_new = self.timestep * self.delta_t, (self.timestep + 1) * self.delta_t
         shifts = integer_shifts(self.velocity_vectors, t_prev, t_new, self.params.pupil_pixel)  # [B, 2]
@@ -614,8 +627,7 @@ class BatchedAOEnv:
             r = self._env_rng(e)
             for k in range(int(counts[e])):
                 noise[e, k] = r.normal(0, 1, size=N)
-        self._noise_dev = torch.from_numpy(noise).to(self.device)  # kept alive until the step has run
-        _lib.check(self.lib.aog_set_extrusion_noise(self._handle, C.c_void_p(self._noise_dev.data_ptr()), max_ext, self._stream()))
+        self.set_extrusion_noise(noise)
 
     def set_extrusion_noise(self, noise):
         """Standard normals for the extrusions of the NEXT ``step`` (dynamic atmosphere, parity runs): ``[B, max_ext, N]`` float64
@@ -683,18 +695,13 @@ class BatchedAOEnv:
     def reset(self, mask=None, seed=None, options=None):
         """AOEnv.reset (AO_env.py:74-103) for every env (or those selected by ``mask``).  ``seed``/``options`` are
         accepted and ignored exactly like the reference.  Returns (obs [B, o^2] float16, {})."""
-        torch = self._torch
-        m = None
-        if mask is not None:
-            m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+        m = None if mask is None else self._torch.as_tensor(mask, device=self.device).to(self._torch.uint8).contiguous()
         if self.atm_type == "semi_dynamic":
             self._generate_screens(mask=m)  # layer.reset() (AO_env.py:76-77)
         obs, obs_raw = self._obs_buffers(m is not None)
         _lib.check(self.lib.aog_reset(self._handle, C.c_void_p(m.data_ptr()) if m is not None else None,
                                       C.c_void_p(obs_raw.data_ptr()), C.c_void_p(obs.data_ptr()), self._stream()))
-        self.last_obs_raw = obs_raw
-        self._last_obs = obs
-        self.observation_frames += 1
+        self._observed(obs, obs_raw)
         return obs, {}
 
     _PIPELINE_END = object()
@@ -713,40 +720,42 @@ class BatchedAOEnv:
         a = self._as_actions(actions)
         if self.atm_type == "dynamic" and self._host_rng:
             self._host_extrusion_noise()
-        if self._persistent_out and out is None and self._step_cache is not None:
+        cached = self._persistent_out and out is None
+        if cached and self._step_cache is not None:
             # persistent outputs: the views of the block and their addresses are made once (a step's host cost drops from ~22 to ~10 us, which
             # matters right after a synchronisation, when the first launches of a burst cost the host twice their steady-state time)
             ret, ptrs = self._step_cache
-            self._launch_step(a, next_actions, ptrs)
-            self.timestep += 1
-            self.last_obs_raw = ret[4]["obs_raw"]
-            self._last_obs = ret[0]
-            self.observation_frames += 1
-            return ret
-        ret, ptrs, obs_raw = self._step_outputs(out)
+        else:
+            ret, ptrs = self._step_outputs(out)
+            if cached:
+                self._step_cache = (ret, ptrs)
         self._launch_step(a, next_actions, ptrs)
-        self.timestep += 1
-        self.last_obs_raw = obs_raw
-        self._last_obs = ret[0]
-        self.observation_frames += 1
-        if self._persistent_out and out is None:
-            self._step_cache = (ret, ptrs)
+        self._observed(ret[0], ret[4]["obs_raw"], step=True)
         return ret
 
+    def _observed(self, obs, obs_raw, step=False):
+        """Bookkeeping after the launches of a reset or (``step``) a step that wrote the observation ``obs`` / ``obs_raw``.  Every such call
+        goes through here: ``observation_frames`` must follow the library's own count of them (the frame of the detector's random stream,
+        which ``get_state`` / ``set_state`` and split batches rely on)."""
+        self.last_obs_raw = obs_raw
+        self._last_obs = obs
+        self.observation_frames += 1
+        if step:
+            self.timestep += 1
+
     def _step_outputs(self, out):
-        """The tensors a step writes and returns: (step tuple, their addresses in aog_step's order, obs_raw)."""
+        """The tensors a step writes and returns: (step tuple, their addresses in aog_step's order)."""
         torch = self._torch
         n = self.obs_dim ** 2
         B = self.num_envs
         # ONE allocation per step: fp32 block (obs_raw | reward | power | strehl), fp16 obs, uint8 done — or none at all when the
         # caller asked for a persistent block (``persistent_outputs``: the single-env wrapper copies it to the host in one transfer)
         nb32, nb16 = 4 * B * (n + 3), 2 * B * n
-        if self._persistent_out:
-            if self._pack is None:
-                self._pack = torch.empty((nb32 + nb16 + B,), dtype=torch.uint8, device=self.device)
-            pack = self._pack
-        else:
+        pack = self._pack if self._persistent_out else None
+        if pack is None:
             pack = torch.empty((nb32 + nb16 + B,), dtype=torch.uint8, device=self.device)
+            if self._persistent_out:
+                self._pack = pack
         f32 = pack[:nb32].view(torch.float32)
         obs_raw = f32[: B * n].view(B, n)
         power = f32[B * (n + 1): B * (n + 2)]
@@ -767,7 +776,7 @@ class BatchedAOEnv:
         if self._trunc is None:
             self._trunc = torch.zeros((B,), dtype=torch.bool, device=self.device)
         ret = (obs, reward, done if done.dtype == torch.bool else done.view(torch.bool), self._trunc, {"power": power, "obs_raw": obs_raw, "strehl": strehl})
-        return ret, ptrs, obs_raw
+        return ret, ptrs
 
     # ------------------------------------------------------------------------------------------------
     # causal policy stepping: the rollout's actor.get_action(obs) -> env.step(action) (algorithm.py:256-262) with the policy attached
@@ -810,24 +819,17 @@ class BatchedAOEnv:
         (``aog_reset_act_noise``)."""
         if mask is not None:
             raise ValueError("reset_with_policy resets the whole batch; reset some envs with reset(mask) and step with an explicit action")
-        torch = self._torch
         net, (action, log_prob, mean), noise = self._policy_net(policy, cov_var, policy_out, ou_noise, action_mode)
         if self.atm_type == "semi_dynamic":
             self._generate_screens(mask=None)  # layer.reset() (AO_env.py:76-77)
-        n = self.obs_dim ** 2
-        obs = torch.empty((self.num_envs, n), dtype=torch.float16, device=self.device)
-        obs_raw = torch.empty((self.num_envs, n), dtype=torch.float32, device=self.device)
+        obs, obs_raw = self._obs_buffers(False)
         p = C.c_void_p
-        args = (self._handle, C.byref(net), p(obs_raw.data_ptr()), p(obs.data_ptr()), p(action.data_ptr()), p(log_prob.data_ptr()),
-                p(mean.data_ptr() if mean is not None else None))
-        if noise is None:
-            _lib.check(self.lib.aog_reset_act(*args, self._stream()))
-        else:
-            _lib.check(self.lib.aog_reset_act_noise(*args, C.byref(noise), self._stream()))
+        # (noise = NULL is the library's aog_reset_act)
+        _lib.check(self.lib.aog_reset_act_noise(self._handle, C.byref(net), p(obs_raw.data_ptr()), p(obs.data_ptr()), p(action.data_ptr()),
+                                                p(log_prob.data_ptr()), p(mean.data_ptr() if mean is not None else None),
+                                                C.byref(noise) if noise is not None else None, self._stream()))
         policy.calls += 1
-        self.last_obs_raw = obs_raw
-        self._last_obs = obs
-        self.observation_frames += 1
+        self._observed(obs, obs_raw)
         return (obs, {}), (action, log_prob, mean)
 
     def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None, ou_noise=None, action_mode="sample"):
@@ -843,19 +845,15 @@ class BatchedAOEnv:
         net, pol, noise = self._policy_net(policy, cov_var, policy_out, ou_noise, action_mode)
         if self.atm_type == "dynamic" and self._host_rng:
             self._host_extrusion_noise()
-        ret, ptrs, obs_raw = self._step_outputs(out)
+        ret, ptrs = self._step_outputs(out)
         p = C.c_void_p
         queried = C.c_int(0)
-        args = (self._handle, C.byref(net), p(a.data_ptr() if a is not None else None), p(ptrs[0]), p(ptrs[1]), p(ptrs[2]), p(ptrs[3]), p(ptrs[4]),
-                p(ptrs[5]), p(pol[0].data_ptr()), p(pol[1].data_ptr()), p(pol[2].data_ptr() if pol[2] is not None else None), C.byref(queried))
-        if noise is None:
-            _lib.check(self.lib.aog_step_act(*args, self._stream()))
-        else:
-            _lib.check(self.lib.aog_step_act_noise(*args, C.byref(noise), self._stream()))
-        self.timestep += 1
-        self.last_obs_raw = obs_raw
-        self._last_obs = ret[0]
-        self.observation_frames += 1
+        # (noise = NULL is the library's aog_step_act)
+        _lib.check(self.lib.aog_step_act_noise(self._handle, C.byref(net), p(a.data_ptr() if a is not None else None), p(ptrs[0]), p(ptrs[1]),
+                                               p(ptrs[2]), p(ptrs[3]), p(ptrs[4]), p(ptrs[5]), p(pol[0].data_ptr()), p(pol[1].data_ptr()),
+                                               p(pol[2].data_ptr() if pol[2] is not None else None), C.byref(queried),
+                                               C.byref(noise) if noise is not None else None, self._stream()))
+        self._observed(ret[0], ret[4]["obs_raw"], step=True)
         if not queried.value:
             return ret, None
         policy.calls += 1
@@ -874,7 +872,7 @@ class BatchedAOEnv:
 
     def _launch_step(self, a, next_actions, ptrs):
         p = C.c_void_p
-        pending = getattr(self, "_next_actions_keepalive", None)
+        pending = self._next_actions_keepalive
         if next_actions is BatchedAOEnv._PIPELINE_END:
             self._next_actions_keepalive = None
             _lib.check(self.lib.aog_step(self._handle, p(a.data_ptr()), p(ptrs[0]), p(ptrs[1]), p(ptrs[2]), p(ptrs[3]), p(ptrs[4]), p(ptrs[5]),
@@ -995,10 +993,10 @@ class BatchedAOEnv:
         """Have every ``step`` add its rewards into ``returns`` ([B] float32 contiguous device tensor; the caller zeroes it at
         episode start) inside the step's last kernel — the episode-return sum of the rollout without a launch of its own.
         ``None`` detaches.  The tensor must stay alive while attached (a reference is kept here)."""
-        torch = self._torch
-        if getattr(self, "_handle", None) is None:   # closed env: nothing to attach to or detach from
+        if not self._handle:   # closed env (or one whose construction failed): nothing to attach to or detach from
             self._returns_ref = None
             return
+        torch = self._torch
         if returns is not None:
             ok = returns.dtype == torch.float32 and tuple(returns.shape) == (self.num_envs,) and returns.is_contiguous() and returns.is_cuda
             if not ok:
@@ -1035,7 +1033,7 @@ class BatchedAOEnv:
         return out
 
     def close(self):
-        h, self._handle = getattr(self, "_handle", None), None
+        h, self._handle = self._handle, None
         if h:
             self.lib.aog_destroy(h)
 

@@ -272,12 +272,9 @@ aog::PrologueArgs prologue_args(const aog_env* e, const float* action) {
   return q;
 }
 
-// action_next (aog_step_pipelined): the prologue of the NEXT step rides in the same launch (k_epilogue_prologue)
-// tail (aog_reset_act / aog_step_act): the policy query on this epilogue's observation and the prologue of the next step from its action ride in
-// the same launch, per workgroup of 16 envs (k_epilogue_act_prologue)
-// mask (masked aog_reset): handles with a detector draw for the masked envs only
-int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
-                    float* strehl, hipStream_t s, const float* action_next = nullptr, const ActTail* tail = nullptr, const uint8_t* mask = nullptr) {
+// the epilogue's arguments for one reset (is_step = false: the step outputs are null) or step, writing into the caller's tensors
+aog::EpilogueArgs epilogue_args(const aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
+                                float* strehl) {
   aog::EpilogueArgs p{};
   p.partials = e->partials;
   p.wfs_coef = e->wfs_coef;
@@ -308,58 +305,53 @@ int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, flo
   p.thr = e->cfg.rew_threshold;
   p.ssim_peak = e->cfg.ssim_ref_peak;
   p.ssim_alpha = e->cfg.ssim_alpha;
-  const size_t lds = epilogue_lds(e);
-  const int n_epi = (e->Bp + aog::kEpiEnvs - 1) / aog::kEpiEnvs;
-  if (e->det_on) {   // the same three launch forms through the kernels that draw the detector's noise
-    const aog::DetectorArgs d = detector_args(e, mask);
-    if (tail) {
-      aog::ActorArgs a = tail->a;
-      aog::PrologueArgs q = prologue_args(e, a.action);
-      const int obs_from_lds = e->obs_sep ? 0 : 1;
-      a.obs = obs;
-      a.obs_f16 = 1;
-      const size_t lds_all = aog::step_act_lds_bytes(lds, tail->lds);   // (<= kLdsBytes: checked by step_act_tail)
-      const void* kernel = tail->noisy ? reinterpret_cast<const void*>(aog::k_epilogue_act_prologue_noise_det)
-                                       : reinterpret_cast<const void*>(aog::k_epilogue_act_prologue_det);
-      if (int rc = aog_host::ensure_dynamic_lds(kernel, lds_all, e->device)) return rc;
-      if (tail->noisy)
-        hipLaunchKernelGGL(aog::k_epilogue_act_prologue_noise_det, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, aog::ActorNoiseArgs{a, tail->nz},
-                           q, obs_from_lds, d);
-      else
-        hipLaunchKernelGGL(aog::k_epilogue_act_prologue_det, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, a, q, obs_from_lds, d);
-    } else if (action_next) {
-      const aog::PrologueArgs q = prologue_args(e, action_next);
-      if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue_prologue_det), lds, e->device)) return rc;
-      hipLaunchKernelGGL(aog::k_epilogue_prologue_det, dim3(n_epi + (e->B + aog::kEpiProEnvs - 1) / aog::kEpiProEnvs), dim3(1024), lds, s, p, q, n_epi, d);
-    } else {
-      if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue_det), lds, e->device)) return rc;
-      hipLaunchKernelGGL(aog::k_epilogue_det, dim3(n_epi), dim3(1024), lds, s, p, d);
-    }
-  } else if (tail) {
-    aog::ActorArgs a = tail->a;
-    aog::PrologueArgs q = prologue_args(e, a.action);
-    const int obs_from_lds = e->obs_sep ? 0 : 1;
-    a.obs = obs;
-    a.obs_f16 = 1;
-    const size_t lds_all = aog::step_act_lds_bytes(lds, tail->lds);   // (<= kLdsBytes: checked by step_act_tail)
-    const void* kernel = tail->noisy ? reinterpret_cast<const void*>(aog::k_epilogue_act_prologue_noise)
-                                     : reinterpret_cast<const void*>(aog::k_epilogue_act_prologue);
-    if (int rc = aog_host::ensure_dynamic_lds(kernel, lds_all, e->device)) return rc;
-    if (tail->noisy)
-      hipLaunchKernelGGL(aog::k_epilogue_act_prologue_noise, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, aog::ActorNoiseArgs{a, tail->nz}, q,
-                         obs_from_lds);
-    else
-      hipLaunchKernelGGL(aog::k_epilogue_act_prologue, dim3(n_epi), dim3(aog::kStepActThreads), lds_all, s, p, a, q, obs_from_lds);
-  } else if (action_next) {
-    const aog::PrologueArgs q = prologue_args(e, action_next);
-    if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue_prologue), lds, e->device)) return rc;
-    hipLaunchKernelGGL(aog::k_epilogue_prologue, dim3(n_epi + (e->B + aog::kEpiProEnvs - 1) / aog::kEpiProEnvs), dim3(1024), lds, s, p, q, n_epi);
-  } else {
-    if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(aog::k_epilogue), lds, e->device)) return rc;
-    hipLaunchKernelGGL(aog::k_epilogue, dim3(n_epi), dim3(1024), lds, s, p);
-  }
+  return p;
+}
+
+// one launch with `lds` bytes of dynamic LDS: the request for it, the launch and its error check
+template <typename... Params, typename... Args>
+int launch_with_lds(const aog_env* e, hipStream_t s, void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, const Args&... args) {
+  if (int rc = aog_host::ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds, e->device)) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
   HIP_TRY(hipGetLastError());
   return AOG_OK;
+}
+
+// The last launch of a reset or step, in one of three forms that are worked out once:
+//   plain                                     k_epilogue               n_epi workgroups of 1024, the epilogue's LDS
+//   action_next (aog_step_pipelined)          k_epilogue_prologue      the prologue of the NEXT step rides in the same launch, in workgroups of
+//                                                                      its own behind the epilogue's
+//   tail (aog_reset_act / aog_step_act)       k_epilogue_act_prologue  the policy query on this epilogue's observation and the prologue of the next
+//                                             (_noise: tail->noisy)    step from its action ride in the same launch, per workgroup of 16 envs
+// Handles with a detector (e->det_on) launch the same form through the _det kernel of that name, which draws the detector's noise: the same
+// grid, block and arguments, its LDS from epilogue_lds, and DetectorArgs appended.
+// mask (masked aog_reset): handles with a detector draw for the masked envs only
+int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
+                    float* strehl, hipStream_t s, const float* action_next = nullptr, const ActTail* tail = nullptr, const uint8_t* mask = nullptr) {
+  const aog::EpilogueArgs p = epilogue_args(e, is_step, obs_raw, obs, reward, done, power, strehl);
+  const size_t lds = epilogue_lds(e);
+  const int n_epi = (e->Bp + aog::kEpiEnvs - 1) / aog::kEpiEnvs;
+  const auto launch = [&](auto* plain, auto* det, dim3 grid, dim3 block, size_t bytes, const auto&... args) {
+    return e->det_on ? launch_with_lds(e, s, det, grid, block, bytes, p, args..., detector_args(e, mask))
+                     : launch_with_lds(e, s, plain, grid, block, bytes, p, args...);
+  };
+  if (tail) {
+    aog::ActorArgs a = tail->a;
+    a.obs = obs;
+    a.obs_f16 = 1;
+    const aog::PrologueArgs q = prologue_args(e, a.action);
+    const int obs_from_lds = e->obs_sep ? 0 : 1;
+    const dim3 grid(n_epi), block(aog::kStepActThreads);
+    const size_t lds_all = aog::step_act_lds_bytes(lds, tail->lds);   // (<= kLdsBytes: checked by step_act_tail)
+    if (tail->noisy)
+      return launch(aog::k_epilogue_act_prologue_noise, aog::k_epilogue_act_prologue_noise_det, grid, block, lds_all,
+                    aog::ActorNoiseArgs{a, tail->nz}, q, obs_from_lds);
+    return launch(aog::k_epilogue_act_prologue, aog::k_epilogue_act_prologue_det, grid, block, lds_all, a, q, obs_from_lds);
+  }
+  if (action_next)
+    return launch(aog::k_epilogue_prologue, aog::k_epilogue_prologue_det, dim3(n_epi + (e->B + aog::kEpiProEnvs - 1) / aog::kEpiProEnvs), dim3(1024), lds,
+                  prologue_args(e, action_next), n_epi);
+  return launch(aog::k_epilogue, aog::k_epilogue_det, dim3(n_epi), dim3(1024), lds);
 }
 
 template <typename T>

@@ -140,6 +140,26 @@ def test_device_path_fails_loudly_without_gpu():
     assert b"abi_version" in lib.aog_last_error()
 
 
+def test_mask_argument_becomes_a_boolean_array_per_env():
+    """The one conversion behind the ``mask`` of set_turbulence / set_detector / reset: None, list, numpy and torch give the same [num_envs]
+    boolean array; a wrong length raises with the caller's name."""
+    import torch
+
+    from adaptive_optics_gym_amd.batched_env import _mask_array
+
+    want = np.array([True, False, True, True])
+    every = _mask_array(None, 4, "set_turbulence")
+    assert every.dtype == bool and every.shape == (4,) and every.all()
+    for mask in ([1, 0, 1, 1], [True, False, True, True], want, want.astype(np.uint8), want[:, None], torch.from_numpy(want),
+                 torch.tensor([1, 0, 2, 1], dtype=torch.uint8)):
+        got = _mask_array(mask, 4, "set_detector")
+        assert got.dtype == bool and got.shape == (4,) and np.array_equal(got, want)
+    for who in ("set_turbulence", "set_detector"):
+        for bad in (want[:3], [1, 0, 1, 1, 0], np.ones((2, 4), dtype=bool)):
+            with pytest.raises(ValueError, match=f"^{who}: mask must have num_envs entries$"):
+                _mask_array(bad, 4, who)
+
+
 def test_shard_range_partitions_exactly():
     for total in (1, 7, 8, 1024, 8192, 8195):
         for world in (1, 2, 3, 8):
