@@ -449,11 +449,12 @@ class BatchedAOEnv:
         self._push_detector()
 
     def _obs_buffers(self, masked):
-        """Fresh (obs float16, obs_raw float32) [B, o^2] for a reset.  A masked reset of an env with a detector draws for the masked envs
-        only and leaves the other rows as they are: those start as copies of the last observation."""
+        """Fresh (obs float16, obs_raw float32) [B, o^2] for a reset.  A masked reset may write the masked envs' rows only (an env with a
+        detector draws for them alone; a handle that keeps its reset observation copies them alone) and leaves the other rows as they are:
+        those start as copies of the last observation."""
         torch = self._torch
         n = self.obs_dim ** 2
-        if masked and self._detector is not None and self._last_obs is not None:
+        if masked and self._last_obs is not None:
             return self._last_obs.clone(), self.last_obs_raw.clone()
         new = torch.zeros if masked and self._detector is not None else torch.empty
         return (new((self.num_envs, n), dtype=torch.float16, device=self.device), new((self.num_envs, n), dtype=torch.float32, device=self.device))

@@ -100,6 +100,7 @@ void poison(aog_env* e, int bits) {
 int clear_poison(aog_env* e) {
   HIP_TRY(hipMemset(e->dev_status, 0, sizeof(int)));
   *static_cast<volatile int*>(e->host_flag) = 0;
+  e->reset_obs_valid = false;   // (whatever the failed call left behind, the next reset observes it afresh)
   return AOG_OK;
 }
 
@@ -362,6 +363,7 @@ int set_screens(aog_env* e, const T* psi, int first, int count, hipStream_t s, b
   if (int rc = refuse_pre_evolved(e, "aog_set_screens")) return rc;
   if (int rcd = x8_drop_ahead(e)) return rcd;   // (work done ahead for the next step read the state this call changes)
   if (count == 0) return AOG_OK;
+  e->reset_obs_valid = false;   // new screens for any env: the cached reset observation is of the old ones
   HIP_TRY(hipSetDevice(e->device));
   const double inv = rev_per_metre(e);
   const int N2 = e->cfg.n_pupil * e->cfg.n_pupil;
@@ -485,6 +487,7 @@ int aog_create(const aog_config* cfg, int device, aog_env** out) {
   // reduces them itself), "hw" (same instructions after an explicit exact reduction), "poly" (degree-7/8 polynomial)
   e->sincos_hw = 2;
   if (const char* sc = getenv("AOG_SINCOS")) e->sincos_hw = strcmp(sc, "poly") == 0 ? 0 : (strcmp(sc, "hwraw") == 0 ? 2 : 1);
+  if (const char* v = getenv("AOG_RESET_CACHE")) e->reset_cache = strcmp(v, "0") != 0;
 
   if (cfg->precision == AOG_PRECISION_FAST) {
     e->A_pad = pick_pad(e->A, kApadOpts, 4);
@@ -624,6 +627,7 @@ int aog_upload_tables(aog_env* e, const aog_tables* t) {
   if (!t->ap_index || !t->modes || !t->gram || !t->wfs_tables || !t->sci_tables || !t->wfs_coef || !t->sci_coef)
     return fail(AOG_ERR_INVALID, "aog_upload_tables: null table pointer");
   HIP_TRY(hipSetDevice(e->device));
+  e->reset_obs_valid = false;   // new tables: the cached reset observation was made with the old ones
   const int n_ap = e->n_ap, A = e->A, N2 = e->cfg.n_pupil * e->cfg.n_pupil;
   for (int p = 0; p < n_ap; ++p) {
     if (t->ap_index[p] < 0 || t->ap_index[p] >= N2) return fail(AOG_ERR_INVALID, "aog_upload_tables: ap_index[%d] out of range", p);
@@ -919,6 +923,7 @@ int aog_set_state(aog_env* e, const void* blob_dev, int64_t timestep, void* stre
   if (!e || !blob_dev) return fail(AOG_ERR_INVALID, "aog_set_state: null argument");
   if (!e->tables_ready) return fail(AOG_ERR_STATE, "aog_set_state before aog_upload_tables");
   e->pro_pending = false;   // (a restored state replaces the mirror: a pending pipelined action is forgotten)
+  e->reset_obs_valid = false;   // (and the screens: the cached reset observation is of the old ones)
   HIP_TRY(hipSetDevice(e->device));
   if (e->pre_evolved) {   // a restored state replaces everything the pending extrusion touches: let it finish, then forget it
     HIP_TRY(hipStreamSynchronize(e->ext_stream));
@@ -1050,6 +1055,15 @@ int step_act_tail(const aog_env* e, const aog_actor* net, const char* who, uint1
   return AOG_OK;
 }
 
+// the whole reset of the envs `mask` selects from the cached observation (k_reset_cached)
+int reset_from_cache(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, hipStream_t s) {
+  const int n = e->B * std::max(e->A_pad, e->n_obs_tab);
+  hipLaunchKernelGGL(aog::k_reset_cached, dim3((n + 255) / 256), dim3(256), 0, s, mask, e->act_dm, e->act_rev, e->act16, e->t_render, e->reset_obs_raw,
+                     e->reset_obs, obs_raw, obs, e->B, e->A, e->A_pad, e->Bp, e->n_obs_tab);
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
 int reset_impl(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, void* stream, const ActTail* tail) {
   if (!e) return fail(AOG_ERR_INVALID, "aog_reset: null handle");
   if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "aog_reset before aog_upload_tables/aog_set_screens");
@@ -1060,12 +1074,33 @@ int reset_impl(aog_env* e, const uint8_t* mask, float* obs_raw, uint16_t* obs, v
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (!mask) e->steps_since_reset = 0;
+  // The screens of such a handle stay between episodes and its mirror restarts flat: the observation is the same bits every time (float64 sums
+  // in a fixed order, no atomics, no noise) until something is installed (reset_obs_valid).  Semi-dynamic handles refill after every
+  // regeneration; dynamic, detector, separable-route and policy-tail resets always run the pupil pass.
+  const bool cacheable = e->reset_cache && !e->cfg.atm_dynamic && !e->det_on && !e->obs_sep && !tail && e->cfg.flat_mirror_start && e->n_obs_tab > 0;
+  if (cacheable && e->reset_obs_valid) {
+    if (int rc = reset_from_cache(e, mask, obs_raw, obs, s)) return rc;
+    e->obs_frame += 1;
+    return AOG_OK;
+  }
+  const bool fill = cacheable && !mask;   // (a masked reset observes the other envs' mirrors as they stand: nothing to keep)
+  if (fill && !e->reset_obs) {
+    const size_t n_el = (size_t)e->B * e->n_obs_tab;
+    int rca = dev_alloc(e, &e->reset_obs_raw, n_el, false);
+    if (rca != AOG_OK || (rca = dev_alloc(e, &e->reset_obs, n_el, false)) != AOG_OK) return rca;
+  }
   const int n = e->B * e->A;
   hipLaunchKernelGGL(aog::k_reset_state, dim3((n + 255) / 256), dim3(256), 0, s, mask, e->act_dm, e->t_render, e->B, e->A, e->cfg.flat_mirror_start);
   int rc = load_actuators(e, s, {e->act_rev, e->act16, nullptr});
   if (rc != AOG_OK || (rc = launch_fused(e, s)) != AOG_OK) return rc;
   if ((rc = launch_obs(e, s, obs_raw, obs, mask)) != AOG_OK) return rc;
-  rc = launch_epilogue(e, false, obs_raw, obs, nullptr, nullptr, nullptr, nullptr, s, nullptr, tail, mask);
+  if (fill) {   // the epilogue writes the cache, and the launch of every later reset hands it to the caller
+    rc = launch_epilogue(e, false, e->reset_obs_raw, e->reset_obs, nullptr, nullptr, nullptr, nullptr, s);
+    if (rc == AOG_OK) rc = reset_from_cache(e, nullptr, obs_raw, obs, s);
+    e->reset_obs_valid = rc == AOG_OK;
+  } else {
+    rc = launch_epilogue(e, false, obs_raw, obs, nullptr, nullptr, nullptr, nullptr, s, nullptr, tail, mask);
+  }
   if (rc == AOG_OK && tail) e->pro_pending = true;   // (the mirror holds the first action: aog_step_act(action = NULL) steps it)
   if (rc == AOG_OK) e->obs_frame += 1;
   return rc;

@@ -129,6 +129,13 @@ struct aog_env {
   float* act_rev = nullptr;      // [A_pad][Bp]
   _Float16* act16 = nullptr;     // [Bp/32][A_pad/16][hi|lo][64][8]
   int32_t* t_render = nullptr;   // [B]
+  // The observation a reset returns, kept between episodes (reset_impl): on a handle whose screens stay (not atm_dynamic), with a flat mirror
+  // start, the table route and no detector, it is the same bits every episode until screens, tables or a state are installed.  Every such
+  // installation clears reset_obs_valid; the next unmasked reset runs the pupil pass again and refills.
+  bool reset_cache = true;       // AOG_RESET_CACHE=0 at aog_create: every reset runs the pupil pass (speed only, never results)
+  bool reset_obs_valid = false;
+  float* reset_obs_raw = nullptr;   // [B][n_obs] fp32, allocated by the first fill
+  uint16_t* reset_obs = nullptr;    // [B][n_obs] f16 bits
   // dynamic atmosphere (cfg.atm_dynamic)
   bool layer_ready = false;
   // ring-direct form (fast MFMA handles): the fused kernel reads the fp32 ring copy of the master screens itself, no per-step repack

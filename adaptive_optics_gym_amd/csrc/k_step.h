@@ -143,6 +143,32 @@ __global__ void k_reset_state(const uint8_t* __restrict__ mask, double* __restri
   if (i == 0) t_render[env] = 0;
 }
 
+// A reset of a flat-start handle whose observation of the flat mirror is cached (aog_env::reset_obs_valid), in one launch for the envs the
+// mask selects (all without one): what k_reset_state writes, what k_load_actuators then writes for those envs' (zero) actuators, and the
+// cached rows into the caller's obs_raw / obs (nullable, like the epilogue's).  Element idx is one (env, padded mode) and one (env, pixel).
+__global__ void k_reset_cached(const uint8_t* __restrict__ mask, double* __restrict__ act_dm, float* __restrict__ act_rev,
+                               _Float16* __restrict__ act16, int32_t* __restrict__ t_render, const float* __restrict__ cache_raw,
+                               const uint16_t* __restrict__ cache_obs, float* __restrict__ obs_raw, uint16_t* __restrict__ obs, int B, int A,
+                               int A_pad, int Bp, int n_obs) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx < B * A_pad) {
+    const int env = idx / A_pad, i = idx % A_pad;
+    if (!mask || mask[env]) {
+      if (i < A) act_dm[(size_t)env * A + i] = 0.0;
+      if (i == 0) t_render[env] = 0;
+      if (act_rev) act_rev[(size_t)i * Bp + env] = 0.f;
+      store_act16(act16, env, i, A_pad, 0.f);
+    }
+  }
+  if (idx < B * n_obs) {
+    const int env = idx / n_obs;
+    if (!mask || mask[env]) {
+      if (obs_raw) obs_raw[idx] = cache_raw[idx];
+      if (obs) obs[idx] = cache_obs[idx];
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K3c  float64 validation form (AOG_PRECISION_FP64): one workgroup per env, everything in float64 from
 // float64 tables; also the general path for shapes the fast kernels are not instantiated for.

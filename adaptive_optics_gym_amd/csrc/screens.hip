@@ -11,6 +11,7 @@ int aog_set_screen_method(aog_env* e, int method) {
   if (!e) return fail(AOG_ERR_INVALID, "aog_set_screen_method: null handle");
   if (method != AOG_SCREENS_TWOBAND && method != AOG_SCREENS_HCIPY) return fail(AOG_ERR_INVALID, "aog_set_screen_method: unknown method %d", method);
   e->screen_method = method;
+  e->reset_obs_valid = false;   // (the regeneration that follows clears it too)
   return AOG_OK;
 }
 
@@ -101,6 +102,7 @@ int aog_set_turbulence(aog_env* e, const double* cn_squared_host, void* stream) 
   if (!e) return fail(AOG_ERR_INVALID, "aog_set_turbulence: null handle");
   if (int rcp = refuse_pre_evolved(e, "aog_set_turbulence")) return rcp;   // (an extrusion launched ahead may be reading the old values)
   HIP_TRY(hipSetDevice(e->device));
+  e->reset_obs_valid = false;   // (the screens drawn at the new values clear it too)
   if (int rcd = x8_drop_ahead(e)) return rcd;   // (the int8 work ahead read the old noise scales)
   if (!cn_squared_host) {   // back to the handle-wide value: today's code, today's bits
     e->turb_cn2.clear();

@@ -340,7 +340,11 @@ int aog_set_actuators(aog_env* env, const double* act_dev, void* stream);
 
 /* AOEnv.reset (AO_env.py:74-103) for the envs with mask_dev[b] != 0 (NULL = all): flatten the mirror iff
  * flat_mirror_start, zero the per-episode step counter, and return the observation of EVERY env
- * (obs_raw_dev [B][o^2] float32 before the cast, obs_dev [B][o^2] IEEE half; either may be NULL). */
+ * (obs_raw_dev [B][o^2] float32 before the cast, obs_dev [B][o^2] IEEE half; either may be NULL).
+ * A masked reset is only bound to write the rows of the envs it selects: hand in buffers whose other rows hold those envs' last observation
+ * (which is what the call would write there).  Handles whose reset observation cannot change between episodes (static screens, flat start,
+ * table route, no detector) keep it after the first unmasked reset and answer later resets, masked or not, from that copy in one launch,
+ * until screens, tables, turbulence values or a state are installed; AOG_RESET_CACHE=0 at aog_create switches this off (same results). */
 int aog_reset(aog_env* env, const uint8_t* mask_dev, float* obs_raw_dev, uint16_t* obs_dev, void* stream);
 
 /* AOEnv.step (AO_env.py:106-153) incl. reward_function (AO_env.py:468-503).
