@@ -129,6 +129,8 @@ SYMBOLS = {
     "aog_step_pipelined": (C.c_int, [C.c_void_p] * 10),
     "aog_focal_image": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "aog_focal_images": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "aog_upload_wavefront_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_wavefront_truth": (C.c_int, [C.c_void_p] * 6),
     "aog_selftest_poisson": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
     "aog_selftest_barrier_timeout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

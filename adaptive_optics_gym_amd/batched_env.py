@@ -160,6 +160,7 @@ class BatchedAOEnv:
         self._persistent_out = False   # see persistent_outputs()
         self._step_cache = None        # (views of the persistent block + their addresses)
         self._pack = None
+        self._wavefront_fit_uploaded = False
 
         self.observation_space = make_box(-1, 1, (self.obs_dim ** 2,), np.float16)  # AO_env.py:45
         self.action_space = make_box(-1, 1, (self.num_modes,), np.float16)          # AO_env.py:46
@@ -246,6 +247,7 @@ class BatchedAOEnv:
                               _dptr(keep["sc"], C.c_double), _dptr(keep["m1"], C.c_double), _dptr(keep["m2"], C.c_double),
                               int(t.focal_m1.shape[0]))
         _lib.check(self.lib.aog_upload_tables(self._handle, C.byref(tabs)))
+        self._wavefront_fit_uploaded = False   # (the library drops the wavefront fit with the old tables; wavefront_truth uploads it again)
         if self.obs_route == "separable":
             om1 = np.ascontiguousarray(np.stack([t.obs_m1.real, t.obs_m1.imag], axis=-1), dtype=np.float64)
             om2 = np.ascontiguousarray(np.stack([t.obs_m2.real, t.obs_m2.imag], axis=-1), dtype=np.float64)
@@ -937,6 +939,47 @@ class BatchedAOEnv:
         out = torch.empty((count, nf, nf, 2), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.aog_focal_images(self._handle, int(first), count, C.c_void_p(out.data_ptr()), self._stream()))
         return torch.view_as_complex(out)
+
+    def wavefront_truth(self, out=None):
+        """Residual wavefront statistics and the best-fit mirror command of every env in its current state (``aog_wavefront_truth``): a dict of
+        float64 device tensors ``rms`` [B] (RMS optical path error over the aperture, metres), ``fit_rms`` [B] (what is left of it after the
+        best correction the mirror's modes can make: the fitting error), ``coef`` [B, A] (least-squares coefficients of the path error on the
+        modes, metres of path) and ``ideal_actuators`` [B, A] (the actuators that remove everything the mirror can reach:
+        ``get_actuators() - coef / 2``).  Stream-ordered, no host synchronisation, nothing a step reads is changed.  ``out``: such a dict to
+        write into.  The fit's host table (``optics_host.wavefront_fit``) is uploaded by the first call.  Raises like ``focal_images`` while a
+        pipelined or policy-attached step has an action pending and between two steps of a lookahead episode."""
+        torch = self._torch
+        if not self._wavefront_fit_uploaded:
+            from .optics_host import wavefront_fit
+
+            modes = np.ascontiguousarray(self.tables.modes, dtype=np.float64)
+            fit = np.ascontiguousarray(wavefront_fit(modes), dtype=np.float64)
+            _lib.check(self.lib.aog_upload_wavefront_fit(self._handle, modes.ctypes.data_as(C.c_void_p), fit.ctypes.data_as(C.c_void_p)))
+            self._wavefront_fit_uploaded = True
+        B, A = self.num_envs, self.num_modes
+        shapes = {"rms": (B,), "fit_rms": (B,), "coef": (B, A), "ideal_actuators": (B, A)}
+        if out is None:
+            out = {k: torch.empty(s, dtype=torch.float64, device=self.device) for k, s in shapes.items()}
+        else:
+            for k, s in shapes.items():
+                t = out.get(k)
+                if t is None or t.dtype != torch.float64 or tuple(t.shape) != s or not t.is_contiguous() or t.device != self.device:
+                    raise ValueError("wavefront_truth(out=...): expected contiguous float64 device tensors rms [B], fit_rms [B], coef [B, A], "
+                                     "ideal_actuators [B, A]")
+        p = C.c_void_p
+        _lib.check(self.lib.aog_wavefront_truth(self._handle, p(out["rms"].data_ptr()), p(out["fit_rms"].data_ptr()), p(out["coef"].data_ptr()),
+                                                p(out["ideal_actuators"].data_ptr()), self._stream()))
+        return out
+
+    def ideal_action(self):
+        """The ideal modal controller's action, [B, A] float64 in the form of ``SH_step()``'s (raw actuators, for an env built with
+        ``SH_operation=True``): the actuators that leave only the fitting error on the screen the last observation saw."""
+        torch = self._torch
+        if not self._wavefront_fit_uploaded:
+            return self.wavefront_truth()["ideal_actuators"]
+        act = torch.empty((self.num_envs, self.num_modes), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.aog_wavefront_truth(self._handle, None, None, None, C.c_void_p(act.data_ptr()), self._stream()))
+        return act
 
     def phase_screen(self, env_index=0):
         """Atmospheric phase at the sensing wavelength [N, N] float32 radians (0 outside the aperture, aperture mean removed) — the

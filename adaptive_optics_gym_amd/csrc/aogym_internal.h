@@ -120,6 +120,14 @@ struct aog_env {
   double* obs_E = nullptr;
   double* obs_T = nullptr;
   double* obs_F = nullptr;
+  // wavefront fit (aog_upload_wavefront_fit, aog_wavefront_truth; wavefront.hip).  Nothing here is read or written by a reset or step.
+  bool wf_ready = false;         // the fit is uploaded (aog_upload_tables clears it)
+  double* wf_fit = nullptr;      // [A][A] P = pinv(Mc' Mc)
+  double* wf_colsum = nullptr;   // [A] column sums of the mode matrix over the aperture
+  _Float16* wf_tab16 = nullptr;  // modes as table operands: [n_ptiles][A_pad rows in blocks of 32][step 2][hi|lo][lane 64][8] (tab16's pixel order)
+  _Float16* wf_act16 = nullptr;  // the call's own copy of the actuators in act16's layout
+  double* wf_slabs = nullptr;    // [pixel chunk][A_pad + 2][Bp] partial sums, allocated by the first call
+  double* wf_w = nullptr;        // float64 handles: [B][n_ap] path error of the call, allocated by the first call
   // state
   float* psi_rev = nullptr;      // [n_quads][Bp][4]  (handles that run the VALU kernel only)
   double* pack_mean = nullptr;   // [B] aperture means of the screens being installed (k_screen_means -> k_pack_tiles)

@@ -129,6 +129,15 @@ def centred_gram(modes: np.ndarray, n_total: int) -> np.ndarray:
     return (c.T @ c + (n_total - modes.shape[0]) * np.outer(mean, mean)) / n_total
 
 
+def wavefront_fit(modes: np.ndarray) -> np.ndarray:
+    """P [A, A] of the wavefront fit (``aog_upload_wavefront_fit``): with Mc = modes - their column means over the aperture, the least-squares
+    coefficients of a path error w [n_ap] on the modes (and a free piston) are c = P (Mc' w), P = pinv(Mc' Mc).  The pseudo-inverse matters:
+    a piston mode (Zernike 1) has a zero column in Mc, its coefficient is 0 and its actuator keeps its value."""
+    m = np.asarray(modes, dtype=np.float64)
+    c = m - m.mean(axis=0)
+    return np.linalg.pinv(c.T @ c, rcond=1e-12, hermitian=True)
+
+
 # ------------------------------------------------------------------------------------------------
 # step-index fiber LP modes (hcipy StepIndexFiber / make_LP_modes; AO_env.py:393)
 # ------------------------------------------------------------------------------------------------

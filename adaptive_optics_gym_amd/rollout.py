@@ -266,14 +266,16 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
 
     ``policy="shack"`` (``algorithm.py:252-253``, the 'SHACK' algorithm): the action of every step comes from ``env.SH_step()`` (the
     Shack-Hartmann integrator on the device; needs an env built with ``SH_operation=True``), ``actor`` may be None and ``log_prob`` holds the
-    reference's constant 1.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
+    reference's constant 1.  ``policy="ideal"``: the ideal modal controller — every step's action is ``env.ideal_action()``, the best-fit
+    mirror command of the state the last observation saw, applied to the next screen (the one-frame lag every controller has): the ceiling
+    Shack-Hartmann and learnt policies are read against.  Same conditions and ``log_prob`` as ``"shack"``.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
     action before the env sees it (and before it is stored, like the reference's in-place ``action +=``), or a ``DeviceOUNoise``
     (``main.py:218-220``: mu 0, theta 0.3, sigma 0.05), which the HIP policy query advances and adds itself: float64 state, Philox normals keyed
     by the global env id (a split batch reproduces the whole one), no extra launch.  Neither is reset here, as in the reference.
 
     ``action_mode="mean"`` (evaluation, ``eval_policy.py:31``): the action is the policy's mean with dropout still active, ``log_prob`` the
     density of ``N(mean, cov_var I)`` there; with ``actor_impl="torch"`` the action is ``actor(obs)``.  A ``DeviceOUNoise`` needs the HIP
-    query, and neither a ``DeviceOUNoise`` nor ``action_mode="mean"`` goes with ``policy="shack"``: ValueError.
+    query, and neither a ``DeviceOUNoise`` nor ``action_mode="mean"`` goes with ``policy="shack"`` or ``"ideal"``: ValueError.
 
     ``fused_policy=True``: the policy query rides with the env step (``env.reset_with_policy`` / ``env.step_with_policy``, one launch where
     the epilogue of step t, the query on its observation and the prologue of step t + 1 take three): needs ``policy="actor"`` resolved to
@@ -289,17 +291,19 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     B = env.num_envs
     if gatherer is None:
         gatherer = EpisodeReturnGatherer(B, env.device, False)
-    if policy not in ("actor", "shack"):
-        raise ValueError("policy must be 'actor' or 'shack'")
+    if policy not in ("actor", "shack", "ideal"):
+        raise ValueError("policy must be 'actor', 'shack' or 'ideal'")
     if action_mode not in ("sample", "mean"):
         raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
-    shack = policy == "shack"
+    ideal = policy == "ideal"
+    shack = policy == "shack" or ideal   # (no policy query either way: the action is a controller's raw actuator vector)
     dev_ou = isinstance(ou_noise, DeviceOUNoise)
     if shack and (dev_ou or action_mode != "sample"):
-        raise ValueError("policy='shack' takes neither a DeviceOUNoise nor action_mode='mean' (the Shack-Hartmann integrator is not a policy query)")
+        raise ValueError(f"policy={policy!r} takes neither a DeviceOUNoise nor action_mode='mean' (the "
+                         f"{'ideal modal controller' if ideal else 'Shack-Hartmann integrator'} is not a policy query)")
     if shack:
         if not getattr(env, "SH_operation", False):
-            raise ValueError("policy='shack' needs an env created with SH_operation=True (AO_env.py:115-116, 254)")
+            raise ValueError(f"policy={policy!r} needs an env created with SH_operation=True (AO_env.py:115-116, 254)")
         actor_impl = "none"
     elif actor_impl == "auto":
         actor_impl = "hip" if actor_layers(actor) is not None and next(actor.parameters()).is_cuda else "torch"
@@ -321,7 +325,7 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         pkw["action_mode"] = action_mode
     if fused_policy:
         if shack:
-            raise ValueError("fused_policy=True needs policy='actor' (the Shack-Hartmann integrator is not a policy query)")
+            raise ValueError("fused_policy=True needs policy='actor' (neither the Shack-Hartmann integrator nor the ideal controller is a policy query)")
         if dev_actor is None:
             raise ValueError("fused_policy=True needs the HIP policy query (actor_impl='hip': a make_actor / reference Actor module with CUDA weights)")
         if ou_noise is not None and not dev_ou:
@@ -358,7 +362,8 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                                "next_obs": torch.empty((n, B, S), dtype=obs.dtype, device=dev), "done": torch.empty((n, B), dtype=torch.bool, device=dev)}
                         mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
                     if shack:
-                        sh_act, _ = env.SH_step()                       # (actuators [B, A] float64, the reference's constant log-probability 1)
+                        # (actuators [B, A] float64, the reference's constant log-probability 1; 'ideal': from the state the last observation saw)
+                        sh_act = env.ideal_action() if ideal else env.SH_step()[0]
                         out["act"][i].copy_(sh_act)
                         out["log_prob"][i].fill_(1.0)
                         action = out["act"][i]

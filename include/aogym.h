@@ -377,6 +377,29 @@ int aog_focal_image(aog_env* env, int env_index, float* field_dev /* [n_focal][n
  * hi + lo: 22 significant bits per factor, exact products), the pupil field formed inside the first product from a dense phase grid. */
 int aog_focal_images(aog_env* env, int first, int count, float* field_dev, void* stream);
 
+/* ---- residual wavefront statistics and the best-fit mirror command (no counterpart in the reference: the truth a controller is read against) ----
+ * Per env, over the n packed aperture pixels p, in float64: w_p = s_p / (2 pi) + 2 (M a)_p is the optical path error in metres (s = the
+ * achromatic screen, M = aog_tables.modes, a = the current actuators), rms = std_p(w), Mc = M - its column means over the aperture,
+ * b = Mc' w, c = P b with P = pinv(Mc' Mc) the least-squares coefficients of w on the modes (metres of path),
+ * fit_rms = sqrt(max(0, rms^2 - b' c / n)) the RMS the best correction leaves, act_ideal = a - c / 2 (path = 2 x surface).
+ *
+ * Host tables of the wavefront fit, float64 HOST pointers: the mode matrix again
+ * (the library keeps no host copy) and P [A][A].  After aog_upload_tables; a later
+ * aog_upload_tables clears them.  Builds the modes' table-operand layout (split f16,
+ * tab16's order, A_pad rows) and the column sums; the buffers are allocated here, not
+ * at aog_create, so handles that never ask keep their device_bytes. */
+int aog_upload_wavefront_fit(aog_env* env, const double* modes_host, const double* fit_host);
+
+/* rms, fit_rms [B]; coef, act_ideal [B][A]; float64 device pointers, each nullable
+ * (at least one non-NULL).  Whole batch, stream-ordered, no host synchronisation.
+ * Fast handles: the split-f16 phase contraction of the step kernels fused with a second matrix-core contraction of that phase against the
+ * modes, float64 sums in a fixed order (a batch split over handles reproduces the whole batch bit for bit); float64 validation handles: a
+ * plain float64 kernel.  Reads the state the last reset or step left and changes nothing a step reads or writes (its actuator operands and
+ * partial sums live in buffers of its own, allocated by the first call).  AOG_ERR_STATE before tables, screens or the fit are installed,
+ * while a pipelined or policy-attached step has an action pending, and between two steps of a lookahead episode. */
+int aog_wavefront_truth(aog_env* env, double* rms_dev, double* fit_rms_dev,
+                        double* coef_dev, double* act_ideal_dev, void* stream);
+
 /* ---- policy query of the rollout (Actor.forward + Actor.get_action, network.py:17-69; caller algorithm.py:216-296) ----
  * mean = W_o drop(relu(W_3 drop(relu(W_2 drop(relu(W_1 obs + b_1)) + b_2)) + b_3)) + b_o with nn.Dropout(dropout_p) ACTIVE
  * (the reference never leaves training mode while acting), action = mean + sqrt(cov_var) eps, eps ~ N(0, I),
