@@ -104,6 +104,7 @@ SYMBOLS = {
     "aog_set_detector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_turbulence_factors": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "aog_fused_plan": (C.c_int, [C.c_int] * 7 + [C.c_void_p]),
     "aog_set_screen_method": (C.c_int, [C.c_void_p, C.c_int]),
     "aog_upload_sh": (C.c_int, [C.c_void_p, C.POINTER(AogShTables)]),
     "aog_sh_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -188,3 +189,15 @@ def check(rc: int):
         if "win_size exceeds image extent" in msg:
             raise ValueError(msg)  # what skimage raises in the reference for smf_ssim with obs_dim=2 (AO_env.py:495)
         raise AogError(f"libaogym error {rc}: {msg}")
+
+
+FUSED_PLAN_FIELDS = ("we", "waves", "heavy", "wg_y", "pair", "chunks_x", "tpc", "n_chunks", "n_ptiles", "n_etiles", "A_pad", "MRW", "lds_tiles",
+                     "lds_ring", "valu_qpc", "valu_chunks")
+
+
+def fused_plan(num_envs, n_ap, n_modes, n_wfs_tables, atm_dynamic=False, pixel_chunks=0, four_wave=False):
+    """The fused pupil pass's launch form for a shape, as aog_create would choose it (aog_fused_plan: host arithmetic only, no device)."""
+    out = (C.c_int32 * len(FUSED_PLAN_FIELDS))()
+    check(load().aog_fused_plan(int(num_envs), int(n_ap), int(n_modes), int(n_wfs_tables), int(bool(atm_dynamic)), int(pixel_chunks),
+                                int(bool(four_wave)), out))
+    return dict(zip(FUSED_PLAN_FIELDS, out))

@@ -226,6 +226,31 @@ int pick_pad(int v, const int* opts, int n) {
 const int kApadOpts[] = {16, 32, 64, 128};
 const int kMrwOpts[] = {7, 12, 20, 28};
 
+const char kFastSizesMsg[] = "%s: fast kernels are built for act_dim <= 128, <= 28 wfs tables and 1 science table; use AOG_PRECISION_FP64 for this shape";
+
+// The fast kernels' padded sizes and the fused pass's launch geometry for a shape: the one place aog_create and aog_fused_plan take them from.
+struct FusedPlan {
+  int Bp, n_ap_pad, A_pad, MRW;
+  aog::FusedGeom geom;
+};
+int plan_fused(const char* who, int num_envs, int n_ap, int n_modes, int n_wfs_tables, bool mfma, bool atm_dynamic, int pixel_chunks, bool four_wave,
+               FusedPlan* p) {
+  p->Bp = round_up(num_envs, 64);
+  p->n_ap_pad = round_up(n_ap, 32);
+  p->A_pad = pick_pad(n_modes, kApadOpts, 4);
+  p->MRW = pick_pad(n_wfs_tables, kMrwOpts, 4);
+  if (p->A_pad < 0 || p->MRW < 0)
+    return fail(AOG_ERR_UNSUPPORTED, kFastSizesMsg, who);
+  p->geom = aog::fused_geometry(p->Bp, p->n_ap_pad, p->A_pad, p->MRW, mfma, atm_dynamic, pixel_chunks, four_wave);
+  if (mfma && !aog::fused_geometry_fits(p->geom, p->A_pad, p->MRW, atm_dynamic))
+    return fail(AOG_ERR_UNSUPPORTED,
+                "%s: the fused pupil pass has no launch form for B=%d n_ap=%d act_dim=%d with %d wfs tables, %s atmosphere: %d waves and %d pixel tiles "
+                "per chunk need %d bytes of LDS (> %zu)",
+                who, num_envs, n_ap, n_modes, n_wfs_tables, atm_dynamic ? "dynamic" : "static", p->geom.waves, p->geom.tpc,
+                aog::FusedLds(p->geom.tpc, p->geom.waves, p->A_pad, p->MRW, atm_dynamic).total, aog_host::kLdsBytes);
+  return AOG_OK;
+}
+
 int launch_fused(aog_env* e, hipStream_t s) {
   const bool timed = e->profile && profile_sampled(e, e->profile_phase++);   // (this launch advances the counter: evolve_layer only reads it)
   TimedRegion tr(e, s, AOG_PROF_FUSED, timed);
@@ -490,18 +515,19 @@ int aog_create(const aog_config* cfg, int device, aog_env** out) {
   if (const char* v = getenv("AOG_RESET_CACHE")) e->reset_cache = strcmp(v, "0") != 0;
 
   if (cfg->precision == AOG_PRECISION_FAST) {
-    e->A_pad = pick_pad(e->A, kApadOpts, 4);
-    e->MRW = pick_pad(e->MRW_used, kMrwOpts, 4);
     e->MRS = 1;
-    if (e->A_pad < 0 || e->MRW < 0 || e->MRS_used != 1) {
-      delete e;
-      return fail(AOG_ERR_UNSUPPORTED,
-                  "aog_create: fast kernels are built for act_dim <= 128, <= 28 wfs tables and 1 science table; "
-                  "use AOG_PRECISION_FP64 for this shape");
-    }
     e->kernel = cfg->kernel == AOG_KERNEL_AUTO ? AOG_KERNEL_MFMA : cfg->kernel;
-    e->geom = aog::fused_geometry(e->Bp, e->n_ap_pad, e->A_pad, e->MRW, e->kernel == AOG_KERNEL_MFMA, cfg->atm_dynamic != 0, cfg->pixel_chunks,
-                                  getenv("AOG_FUSED_4WAVE") != nullptr);
+    FusedPlan plan;
+    int prc = plan_fused("aog_create", e->B, e->n_ap, e->A, e->MRW_used, e->kernel == AOG_KERNEL_MFMA, cfg->atm_dynamic != 0, cfg->pixel_chunks,
+                         getenv("AOG_FUSED_4WAVE") != nullptr, &plan);
+    if (prc == AOG_OK && e->MRS_used != 1) prc = fail(AOG_ERR_UNSUPPORTED, kFastSizesMsg, "aog_create");
+    if (prc != AOG_OK) {
+      delete e;
+      return prc;
+    }
+    e->A_pad = plan.A_pad;
+    e->MRW = plan.MRW;
+    e->geom = plan.geom;
   } else {
     e->A_pad = round_up(e->A, 8);
     e->MRW = e->MRW_used;
@@ -567,6 +593,19 @@ int aog_create(const aog_config* cfg, int device, aog_env** out) {
   }
 #undef TRY_ALLOC
   *out = e;
+  return AOG_OK;
+}
+
+int aog_fused_plan(int num_envs, int n_ap, int n_modes, int n_wfs_tables, int atm_dynamic, int pixel_chunks, int four_wave, int32_t* out) {
+  if (!out || num_envs < 1 || n_ap < 1 || n_modes < 1 || n_wfs_tables < 1 || pixel_chunks < 0) return fail(AOG_ERR_INVALID, "aog_fused_plan: bad argument");
+  FusedPlan p;
+  if (int rc = plan_fused("aog_fused_plan", num_envs, n_ap, n_modes, n_wfs_tables, true, atm_dynamic != 0, pixel_chunks, four_wave != 0, &p)) return rc;
+  const aog::FusedGeom& g = p.geom;
+  const int32_t v[AOG_FUSED_PLAN_FIELDS] = {
+      g.we, g.waves, g.heavy, g.wg_y, g.pair, g.chunks_x, g.tpc, g.n_chunks, p.n_ap_pad / 32, p.Bp / 32, p.A_pad, p.MRW,
+      aog::FusedLds(g.tpc, g.waves, p.A_pad, p.MRW, false).total, aog::FusedLds(g.tpc, g.waves, p.A_pad, p.MRW, atm_dynamic != 0).total,
+      g.valu_qpc, g.valu_chunks};
+  memcpy(out, v, sizeof v);
   return AOG_OK;
 }
 

@@ -49,24 +49,42 @@ struct FusedLds {
     const int fit = ((int)kLdsBytes - fixed) / kSciTile;
     return fit < 4096 ? fit : 4096;
   }
+  // Longest chunk that fits beside the areas of the layout that is actually launched: a static handle never holds transpose tiles, a
+  // dynamic one counts as ring-direct (the larger of its two forms).  No slack.  Never below tile_budget.
+  static constexpr int tile_fit(int waves, int A_PAD, int MRW, bool atm_dynamic) {
+    const int fit = ((int)kLdsBytes - FusedLds(0, waves, A_PAD, MRW, atm_dynamic).total) / kSciTile;
+    return fit < 4096 ? fit : 4096;
+  }
+  // The cap fused_geometry applies: tile_budget wherever it is positive (the shapes that always launched keep their chunk counts); where it
+  // is not, because it counts transpose tiles that a static A_PAD = 128 handle does not have, tile_fit.  <= 0: no chunk fits this form.
+  static constexpr int tile_cap(int waves, int A_PAD, int MRW, bool atm_dynamic) {
+    const int budget = tile_budget(waves, A_PAD, MRW, atm_dynamic);
+    return budget > 0 ? budget : tile_fit(waves, A_PAD, MRW, atm_dynamic);
+  }
+  // whether fused_geometry may choose `waves` waves per workgroup for this variant
+  static constexpr bool form_fits(int waves, int A_PAD, int MRW, bool atm_dynamic) { return tile_cap(waves, A_PAD, MRW, atm_dynamic) > 0; }
 };
 
-// every variant the library instantiates: the areas follow each other without overlap on 16-byte boundaries, and a chunk as long as the
-// budget allows fits the CU's LDS whether or not the handle turns out ring-direct
+// every variant the library instantiates: the areas follow each other without overlap on 16-byte boundaries; every form fused_geometry
+// can choose for a variant (8 waves only where form_fits, 4 waves everywhere) has a positive cap, and a chunk as long as the cap allows
+// fits the CU's LDS whether or not the handle turns out ring-direct
 constexpr bool fused_lds_sound() {
   for (int waves = 4; waves <= 8; waves += 4)
     for (int A_PAD = 16; A_PAD <= 128; A_PAD *= 2)
       for (int MRW : {7, 12, 20, 28})
         for (int dyn = 0; dyn < 3; ++dyn) {   // static, dynamic through psi_tile, ring-direct
-          const int tiles = FusedLds::tile_budget(waves, A_PAD, MRW, dyn > 0);
+          const int tiles = FusedLds::tile_cap(waves, A_PAD, MRW, dyn > 0);
+          const bool chosen = waves == 4 || FusedLds::form_fits(waves, A_PAD, MRW, dyn > 0);
+          if (chosen && tiles <= 0) return false;
+          if (tiles < FusedLds::tile_budget(waves, A_PAD, MRW, dyn > 0) || tiles > FusedLds::tile_fit(waves, A_PAD, MRW, dyn > 0)) return false;
           const FusedLds l(tiles > 0 ? tiles : 1, waves, A_PAD, MRW, dyn == 2);
           if (l.op_off < l.sci_bytes || l.xp_off < l.op_off + l.op_bytes || l.acc_off < l.xp_off + l.xp_bytes || l.total < l.acc_off + l.acc_bytes) return false;
           if (l.op_off % 16 || l.xp_off % 16 || l.acc_off % 16) return false;
-          if (tiles > 0 && (size_t)l.total > kLdsBytes) return false;
+          if (chosen && (size_t)l.total > kLdsBytes) return false;
         }
   return true;
 }
-static_assert(fused_lds_sound(), "k_fused_tab's LDS areas overlap, are misaligned or exceed the budget they were sized by");
+static_assert(fused_lds_sound(), "k_fused_tab's LDS areas overlap, are misaligned, exceed the cap they were sized by, or a form that can be chosen has no room for a chunk");
 
 // Launch geometry of the fused kernels.  The chunk counts and the tiles per chunk fix the order of the float64 sums, so this is part of the
 // numerical contract, not a tuning detail.
@@ -83,6 +101,8 @@ struct FusedGeom {
   int n_chunks = 0;   // partial slabs the epilogue sums
 };
 // pixel_chunks: the caller's choice (cfg.pixel_chunks), 0 = automatic.  four_wave: keep 4-wave workgroups (AOG_FUSED_4WAVE).
+// A variant whose 8-wave fixed areas leave no room for a chunk (FusedLds::form_fits) keeps 4-wave workgroups at every batch size.  The
+// result's tpc can still exceed what the CU holds if no form fits at all: fused_geometry_fits says so, and aog_create refuses the shape.
 constexpr FusedGeom fused_geometry(int Bp, int n_ap_pad, int A_pad, int MRW, bool mfma, bool atm_dynamic, int pixel_chunks, bool four_wave) {
   FusedGeom g;
   const int n_quads = n_ap_pad / 4, n_ptiles = n_ap_pad / 32, n_etiles = Bp / 32, n_groups = Bp / 64;
@@ -94,7 +114,7 @@ constexpr FusedGeom fused_geometry(int Bp, int n_ap_pad, int A_pad, int MRW, boo
   // Asymmetric wave pairs (see k_fused_tab): with at least 4 env tiles the kernel runs 8-wave workgroups, one per CU, whose two pixel
   // sub-chunks split a chunk about 2 : 1 with the priority on the larger share.  (Eight waves of the many-table variants need
   // 8 x 2 LIVE x 512 B of LDS — 128 KB at o = 5 — beside the chunk's science rows: one workgroup per CU, which is what this form runs.)
-  const bool asym = mfma && n_etiles >= 4 && !four_wave;
+  const bool asym = mfma && n_etiles >= 4 && !four_wave && FusedLds::form_fits(8, A_pad, MRW, atm_dynamic);
   g.waves = asym ? 8 : 4;
   g.heavy = asym ? 672 : 0;
   g.wg_y = (n_etiles + g.we - 1) / g.we;
@@ -102,13 +122,17 @@ constexpr FusedGeom fused_geometry(int Bp, int n_ap_pad, int A_pad, int MRW, boo
   // P pixel chunks (proportional split of the tiles), 8 waves per CU when the batch allows.  Every variant keeps float64 sums, so a chunk
   // may be as long as its science rows fit in the LDS.
   int Pm = pixel_chunks > 0 ? pixel_chunks : std::max(1, (asym ? 256 : 256 * 2) / g.wg_y);
-  const int max_tpc = FusedLds::tile_budget(g.waves, A_pad, MRW, atm_dynamic);
+  const int max_tpc = FusedLds::tile_cap(g.waves, A_pad, MRW, atm_dynamic);
   if (max_tpc > 0) Pm = std::max(Pm, (n_ptiles + max_tpc - 1) / max_tpc);
   Pm = std::min(Pm, n_ptiles);
   g.chunks_x = Pm;
   g.tpc = (n_ptiles + Pm - 1) / Pm;
   g.n_chunks = mfma ? g.chunks_x * (g.waves / g.we) : g.valu_chunks;
   return g;
+}
+// whether the geometry's longest chunk fits the CU's LDS in every layout the handle may launch it with
+constexpr bool fused_geometry_fits(const FusedGeom& g, int A_pad, int MRW, bool atm_dynamic) {
+  return g.chunks_x >= 1 && g.tpc >= 1 && (size_t)FusedLds(g.tpc, g.waves, A_pad, MRW, atm_dynamic).total <= kLdsBytes;
 }
 
 // The shapes of BASELINE.md's configs 2 and 3 (n_ap = 51468 at N = 256, A = 64), pinned: a change of any of these numbers changes the order of
@@ -121,5 +145,14 @@ static_assert(geom_is(fused_geometry(1024, 51488, 64, 7, true, false, 0, false),
 static_assert(FusedLds(51, 8, 64, 7, false).total == 6528, "config 2");
 static_assert(geom_is(fused_geometry(4096, 51488, 64, 28, true, false, 0, false), 4, 8, 672, 32, 0, 8, 202, 16, 272, 48), "config 3: B = 4096, o = 5");
 static_assert(FusedLds(202, 8, 64, 28, false).acc_off == 25856 && FusedLds(202, 8, 64, 28, false).total == 156928, "config 3");
+// A shape that runs 4-wave workgroups because its 8-wave fixed areas (184 320 bytes ring-direct) leave no room for a chunk: config 4 (dynamic
+// atmosphere, B = 1024) with the 5 x 5 observation.  And a 128-mode shape that keeps 8 waves: its budget counts transpose tiles a static
+// handle does not have (-32), its real layout fits, and it launched before the form was chosen by fit.
+static_assert(!FusedLds::form_fits(8, 64, 28, true) && FusedLds::form_fits(4, 64, 28, true), "dynamic, A_pad = 64, 28 tables");
+static_assert(geom_is(fused_geometry(1024, 51488, 64, 28, true, true, 0, false), 4, 4, 0, 8, 1, 64, 26, 64, 72, 179), "config 4 at o = 5: 4-wave form");
+static_assert(FusedLds(26, 4, 64, 28, true).total == 120064, "config 4 at o = 5");
+static_assert(FusedLds::tile_budget(8, 128, 7, false) == -32 && FusedLds::tile_cap(8, 128, 7, false) == 256, "static, A_pad = 128, 7 tables");
+static_assert(geom_is(fused_geometry(1024, 51488, 128, 7, true, false, 0, false), 4, 8, 672, 8, 0, 32, 51, 64, 72, 179), "B = 1024, A_pad = 128, o = 2");
+static_assert(FusedLds(51, 8, 128, 7, false).total == 137600, "B = 1024, A_pad = 128, o = 2");
 
 }  // namespace aog

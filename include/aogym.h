@@ -267,6 +267,17 @@ int aog_set_detector(aog_env* env, const double* photons_host, const double* rea
 int aog_turbulence_factors(int n_pupil, int oversampling, double pixel_pitch, const double* cn_squared, int count, double table_sqrt_cn_squared,
                            float* amp_high, float* amp_low, float* crop_scale, double* sqrt_cn_squared, double* x8_noise_scale);
 
+/* The launch form aog_create chooses for the fused pupil pass of a fast matrix-core handle (pure host function, no handle or device; ABI
+ * stays 22, no new struct): the values the constructor and the launcher compute, from the same definition.  four_wave: as the environment
+ * variable AOG_FUSED_4WAVE.  out[AOG_FUSED_PLAN_FIELDS], in this order: env tiles per workgroup, waves per workgroup, heavy share (x / 1024,
+ * 0 = interleaved sub-chunks), workgroups per pixel chunk, paired workgroup map (0 / 1), pixel chunks, longest chunk in pixel tiles, partial
+ * slabs (aog_info.pixel_chunks), pixel tiles, env tiles, padded mode count, padded table count, bytes of dynamic LDS per workgroup when the
+ * screens come from the packed tiles (every static handle; a dynamic one that repacks), the same when a dynamic handle reads its ring
+ * directly (equal to the former for atm_dynamic = 0: aog_create does not know yet which of the two a dynamic handle gets), and the vector
+ * kernel's pixel quads per chunk and chunks.  AOG_ERR_UNSUPPORTED, with the message aog_create gives, for a shape no form fits. */
+#define AOG_FUSED_PLAN_FIELDS 16
+int aog_fused_plan(int num_envs, int n_ap, int n_modes, int n_wfs_tables, int atm_dynamic, int pixel_chunks, int four_wave, int32_t* out);
+
 /* How aog_generate_screens draws a screen.  Both methods draw the same zero-mean stationary Gaussian field on the N x N pupil up to
  * max |dC(r)| < 1e-4 C(0) over every lag r of the pupil (tests/test_screen_twoband.py evaluates both covariance functions exactly on
  * the host in float64), i.e. they are statistically equivalent to hcipy's layer.reset() (AO_env.py:77), not draw-for-draw.

@@ -802,23 +802,20 @@ def test_dynamic_extrusion_kernel_variants_agree(monkeypatch, N, vel):
             np.testing.assert_allclose(s_other, s_split, rtol=1e-11, atol=1e-13 * np.abs(s_split).max())
 
 
-@pytest.mark.parametrize("N,vel", [(64, 70.0), (96, 45.0), (240, 12.0)])
-def test_dynamic_ring_direct_matches_oracle(N, vel):
-    """The step kernel reading the screens straight from the toroidal fp32 ring (per-lane 16-byte loads through the origin offsets, groups
-    that straddle an aperture row end patched from the next row) against the oracle's InfiniteAtmosphericLayer fed the same normals:
-    several pupil sizes (row lengths not multiples of 4 -> straddling groups; 240 = the reference's size), winds that wrap the ring."""
+def _ring_direct_oracle_replay(N, vel, B=37, A=16, o=2, T=12, steps=24, ids=None, seed=4):
+    """A ring-direct batch against the oracle's InfiniteAtmosphericLayer fed the same normals (ScriptedRNG): the envs `ids`, every step,
+    with the reset at each episode end.  Shared by the ring-direct tests of this file and of test_gpu_fused_geometry.py."""
     torch = _torch()
     from helpers import ScriptedRNG, device_mode_stencil_draws
     from adaptive_optics_gym_amd import BatchedAOEnv
     from adaptive_optics_gym_amd.atmosphere_host import integer_shifts
     from oracle.ao_env_oracle import AOEnvOracle
 
-    B, A, T, seed = 37, 16, 12, 4
-    kw = dict(atm_type="dynamic", atm_vel=vel, atm_fried=0.15, act_type="num_actuators", act_dim=A, obs_dim=2, timesteps_per_episode=T)
+    kw = dict(atm_type="dynamic", atm_vel=vel, atm_fried=0.15, act_type="num_actuators", act_dim=A, obs_dim=o, timesteps_per_episode=T)
     env = BatchedAOEnv(B, "cuda:0", num_pupil_pixels=N, seed=seed, screen_source="device", screen_oversampling=4, verbose=False, **kw)
     assert env.info.reserved == 1
     geo = device_mode_stencil_draws(seed, B, N)
-    ids = [0, 17, B - 1]
+    ids = [0, 17, B - 1] if ids is None else list(ids)
     refs = {}
     for b in ids:
         refs[b] = AOEnvOracle(num_pupil_pixels=N, screen=env.get_screens(b, 1)[0].cpu().numpy().ravel(),
@@ -828,7 +825,7 @@ def test_dynamic_ring_direct_matches_oracle(N, vel):
         refs[b].reset()
         _assert_obs_close(env.last_obs_raw[b].double().cpu().numpy(), refs[b].last_obs_raw)
     gen = torch.Generator("cuda").manual_seed(5)
-    for t in range(2 * T):                       # two episodes: the origins travel more than once around the ring at the fast winds
+    for t in range(steps):
         a = torch.randn((B, A), device="cuda", generator=gen)
         counts = np.abs(integer_shifts(env.velocity_vectors, env.timestep * env.delta_t, (env.timestep + 1) * env.delta_t,
                                        env.params.pupil_pixel)).sum(axis=1)
@@ -848,7 +845,17 @@ def test_dynamic_ring_direct_matches_oracle(N, vel):
                 refs[b].reset()
                 _assert_obs_close(env.last_obs_raw[b].double().cpu().numpy(), refs[b].last_obs_raw)
     assert env.device_status() == 0
+    n_chunks = env.info.pixel_chunks
     env.close()
+    return n_chunks
+
+
+@pytest.mark.parametrize("N,vel", [(64, 70.0), (96, 45.0), (240, 12.0)])
+def test_dynamic_ring_direct_matches_oracle(N, vel):
+    """The step kernel reading the screens straight from the toroidal fp32 ring (per-lane 16-byte loads through the origin offsets, groups
+    that straddle an aperture row end patched from the next row) against the oracle's InfiniteAtmosphericLayer fed the same normals:
+    several pupil sizes (row lengths not multiples of 4 -> straddling groups; 240 = the reference's size), winds that wrap the ring."""
+    _ring_direct_oracle_replay(N, vel)       # two episodes: the origins travel more than once around the ring at the fast winds
 
 
 @pytest.mark.parametrize("method", ["twoband", "hcipy16"])
