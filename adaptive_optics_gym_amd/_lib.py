@@ -132,6 +132,10 @@ SYMBOLS = {
     "aog_focal_images": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "aog_upload_wavefront_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_wavefront_truth": (C.c_int, [C.c_void_p] * 6),
+    "aog_upload_science": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int]),
+    "aog_science_integrate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_science_clear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_science_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_selftest_poisson": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
     "aog_selftest_barrier_timeout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -79,6 +79,12 @@ class BatchedAOEnv:
     a detector, bit for bit — the reward is the training signal of the true state.  The noise is drawn inside the step kernels from a
     Philox stream keyed by (seed, global env id, pixel, frame), so split batches reproduce whole ones and ``get_state`` / ``set_state``
     resume it.  ``set_detector`` changes the values per episode; ``detector_parameters`` shows them.
+
+    ``science_window`` (default None: no camera) switches the science camera on: an even number w of focal samples, 2 .. 240; the camera
+    sees the centred w x w window of the science arm's 240 x 240 focal grid (4 samples per lambda_sci / D) and keeps one float64 long
+    exposure per env.  ``science_integrate`` adds the current frame (normalised so that its centre pixel is that step's Strehl ratio),
+    ``science_clear`` empties, ``science_exposure`` reads the mean PSF, its Strehl and the encircled energy inside ``science_radii``
+    (lambda_sci / D; default 1, 2, 3, 5, 8 clipped to the window).  Off the step path: a step computes the same bits with or without it.
     """
 
     def __init__(self, num_envs=1, device=None, atm_type="quasi_static", atm_vel=0, atm_fried=0.15,
@@ -87,7 +93,7 @@ class BatchedAOEnv:
                  num_pupil_pixels=240, seed=None, screen_source="device", screen_oversampling=16, screens=None,
                  precision="fast", kernel="auto", pixel_chunks=0, rng=None, verbose=True, params=None,
                  global_env_offset=0, total_envs=None, sh_fft_precision="single", screen_method="twoband", tables=None, extrusion="auto",
-                 obs_photons=None, obs_read_noise=0.0, obs_background=0.0):
+                 obs_photons=None, obs_read_noise=0.0, obs_background=0.0, science_window=None, science_radii=None):
         import torch
 
         self._handle = None   # (first: close() and accumulate_returns() read it on an env whose construction failed below)
@@ -161,6 +167,9 @@ class BatchedAOEnv:
         self._step_cache = None        # (views of the persistent block + their addresses)
         self._pack = None
         self._wavefront_fit_uploaded = False
+        self._science = None           # optics_host.ScienceTables of the science camera (science_window)
+        self._science_uploaded = False
+        self.science_window = self.science_radii = None
 
         self.observation_space = make_box(-1, 1, (self.obs_dim ** 2,), np.float16)  # AO_env.py:45
         self.action_space = make_box(-1, 1, (self.num_modes,), np.float16)          # AO_env.py:46
@@ -176,6 +185,14 @@ class BatchedAOEnv:
             raise ValueError(f"tables= were built for the {tables.obs_route!r} observation route; this handle takes {self.obs_route!r}")
         self.tables: HostTables = tables if tables is not None else build_tables(self.params, act_type, self.num_modes, self.obs_dim,
                                                                                  obs_route=self.obs_route)
+        if science_window is not None:
+            from .optics_host import science_tables
+
+            self._science = science_tables(self.params, science_window, science_radii)   # (ValueError before anything is created)
+            self.science_window = self._science.window
+            self.science_radii = self._science.radii.copy()
+        elif science_radii is not None:
+            raise ValueError("science_radii without science_window: the science camera is off")
         self._create_handle(precision, kernel, pixel_chunks)
         self._upload_tables()
         layer = self._draw_wind_and_stencils()
@@ -248,6 +265,8 @@ class BatchedAOEnv:
                               int(t.focal_m1.shape[0]))
         _lib.check(self.lib.aog_upload_tables(self._handle, C.byref(tabs)))
         self._wavefront_fit_uploaded = False   # (the library drops the wavefront fit with the old tables; wavefront_truth uploads it again)
+        self._science_uploaded = False         # (and the science camera)
+        self._upload_science()
         if self.obs_route == "separable":
             om1 = np.ascontiguousarray(np.stack([t.obs_m1.real, t.obs_m1.imag], axis=-1), dtype=np.float64)
             om2 = np.ascontiguousarray(np.stack([t.obs_m2.real, t.obs_m2.imag], axis=-1), dtype=np.float64)
@@ -980,6 +999,65 @@ class BatchedAOEnv:
         act = torch.empty((self.num_envs, self.num_modes), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.aog_wavefront_truth(self._handle, None, None, None, C.c_void_p(act.data_ptr()), self._stream()))
         return act
+
+    # ------------------------------------------------------------------------------------------------
+    # science camera
+    def _upload_science(self):
+        """The camera's host tables to the handle (``aog_upload_science``); no-op without ``science_window`` or when they are there."""
+        t = self._science
+        if t is None or self._science_uploaded:
+            return
+        m1 = np.ascontiguousarray(np.stack([t.m1.real, t.m1.imag], axis=-1), dtype=np.float64)
+        m2 = np.ascontiguousarray(np.stack([t.m2.real, t.m2.imag], axis=-1), dtype=np.float64)
+        bins = np.ascontiguousarray(t.ee_bin, dtype=np.int32)
+        _lib.check(self.lib.aog_upload_science(self._handle, m1.ctypes.data_as(C.c_void_p), m2.ctypes.data_as(C.c_void_p), int(t.window),
+                                               float(t.phase_ratio), float(t.peak_fraction), bins.ctypes.data_as(C.c_void_p), int(t.radii.size)))
+        self._science_uploaded = True
+
+    def _science_mask(self, mask, who):
+        """``who``'s checks, then its mask as a device pointer (None: every env) and the tensor that keeps it alive."""
+        if self._science is None:
+            raise ValueError(f"{who}: this environment was built without a science camera (science_window=...)")
+        self._upload_science()
+        if mask is None:
+            return None, None
+        sel = _mask_array(mask, self.num_envs, who)
+        m = self._torch.from_numpy(sel.astype(np.uint8)).to(self.device)
+        return C.c_void_p(m.data_ptr()), m
+
+    def science_integrate(self, mask=None):
+        """Add the current science-arm frame of every env (or those ``mask`` selects) to its long exposure (``aog_science_integrate``).
+        Stream-ordered; reads the state the last ``reset`` / ``step`` left and changes nothing a step reads.  Raises like ``focal_images``
+        while a pipelined or policy-attached step has an action pending and between two steps of a lookahead episode."""
+        ptr, _keep = self._science_mask(mask, "science_integrate")   # (the mask lives until the launches are queued: torch frees in stream order)
+        _lib.check(self.lib.aog_science_integrate(self._handle, ptr, self._stream()))
+
+    def science_clear(self, mask=None):
+        """Empty the long exposure (and frame count) of every env, or of those ``mask`` selects."""
+        ptr, _keep = self._science_mask(mask, "science_clear")
+        _lib.check(self.lib.aog_science_clear(self._handle, ptr, self._stream()))
+
+    def science_exposure(self, first=0, count=None, image=True):
+        """The long exposures of envs [first, first + count), default all, as a dict of device tensors: ``psf`` [count, w, w] float64 the
+        mean frame (``image=False``: left out), ``strehl`` [count] its centre pixel (the long-exposure Strehl ratio),
+        ``encircled_energy`` [count, len(science_radii)] the share of the beam's power inside each of ``science_radii`` (lambda_sci / D),
+        ``frames`` [count] int32.  An env with no frames reads as zeros.  A range outside the batch raises ``ValueError``."""
+        torch = self._torch
+        self._science_mask(None, "science_exposure")
+        first = int(first)
+        count = self.num_envs - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > self.num_envs:
+            raise ValueError(f"science_exposure: envs [{first}, {first + count}) lie outside [0, {self.num_envs})")
+        w, n_ee = self._science.window, int(self._science.radii.size)
+        out = {"strehl": torch.empty((count,), dtype=torch.float64, device=self.device),
+               "encircled_energy": torch.empty((count, n_ee), dtype=torch.float64, device=self.device),
+               "frames": torch.empty((count,), dtype=torch.int32, device=self.device)}
+        if image:
+            out["psf"] = torch.empty((count, w, w), dtype=torch.float64, device=self.device)
+        p = C.c_void_p
+        _lib.check(self.lib.aog_science_read(self._handle, int(first), count, p(out["psf"].data_ptr()) if image else None, p(out["strehl"].data_ptr()),
+                                             p(out["encircled_energy"].data_ptr()), p(out["frames"].data_ptr()), self._stream()))
+        return out
 
     def phase_screen(self, env_index=0):
         """Atmospheric phase at the sensing wavelength [N, N] float32 radians (0 outside the aperture, aperture mean removed) — the

@@ -128,8 +128,30 @@ struct aog_env {
   _Float16* wf_act16 = nullptr;  // the call's own copy of the actuators in act16's layout
   double* wf_slabs = nullptr;    // [pixel chunk][A_pad + 2][Bp] partial sums, allocated by the first call
   double* wf_w = nullptr;        // float64 handles: [B][n_ap] path error of the call, allocated by the first call
+  // science camera (aog_upload_science, aog_science_*; science.hip).  Nothing here is read or written by a reset or step, and none of it
+  // is part of the aog_get_state blob.
+  bool sci_ready = false;        // the camera is uploaded (aog_upload_tables clears it)
+  int sci_w = 0, sci_n_ee = 0;   // window side, number of encircled-energy radii
+  int sci_chunk = 0;             // envs per round of the phase grid / T' work buffers (whole env tiles)
+  double sci_ratio = 0, sci_peak = 0;   // lambda_wfs / lambda_sci; the unaberrated peak's share of the beam's power
+  float sci_unscale = 1.f;       // 2^-(e1 + e2) of the operand tables
+  _Float16* sci_m1s = nullptr;   // K4's m1s layout with ceil(w / 32) v blocks
+  _Float16* sci_m2s = nullptr;   // K4's m2s layout with ceil(w / 32) u blocks
+  int32_t* sci_ap_yx = nullptr;  // [n_ap] iy << 16 | ix of aperture pixel p
+  float* sci_grid = nullptr;     // [sci_chunk][Nyp][Nxp] phases at the science wavelength (revolutions, reduced), kShOutside outside the aperture
+  _Float16* sci_T16 = nullptr;   // [sci_chunk][Nxp / 32][ceil(w / 32)][2][4][64][8]
+  _Float16* sci_act16 = nullptr; // the calls' own copy of the actuators in act16's layout, and their third f16 term
+  _Float16* sci_act_ll = nullptr;
+  double* sci_m1d = nullptr;     // float64 handles: m1 [w][N], m2 [N][w] complex, E [N][N], T [w][N], F [w][w] complex
+  double* sci_m2d = nullptr;
+  double* sci_E = nullptr;
+  double* sci_T = nullptr;
+  double* sci_F = nullptr;
+  int32_t* sci_bin = nullptr;    // [w][w] radial bin of each pixel of the window (-1: outside every radius)
+  double* sci_exposure = nullptr;   // [B][w][w] sum of the integrated frames
+  int32_t* sci_frames = nullptr;    // [B] frames integrated
   // state
-  float* psi_rev = nullptr;      // [n_quads][Bp][4]  (handles that run the VALU kernel only)
+  float* psi_rev = nullptr;     // [n_quads][Bp][4]  (handles that run the VALU kernel only)
   double* pack_mean = nullptr;   // [B] aperture means of the screens being installed (k_screen_means -> k_pack_tiles)
   float* psi_tile = nullptr;     // [Bp/32][n_ptiles][4][64][4]
   double* psi64 = nullptr;       // validation: [B][n_ap]

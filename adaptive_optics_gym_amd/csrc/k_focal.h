@@ -1,6 +1,7 @@
 // K4: focal-plane field export (single env float64 form and the batched split-f16 matrix-core form).
 #pragma once
 #include "k_common.h"
+#include "k_mft_mma.h"
 
 namespace aog {
 
@@ -45,45 +46,6 @@ __global__ void k_focal_field(const float* __restrict__ psi_tile, const double* 
 // transposition happens anywhere.  Workgroup = 4 waves = 4 x 32 columns (v blocks / u blocks) of ONE 128-row span; per k-step the four
 // waves produce the span's four A tiles into LDS (pass 1: one x tile each — 8 loads, 16 transcendentals, mask split; pass 2: one copied
 // T' tile each), every wave then runs 4 tiles x 12 matrix instructions against its own B tile from the L2-resident table.
-constexpr int kFocalTile = 4 * 64;   // f16x8 per operand tile
-// hi = x rounded to nearest f16, lo = x - hi rounded to nearest: an unbiased 22-bit operand.  (The step kernel's cheaper split by mask
-// truncates both halves; here the truncation error — a fixed non-linear function of cos / sin of the phase — showed up as ghost terms of
-// 1e-7 of the peak amplitude, the whole error budget of a pixel 30 dB down; this path has the vector slots to round properly.)
-__device__ __forceinline__ void split8(const float (&x)[8], f16x8& hi, f16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const _Float16 h = (_Float16)x[j];
-    hi[j] = h;
-    lo[j] = (_Float16)(x[j] - (float)h);
-  }
-}
-__device__ __forceinline__ f16x8 neg8(f16x8 v) {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  return __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4, v) ^ 0x80008000u);
-}
-// one A tile (LDS, [part][lane]) against a wave's B tile (registers; nbh, nbl = -Bi): Cr += Ar Br - Ai Bi, Ci += Ar Bi + Ai Br
-__device__ __forceinline__ void focal_mma_tile(const f16x8* __restrict__ a_tile, int lane, const f16x8 (&b)[4], f16x8 nbh, f16x8 nbl, f32x16& cr, f32x16& ci) {
-  const f16x8 arh = a_tile[0 * 64 + lane], arl = a_tile[1 * 64 + lane], aih = a_tile[2 * 64 + lane], ail = a_tile[3 * 64 + lane];
-  // (the two accumulation chains alternate; small terms first)
-  cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(arl, b[0], cr, 0, 0, 0);
-  ci = __builtin_amdgcn_mfma_f32_32x32x16_f16(arl, b[2], ci, 0, 0, 0);
-  cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(arh, b[1], cr, 0, 0, 0);
-  ci = __builtin_amdgcn_mfma_f32_32x32x16_f16(arh, b[3], ci, 0, 0, 0);
-  cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(ail, nbh, cr, 0, 0, 0);
-  ci = __builtin_amdgcn_mfma_f32_32x32x16_f16(ail, b[0], ci, 0, 0, 0);
-  cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(aih, nbl, cr, 0, 0, 0);
-  ci = __builtin_amdgcn_mfma_f32_32x32x16_f16(aih, b[1], ci, 0, 0, 0);
-  cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(arh, b[0], cr, 0, 0, 0);
-  ci = __builtin_amdgcn_mfma_f32_32x32x16_f16(arh, b[2], ci, 0, 0, 0);
-  cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(aih, nbh, cr, 0, 0, 0);
-  ci = __builtin_amdgcn_mfma_f32_32x32x16_f16(aih, b[0], ci, 0, 0, 0);
-}
-// one k-step of a wave: its four A tiles (LDS, [tile][part][lane]) against its B tile
-__device__ __forceinline__ void focal_mma(const f16x8* __restrict__ a_lds, int lane, const f16x8 (&b)[4], f32x16 (&cr)[4], f32x16 (&ci)[4]) {
-  const f16x8 nbh = neg8(b[2]), nbl = neg8(b[3]);
-#pragma unroll
-  for (int t = 0; t < 4; ++t) focal_mma_tile(a_lds + t * kFocalTile, lane, b, nbh, nbl, cr[t], ci[t]);
-}
 // pass 1.  grid (Nxp / 128, nfp / 128, envs); phase [env][Nyp][Nxp]; m1s [nfp / 32][Nyp / 16] tiles; T16 [env][Nxp / 32][nfp / 32][2] tiles
 __global__ __launch_bounds__(256, 2) void k_focal_pass1(const float* __restrict__ phase, const f16x8* __restrict__ m1s, f16x8* __restrict__ T16, int Nxp,
                                                         int Nyp, int nfp) {

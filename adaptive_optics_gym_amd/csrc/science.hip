@@ -1,0 +1,200 @@
+// K13: the science camera (aog_upload_science, aog_science_integrate, aog_science_clear, aog_science_read).  A translation unit of its
+// own: the kernels a step launches keep their code objects as they are.
+#include "host_common.h"
+#include "k_science.h"
+
+using namespace aog_host;
+
+namespace {
+
+constexpr int kScienceMaxRadii = 32, kScienceMaxWindow = 4096;
+
+// x padded to pass 1's 128-column spans, y to whole k-steps, the window to whole 32-column blocks
+int sci_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 128); }
+int sci_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
+int sci_nvb(const aog_env* e) { return (e->sci_w + 31) / 32; }
+
+void release_science(aog_env* e) {
+  e->sci_ready = false;
+  dev_release(e, &e->sci_m1s);
+  dev_release(e, &e->sci_m2s);
+  dev_release(e, &e->sci_ap_yx);
+  dev_release(e, &e->sci_grid);
+  dev_release(e, &e->sci_T16);
+  dev_release(e, &e->sci_act16);
+  dev_release(e, &e->sci_act_ll);
+  dev_release(e, &e->sci_m1d);
+  dev_release(e, &e->sci_m2d);
+  dev_release(e, &e->sci_E);
+  dev_release(e, &e->sci_T);
+  dev_release(e, &e->sci_F);
+  dev_release(e, &e->sci_bin);
+  dev_release(e, &e->sci_exposure);
+  dev_release(e, &e->sci_frames);
+}
+
+template <int A_PAD>
+void launch_science_phase(aog_env* e, hipStream_t s, int etile0, int n_et, size_t grid_env, int Nxp, const uint8_t* mask) {
+  constexpr int NSTEP = A_PAD / 16;
+  hipLaunchKernelGGL((aog::k_science_phase<A_PAD>), dim3((e->n_ptiles + 3) / 4, n_et), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
+                     reinterpret_cast<const aog::f32x4*>(e->psi_tile) + (size_t)etile0 * e->n_ptiles * 4 * 64,
+                     reinterpret_cast<const aog::f16x8*>(e->sci_act16) + (size_t)etile0 * NSTEP * 2 * 64,
+                     reinterpret_cast<const aog::f16x8*>(e->sci_act_ll) + (size_t)etile0 * NSTEP * 64, e->sci_ap_yx, e->sci_grid, grid_env, Nxp, e->n_ptiles,
+                     n_et, e->n_ap, e->B - etile0 * 32, e->sci_ratio, mask ? mask + (size_t)etile0 * 32 : nullptr);
+}
+
+// the checks every call on an uploaded camera shares (aog_focal_images' preconditions)
+int science_ready(aog_env* e, const char* who) {
+  if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "%s before aog_upload_tables/aog_set_screens", who);
+  if (!e->sci_ready) return fail(AOG_ERR_STATE, "%s: the science camera was not uploaded (aog_upload_science, again after aog_upload_tables)", who);
+  if (int rc = check_poisoned(e, who)) return rc;
+  return refuse_pre_evolved(e, who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int aog_upload_science(aog_env* e, const double* m1_host, const double* m2_host, int window, double phase_ratio, double peak_fraction,
+                       const int32_t* ee_bin_host, int n_ee) {
+  if (!e || !m1_host || !m2_host || !ee_bin_host) return fail(AOG_ERR_INVALID, "aog_upload_science: null argument");
+  if (!e->tables_ready) return fail(AOG_ERR_STATE, "aog_upload_science before aog_upload_tables");
+  // (the focal grid's size 2 q num_airy is not in aog_config: the caller's tables define the grid, BatchedAOEnv holds w to it; the cap
+  // here only bounds the exposure's size)
+  if (window < 2 || (window & 1) || window > kScienceMaxWindow)
+    return fail(AOG_ERR_INVALID, "aog_upload_science: window = %d must be even and in [2, %d]", window, kScienceMaxWindow);
+  if (n_ee < 1 || n_ee > kScienceMaxRadii) return fail(AOG_ERR_INVALID, "aog_upload_science: n_ee = %d outside [1, %d]", n_ee, kScienceMaxRadii);
+  if (!(phase_ratio > 0.0) || !(peak_fraction > 0.0)) return fail(AOG_ERR_INVALID, "aog_upload_science: phase_ratio and peak_fraction must be positive");
+  const int w = window, N = e->cfg.n_pupil;
+  for (int i = 0; i < w * w; ++i)
+    if (ee_bin_host[i] < -1 || ee_bin_host[i] >= n_ee) return fail(AOG_ERR_INVALID, "aog_upload_science: ee_bin[%d] = %d outside [-1, %d)", i, ee_bin_host[i], n_ee);
+  if (int rc = refuse_pre_evolved(e, "aog_upload_science")) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());   // (a camera uploaded before may still be integrating into the buffers given back here)
+  release_science(e);
+  e->sci_w = w;
+  e->sci_n_ee = n_ee;
+  e->sci_ratio = phase_ratio;
+  e->sci_peak = peak_fraction;
+  int rc;
+  if ((rc = upload(e, &e->sci_bin, ee_bin_host, (size_t)w * w)) != AOG_OK) return rc;
+  if ((rc = dev_alloc(e, &e->sci_exposure, (size_t)e->B * w * w, true)) != AOG_OK) return rc;
+  if ((rc = dev_alloc(e, &e->sci_frames, (size_t)e->B, true)) != AOG_OK) return rc;
+  if (e->cfg.precision == AOG_PRECISION_FP64) {
+    if ((rc = upload(e, &e->sci_m1d, m1_host, (size_t)w * N * 2)) != AOG_OK) return rc;
+    if ((rc = upload(e, &e->sci_m2d, m2_host, (size_t)w * N * 2)) != AOG_OK) return rc;
+    if ((rc = dev_alloc(e, &e->sci_E, (size_t)N * N * 2, true)) != AOG_OK) return rc;   // (zero outside the aperture, for good)
+    if ((rc = dev_alloc(e, &e->sci_T, (size_t)w * N * 2, false)) != AOG_OK) return rc;
+    if ((rc = dev_alloc(e, &e->sci_F, (size_t)w * w * 2, false)) != AOG_OK) return rc;
+    e->sci_ready = true;
+    return AOG_OK;
+  }
+  const int Nxp = sci_nxp(e), Nyp = sci_nyp(e), nvb = sci_nvb(e);
+  std::vector<_Float16> m1s, m2s;
+  e->sci_unscale = mft_operand_tables(m1_host, m2_host, N, w, nvb * 32, Nxp, Nyp, m1s, m2s);
+  if ((rc = upload(e, &e->sci_m1s, m1s)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->sci_m2s, m2s)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->sci_ap_yx, ap_yx_table(e))) != AOG_OK) return rc;
+  // work buffers for a chunk of whole env tiles, as K4's: the phase grid (every pixel starts out as "outside the aperture": only aperture
+  // pixels are ever written) and T' (split f16, pass 2's operand order)
+  const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * nvb * 2 * 4 * 64 * 8;
+  const size_t cap = std::max<size_t>(32, (((size_t)256 << 20) / std::max(grid_env * 4, t16_env * 2)) / 32 * 32);
+  e->sci_chunk = (int)std::min<size_t>((size_t)e->n_etiles * 32, cap);
+  if (const char* v = getenv("AOG_SCIENCE_CHUNK")) e->sci_chunk = std::max(32, std::min(e->sci_chunk, atoi(v) / 32 * 32));   // (tests: several chunks at small sizes)
+  if ((rc = dev_alloc(e, &e->sci_grid, (size_t)e->sci_chunk * grid_env, false)) != AOG_OK) return rc;
+  if ((rc = dev_alloc(e, &e->sci_T16, (size_t)e->sci_chunk * t16_env, false)) != AOG_OK) return rc;
+  if ((rc = dev_alloc(e, &e->sci_act16, (size_t)e->n_etiles * 32 * e->A_pad * 2, true)) != AOG_OK) return rc;
+  if ((rc = dev_alloc(e, &e->sci_act_ll, (size_t)e->n_etiles * 32 * e->A_pad, true)) != AOG_OK) return rc;
+  std::vector<float> fill(grid_env, aog::kShOutside);
+  for (int i = 0; i < e->sci_chunk; ++i)
+    HIP_TRY(hipMemcpy(e->sci_grid + (size_t)i * grid_env, fill.data(), sizeof(float) * grid_env, hipMemcpyHostToDevice));
+  e->sci_ready = true;
+  return AOG_OK;
+}
+
+int aog_science_integrate(aog_env* e, const uint8_t* mask_dev, void* stream) {
+  if (!e) return fail(AOG_ERR_INVALID, "aog_science_integrate: null argument");
+  if (int rc = science_ready(e, "aog_science_integrate")) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int N = e->cfg.n_pupil, w = e->sci_w, w2 = w * w;
+  if (e->cfg.precision == AOG_PRECISION_FP64) {
+    double2* E = reinterpret_cast<double2*>(e->sci_E);
+    double2* T = reinterpret_cast<double2*>(e->sci_T);
+    double2* F = reinterpret_cast<double2*>(e->sci_F);
+    for (int env = 0; env < e->B; ++env) {
+      hipLaunchKernelGGL(aog::k_science_field64, dim3((e->n_ap + 255) / 256), dim3(256), 0, s, e->psi64, e->modes64, e->act_dm, e->ap_index, E, env, e->n_ap,
+                         e->A, e->cfg.wavelength_wfs, e->sci_ratio, mask_dev);
+      hipLaunchKernelGGL(aog::k_science_cgemm64, dim3((w * N + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->sci_m1d), E, T, w, N, N, env,
+                         mask_dev);
+      hipLaunchKernelGGL(aog::k_science_cgemm64, dim3((w2 + 255) / 256), dim3(256), 0, s, T, reinterpret_cast<const double2*>(e->sci_m2d), F, w, N, w, env,
+                         mask_dev);
+      hipLaunchKernelGGL(aog::k_science_accum64, dim3((w2 + 255) / 256), dim3(256), 0, s, F, e->sci_exposure, e->sci_frames, w2, env, mask_dev);
+    }
+    HIP_TRY(hipGetLastError());
+    return AOG_OK;
+  }
+  int rc;
+  // psi_tile holding the screens the last step read, refreshed the way aog_wavefront_truth does it (psi_tile alone: nothing a step reads is
+  // touched); the actuator operands are the call's own copy
+  if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
+  if ((rc = load_actuators(e, s, {nullptr, e->sci_act16, e->sci_act_ll})) != AOG_OK) return rc;
+  const int Nxp = sci_nxp(e), Nyp = sci_nyp(e), nvb = sci_nvb(e), nwg = (nvb + 3) / 4;
+  // windows of at most two 32-column blocks: the four waves of a workgroup share the two blocks (k_science_pass1); AOG_SCIENCE_SPLIT=0
+  // keeps the one-block-per-wave form with idle waves (same bits; tests and measurements)
+  int split = nvb <= 2;
+  if (const char* v = getenv("AOG_SCIENCE_SPLIT")) split = split && atoi(v) != 0;
+  const size_t grid_env = (size_t)Nyp * Nxp;
+  for (int env0 = 0; env0 < e->B; env0 += e->sci_chunk) {
+    const int n = std::min(e->sci_chunk, e->B - env0), n_et = (n + 31) / 32;
+    switch (e->A_pad) {
+      case 16: launch_science_phase<16>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
+      case 32: launch_science_phase<32>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
+      case 64: launch_science_phase<64>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
+      default: launch_science_phase<128>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
+    }
+    hipLaunchKernelGGL(aog::k_science_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->sci_grid, reinterpret_cast<const aog::f16x8*>(e->sci_m1s),
+                       reinterpret_cast<aog::f16x8*>(e->sci_T16), Nxp, Nyp, nvb, mask_dev, env0, split);
+    hipLaunchKernelGGL(aog::k_science_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->sci_T16),
+                       reinterpret_cast<const aog::f16x8*>(e->sci_m2s), e->sci_exposure, e->sci_frames, Nxp, nvb, w, e->sci_unscale, mask_dev, env0, split);
+    HIP_TRY(hipGetLastError());
+  }
+  return AOG_OK;
+}
+
+int aog_science_clear(aog_env* e, const uint8_t* mask_dev, void* stream) {
+  if (!e) return fail(AOG_ERR_INVALID, "aog_science_clear: null argument");
+  if (int rc = science_ready(e, "aog_science_clear")) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  const int w2 = e->sci_w * e->sci_w;
+  hipLaunchKernelGGL(aog::k_science_clear, dim3(std::min((w2 + 255) / 256, 64), e->B), dim3(256), 0, static_cast<hipStream_t>(stream), e->sci_exposure,
+                     e->sci_frames, mask_dev, w2);
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
+int aog_science_read(aog_env* e, int first, int count, double* psf_dev, double* strehl_dev, double* ee_dev, int32_t* frames_dev, void* stream) {
+  if (!e) return fail(AOG_ERR_INVALID, "aog_science_read: null argument");
+  if (!psf_dev && !strehl_dev && !ee_dev && !frames_dev) return fail(AOG_ERR_INVALID, "aog_science_read: every output pointer is null");
+  if (int rc = science_ready(e, "aog_science_read")) return rc;
+  if (int rc = check_env_range("aog_science_read", first, count, e->B)) return rc;
+  if (count == 0) return AOG_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  aog::ScienceFinishArgs p{};
+  p.exposure = e->sci_exposure;
+  p.frames = e->sci_frames;
+  p.bin = e->sci_bin;
+  p.psf = psf_dev;
+  p.strehl = strehl_dev;
+  p.ee = ee_dev;
+  p.frames_out = frames_dev;
+  p.first = first;
+  p.w = e->sci_w;
+  p.n_ee = e->sci_n_ee;
+  p.peak_fraction = e->sci_peak;
+  hipLaunchKernelGGL(aog::k_science_finish, dim3(count), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
+}  // extern "C"

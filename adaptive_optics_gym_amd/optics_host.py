@@ -325,3 +325,64 @@ def build_tables(params: OpticalParams, act_type: str, act_dim: int, obs_dim: in
                       focal_m1=amp * pix_area / (1j * lam * f) * np.exp(-1j * kappa * np.outer(Xf, ax)),
                       focal_m2=np.exp(-1j * kappa * np.outer(ax, Xf)), lp_modes=lps, focal_pixel_area=dAf, obs_route=obs_route,
                       obs_m1=obs_m1, obs_m2=obs_m2)
+
+
+# ------------------------------------------------------------------------------------------------
+# science camera: a centred window of the science arm's focal grid (AO_env.py:314-316, 479-483)
+# ------------------------------------------------------------------------------------------------
+SCIENCE_DEFAULT_RADII = (1.0, 2.0, 3.0, 5.0, 8.0)
+
+
+@dataclass
+class ScienceTables:
+    window: int                     # w: rows and columns [c - w/2, c + w/2) of the n_s x n_s grid, c = n_s / 2 the on-axis sample
+    m1: np.ndarray                  # [w, N] complex, 1 / n_ap folded in: a flat wavefront gives 1 at the centre pixel
+    m2: np.ndarray                  # [N, w] complex
+    phase_ratio: float              # lambda_wfs / lambda_sci: the residual in revolutions of the sensing wavelength -> the science arm's
+    peak_fraction: float            # unaberrated_PSF.max() of a unit-power beam: the peak pixel's share of the beam's power
+    radii: np.ndarray               # [n_ee] encircled-energy radii in lambda_sci / D, ascending
+    ee_bin: np.ndarray              # [w, w] int32: the smallest k with r <= radii[k], -1 outside every radius
+
+
+def science_window_limit(params: OpticalParams) -> int:
+    return int(2 * params.focal_q * params.focal_num_airy)
+
+
+def science_tables(params: OpticalParams, window: int, radii=None) -> ScienceTables:
+    """Host tables of the science camera (``aog_upload_science``).  I = |m1 E m2|^2 with E = exp(i phi_sci) on the aperture is
+    ``wf_sci_focal_plane.power / (unaberrated_PSF.max() * total_power)`` on the window; its centre pixel is the Strehl ratio of
+    ``build_tables``' science row.  ``radii`` (lambda_sci / D, ascending, each circle inside the window) default to 1, 2, 3, 5, 8 clipped
+    to the largest circle the window holds whole, (w/2 - 1) / q."""
+    n_s = science_window_limit(params)
+    w = int(window)
+    if w != window or w < 2 or w > n_s or w % 2:
+        raise ValueError(f"science_window must be an even number of focal samples in [2, {n_s}], got {window!r}")
+    N, D, q = params.num_pupil_pixels, params.telescope_diameter, params.focal_q
+    lam_s = params.wavelength_sci
+    ax = centred_axis(N, D)
+    n_ap = int(np.count_nonzero(aperture_mask(N, D)))
+    Xs = focal_axis(q, params.focal_num_airy, lam_s / D)
+    c = n_s // 2
+    Xw = Xs[c - w // 2:c + w // 2]
+    m1 = np.exp(-1j * (2 * np.pi / lam_s) * np.outer(Xw, ax)) / n_ap
+    m2 = np.exp(-1j * (2 * np.pi / lam_s) * np.outer(ax, Xw))
+    # FraunhoferPropagator at focal length 1: field = sum E dA exp(..) / (i lambda), power = |field|^2 dX^2, unit-power amplitude^2 = 1 / (n_ap dA)
+    peak_fraction = n_ap * (D / N) ** 2 * (Xs[1] - Xs[0]) ** 2 / lam_s ** 2
+    r_max = (w // 2 - 1) / q
+    if radii is None:
+        rr = np.unique(np.minimum(np.asarray(SCIENCE_DEFAULT_RADII), r_max))
+        rr = rr[rr > 0]
+        if rr.size == 0:
+            rr = np.array([0.0])   # (w = 2: the on-axis pixel alone)
+    else:
+        rr = np.asarray(radii, dtype=np.float64).reshape(-1)
+        if rr.size < 1 or rr.size > 32 or np.any(rr < 0) or np.any(np.diff(rr) <= 0) or rr[-1] > r_max:
+            raise ValueError(f"science_radii must be 1 .. 32 ascending radii in lambda/D, none above (window/2 - 1) / q = {r_max}")
+    # squared radius in focal samples, exact in integers: pixel (v, u) is inside radius R when iv^2 + iu^2 <= (R q)^2
+    i = np.arange(w) - w // 2
+    r2 = (i[:, None] ** 2 + i[None, :] ** 2).astype(np.float64)
+    ee_bin = np.full((w, w), -1, dtype=np.int32)
+    for k in range(rr.size - 1, -1, -1):
+        ee_bin[r2 <= (rr[k] * q) ** 2 * (1 + 1e-12)] = k
+    return ScienceTables(window=w, m1=m1, m2=m2, phase_ratio=params.wavelength_wfs / lam_s, peak_fraction=float(peak_fraction),
+                         radii=rr.astype(np.float64), ee_bin=ee_bin)

@@ -252,7 +252,8 @@ class DeviceActor:
 
 
 def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, generator=None, actor_impl: str = "auto", seed: int = 0,
-            dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None, fused_policy: bool = False, action_mode: str = "sample"):
+            dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None, fused_policy: bool = False, action_mode: str = "sample",
+            science: bool = False):
     """Collect ``episodes`` lock-step episodes from ``env`` (a ``BatchedAOEnv``).
 
     ``actor_impl``: "hip" = the fused policy-query kernel (``DeviceActor``), "torch" = the module's own forward +
@@ -281,7 +282,11 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     the epilogue of step t, the query on its observation and the prologue of step t + 1 take three): needs ``policy="actor"`` resolved to
     ``actor_impl="hip"``, and takes a ``DeviceOUNoise`` and ``action_mode`` but not the torch ``OrnsteinUhlenbeckNoise`` (that noise would have
     to be added between the query and the prologue); ValueError otherwise.  Returns the same dict, bit for bit, as the unfused loop with the
-    same ``DeviceActor`` (seed and call counter) and, if any, an OU state equal to the unfused loop's."""
+    same ``DeviceActor`` (seed and call counter) and, if any, an OU state equal to the unfused loop's.
+
+    ``science=True`` (an env built with ``science_window``): ``env.science_integrate()`` after every step, never cleared here — read the
+    long exposure with ``env.science_exposure()`` afterwards.  The transitions are those of ``science=False`` bit for bit.  Not with
+    ``fused_policy`` or ``lookahead`` (the camera is refused while the next action or the next screens are already in place): ValueError."""
     import numpy as np
     import torch
 
@@ -331,6 +336,12 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         if ou_noise is not None and not dev_ou:
             raise ValueError("fused_policy=True cannot add the torch ou_noise: the noise would have to enter between the policy query and the "
                              "prologue (a DeviceOUNoise is added inside the query)")
+    if science:
+        if getattr(env, "science_window", None) is None:
+            raise ValueError("science=True needs an env created with science_window=...")
+        if fused_policy or lookahead:
+            raise ValueError("science=True goes with neither fused_policy nor lookahead: between two such steps the mirror or the screens already "
+                             "belong to the next step and the camera is refused")
     import inspect
 
     step_takes_out = "out" in inspect.signature(env.step).parameters
@@ -387,6 +398,8 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                         out["rew"][i].copy_(rew)
                         out["next_obs"][i].copy_(next_obs)
                         out["done"][i].copy_(done)
+                    if science:
+                        env.science_integrate()
                     if _t == 0:
                         out["obs"][i].copy_(obs)
                     obs = next_obs

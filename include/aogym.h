@@ -411,6 +411,47 @@ int aog_upload_wavefront_fit(aog_env* env, const double* modes_host, const doubl
 int aog_wavefront_truth(aog_env* env, double* rms_dev, double* fit_rms_dev,
                         double* coef_dev, double* act_ideal_dev, void* stream);
 
+/* ---- science camera: long-exposure PSF, Strehl and encircled energy (the image AO_env.py:479 forms every step and reads one pixel of) ----
+ * The camera sees a centred window of w x w samples of the science arm's focal grid (make_focal_grid(q, num_airy, lambda_sci / D): n_s =
+ * 2 q num_airy samples per axis, on-axis sample c = n_s / 2): rows and columns [c - w/2, c + w/2), w even.  A frame of an env is
+ *   I[v][u] = | sum_{y,x} m1[v][y] E[y][x] m2[x][u] |^2,  E = exp(2 pi i u_p phase_ratio) on the aperture, 0 outside,
+ * u_p the residual phase in revolutions of the sensing wavelength (screen + mirror, as the step kernels form it), phase_ratio =
+ * lambda_wfs / lambda_sci.  m1, m2 are the window's Fraunhofer matrices with the normalisation folded into m1 so that a flat wavefront
+ * gives I[w/2][w/2] = 1: a frame's centre pixel IS that step's Strehl ratio, and I = wf_sci_focal_plane.power / (unaberrated_PSF.max() x
+ * total power).  Per env the library keeps the float64 sum of the integrated frames (the exposure) and their number.  Neither is part of
+ * the aog_get_state blob: a restored state continues with whatever the camera holds.
+ *
+ * Host tables, float64 / int32 HOST pointers: m1 [w][N][2], m2 [N][w][2] (re, im), ee_bin [w*w] the radial bin 0 .. n_ee - 1 of each
+ * window pixel (-1 = outside every radius), peak_fraction = the unaberrated peak's share of the beam's power (unaberrated_PSF.max() of a
+ * unit-power beam).  After aog_upload_tables; a later aog_upload_tables clears the camera.  Builds the split-f16 operand tables of the
+ * matrix-core path; every buffer of the camera is allocated here, not at aog_create, so handles that never ask keep their device_bytes.
+ * A second upload replaces the first (and its exposures).  AOG_ERR_INVALID for an odd window, one outside [2, 4096] or n_ee outside
+ * [1, 32].  The focal grid's size n_s is not part of aog_config — m1 / m2 define the grid — so w <= n_s is the caller's to hold
+ * (BatchedAOEnv raises ValueError above 240); the library's cap bounds the exposure's size only.  phase_ratio is used as given on fast
+ * and float64 handles alike. */
+int aog_upload_science(aog_env* env, const double* m1_host, const double* m2_host, int window, double phase_ratio, double peak_fraction,
+                       const int32_t* ee_bin_host, int n_ee);
+
+/* Add the current frame of every env (mask_dev: nullable [B] uint8 device array, non-zero = selected) to its exposure and count it.
+ * Stream-ordered, no host synchronisation; frames add in stream order, one thread owns one pixel (no atomics), so an exposure does not
+ * depend on how the envs are grouped into handles, masks or chunks.  Fast handles: a phase grid at the science wavelength (the
+ * split-f16 phase contraction of the step kernels, scaled by phase_ratio before it is reduced to a revolution), then K4's two
+ * matrix-core products on the window's geometry, the second squaring its accumulators into the exposure instead of writing a field.
+ * Float64 validation handles: per env, plain float64 kernels.  Reads the state the last reset or step left and changes nothing a step
+ * reads or writes (actuator operands and work buffers are the camera's own).  AOG_ERR_STATE before tables, screens or aog_upload_science,
+ * while a pipelined or policy-attached step has an action pending, and between two steps of a lookahead episode. */
+int aog_science_integrate(aog_env* env, const uint8_t* mask_dev, void* stream);
+
+/* Zero the exposure and frame count of the selected envs (mask_dev as above).  Same preconditions. */
+int aog_science_clear(aog_env* env, const uint8_t* mask_dev, void* stream);
+
+/* Read envs [first, first + count): psf [count][w][w] the mean frame (exposure / frames), strehl [count] its centre pixel, ee
+ * [count][n_ee] the encircled energy EE_k = peak_fraction x sum of the mean frame over the pixels of bins <= k (a share of the beam's
+ * power), frames [count] int32.  float64 device pointers but frames_dev; each nullable, at least one non-NULL.  Sums run in float64 in a
+ * fixed order per env.  An env with no frames reads as zeros.  Stream-ordered; same preconditions. */
+int aog_science_read(aog_env* env, int first, int count, double* psf_dev, double* strehl_dev, double* ee_dev, int32_t* frames_dev,
+                     void* stream);
+
 /* ---- policy query of the rollout (Actor.forward + Actor.get_action, network.py:17-69; caller algorithm.py:216-296) ----
  * mean = W_o drop(relu(W_3 drop(relu(W_2 drop(relu(W_1 obs + b_1)) + b_2)) + b_3)) + b_o with nn.Dropout(dropout_p) ACTIVE
  * (the reference never leaves training mode while acting), action = mean + sqrt(cov_var) eps, eps ~ N(0, I),
