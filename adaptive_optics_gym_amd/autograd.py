@@ -1,0 +1,48 @@
+"""``env.step`` as a differentiable function of the action (``torch.autograd``)."""
+from __future__ import annotations
+
+import torch
+
+
+class _StepOutputs(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, action, env):
+        a = env._as_actions(action.detach())
+        env.step(a)
+        # the float64 outputs of the gradient's own forward half: what backward differentiates
+        one = torch.ones(env.num_envs, dtype=torch.float64, device=env.device)
+        _, vals = env.output_gradient(g_strehl=one, wrt=None, with_values=True)
+        ctx.env = env
+        ctx.epoch = env.state_epoch
+        ctx.action = a
+        ctx.in_dtype = action.dtype
+        n = env.obs_dim ** 2
+        return vals[:, :n].contiguous(), vals[:, n].contiguous(), vals[:, n + 1].contiguous()
+
+    @staticmethod
+    def backward(ctx, g_obs, g_power, g_strehl):
+        env = ctx.env
+        if env.state_epoch != ctx.epoch:
+            raise RuntimeError("step_outputs: the environment has been stepped, reset or restored since this step; its gradient is that of the "
+                               "state the step left and can only be taken before the state moves on")
+        sep = env.obs_route == "separable"
+        grad = env.output_gradient(g_obs=None if sep else g_obs, g_power=g_power, g_strehl=g_strehl, wrt="action", action=ctx.action)
+        return grad.to(ctx.in_dtype), None
+
+
+def step_outputs(env, action):
+    """Step ``env`` (a ``BatchedAOEnv``) with ``action`` [B, A] and return ``(obs_raw [B, o^2], power [B], strehl [B])`` as float64 tensors
+    that are differentiable with respect to ``action``.
+
+    The forward pass is ``env.step(action)``; the values are the float64 ones ``output_gradient`` evaluates at that state (the step's own
+    float32 outputs rounded from the same sums).  The backward pass is ONE ``env.output_gradient(wrt="action")`` call with the incoming
+    cotangents.  The gradient is that of the state at this step: backward raises ``RuntimeError`` once the env has been stepped, reset or
+    restored since, so call ``backward()`` (or ``torch.autograd.grad``) before the next step.
+
+    One step is the whole chain here: the atmosphere never depends on the action, and a step sets the mirror absolutely from its action
+    (AO_env.py:115-120), so nothing step t returns depends on an earlier action — the sum of per-step gradients is the exact policy
+    gradient of an episode's return.  The Strehl reward (AO_env.py:476) is ``strehl`` itself; the SSIM reward (AO_env.py:487) is a function
+    of ``obs_raw`` and ``power`` that callers write in torch and chain through these outputs.  On the separable observation route the
+    observation has no gradient (``obs_raw`` comes back as NaN and its cotangent is ignored); power and Strehl do."""
+    obs_raw, power, strehl = _StepOutputs.apply(action, env)
+    return obs_raw, power, strehl

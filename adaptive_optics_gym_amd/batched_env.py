@@ -266,6 +266,8 @@ class BatchedAOEnv:
         _lib.check(self.lib.aog_upload_tables(self._handle, C.byref(tabs)))
         self._wavefront_fit_uploaded = False   # (the library drops the wavefront fit with the old tables; wavefront_truth uploads it again)
         self._science_uploaded = False         # (and the science camera)
+        self._gradient_uploaded = False        # (and the gradient's operand tables; output_gradient uploads them again)
+        self._upload_keep = (keep, tabs)       # (output_gradient hands the same host tables to aog_upload_gradient)
         self._upload_science()
         if self.obs_route == "separable":
             om1 = np.ascontiguousarray(np.stack([t.obs_m1.real, t.obs_m1.imag], axis=-1), dtype=np.float64)
@@ -710,6 +712,7 @@ class BatchedAOEnv:
         screens = screens.to(self.device).contiguous()
         fn = self.lib.aog_set_screens_f64 if screens.dtype == torch.float64 else self.lib.aog_set_screens_f32
         _lib.check(fn(self._handle, C.c_void_p(screens.data_ptr()), int(first), int(screens.shape[0]), self._stream()))
+        self.state_epoch += 1
         # the kernel is stream-ordered; keep the source alive until it has run
         torch.cuda.current_stream(self.device).synchronize()
 
@@ -727,6 +730,11 @@ class BatchedAOEnv:
         return obs, {}
 
     _PIPELINE_END = object()
+    # counts every change of the state output_gradient reads (reset, step, set_actuators, set_screens, set_state): autograd.step_outputs
+    # refuses a backward pass once it has moved
+    state_epoch = 0
+    _last_action = None
+    _gradient_uploaded = False
 
     def step(self, actions, out=None, next_actions=_PIPELINE_END):
         """AOEnv.step (AO_env.py:106-153).  ``actions``: [B, A] float32 tensor on the device.
@@ -752,6 +760,7 @@ class BatchedAOEnv:
             if cached:
                 self._step_cache = (ret, ptrs)
         self._launch_step(a, next_actions, ptrs)
+        self._last_action = a   # (output_gradient(wrt="action") differentiates through it)
         self._observed(ret[0], ret[4]["obs_raw"], step=True)
         return ret
 
@@ -762,6 +771,9 @@ class BatchedAOEnv:
         self.last_obs_raw = obs_raw
         self._last_obs = obs
         self.observation_frames += 1
+        self.state_epoch += 1
+        if not step:
+            self._last_action = None
         if step:
             self.timestep += 1
 
@@ -938,6 +950,8 @@ class BatchedAOEnv:
         torch = self._torch
         a = torch.as_tensor(act, device=self.device).to(torch.float64).reshape(self.num_envs, self.num_modes).contiguous()
         _lib.check(self.lib.aog_set_actuators(self._handle, C.c_void_p(a.data_ptr()), self._stream()))
+        self.state_epoch += 1
+        self._last_action = None
         torch.cuda.current_stream(self.device).synchronize()
 
     def focal_image(self, env_index=0):
@@ -999,6 +1013,53 @@ class BatchedAOEnv:
         act = torch.empty((self.num_envs, self.num_modes), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.aog_wavefront_truth(self._handle, None, None, None, C.c_void_p(act.data_ptr()), self._stream()))
         return act
+
+    # ------------------------------------------------------------------------------------------------
+    # analytic gradient
+    def output_gradient(self, g_obs=None, g_power=None, g_strehl=None, wrt="actuators", action=None, with_values=False):
+        """Vector-Jacobian product of the optical outputs at the state the last reset or step left (``aog_output_gradient``): the gradient of
+        ``L = sum(g_obs * obs_raw) + sum(g_power * power) + sum(g_strehl * strehl)`` (cotangents: [B, o^2], [B], [B]; ``None`` = zero, at
+        least one given) as a float64 device tensor [B, A].  ``wrt="actuators"``: with respect to ``get_actuators()`` (per metre of surface);
+        ``wrt="action"``: with respect to the float32 action through the normalisation of AO_env.py:119-120 (``action`` defaults to the last
+        action passed to ``step()``; not on ``SH_operation`` environments, whose action is the actuators).  The atmosphere never depends on
+        the action and a step sets the mirror absolutely, so this one-step gradient is the complete derivative of everything step t returns
+        with respect to the policy.  The observation noise of ``set_detector`` does not enter: the gradient is of the clean outputs.
+        ``with_values=True`` returns ``(grad, values)`` with ``values`` [B, o^2 + 2] the float64 obs_raw, power and Strehl the gradient was
+        taken at (NaN observation entries on the separable route, where ``g_obs`` is not available).  The Strehl reward is the Strehl itself
+        (AO_env.py:476-487); callers chain the SSIM reward themselves.  Stream-ordered, no host synchronisation, nothing a step reads is
+        changed; ``wrt=None`` (with ``with_values=True``) runs the forward half alone and returns ``(None, values)``; raises like
+        ``wavefront_truth`` while an action is pending and between two steps of a lookahead episode."""
+        torch = self._torch
+        if wrt not in ("actuators", "action", None):
+            raise ValueError("output_gradient: wrt must be 'actuators' or 'action' (or None with with_values=True: the values alone)")
+        if wrt is None and not with_values:
+            raise ValueError("output_gradient: wrt=None asks for the values alone and needs with_values=True")
+        if not self._gradient_uploaded:
+            _lib.check(self.lib.aog_upload_gradient(self._handle, C.byref(self._upload_keep[1])))
+            self._gradient_uploaded = True
+        B, A, n = self.num_envs, self.num_modes, self.obs_dim ** 2
+
+        def cot(x, shape, name):
+            if x is None:
+                return None
+            t = torch.as_tensor(x, device=self.device).to(torch.float64)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"output_gradient: {name} must have shape {shape}")
+            return t.contiguous()
+
+        go, gp, gs = cot(g_obs, (B, n), "g_obs"), cot(g_power, (B,), "g_power"), cot(g_strehl, (B,), "g_strehl")
+        a = None
+        if wrt == "action":
+            a = self._last_action if action is None else self._as_actions(action)
+            if a is None:
+                raise ValueError("output_gradient(wrt='action'): no action given and no step() taken since the last reset")
+        grad = torch.empty((B, A), dtype=torch.float64, device=self.device) if wrt is not None else None
+        values = torch.empty((B, n + 2), dtype=torch.float64, device=self.device) if with_values else None
+        p = C.c_void_p
+        ptr = lambda t: p(t.data_ptr()) if t is not None else None
+        _lib.check(self.lib.aog_output_gradient(self._handle, ptr(go), ptr(gp), ptr(gs), ptr(a), ptr(grad) if wrt == "actuators" else None,
+                                                ptr(grad) if wrt == "action" else None, ptr(values), self._stream()))
+        return (grad, values) if with_values else grad
 
     # ------------------------------------------------------------------------------------------------
     # science camera
@@ -1095,6 +1156,8 @@ class BatchedAOEnv:
         if blob.numel() != int(self.lib.aog_state_bytes(self._handle)):
             raise ValueError("state blob does not match this environment's configuration")
         _lib.check(self.lib.aog_set_state(self._handle, C.c_void_p(blob.data_ptr()), int(state["lib_timestep"]), self._stream()))
+        self.state_epoch += 1
+        self._last_action = None
         torch.cuda.current_stream(self.device).synchronize()
         self.timestep = int(state["timestep"])
         self.episode_no = int(state["episode_no"])

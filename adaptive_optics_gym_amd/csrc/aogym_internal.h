@@ -128,6 +128,21 @@ struct aog_env {
   _Float16* wf_act16 = nullptr;  // the call's own copy of the actuators in act16's layout
   double* wf_slabs = nullptr;    // [pixel chunk][A_pad + 2][Bp] partial sums, allocated by the first call
   double* wf_w = nullptr;        // float64 handles: [B][n_ap] path error of the call, allocated by the first call
+  // output gradient (aog_upload_gradient, aog_output_gradient; gradient.hip).  Nothing here is read or written by a reset or step.
+  bool grad_ready = false;         // the gradient's tables are uploaded (aog_upload_tables clears it)
+  float grad_tscale = 1.f;         // power of two the table operands are scaled by
+  _Float16* grad_ftab16 = nullptr; // wfs tables as A operands of the forward sums: [n_ptiles][step 2][hi|lo][64][8] (tab16's order, 32 table rows)
+  _Float16* grad_ttab16 = nullptr; // the same tables transposed (32 pixel rows, K = 32 tables): [n_ptiles][step 2][hi|lo][64][8]
+  _Float16* grad_mtab16 = nullptr; // modes as table operands (wf_tab16's recipe)
+  double* grad_stab = nullptr;     // [n_ptiles][h 2][16] science table in accumulator order
+  _Float16* grad_act16 = nullptr;  // the call's own copy of the actuators in act16's layout
+  _Float16* grad_cop16 = nullptr;  // [n_etiles][step 2][re|im][hi|lo][64][8] C of every env as B operands
+  float* grad_csci = nullptr;      // [Bp][2] the science arm's C
+  double* grad_fslabs = nullptr;   // forward partial sums [pixel chunk][rows][Bp], allocated by the first call (as the four below)
+  double* grad_bslabs = nullptr;   // backward partial sums [pixel chunk][A rows][Bp]
+  double* grad_cbuf = nullptr;     // [B][tables][2] C / cscale
+  double* grad_cscale = nullptr;   // [B]
+  double* grad_trig = nullptr;     // float64 handles: [B][n_ap][4]
   // science camera (aog_upload_science, aog_science_*; science.hip).  Nothing here is read or written by a reset or step, and none of it
   // is part of the aog_get_state blob.
   bool sci_ready = false;        // the camera is uploaded (aog_upload_tables clears it)

@@ -452,6 +452,46 @@ int aog_science_clear(aog_env* env, const uint8_t* mask_dev, void* stream);
 int aog_science_read(aog_env* env, int first, int count, double* psf_dev, double* strehl_dev, double* ee_dev, int32_t* frames_dev,
                      void* stream);
 
+/* ---- analytic gradient of observation, power and Strehl with respect to the mirror (no counterpart in the reference) ----
+ * The atmosphere never depends on the action and AOEnv.step sets the mirror absolutely (AO_env.py:115-120): every output of step t depends
+ * on the policy through action t alone, so this one-step vector-Jacobian product is the whole differentiable simulator.
+ * With the names of aog_tables — phi_p the sensing-arm phase in radians on packed aperture pixel p, E_p = exp(i phi_p),
+ * Z_j = sum_m coef[j][m] sum_p E_p g_m(p) — and the cotangents gbar_j (g_obs for the rows of the observation, g_power for every fiber-mode
+ * row), the call differentiates  L = sum_j gbar_j |Z_j|^2 + g_strehl |Z_sci|^2  per env:
+ *     C_m     = sum_j gbar_j conj(Z_j) coef[j][m]
+ *     H_p     = sum_m C_m g_m(p)
+ *     q_p     = 2 Re(i E_p H_p)                         = dL/dphi_p
+ *     dL/da_k = (4 pi / lambda_wfs) sum_p M_pk q_p      (a = actuators, metres of surface; M = aog_tables.modes)
+ * The science arm is the same with sci_tables, sci_coef and E^sci_p = exp(i r phi_p), r = lambda_wfs / lambda_sci; its q_p carries an extra
+ * factor r.  Action chain (AO_env.py:119-120): v_k = action_k / (k + 10), n = sqrt(v' G v) with G = aog_tables.gram, c =
+ * cfg.surface_rms_target, a = c v / n; with g = dL/da:  dL/dv = (c / n) (g - (g . v) (G v) / n^2),  dL/daction_k = (dL/dv)_k / (k + 10), in
+ * float64 without fused multiply-add.  A zero action gives NaN, as the forward does.  The outputs are invariant to the action's scale, so
+ * action . dL/daction = 0.  The detector (aog_set_detector) does not enter: the gradient is of the clean outputs.
+ *
+ * Host tables of the gradient: the aog_tables given to aog_upload_tables, again (the library keeps no host copy; modes, wfs_tables and
+ * sci_tables are read).  After aog_upload_tables; a later aog_upload_tables clears the upload.  Fast handles build the operand tables of
+ * the matrix-core kernels here (the wfs tables as forward operands and transposed, the modes as table operands); every buffer is allocated
+ * here or by the first aog_output_gradient, so handles that never ask keep their device_bytes. */
+int aog_upload_gradient(aog_env* env, const aog_tables* tables);
+
+/* The vector-Jacobian product at the state the last reset / step left.
+ * cotangents (float64 device, each nullable, at least one non-NULL): g_obs [B][o^2], g_power [B], g_strehl [B]
+ * outputs (float64 device, each nullable, at least one non-NULL):
+ *   grad_act [B][A]      dL/d actuators (per metre of surface)
+ *   grad_action [B][A]   dL/d action through the chain above (needs action_dev [B][A] float32, the action that produced the current
+ *                        actuators; AOG_ERR_INVALID on sh_operation handles or without action_dev)
+ *   values [B][o^2 + 2]  the float64 obs_raw, power, Strehl the gradient was taken at (the forward of this call; on the separable
+ *                        observation route the o^2 observation entries are NaN)
+ * Whole batch, stream-ordered, no host synchronisation, no atomics; an env's results depend on its own operands only, so a batch split
+ * over two handles reproduces the whole batch bit for bit.  Fast handles: a forward pupil pass of the call's own (the step's partial sums
+ * are not read), a float64 kernel per env for Z, the values and C, the pupil pass backwards on the matrix cores, a finish kernel; float64
+ * validation handles: plain float64 kernels.  Reads the state the last reset or step left and changes nothing a step reads or writes.
+ * AOG_ERR_STATE before tables, screens or aog_upload_gradient, while a pipelined or policy-attached step has an action pending, between
+ * two steps of a lookahead episode and on a poisoned handle.  On separable-observation handles (cfg.obs_separable = 1) g_obs must be NULL
+ * (AOG_ERR_UNSUPPORTED otherwise); power and Strehl gradients work there, because the wfs tables are the fiber modes. */
+int aog_output_gradient(aog_env* env, const double* g_obs_dev, const double* g_power_dev, const double* g_strehl_dev,
+                        const float* action_dev, double* grad_act_dev, double* grad_action_dev, double* values_dev, void* stream);
+
 /* ---- policy query of the rollout (Actor.forward + Actor.get_action, network.py:17-69; caller algorithm.py:216-296) ----
  * mean = W_o drop(relu(W_3 drop(relu(W_2 drop(relu(W_1 obs + b_1)) + b_2)) + b_3)) + b_o with nn.Dropout(dropout_p) ACTIVE
  * (the reference never leaves training mode while acting), action = mean + sqrt(cov_var) eps, eps ~ N(0, I),
