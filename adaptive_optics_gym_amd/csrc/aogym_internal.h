@@ -13,6 +13,13 @@ namespace aog {
 struct X8Table;
 }
 
+// Work buffers of a split-f16 Fraunhofer transform (K4, K11, the science camera) for a chunk of whole env tiles (focal.hip: mft_work_alloc)
+struct MftWork {
+  float* grid = nullptr;      // [chunk][Nyp][Nxp] reduced phases (revolutions), kShOutside outside the aperture and in the padding
+  _Float16* T16 = nullptr;    // [chunk][Nxp / 32][v blocks][2][4][64][8]: T' = m1' E, split, pass 2's operand order
+  int chunk = 0;              // envs per round of phase grid + pass 1 + pass 2
+};
+
 struct aog_env {
   aog_config cfg{};
   int device = 0;
@@ -98,20 +105,16 @@ struct aog_env {
   _Float16* focal_m1s = nullptr; // split-f16 operand tiles of the batched matrix-core path (aog_focal_images): m1 2^e1, [v block][k-step][4][64][8]
   _Float16* focal_m2s = nullptr; // m2 2^e2, [u block][x tile][2][4][64][8] (x in the order pass 1's accumulators hold it)
   float focal_unscale = 1.f;     // 2^-(e1 + e2)
-  int32_t* focal_ap_yx = nullptr;  // [n_ap] iy << 16 | ix of aperture pixel p
-  float* focal_grid = nullptr;   // [focal_chunk][Nyp][Nxp] reduced phases (revolutions), kShOutside outside the aperture
+  int32_t* focal_ap_yx = nullptr;  // [n_ap] iy << 16 | ix of aperture pixel p (K4, K11 and the science camera: whoever comes first uploads it)
+  MftWork focal_work;            // allocated by the first aog_focal_images; Nxp = N rounded up to 128, nfp / 32 v blocks
   _Float16* focal_act_ll = nullptr;  // [n_etiles][A_pad / 16][64][8] third f16 term of the actuators (K4 phases)
-  _Float16* focal_T16 = nullptr; // [focal_chunk][Nxp / 32][nfp / 32][2][4][64][8]: T' = m1' E, split, pass 2's operand order
-  int focal_chunk = 0;
   // separable observation route (cfg.obs_separable, aog_upload_obs_mft; K11, k_obs.h)
   bool obs_sep = false;
   bool obs_ready = false;        // aog_upload_obs_mft done
   _Float16* obs_m1s = nullptr;   // m1 2^e1, K4's m1s layout with one v block: [Nyp / 16][4][64][8]
   _Float16* obs_m2s = nullptr;   // m2 2^e2, K4's m2s layout with one u block: [Nxp / 32][2][4][64][8]
   float obs_unscale = 1.f;
-  int obs_chunk = 0;             // envs per round of the phase grid / pass 1 work buffers (whole env tiles)
-  float* obs_grid = nullptr;     // [obs_chunk][Nyp][Nxp] reduced phases, kShOutside outside the aperture (Nxp = N rounded up to 32)
-  _Float16* obs_T16 = nullptr;   // [obs_chunk][Nxp / 32][2][4][64][8]
+  MftWork obs_work;              // Nxp = N rounded up to 32, one v block
   _Float16* obs_act16 = nullptr; // actuators of the step being observed in the phase kernel's operand layouts (hi | lo, third term):
   _Float16* obs_act_ll = nullptr;//   their own buffers, so that nothing the fused kernel or a pipelined prologue reads is touched
   double* obs_pw = nullptr;      // [B][o^2] float64 powers of the last observation (the SSIM reward reads them)
@@ -147,14 +150,11 @@ struct aog_env {
   // is part of the aog_get_state blob.
   bool sci_ready = false;        // the camera is uploaded (aog_upload_tables clears it)
   int sci_w = 0, sci_n_ee = 0;   // window side, number of encircled-energy radii
-  int sci_chunk = 0;             // envs per round of the phase grid / T' work buffers (whole env tiles)
   double sci_ratio = 0, sci_peak = 0;   // lambda_wfs / lambda_sci; the unaberrated peak's share of the beam's power
   float sci_unscale = 1.f;       // 2^-(e1 + e2) of the operand tables
   _Float16* sci_m1s = nullptr;   // K4's m1s layout with ceil(w / 32) v blocks
   _Float16* sci_m2s = nullptr;   // K4's m2s layout with ceil(w / 32) u blocks
-  int32_t* sci_ap_yx = nullptr;  // [n_ap] iy << 16 | ix of aperture pixel p
-  float* sci_grid = nullptr;     // [sci_chunk][Nyp][Nxp] phases at the science wavelength (revolutions, reduced), kShOutside outside the aperture
-  _Float16* sci_T16 = nullptr;   // [sci_chunk][Nxp / 32][ceil(w / 32)][2][4][64][8]
+  MftWork sci_work;              // phases at the science wavelength; Nxp = N rounded up to 128, ceil(w / 32) v blocks
   _Float16* sci_act16 = nullptr; // the calls' own copy of the actuators in act16's layout, and their third f16 term
   _Float16* sci_act_ll = nullptr;
   double* sci_m1d = nullptr;     // float64 handles: m1 [w][N], m2 [N][w] complex, E [N][N], T [w][N], F [w][w] complex

@@ -48,6 +48,29 @@ float mft_operand_tables(const double* m1, const double* m2, int N, int nf, int 
   return (float)(1.0 / (s1 * s2));
 }
 
+int mft_work_alloc(aog_env* e, MftWork* w, size_t grid_env, size_t t16_env, size_t cap_envs, const char* chunk_env) {
+  w->chunk = (int)std::min<size_t>((size_t)e->n_etiles * 32, std::max<size_t>(32, cap_envs / 32 * 32));
+  if (const char* v = chunk_env ? getenv(chunk_env) : nullptr) w->chunk = std::max(32, std::min(w->chunk, atoi(v) / 32 * 32));
+  if (int rc = dev_alloc(e, &w->grid, (size_t)w->chunk * grid_env, false)) return rc;
+  if (int rc = dev_alloc(e, &w->T16, (size_t)w->chunk * t16_env, false)) return rc;
+  const size_t n_fill = (size_t)w->chunk * grid_env;
+  hipLaunchKernelGGL(aog::k_obs_fill, dim3((unsigned)std::min<size_t>((n_fill + 255) / 256, 4096)), dim3(256), 0, nullptr, w->grid, n_fill, aog::kShOutside);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return AOG_OK;
+}
+
+void launch_focal_field(aog_env* e, hipStream_t s, double* E, int env, double ratio, const uint8_t* mask) {
+  const bool fast = e->cfg.precision == AOG_PRECISION_FAST;
+  hipLaunchKernelGGL(aog::k_focal_field, dim3((e->n_ap + 255) / 256), dim3(256), 0, s, fast ? e->psi_tile : nullptr, fast ? nullptr : e->psi64,
+                     e->modes_f32, e->modes64, e->act_rev, e->act_dm, e->ap_index, reinterpret_cast<double2*>(E), env, e->n_ap, e->n_ptiles, e->A,
+                     e->A_pad, e->Bp, e->cfg.wavelength_wfs, ratio, mask);
+}
+void launch_cgemm64(hipStream_t s, const double* a, const double* b, double* out, float* out32, int R, int K, int Cn, const uint8_t* mask, int env) {
+  hipLaunchKernelGGL(aog::k_cgemm_small, dim3((R * Cn + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(a),
+                     reinterpret_cast<const double2*>(b), reinterpret_cast<double2*>(out), reinterpret_cast<float2*>(out32), R, K, Cn, mask, env);
+}
+
 // K11 geometry: x padded to whole 32-column tiles (one wave each), y to whole 16-row k-steps
 static int obs_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 32); }
 static int obs_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
@@ -58,17 +81,11 @@ int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const u
   if (e->cfg.precision == AOG_PRECISION_FP64) {
     // validation form: per env, E on the pupil grid (k_focal_field writes the aperture pixels; the rest of obs_E stays 0), then the two
     // products in float64
-    double2* E = reinterpret_cast<double2*>(e->obs_E);
-    double2* T = reinterpret_cast<double2*>(e->obs_T);
-    double2* F = reinterpret_cast<double2*>(e->obs_F);
+    const double2* F = reinterpret_cast<const double2*>(e->obs_F);
     for (int env = 0; env < e->B; ++env) {
-      hipLaunchKernelGGL(aog::k_focal_field, dim3((e->n_ap + 255) / 256), dim3(256), 0, s, (const float*)nullptr, e->psi64, (const float*)nullptr,
-                         e->modes64, (const float*)nullptr, e->act_dm, e->ap_index, E, env, e->n_ap, e->n_ptiles, e->A, e->A_pad, e->Bp,
-                         e->cfg.wavelength_wfs);
-      hipLaunchKernelGGL(aog::k_cgemm_small, dim3((o * N + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->obs_m1d), E, T,
-                         (float2*)nullptr, o, N, N);
-      hipLaunchKernelGGL(aog::k_cgemm_small, dim3((n_obs + 255) / 256), dim3(256), 0, s, T, reinterpret_cast<const double2*>(e->obs_m2d),
-                         F + (size_t)env * n_obs, (float2*)nullptr, o, N, o);
+      launch_focal_field(e, s, e->obs_E, env);
+      launch_cgemm64(s, e->obs_m1d, e->obs_E, e->obs_T, nullptr, o, N, N);
+      launch_cgemm64(s, e->obs_T, e->obs_m2d, e->obs_F + (size_t)env * n_obs * 2, nullptr, o, N, o);
     }
     const int n = e->B * n_obs;
     if (e->det_on)
@@ -82,18 +99,18 @@ int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const u
   if (int rc = load_actuators(e, s, {nullptr, e->obs_act16, e->obs_act_ll})) return rc;   // (own copies: act_rev / act16 are not touched)
   const int Nxp = obs_nxp(e), Nyp = obs_nyp(e), nxt = Nxp / 32;
   const size_t grid_env = (size_t)Nyp * Nxp;
-  for (int env0 = 0; env0 < e->B; env0 += e->obs_chunk) {
-    const int n = std::min(e->obs_chunk, e->B - env0), n_et = (n + 31) / 32;
-    aog_host::launch_phase_grid(e, s, e->obs_act16, e->obs_act_ll, e->obs_grid, grid_env, Nxp, env0 / 32, n_et);
-    hipLaunchKernelGGL(aog::k_obs_pass1, dim3((n * nxt + 3) / 4), dim3(256), 0, s, e->obs_grid, reinterpret_cast<const aog::f16x8*>(e->obs_m1s),
-                       reinterpret_cast<aog::f16x8*>(e->obs_T16), Nxp, Nyp, n);
+  for (int env0 = 0; env0 < e->B; env0 += e->obs_work.chunk) {
+    const int n = std::min(e->obs_work.chunk, e->B - env0), n_et = (n + 31) / 32;
+    aog_host::launch_phase_grid(e, s, e->obs_act16, e->obs_act_ll, e->obs_work.grid, grid_env, Nxp, env0 / 32, n_et);
+    hipLaunchKernelGGL(aog::k_obs_pass1, dim3((n * nxt + 3) / 4), dim3(256), 0, s, e->obs_work.grid, reinterpret_cast<const aog::f16x8*>(e->obs_m1s),
+                       reinterpret_cast<aog::f16x8*>(e->obs_work.T16), Nxp, Nyp, n);
     const size_t off = (size_t)env0 * n_obs;
     if (e->det_on)
-      hipLaunchKernelGGL(aog::k_obs_pass2_det, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_T16),
+      hipLaunchKernelGGL(aog::k_obs_pass2_det, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_work.T16),
                          reinterpret_cast<const aog::f16x8*>(e->obs_m2s), nxt, n, o, e->obs_unscale, e->obs_pw + off, obs_raw ? obs_raw + off : nullptr,
                          obs ? obs + off : nullptr, detector_args(e, mask), env0);
     else
-      hipLaunchKernelGGL(aog::k_obs_pass2, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_T16),
+      hipLaunchKernelGGL(aog::k_obs_pass2, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_work.T16),
                          reinterpret_cast<const aog::f16x8*>(e->obs_m2s), nxt, n, o, e->obs_unscale, e->obs_pw + off, obs_raw ? obs_raw + off : nullptr,
                          obs ? obs + off : nullptr);
   }
@@ -131,20 +148,11 @@ int aog_upload_obs_mft(aog_env* e, const aog_obs_mft* t) {
   if ((rc = upload(e, &e->obs_m2s, m2s)) != AOG_OK) return rc;
   // (shared with K4: where each packed aperture pixel lies on the pupil grid)
   if (!e->focal_ap_yx && (rc = upload(e, &e->focal_ap_yx, ap_yx_table(e))) != AOG_OK) return rc;
-  // work buffers for whole env tiles, at most ~512 MB: the phase grid (every pixel starts out as "outside the aperture": only aperture pixels
-  // are ever written) and T'
+  // work buffers for whole env tiles, at most ~512 MB together
   const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * 2 * 4 * 64 * 8;
-  const size_t cap = std::max<size_t>(32, (((size_t)512 << 20) / (grid_env * 4 + t16_env * 2)) / 32 * 32);
-  e->obs_chunk = (int)std::min<size_t>((size_t)e->n_etiles * 32, cap);
-  if ((rc = dev_alloc(e, &e->obs_grid, (size_t)e->obs_chunk * grid_env, false)) != AOG_OK) return rc;
-  if ((rc = dev_alloc(e, &e->obs_T16, (size_t)e->obs_chunk * t16_env, false)) != AOG_OK) return rc;
+  if ((rc = mft_work_alloc(e, &e->obs_work, grid_env, t16_env, ((size_t)512 << 20) / (grid_env * 4 + t16_env * 2), nullptr)) != AOG_OK) return rc;
   if ((rc = dev_alloc(e, &e->obs_act16, (size_t)e->n_etiles * 32 * e->A_pad * 2, true)) != AOG_OK) return rc;
   if ((rc = dev_alloc(e, &e->obs_act_ll, (size_t)e->n_etiles * 32 * e->A_pad, true)) != AOG_OK) return rc;
-  const size_t n_fill = (size_t)e->obs_chunk * grid_env;
-  hipLaunchKernelGGL(aog::k_obs_fill, dim3((unsigned)std::min<size_t>((n_fill + 255) / 256, 4096)), dim3(256), 0, nullptr, e->obs_grid, n_fill,
-                     aog::kShOutside);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
   e->obs_ready = true;
   return AOG_OK;
 }
@@ -161,13 +169,9 @@ int aog_focal_image(aog_env* e, int env_index, float* field_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int N = e->cfg.n_pupil, nf = e->n_focal;
   HIP_TRY(hipMemsetAsync(e->focal_E, 0, sizeof(double) * 2 * N * N, s));
-  hipLaunchKernelGGL(aog::k_focal_field, dim3((e->n_ap + 255) / 256), dim3(256), 0, s, fast ? e->psi_tile : nullptr,
-                     fast ? nullptr : e->psi64, e->modes_f32, e->modes64, e->act_rev, e->act_dm, e->ap_index,
-                     reinterpret_cast<double2*>(e->focal_E), env_index, e->n_ap, e->n_ptiles, e->A, e->A_pad, e->Bp, e->cfg.wavelength_wfs);
-  hipLaunchKernelGGL(aog::k_cgemm_small, dim3((nf * N + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->focal_m1),
-                     reinterpret_cast<const double2*>(e->focal_E), reinterpret_cast<double2*>(e->focal_T), (float2*)nullptr, nf, N, N);
-  hipLaunchKernelGGL(aog::k_cgemm_small, dim3((nf * nf + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->focal_T),
-                     reinterpret_cast<const double2*>(e->focal_m2), (double2*)nullptr, reinterpret_cast<float2*>(field_dev), nf, N, nf);
+  launch_focal_field(e, s, e->focal_E, env_index);
+  launch_cgemm64(s, e->focal_m1, e->focal_E, e->focal_T, nullptr, nf, N, N);
+  launch_cgemm64(s, e->focal_T, e->focal_m2, nullptr, field_dev, nf, N, nf);
   HIP_TRY(hipGetLastError());
   return AOG_OK;
 }
@@ -187,32 +191,24 @@ int aog_focal_images(aog_env* e, int first, int count, float* field_dev, void* s
   int rc;
   const int Nxp = round_up(N, 128), Nyp = round_up(N, 16), nfp = round_up(nf, 128);
   const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * (nfp / 32) * 2 * 4 * 64 * 8;
-  if (!e->focal_grid) {
-    // work buffers on first use, for a chunk of whole env tiles: the phase grid (every pixel starts out as "outside the aperture": only
-    // aperture pixels are ever written) and T' (split f16, pass 2's operand order)
-    const size_t cap = std::max<size_t>(32, (((size_t)256 << 20) / std::max(grid_env * 4, t16_env * 2)) / 32 * 32);
-    e->focal_chunk = (int)std::min<size_t>((size_t)e->n_etiles * 32, cap);
-    if (const char* v = getenv("AOG_FOCAL_CHUNK")) e->focal_chunk = std::max(32, std::min(e->focal_chunk, atoi(v) / 32 * 32));   // (tests: several chunks at small sizes)
-    if ((rc = dev_alloc(e, &e->focal_grid, (size_t)e->focal_chunk * grid_env, false)) != AOG_OK) return rc;
-    if ((rc = dev_alloc(e, &e->focal_T16, (size_t)e->focal_chunk * t16_env, false)) != AOG_OK) return rc;
+  if (!e->focal_work.grid) {   // work buffers on first use, at most ~256 MB each
+    if ((rc = mft_work_alloc(e, &e->focal_work, grid_env, t16_env, ((size_t)256 << 20) / std::max(grid_env * 4, t16_env * 2), "AOG_FOCAL_CHUNK")) != AOG_OK)
+      return rc;
     if ((rc = dev_alloc(e, &e->focal_act_ll, (size_t)e->n_etiles * 32 * e->A_pad, true)) != AOG_OK) return rc;
-    std::vector<float> fill(grid_env, aog::kShOutside);
-    for (int i = 0; i < e->focal_chunk; ++i)
-      HIP_TRY(hipMemcpy(e->focal_grid + (size_t)i * grid_env, fill.data(), sizeof(float) * grid_env, hipMemcpyHostToDevice));
   }
   // psi_tile is always current for quasi_static / semi_dynamic handles; dynamic ones refresh it here when the step kernel does not use it
   if ((rc = ensure_tiles(e, s)) != AOG_OK) return rc;
   if (e->cfg.atm_dynamic && !e->ring_direct && e->kernel != AOG_KERNEL_MFMA && (rc = pack_from_master(e, 0, e->B, s)) != AOG_OK) return rc;
   // u = psi + Mt a with the CURRENT mirror state of every env (act16 is rewritten from act_dm: the VALU step kernel does not keep it)
   if ((rc = load_actuators(e, s, {e->act_rev, e->act16, e->focal_act_ll})) != AOG_OK) return rc;
-  for (int env0 = first / 32 * 32; env0 < first + count; env0 += e->focal_chunk) {
-    const int env1 = std::min(first + count, env0 + e->focal_chunk);          // envs [lo, env1) of this chunk are asked for
+  for (int env0 = first / 32 * 32; env0 < first + count; env0 += e->focal_work.chunk) {
+    const int env1 = std::min(first + count, env0 + e->focal_work.chunk);          // envs [lo, env1) of this chunk are asked for
     const int lo = std::max(first, env0), n_et = (env1 - env0 + 31) / 32;
-    aog_host::launch_phase_grid(e, s, e->act16, e->focal_act_ll, e->focal_grid, grid_env, Nxp, env0 / 32, n_et);
+    aog_host::launch_phase_grid(e, s, e->act16, e->focal_act_ll, e->focal_work.grid, grid_env, Nxp, env0 / 32, n_et);
     const size_t skip = (size_t)(lo - env0);
-    hipLaunchKernelGGL(aog::k_focal_pass1, dim3(Nxp / 128, nfp / 128, env1 - lo), dim3(256), 0, s, e->focal_grid + skip * grid_env,
-                       reinterpret_cast<const aog::f16x8*>(e->focal_m1s), reinterpret_cast<aog::f16x8*>(e->focal_T16), Nxp, Nyp, nfp);
-    hipLaunchKernelGGL(aog::k_focal_pass2, dim3(nfp / 128, nfp / 128, env1 - lo), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->focal_T16),
+    hipLaunchKernelGGL(aog::k_focal_pass1, dim3(Nxp / 128, nfp / 128, env1 - lo), dim3(256), 0, s, e->focal_work.grid + skip * grid_env,
+                       reinterpret_cast<const aog::f16x8*>(e->focal_m1s), reinterpret_cast<aog::f16x8*>(e->focal_work.T16), Nxp, Nyp, nfp);
+    hipLaunchKernelGGL(aog::k_focal_pass2, dim3(nfp / 128, nfp / 128, env1 - lo), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->focal_work.T16),
                        reinterpret_cast<const aog::f16x8*>(e->focal_m2s), reinterpret_cast<float2*>(field_dev) + (size_t)(lo - first) * nf * nf, Nxp, nfp,
                        nf, e->focal_unscale);
     HIP_TRY(hipGetLastError());

@@ -145,6 +145,16 @@ aog::DetectorArgs detector_args(const aog_env* e, const uint8_t* mask);
 // m2s [nfp / 32][Nxp / 32][2] tiles), each matrix scaled by a power of two; returns the unscale factor 2^-(e1 + e2)
 float mft_operand_tables(const double* m1, const double* m2, int N, int nf, int nfp, int Nxp, int Nyp, std::vector<_Float16>& m1s,
                          std::vector<_Float16>& m2s);
+// focal.hip: the work buffers of such a transform.  The chunk is the handle's whole env tiles, capped at cap_envs (the caller's memory rule)
+// rounded down to whole tiles, at least one, and at the value of the environment variable chunk_env (nullable; tests: several chunks at small
+// sizes); the grid starts out as "outside the aperture" everywhere (only aperture pixels are ever written).  Blocking.
+int mft_work_alloc(aog_env* e, MftWork* w, size_t grid_env, size_t t16_env, size_t cap_envs, const char* chunk_env);
+// focal.hip: the steps of the float64 validation forms for one env (K4's single-env export, K11, the science camera).  launch_focal_field:
+// E = exp(2 pi i ratio u_p) on the aperture pixels of the [N][N] complex grid E (the rest is left as it is); launch_cgemm64: out [R][Cn]
+// (and / or its complex64 copy out32) = a [R][K] b [K][Cn], complex row-major.  mask (nullable): nothing happens for an env it leaves out.
+void launch_focal_field(aog_env* e, hipStream_t s, double* E, int env, double ratio = 1.0, const uint8_t* mask = nullptr);
+void launch_cgemm64(hipStream_t s, const double* a, const double* b, double* out, float* out32, int R, int K, int Cn, const uint8_t* mask = nullptr,
+                    int env = 0);
 // screens.hip: the factors through which Cn^2 enters (null outputs are skipped) — the handle-wide value's and every per-env value's
 void turbulence_factors(int N, int oversampling, double pixel_pitch, double cn_squared, float* amp_high, float* amp_low, float* crop_scale,
                         double* sqrt_cn_squared);

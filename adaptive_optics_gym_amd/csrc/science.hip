@@ -18,9 +18,8 @@ void release_science(aog_env* e) {
   e->sci_ready = false;
   dev_release(e, &e->sci_m1s);
   dev_release(e, &e->sci_m2s);
-  dev_release(e, &e->sci_ap_yx);
-  dev_release(e, &e->sci_grid);
-  dev_release(e, &e->sci_T16);
+  dev_release(e, &e->sci_work.grid);   // (focal_ap_yx stays: K4 and K11 use it too)
+  dev_release(e, &e->sci_work.T16);
   dev_release(e, &e->sci_act16);
   dev_release(e, &e->sci_act_ll);
   dev_release(e, &e->sci_m1d);
@@ -39,7 +38,7 @@ void launch_science_phase(aog_env* e, hipStream_t s, int etile0, int n_et, size_
   hipLaunchKernelGGL((aog::k_science_phase<A_PAD>), dim3((e->n_ptiles + 3) / 4, n_et), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
                      reinterpret_cast<const aog::f32x4*>(e->psi_tile) + (size_t)etile0 * e->n_ptiles * 4 * 64,
                      reinterpret_cast<const aog::f16x8*>(e->sci_act16) + (size_t)etile0 * NSTEP * 2 * 64,
-                     reinterpret_cast<const aog::f16x8*>(e->sci_act_ll) + (size_t)etile0 * NSTEP * 64, e->sci_ap_yx, e->sci_grid, grid_env, Nxp, e->n_ptiles,
+                     reinterpret_cast<const aog::f16x8*>(e->sci_act_ll) + (size_t)etile0 * NSTEP * 64, e->focal_ap_yx, e->sci_work.grid, grid_env, Nxp, e->n_ptiles,
                      n_et, e->n_ap, e->B - etile0 * 32, e->sci_ratio, mask ? mask + (size_t)etile0 * 32 : nullptr);
 }
 
@@ -94,20 +93,14 @@ int aog_upload_science(aog_env* e, const double* m1_host, const double* m2_host,
   e->sci_unscale = mft_operand_tables(m1_host, m2_host, N, w, nvb * 32, Nxp, Nyp, m1s, m2s);
   if ((rc = upload(e, &e->sci_m1s, m1s)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->sci_m2s, m2s)) != AOG_OK) return rc;
-  if ((rc = upload(e, &e->sci_ap_yx, ap_yx_table(e))) != AOG_OK) return rc;
-  // work buffers for a chunk of whole env tiles, as K4's: the phase grid (every pixel starts out as "outside the aperture": only aperture
-  // pixels are ever written) and T' (split f16, pass 2's operand order)
+  // (shared with K4 and K11; written again in place, since aog_upload_tables may have changed the aperture since it was made)
+  if ((rc = upload(e, &e->focal_ap_yx, ap_yx_table(e), true)) != AOG_OK) return rc;
+  // work buffers as K4's, at most ~256 MB each
   const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * nvb * 2 * 4 * 64 * 8;
-  const size_t cap = std::max<size_t>(32, (((size_t)256 << 20) / std::max(grid_env * 4, t16_env * 2)) / 32 * 32);
-  e->sci_chunk = (int)std::min<size_t>((size_t)e->n_etiles * 32, cap);
-  if (const char* v = getenv("AOG_SCIENCE_CHUNK")) e->sci_chunk = std::max(32, std::min(e->sci_chunk, atoi(v) / 32 * 32));   // (tests: several chunks at small sizes)
-  if ((rc = dev_alloc(e, &e->sci_grid, (size_t)e->sci_chunk * grid_env, false)) != AOG_OK) return rc;
-  if ((rc = dev_alloc(e, &e->sci_T16, (size_t)e->sci_chunk * t16_env, false)) != AOG_OK) return rc;
+  if ((rc = mft_work_alloc(e, &e->sci_work, grid_env, t16_env, ((size_t)256 << 20) / std::max(grid_env * 4, t16_env * 2), "AOG_SCIENCE_CHUNK")) != AOG_OK)
+    return rc;
   if ((rc = dev_alloc(e, &e->sci_act16, (size_t)e->n_etiles * 32 * e->A_pad * 2, true)) != AOG_OK) return rc;
   if ((rc = dev_alloc(e, &e->sci_act_ll, (size_t)e->n_etiles * 32 * e->A_pad, true)) != AOG_OK) return rc;
-  std::vector<float> fill(grid_env, aog::kShOutside);
-  for (int i = 0; i < e->sci_chunk; ++i)
-    HIP_TRY(hipMemcpy(e->sci_grid + (size_t)i * grid_env, fill.data(), sizeof(float) * grid_env, hipMemcpyHostToDevice));
   e->sci_ready = true;
   return AOG_OK;
 }
@@ -119,17 +112,12 @@ int aog_science_integrate(aog_env* e, const uint8_t* mask_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int N = e->cfg.n_pupil, w = e->sci_w, w2 = w * w;
   if (e->cfg.precision == AOG_PRECISION_FP64) {
-    double2* E = reinterpret_cast<double2*>(e->sci_E);
-    double2* T = reinterpret_cast<double2*>(e->sci_T);
-    double2* F = reinterpret_cast<double2*>(e->sci_F);
     for (int env = 0; env < e->B; ++env) {
-      hipLaunchKernelGGL(aog::k_science_field64, dim3((e->n_ap + 255) / 256), dim3(256), 0, s, e->psi64, e->modes64, e->act_dm, e->ap_index, E, env, e->n_ap,
-                         e->A, e->cfg.wavelength_wfs, e->sci_ratio, mask_dev);
-      hipLaunchKernelGGL(aog::k_science_cgemm64, dim3((w * N + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->sci_m1d), E, T, w, N, N, env,
-                         mask_dev);
-      hipLaunchKernelGGL(aog::k_science_cgemm64, dim3((w2 + 255) / 256), dim3(256), 0, s, T, reinterpret_cast<const double2*>(e->sci_m2d), F, w, N, w, env,
-                         mask_dev);
-      hipLaunchKernelGGL(aog::k_science_accum64, dim3((w2 + 255) / 256), dim3(256), 0, s, F, e->sci_exposure, e->sci_frames, w2, env, mask_dev);
+      launch_focal_field(e, s, e->sci_E, env, e->sci_ratio, mask_dev);
+      launch_cgemm64(s, e->sci_m1d, e->sci_E, e->sci_T, nullptr, w, N, N, mask_dev, env);
+      launch_cgemm64(s, e->sci_T, e->sci_m2d, e->sci_F, nullptr, w, N, w, mask_dev, env);
+      hipLaunchKernelGGL(aog::k_science_accum64, dim3((w2 + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->sci_F), e->sci_exposure,
+                         e->sci_frames, w2, env, mask_dev);
     }
     HIP_TRY(hipGetLastError());
     return AOG_OK;
@@ -145,17 +133,17 @@ int aog_science_integrate(aog_env* e, const uint8_t* mask_dev, void* stream) {
   int split = nvb <= 2;
   if (const char* v = getenv("AOG_SCIENCE_SPLIT")) split = split && atoi(v) != 0;
   const size_t grid_env = (size_t)Nyp * Nxp;
-  for (int env0 = 0; env0 < e->B; env0 += e->sci_chunk) {
-    const int n = std::min(e->sci_chunk, e->B - env0), n_et = (n + 31) / 32;
+  for (int env0 = 0; env0 < e->B; env0 += e->sci_work.chunk) {
+    const int n = std::min(e->sci_work.chunk, e->B - env0), n_et = (n + 31) / 32;
     switch (e->A_pad) {
       case 16: launch_science_phase<16>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
       case 32: launch_science_phase<32>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
       case 64: launch_science_phase<64>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
       default: launch_science_phase<128>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
     }
-    hipLaunchKernelGGL(aog::k_science_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->sci_grid, reinterpret_cast<const aog::f16x8*>(e->sci_m1s),
-                       reinterpret_cast<aog::f16x8*>(e->sci_T16), Nxp, Nyp, nvb, mask_dev, env0, split);
-    hipLaunchKernelGGL(aog::k_science_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->sci_T16),
+    hipLaunchKernelGGL(aog::k_science_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->sci_work.grid, reinterpret_cast<const aog::f16x8*>(e->sci_m1s),
+                       reinterpret_cast<aog::f16x8*>(e->sci_work.T16), Nxp, Nyp, nvb, mask_dev, env0, split);
+    hipLaunchKernelGGL(aog::k_science_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->sci_work.T16),
                        reinterpret_cast<const aog::f16x8*>(e->sci_m2s), e->sci_exposure, e->sci_frames, Nxp, nvb, w, e->sci_unscale, mask_dev, env0, split);
     HIP_TRY(hipGetLastError());
   }

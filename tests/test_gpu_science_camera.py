@@ -10,9 +10,10 @@ pytestmark = pytest.mark.gpu
 
 RTOL = 1e-5
 # (N, B, act_type, A, window, precision): partial env tiles and a ragged 240 inside 256; N no multiple of 32 or 128; a window that is no
-# multiple of 32; the float64 validation form
+# multiple of 32; the float64 validation form; five 32-column blocks (pass 1's second workgroup has three waves without a block, pass 2's
+# second workgroup row one block)
 SHAPES = [(64, 37, "num_actuators", 16, 240, "fast"), (240, 3, "num_actuators", 64, 64, "fast"), (128, 5, "zernike", 6, 48, "fast"),
-          (64, 2, "num_actuators", 16, 240, "fp64")]
+          (64, 2, "num_actuators", 16, 240, "fp64"), (64, 3, "num_actuators", 16, 160, "fast")]
 
 
 def _torch():
