@@ -1,13 +1,15 @@
 """MI355X-native implementation of the AOEnv.reset()/step() hot path of payamparvizi/adaptive_optics_gym.
 
     from adaptive_optics_gym_amd import BatchedAOEnv      # B envs on one GPU, torch tensors
+    from adaptive_optics_gym_amd import LayeredAOEnv      # the same over several frozen-flow wind layers per env
     from adaptive_optics_gym_amd.envs import AOEnv        # the reference's single-env gym API
     import gym_AO                                         # registers 'AO-v0' like the reference (needs gymnasium)
 """
 from .batched_env import BatchedAOEnv  # noqa: F401
+from .layered import LayeredAOEnv  # noqa: F401
 from .params import OpticalParams  # noqa: F401
 
-__all__ = ["BatchedAOEnv", "OpticalParams", "register"]
+__all__ = ["BatchedAOEnv", "LayeredAOEnv", "OpticalParams", "register"]
 
 
 def register():

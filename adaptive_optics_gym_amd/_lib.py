@@ -98,6 +98,8 @@ SYMBOLS = {
     "aog_set_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
     "aog_set_extrusion_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "aog_set_rng_seed": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "aog_evolve_atmosphere": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "aog_install_layer_sum": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
     "aog_get_screens_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aog_generate_screens": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "aog_set_turbulence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -664,6 +664,27 @@ class BatchedAOEnv:
         self._noise_dev = n   # kept alive until the step has run
         _lib.check(self.lib.aog_set_extrusion_noise(self._handle, C.c_void_p(n.data_ptr()), int(n.shape[1]), self._stream()))
 
+    def evolve_atmosphere(self):
+        """The atmosphere half of ``step`` and nothing else (``aog_evolve_atmosphere``; dynamic atmosphere only): the clock advances one
+        ``delta_t`` and the wind extrusion brings the screens there — after k calls ``get_screens()`` is bit for bit that of a same-seed twin
+        stepped k times.  Host-RNG mode draws the step's normals from the envs' numpy streams first, as ``step`` does.  The layers of a
+        ``layered.LayeredAOEnv`` advance through this."""
+        if self.atm_type != "dynamic":
+            raise RuntimeError("evolve_atmosphere: only a dynamic atmosphere evolves between steps")
+        if self._host_rng:
+            self._host_extrusion_noise()
+        _lib.check(self.lib.aog_evolve_atmosphere(self._handle, self._stream()))
+        self.timestep += 1
+        self.state_epoch += 1
+
+    def install_layer_sum(self, layers):
+        """Install the float64 sum of the current screens of ``layers`` (1 .. 8 dynamic ``BatchedAOEnv`` of this env's batch, pupil and
+        device) as this quasi-static env's screens (``aog_install_layer_sum``): aperture mean removed, stream-ordered, no host
+        synchronisation.  Actuators and counters stay; the next ``reset`` / ``step`` observes the new screens."""
+        handles = (C.c_void_p * len(layers))(*[lay._handle.value for lay in layers])
+        _lib.check(self.lib.aog_install_layer_sum(self._handle, handles, len(layers), self._stream()))
+        self.state_epoch += 1
+
     def lookahead(self, enable=True):
         """Dynamic atmosphere, device random stream: let every ``step`` launch the NEXT step's wind extrusion on a stream of the library's
         own, beside its epilogue and the caller's policy query (``aog_set_lookahead``).  Same results bit for bit; between two steps of an

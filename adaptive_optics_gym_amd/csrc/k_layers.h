@@ -1,0 +1,139 @@
+// Layered atmosphere: the float64 master screens of up to 8 dynamic handles, each read through its own ring origin, summed into the
+// screen layouts of a quasi-static front handle (aog_install_layer_sum).
+#pragma once
+#include "k_common.h"
+
+namespace aog {
+
+constexpr int kMaxLayers = 8;
+
+// the layers of one installation, by value in the kernel arguments (every index into these arrays is a compile-time constant)
+struct LayerSources {
+  const double* master[kMaxLayers];    // [B][N * N] toroidal float64 screens
+  const int32_t* origin[kMaxLayers];   // [B][2] (ox, oy): logical pixel (iy, ix) lives at ((iy + oy) mod N, (ix + ox) mod N)
+};
+
+// physical offset of logical pixel (iy, ix) in a ring with origin (ox, oy); each axis wraps on its own
+__device__ __forceinline__ int layer_phys(int iy, int ix, int oy, int ox, int N) {
+  int py = iy + oy, px = ix + ox;
+  if (py >= N) py -= N;
+  if (px >= N) px -= N;
+  return py * N + px;
+}
+
+// s = master_0 + master_1 + ... in layer order at one pixel of one env (the one definition of that order: the three kernels below and
+// the host restatement of the tests add the layers like this)
+template <int L>
+__device__ __forceinline__ double layer_sum_at(const LayerSources& src, size_t env_base, int iy, int ix, const int (&oy)[L], const int (&ox)[L], int N) {
+  double v[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) v[l] = src.master[l][env_base + layer_phys(iy, ix, oy[l], ox[l], N)];
+  double s = v[0];
+#pragma unroll
+  for (int l = 1; l < L; ++l) s += v[l];
+  return s;
+}
+
+// Pass 1: the aperture mean of this step's sum, one workgroup per env: per-thread strided sums, then block_reduce_sum (a fixed order, no
+// atomics: the mean of an env is the same bits in whatever batch the env sits).  Eight pixels x L layers are requested together.
+template <int L>
+__global__ __launch_bounds__(256) void k_layer_mean(LayerSources src, const int32_t* __restrict__ ap_index, double* __restrict__ mean, int N, int n_ap) {
+  __shared__ double sm[8];
+  const int env = blockIdx.x;
+  const size_t env_base = (size_t)env * N * N;
+  int oy[L], ox[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    ox[l] = src.origin[l][2 * env];
+    oy[l] = src.origin[l][2 * env + 1];
+  }
+  double acc = 0;
+  for (int p0 = threadIdx.x; p0 < n_ap; p0 += 8 * (int)blockDim.x) {
+    double s[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int p = p0 + u * (int)blockDim.x;
+      const int flat = ap_index[p < n_ap ? p : n_ap - 1], iy = flat / N, ix = flat - iy * N;
+      s[u] = layer_sum_at<L>(src, env_base, iy, ix, oy, ox, N);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (p0 + u * (int)blockDim.x < n_ap) acc += s[u];
+  }
+  const double total = block_reduce_sum(acc, sm);
+  if (threadIdx.x == 0) mean[env] = total / (double)n_ap;
+}
+
+// Pass 2, fast MFMA handles: k_repack_master's layout (k_extrude.h).  One workgroup = one 32-env tile x kLayerIters pairs of 32-pixel
+// tiles; a wave gathers 64 consecutive packed pixels of its 8 envs from every layer (coalesced along x, 8 L loads in flight), the block
+// transposes through a padded LDS tile and every wave writes whole 1-KiB rows of psi_tile.  Unlike the repack it subtracts the exact mean
+// of THIS sum (pass 1) and accumulates nothing.  The staging row is 68 floats: the transposed float4 reads of lanes e = 0 .. 15 start 4 e
+// banks apart (one 16-B slot each, 16 distinct slots of the 64-bank row), the row-wise 4-byte writes are consecutive.
+// Pad pixels (p >= n_ap) and pad envs (>= B, whole pad env tiles included) are written as exact zeros.
+constexpr int kLayerIters = 4;
+template <int L>
+__global__ __launch_bounds__(256) void k_layer_sum_tiles(LayerSources src, const int32_t* __restrict__ ap_index, const double* __restrict__ mean,
+                                                          float* __restrict__ psi_tile, int B, int N, int n_ap, int n_ptiles, double inv_two_pi_lambda) {
+  constexpr int LD = 68;
+  __shared__ float stage[32 * LD];
+  const int et = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int it = 0; it < kLayerIters; ++it) {
+    const int pt0 = (blockIdx.x * kLayerIters + it) * 2;
+    if (pt0 >= n_ptiles) break;   // uniform
+    const int p = pt0 * 32 + lane;
+    const bool valid_p = p < n_ap;
+    const int flat = ap_index[valid_p ? p : n_ap - 1];   // logical pupil coordinates of this lane's packed pixel (same for every env and layer)
+    const int iy = flat / N, ix = flat - iy * N;
+    double s[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {   // (the env, and with it the origins, is wave-uniform: scalar loads)
+      const int env = min(et * 32 + wave * 8 + q, B - 1);
+      int oy[L], ox[L];
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        ox[l] = src.origin[l][2 * env];
+        oy[l] = src.origin[l][2 * env + 1];
+      }
+      s[q] = layer_sum_at<L>(src, (size_t)env * N * N, iy, ix, oy, ox, N);
+    }
+    if (it) __syncthreads();   // the previous iteration's rows have left the staging tile
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int e = wave * 8 + q;
+      const bool ok = valid_p && et * 32 + e < B;
+      stage[e * LD + lane] = ok ? (float)((s[q] - mean[min(et * 32 + e, B - 1)]) * inv_two_pi_lambda) : 0.f;
+    }
+    __syncthreads();
+    // rows of psi_tile: [et][pt][g][lane = 32 h + e][4]; this pass owns pt0, pt0 + 1 (8 rows); wave w writes rows 2w, 2w+1
+    for (int rr = 0; rr < 2; ++rr) {
+      const int row = wave * 2 + rr, tl = row >> 2, g = row & 3;
+      const int pt = pt0 + tl;
+      if (pt >= n_ptiles) continue;
+      const int h = lane >> 5, e = lane & 31;
+      const float* from = stage + e * LD + tl * 32 + 8 * g + 4 * h;
+      reinterpret_cast<float4*>(psi_tile)[(((size_t)et * n_ptiles + pt) * 4 + g) * 64 + lane] = make_float4(from[0], from[1], from[2], from[3]);
+    }
+  }
+}
+
+// Pass 2, float64 validation handles: psi64 [B][n_ap] = s - mean in hcipy's units, one workgroup per env
+template <int L>
+__global__ __launch_bounds__(256) void k_layer_sum_f64(LayerSources src, const int32_t* __restrict__ ap_index, const double* __restrict__ mean,
+                                                        double* __restrict__ psi64, int N, int n_ap) {
+  const int env = blockIdx.x;
+  const size_t env_base = (size_t)env * N * N;
+  int oy[L], ox[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    ox[l] = src.origin[l][2 * env];
+    oy[l] = src.origin[l][2 * env + 1];
+  }
+  const double mu = mean[env];
+  for (int p = threadIdx.x; p < n_ap; p += blockDim.x) {
+    const int flat = ap_index[p], iy = flat / N, ix = flat - iy * N;
+    psi64[(size_t)env * n_ap + p] = layer_sum_at<L>(src, env_base, iy, ix, oy, ox, N) - mu;
+  }
+}
+
+}  // namespace aog

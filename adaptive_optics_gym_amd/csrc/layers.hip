@@ -1,0 +1,88 @@
+// Layered atmosphere (several frozen-flow layers per env): the atmosphere-only step of a layer handle and the installation of the layers'
+// sum in a quasi-static front handle.  No existing launch changes: a handle that never comes here runs what it ran before.
+#include "host_common.h"
+#include "k_layers.h"
+
+using namespace aog_host;
+
+namespace {
+
+// launches `KERNEL<L>` for the run-time layer count (1 .. kMaxLayers)
+#define AOG_LAYER_DISPATCH(L, KERNEL, grid, block, s, ...)                                               \
+  switch (L) {                                                                                           \
+    case 1: hipLaunchKernelGGL((aog::KERNEL<1>), grid, block, 0, s, __VA_ARGS__); break;                 \
+    case 2: hipLaunchKernelGGL((aog::KERNEL<2>), grid, block, 0, s, __VA_ARGS__); break;                 \
+    case 3: hipLaunchKernelGGL((aog::KERNEL<3>), grid, block, 0, s, __VA_ARGS__); break;                 \
+    case 4: hipLaunchKernelGGL((aog::KERNEL<4>), grid, block, 0, s, __VA_ARGS__); break;                 \
+    case 5: hipLaunchKernelGGL((aog::KERNEL<5>), grid, block, 0, s, __VA_ARGS__); break;                 \
+    case 6: hipLaunchKernelGGL((aog::KERNEL<6>), grid, block, 0, s, __VA_ARGS__); break;                 \
+    case 7: hipLaunchKernelGGL((aog::KERNEL<7>), grid, block, 0, s, __VA_ARGS__); break;                 \
+    default: hipLaunchKernelGGL((aog::KERNEL<8>), grid, block, 0, s, __VA_ARGS__); break;                \
+  }
+
+}  // namespace
+
+extern "C" {
+
+int aog_evolve_atmosphere(aog_env* e, void* stream) {
+  if (!e) return fail(AOG_ERR_INVALID, "aog_evolve_atmosphere: null handle");
+  if (!e->cfg.atm_dynamic) return fail(AOG_ERR_STATE, "aog_evolve_atmosphere: handle was not created with atm_dynamic = 1");
+  if (!e->layer_ready) return fail(AOG_ERR_STATE, "aog_evolve_atmosphere: aog_upload_layer / aog_set_wind not called");
+  if (!e->screens_ready) return fail(AOG_ERR_STATE, "aog_evolve_atmosphere before any screen was installed");
+  if (e->lookahead) return fail(AOG_ERR_STATE, "aog_evolve_atmosphere: not together with aog_set_lookahead (aog_step evolves such a handle ahead of time)");
+  if (int rc = refuse_pre_evolved(e, "aog_evolve_atmosphere")) return rc;
+  if (int rc = check_poisoned(e, "aog_evolve_atmosphere")) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  e->timestep += 1;   // as step_body: from here on a failure leaves counters and ring out of step with each other
+  e->steps_since_reset += 1;
+  e->sh_sums_ready = false;
+  const int rc = evolve_layer(e, static_cast<hipStream_t>(stream), e->timestep);
+  if (rc != AOG_OK) poison(e, 2);
+  return rc;
+}
+
+int aog_install_layer_sum(aog_env* dst, aog_env* const* layers, int n_layers, void* stream) {
+  if (!dst || !layers) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: null argument");
+  if (n_layers < 1 || n_layers > aog::kMaxLayers) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: %d layers (1 .. %d)", n_layers, aog::kMaxLayers);
+  if (dst->cfg.atm_dynamic) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: the front handle must not be atm_dynamic (its screens are installed, not evolved)");
+  if (!dst->tables_ready) return fail(AOG_ERR_INVALID, "aog_install_layer_sum before aog_upload_tables");
+  aog::LayerSources src{};
+  for (int l = 0; l < n_layers; ++l) {
+    const aog_env* y = layers[l];
+    if (!y) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: layer %d is null", l);
+    if (!y->cfg.atm_dynamic || !y->screens_ready || !y->psi_master)
+      return fail(AOG_ERR_INVALID, "aog_install_layer_sum: layer %d is not a dynamic handle with screens", l);
+    if (y->device != dst->device || y->cfg.n_pupil != dst->cfg.n_pupil || y->B != dst->B || y->cfg.env_id_base != dst->cfg.env_id_base)
+      return fail(AOG_ERR_INVALID, "aog_install_layer_sum: layer %d (device %d, N %d, B %d, env_id_base %d) does not match the front handle (device %d, N %d, B %d, "
+                  "env_id_base %d)", l, y->device, y->cfg.n_pupil, y->B, y->cfg.env_id_base, dst->device, dst->cfg.n_pupil, dst->B, dst->cfg.env_id_base);
+    if (y->pre_evolved) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: the atmosphere of layer %d already stands at the next step (aog_set_lookahead)", l);
+    if (int rc = check_poisoned(y, "aog_install_layer_sum (layer)")) return rc;
+    src.master[l] = y->psi_master;
+    src.origin[l] = y->origin;
+  }
+  const bool fast = dst->cfg.precision == AOG_PRECISION_FAST;
+  if (fast && dst->kernel != AOG_KERNEL_MFMA)
+    return fail(AOG_ERR_UNSUPPORTED, "aog_install_layer_sum: the front handle runs the VALU kernel (its screen layout is not written here; use kernel 'auto' or 'mfma')");
+  if (int rc = check_poisoned(dst, "aog_install_layer_sum")) return rc;
+  HIP_TRY(hipSetDevice(dst->device));
+  if (!dst->layer_mean)
+    if (int rc = dev_alloc(dst, &dst->layer_mean, (size_t)dst->B, false)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int N = dst->cfg.n_pupil;
+  // pass 1 reads every master once; pass 2 reads them again (8 n_ap bytes per env and layer, mostly from L2 / Infinity Cache)
+  AOG_LAYER_DISPATCH(n_layers, k_layer_mean, dim3(dst->B), dim3(256), s, src, dst->ap_index, dst->layer_mean, N, dst->n_ap);
+  if (fast) {
+    const dim3 grid(((dst->n_ptiles + 1) / 2 + aog::kLayerIters - 1) / aog::kLayerIters, dst->n_etiles);
+    AOG_LAYER_DISPATCH(n_layers, k_layer_sum_tiles, grid, dim3(256), s, src, dst->ap_index, dst->layer_mean, dst->psi_tile, dst->B, N, dst->n_ap, dst->n_ptiles,
+                       rev_per_metre(dst));
+  } else {
+    AOG_LAYER_DISPATCH(n_layers, k_layer_sum_f64, dim3(dst->B), dim3(256), s, src, dst->ap_index, dst->layer_mean, dst->psi64, N, dst->n_ap);
+  }
+  HIP_TRY(hipGetLastError());
+  dst->screens_ready = true;
+  dst->reset_obs_valid = false;   // new screens: the kept reset observation is of the old ones
+  dst->sh_sums_ready = false;
+  return AOG_OK;
+}
+
+}  // extern "C"

@@ -216,6 +216,28 @@ int aog_set_lookahead(aog_env* env, int enable);
 int aog_set_extrusion_noise(aog_env* env, const double* noise_dev, int max_ext, void* stream);
 int aog_set_rng_seed(aog_env* env, uint64_t seed);
 
+/* Layered atmosphere: several frozen-flow layers per env, each an ordinary dynamic handle, summed into a quasi-static FRONT handle that
+ * steps with the static fused kernel (on axis and conjugated to the pupil, L layers are exactly the sum of L independent screens).
+ *
+ * aog_evolve_atmosphere: the atmosphere half of aog_step and nothing else — timestep += 1, steps_since_reset += 1 and the wind extrusion
+ * to that timestep; normals handed over with aog_set_extrusion_noise are consumed exactly as a step consumes them.  After k calls the
+ * screens are bit for bit those of a twin that made k aog_step calls (the extrusion never reads the action).  AOG_ERR_STATE on a handle
+ * that is not atm_dynamic, has no layer or screens, has lookahead on, whose atmosphere already stands at the next step, that has an action
+ * pending or is poisoned; a failure after the counters moved poisons the handle as a failed aog_step does.
+ *
+ * aog_install_layer_sum: for env b and aperture pixel p, s = sum over l of master_l[b][(p + origin_l[b]) mod N] in float64 and in layer
+ * order (each layer read through its own ring origin, each axis wrapping on its own); the aperture mean of s, summed in a fixed order,
+ * is removed and float((s - mean) / (2 pi lambda_wfs)) is written into dst's fp32 screen tiles (MFMA accumulator order; pad pixels and
+ * pad envs exactly 0); float64 validation handles get s - mean in their float64 screens.  dst: not atm_dynamic, tables uploaded
+ * (AOG_ERR_INVALID otherwise; AOG_ERR_UNSUPPORTED on a handle that runs the VALU kernel); layers: 1 .. 8 dynamic handles with screens,
+ * on dst's device, with dst's n_pupil, num_envs and env_id_base (AOG_ERR_INVALID otherwise).  A screen installation: on success dst has
+ * screens and its kept reset observation is dropped; actuators, counters and the observation count stay, and an action a pipelined or
+ * policy-attached step left pending stays pending.  Stream-ordered on `stream` (which must be the stream the layers evolve on), no host
+ * synchronisation, no atomics; an env's output depends on that env's data only, so two handles of B / 2 reproduce one of B bit for bit.
+ * The [B] float64 work buffer of the means is allocated by dst's first call. */
+int aog_evolve_atmosphere(aog_env* env, void* stream);
+int aog_install_layer_sum(aog_env* dst, aog_env* const* layers, int n_layers, void* stream);
+
 /* layer._achromatic_screen of envs [first, first + count) as plain [count][N][N] float64 (hcipy's unit: phase * lambda).  Dynamic
  * handles return their float64 master screens; quasi_static / semi_dynamic handles return the stored screen exactly as the step
  * kernels read it: aperture pixels only (0 outside), aperture mean removed, fp32 values widened without rounding. */
