@@ -140,6 +140,7 @@ SYMBOLS = {
     "aog_science_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_upload_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_output_gradient": (C.c_int, [C.c_void_p] * 9),
+    "aog_upload_gradient_obs": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_selftest_poisson": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
     "aog_selftest_barrier_timeout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

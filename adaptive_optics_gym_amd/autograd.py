@@ -25,8 +25,8 @@ class _StepOutputs(torch.autograd.Function):
         if env.state_epoch != ctx.epoch:
             raise RuntimeError("step_outputs: the environment has been stepped, reset or restored since this step; its gradient is that of the "
                                "state the step left and can only be taken before the state moves on")
-        sep = env.obs_route == "separable"
-        grad = env.output_gradient(g_obs=None if sep else g_obs, g_power=g_power, g_strehl=g_strehl, wrt="action", action=ctx.action)
+        no_obs = env.obs_route == "separable" and not env.obs_gradient
+        grad = env.output_gradient(g_obs=None if no_obs else g_obs, g_power=g_power, g_strehl=g_strehl, wrt="action", action=ctx.action)
         return grad.to(ctx.in_dtype), None
 
 
@@ -43,6 +43,7 @@ def step_outputs(env, action):
     (AO_env.py:115-120), so nothing step t returns depends on an earlier action — the sum of per-step gradients is the exact policy
     gradient of an episode's return.  The Strehl reward (AO_env.py:476) is ``strehl`` itself; the SSIM reward (AO_env.py:487) is a function
     of ``obs_raw`` and ``power`` that callers write in torch and chain through these outputs.  On the separable observation route the
-    observation has no gradient (``obs_raw`` comes back as NaN and its cotangent is ignored); power and Strehl do."""
+    observation has its gradient on envs made with ``obs_gradient=True``; without it ``obs_raw`` comes back as NaN and its cotangent is
+    ignored, while power and Strehl keep theirs."""
     obs_raw, power, strehl = _StepOutputs.apply(action, env)
     return obs_raw, power, strehl

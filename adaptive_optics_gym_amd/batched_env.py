@@ -85,6 +85,11 @@ class BatchedAOEnv:
     exposure per env.  ``science_integrate`` adds the current frame (normalised so that its centre pixel is that step's Strehl ratio),
     ``science_clear`` empties, ``science_exposure`` reads the mean PSF, its Strehl and the encircled energy inside ``science_radii``
     (lambda_sci / D; default 1, 2, 3, 5, 8 clipped to the window).  Off the step path: a step computes the same bits with or without it.
+
+    ``obs_gradient`` (default False) switches the observation gradient of the separable observation route on (``obs_dim`` 6 .. 32; float64
+    envs from 8): ``output_gradient`` then takes ``g_obs`` and returns the float64 ``obs_raw`` in its values, and ``autograd.step_outputs``
+    differentiates through the observation.  ``ValueError`` on a table-route env, which has that gradient already; ``env.obs_gradient``
+    reads the flag.  Off the step path as well; its work buffers are allocated by the first ``output_gradient`` call.
     """
 
     def __init__(self, num_envs=1, device=None, atm_type="quasi_static", atm_vel=0, atm_fried=0.15,
@@ -93,7 +98,7 @@ class BatchedAOEnv:
                  num_pupil_pixels=240, seed=None, screen_source="device", screen_oversampling=16, screens=None,
                  precision="fast", kernel="auto", pixel_chunks=0, rng=None, verbose=True, params=None,
                  global_env_offset=0, total_envs=None, sh_fft_precision="single", screen_method="twoband", tables=None, extrusion="auto",
-                 obs_photons=None, obs_read_noise=0.0, obs_background=0.0, science_window=None, science_radii=None):
+                 obs_photons=None, obs_read_noise=0.0, obs_background=0.0, science_window=None, science_radii=None, obs_gradient=False):
         import torch
 
         self._handle = None   # (first: close() and accumulate_returns() read it on an env whose construction failed below)
@@ -180,6 +185,10 @@ class BatchedAOEnv:
         if precision not in _lib.AOG_PRECISION:
             raise ValueError("precision must be 'fast' or 'fp64'")
         self.obs_route = obs_route_for(precision, self.obs_dim)
+        if obs_gradient and self.obs_route != "separable":
+            raise ValueError("obs_gradient=True switches the observation gradient of the separable observation route on; this env takes the table "
+                             "route, where output_gradient has it already")
+        self._obs_gradient = bool(obs_gradient)
         # (tables=: the HostTables of another instance with the same params / act_type / act_dim / obs_dim / route, to skip the host precompute)
         if tables is not None and tables.obs_route != self.obs_route:
             raise ValueError(f"tables= were built for the {tables.obs_route!r} observation route; this handle takes {self.obs_route!r}")
@@ -266,7 +275,7 @@ class BatchedAOEnv:
         _lib.check(self.lib.aog_upload_tables(self._handle, C.byref(tabs)))
         self._wavefront_fit_uploaded = False   # (the library drops the wavefront fit with the old tables; wavefront_truth uploads it again)
         self._science_uploaded = False         # (and the science camera)
-        self._gradient_uploaded = False        # (and the gradient's operand tables; output_gradient uploads them again)
+        self._gradient_uploaded = False        # (and the gradient's operand tables, the observation's among them; output_gradient uploads them again)
         self._upload_keep = (keep, tabs)       # (output_gradient hands the same host tables to aog_upload_gradient)
         self._upload_science()
         if self.obs_route == "separable":
@@ -274,6 +283,7 @@ class BatchedAOEnv:
             om2 = np.ascontiguousarray(np.stack([t.obs_m2.real, t.obs_m2.imag], axis=-1), dtype=np.float64)
             mft = _lib.AogObsMft(self.obs_dim, 0, _dptr(om1, C.c_double), _dptr(om2, C.c_double))
             _lib.check(self.lib.aog_upload_obs_mft(self._handle, C.byref(mft)))
+            self._obs_mft_keep = (om1, om2, mft)   # (output_gradient hands the same host matrices to aog_upload_gradient_obs)
         _lib.check(self.lib.aog_set_screen_method(self._handle, _lib.AOG_SCREENS[self.screen_method]))
         self.info = _lib.AogInfo()
         _lib.check(self.lib.aog_get_info(self._handle, C.byref(self.info)))
@@ -1037,6 +1047,11 @@ class BatchedAOEnv:
 
     # ------------------------------------------------------------------------------------------------
     # analytic gradient
+    @property
+    def obs_gradient(self):
+        """True when ``output_gradient`` takes ``g_obs`` on this separable-route env (the ``obs_gradient=True`` keyword; read-only)."""
+        return self._obs_gradient
+
     def output_gradient(self, g_obs=None, g_power=None, g_strehl=None, wrt="actuators", action=None, with_values=False):
         """Vector-Jacobian product of the optical outputs at the state the last reset or step left (``aog_output_gradient``): the gradient of
         ``L = sum(g_obs * obs_raw) + sum(g_power * power) + sum(g_strehl * strehl)`` (cotangents: [B, o^2], [B], [B]; ``None`` = zero, at
@@ -1046,7 +1061,10 @@ class BatchedAOEnv:
         the action and a step sets the mirror absolutely, so this one-step gradient is the complete derivative of everything step t returns
         with respect to the policy.  The observation noise of ``set_detector`` does not enter: the gradient is of the clean outputs.
         ``with_values=True`` returns ``(grad, values)`` with ``values`` [B, o^2 + 2] the float64 obs_raw, power and Strehl the gradient was
-        taken at (NaN observation entries on the separable route, where ``g_obs`` is not available).  The Strehl reward is the Strehl itself
+        taken at.  On the separable observation route (``obs_dim`` 6 .. 32; float64 envs from 8) the observation is a matrix Fourier transform and
+        its gradient is opt-in: an env made with ``obs_gradient=True`` (``aog_upload_gradient_obs``) takes ``g_obs`` and returns the float64
+        ``obs_raw`` in ``values``; without it ``g_obs`` is refused there and the observation entries of ``values`` are NaN, while power and
+        Strehl have their gradients either way.  The Strehl reward is the Strehl itself
         (AO_env.py:476-487); callers chain the SSIM reward themselves.  Stream-ordered, no host synchronisation, nothing a step reads is
         changed; ``wrt=None`` (with ``with_values=True``) runs the forward half alone and returns ``(None, values)``; raises like
         ``wavefront_truth`` while an action is pending and between two steps of a lookahead episode."""
@@ -1057,6 +1075,8 @@ class BatchedAOEnv:
             raise ValueError("output_gradient: wrt=None asks for the values alone and needs with_values=True")
         if not self._gradient_uploaded:
             _lib.check(self.lib.aog_upload_gradient(self._handle, C.byref(self._upload_keep[1])))
+            if self._obs_gradient:
+                _lib.check(self.lib.aog_upload_gradient_obs(self._handle, C.byref(self._obs_mft_keep[2])))
             self._gradient_uploaded = True
         B, A, n = self.num_envs, self.num_modes, self.obs_dim ** 2
 

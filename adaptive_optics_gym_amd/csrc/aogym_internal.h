@@ -146,6 +146,24 @@ struct aog_env {
   double* grad_cbuf = nullptr;     // [B][tables][2] C / cscale
   double* grad_cscale = nullptr;   // [B]
   double* grad_trig = nullptr;     // float64 handles: [B][n_ap][4]
+  // observation gradient of the separable route (aog_upload_gradient_obs; gradient_obs.hip, k_gradient_obs.h).  Off the step path like the
+  // block above; the phase grid and T' of a call go through obs_work, which every step rewrites in full before it reads it.
+  bool gobs_ready = false;         // the transposed operand tables are uploaded (aog_upload_tables clears it)
+  int gobs_chunk = 0;              // envs per round: obs_work.chunk, or less through AOG_GRAD_OBS_CHUNK (whole env tiles)
+  double gobs_unscale = 1.0;       // 2^-(e1 + e2) of the two tables below
+  _Float16* gobs_m1t = nullptr;    // m1' 2^e1 as A operands: [ceil(Nyp / 32)][step 2][4][64][8], row y, K = v in the order accumulators hold it
+  _Float16* gobs_m2t = nullptr;    // m2' 2^e2 as B operands: [Nxp / 32][step 2][4][64][8], column x, K = u
+  _Float16* gobs_act_ll = nullptr; // the call's own third f16 term of the actuators (grad_act16 holds the first two)
+  _Float16* gobs_wop = nullptr;    // [chunk][step 2][4][64][8] W / wscale of every env as A operands (row v, K = u)
+  double* gobs_wscale = nullptr;   // [B] the power of two W was divided by
+  double* gobs_slabs = nullptr;    // [pixel chunk][A rows][Bp] partial sums of the modes contraction of the observation's q
+  double* gobs_m1td = nullptr;     // float64 handles: m1' [N][o], m2' [o][N] complex, F / W [o^2], P [N][o], H [N][N] complex, q [n_ap]
+  double* gobs_m2td = nullptr;
+  double* gobs_F = nullptr;
+  double* gobs_W = nullptr;
+  double* gobs_P = nullptr;
+  double* gobs_H = nullptr;
+  double* gobs_q = nullptr;
   // science camera (aog_upload_science, aog_science_*; science.hip).  Nothing here is read or written by a reset or step, and none of it
   // is part of the aog_get_state blob.
   bool sci_ready = false;        // the camera is uploaded (aog_upload_tables clears it)

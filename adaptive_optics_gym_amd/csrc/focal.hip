@@ -75,6 +75,12 @@ void launch_cgemm64(hipStream_t s, const double* a, const double* b, double* out
 static int obs_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 32); }
 static int obs_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
 
+void launch_obs_pass1(aog_env* e, hipStream_t s, int n) {
+  const int Nxp = obs_nxp(e), Nyp = obs_nyp(e);
+  hipLaunchKernelGGL(aog::k_obs_pass1, dim3((n * (Nxp / 32) + 3) / 4), dim3(256), 0, s, e->obs_work.grid, reinterpret_cast<const aog::f16x8*>(e->obs_m1s),
+                     reinterpret_cast<aog::f16x8*>(e->obs_work.T16), Nxp, Nyp, n);
+}
+
 int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const uint8_t* mask) {
   if (!e->obs_sep) return AOG_OK;
   const int N = e->cfg.n_pupil, o = e->cfg.obs_dim, n_obs = e->n_obs;
@@ -102,8 +108,7 @@ int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const u
   for (int env0 = 0; env0 < e->B; env0 += e->obs_work.chunk) {
     const int n = std::min(e->obs_work.chunk, e->B - env0), n_et = (n + 31) / 32;
     aog_host::launch_phase_grid(e, s, e->obs_act16, e->obs_act_ll, e->obs_work.grid, grid_env, Nxp, env0 / 32, n_et);
-    hipLaunchKernelGGL(aog::k_obs_pass1, dim3((n * nxt + 3) / 4), dim3(256), 0, s, e->obs_work.grid, reinterpret_cast<const aog::f16x8*>(e->obs_m1s),
-                       reinterpret_cast<aog::f16x8*>(e->obs_work.T16), Nxp, Nyp, n);
+    launch_obs_pass1(e, s, n);
     const size_t off = (size_t)env0 * n_obs;
     if (e->det_on)
       hipLaunchKernelGGL(aog::k_obs_pass2_det, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_work.T16),

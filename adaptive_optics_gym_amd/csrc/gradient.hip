@@ -119,9 +119,11 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
     return fail(AOG_ERR_STATE, "aog_output_gradient: the gradient's tables were not uploaded (aog_upload_gradient, again after aog_upload_tables)");
   if (int rc = check_poisoned(e, "aog_output_gradient")) return rc;
   if (int rc = refuse_pre_evolved(e, "aog_output_gradient")) return rc;
-  if (g_obs_dev && e->obs_sep)
+  if (g_obs_dev && e->obs_sep && !e->gobs_ready)
     return fail(AOG_ERR_UNSUPPORTED, "aog_output_gradient: g_obs on the separable observation route (cfg.obs_separable = 1: the observation is a "
                 "matrix Fourier transform, not a row of wfs_coef); the power and Strehl gradients are available");
+  // the observation's part on the separable route (aog_upload_gradient_obs): its values and, with g_obs, its q (gradient_obs.hip)
+  const bool obs_part = e->obs_sep && e->gobs_ready && (g_obs_dev || values_dev);
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool fast = e->cfg.precision == AOG_PRECISION_FAST;
@@ -138,7 +140,7 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
     // psi_tile holding the screens the last step read, refreshed the way aog_wavefront_truth does it (psi_tile alone: nothing a step reads is
     // touched); the actuator operands are the call's own copy
     if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
-    if ((rc = load_actuators(e, s, {nullptr, e->grad_act16, nullptr})) != AOG_OK) return rc;
+    if ((rc = load_actuators(e, s, {nullptr, e->grad_act16, obs_part ? e->gobs_act_ll : nullptr})) != AOG_OK) return rc;
     switch (e->A_pad) {
       case 16: launch_forward<16>(e, s, n_chunks, ratio); break;
       case 32: launch_forward<32>(e, s, n_chunks, ratio); break;
@@ -176,6 +178,7 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
   c.csci = fast ? e->grad_csci : nullptr;
   hipLaunchKernelGGL(aog::k_grad_coef, dim3(e->B), dim3(256), 0, s, c);
   HIP_TRY(hipGetLastError());
+  if (obs_part && (rc = grad_obs_part(e, s, g_obs_dev, values_dev)) != AOG_OK) return rc;   // (behind k_grad_coef: the observation slots of values)
   if (!grad_act_dev && !grad_action_dev) return AOG_OK;   // (the values alone)
   if (fast) {
     switch (e->A_pad) {
@@ -203,6 +206,15 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
   f.factor = 4.0 * M_PI / e->cfg.wavelength_wfs;
   if (fast) f.factor /= (double)aog::kModeScale * (double)e->grad_tscale * (double)aog::kGradQScale;
   f.target = e->cfg.surface_rms_target;
+  if (obs_part && g_obs_dev) {
+    // the slabs of the observation's q: wscale and the operand scales of m1' m2' (fast); the 2 of q = 2 Re(..) is applied here
+    f.slabs2 = e->gobs_slabs;
+    f.cscale2 = fast ? e->gobs_wscale : nullptr;
+    f.n_chunks2 = n_chunks;
+    f.rows2 = brows;
+    f.factor2 = 4.0 * M_PI / e->cfg.wavelength_wfs;
+    if (fast) f.factor2 *= 2.0 * e->gobs_unscale / (double)aog::kModeScale;
+  }
   hipLaunchKernelGGL(aog::k_grad_finish, dim3(e->B), dim3(256), 0, s, f);
   HIP_TRY(hipGetLastError());
   return AOG_OK;

@@ -139,6 +139,8 @@ void launch_phase_field(aog_env* e, hipStream_t s, const _Float16* act16, float*
 // focal.hip (K11): the observation of the separable route for every env — |F|^2 into obs_pw and the caller's obs_raw / obs (nullable)
 // (mask: the masked reset's; handles with a detector draw for the masked envs only)
 int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const uint8_t* mask = nullptr);
+// focal.hip (K11): pass 1 alone for the first n envs of obs_work — grid -> T16 (the observation gradient runs its own pass 2 behind it)
+void launch_obs_pass1(aog_env* e, hipStream_t s, int n);
 // the detector's kernel arguments for the observation this call writes (e->det_on): frame = e->obs_frame
 aog::DetectorArgs detector_args(const aog_env* e, const uint8_t* mask);
 // split-f16 operand tables of a Fraunhofer matrix Fourier transform m1 [nf][N] . E . m2 [N][nf] (K4's layouts: m1s [nfp / 32][Nyp / 16] tiles,
@@ -155,6 +157,10 @@ int mft_work_alloc(aog_env* e, MftWork* w, size_t grid_env, size_t t16_env, size
 void launch_focal_field(aog_env* e, hipStream_t s, double* E, int env, double ratio = 1.0, const uint8_t* mask = nullptr);
 void launch_cgemm64(hipStream_t s, const double* a, const double* b, double* out, float* out32, int R, int K, int Cn, const uint8_t* mask = nullptr,
                     int env = 0);
+// gradient_obs.hip (K14 on the separable route, after aog_upload_gradient_obs): the observation's part of one aog_output_gradient call, behind
+// its k_grad_coef — the float64 obs_raw into the observation slots of `values` (nullable) and, with g_obs (nullable), the modes contraction of
+// the observation's q into e->gobs_slabs for k_grad_finish.  The actuator operands (grad_act16, gobs_act_ll) are the caller's.
+int grad_obs_part(aog_env* e, hipStream_t s, const double* g_obs_dev, double* values_dev);
 // screens.hip: the factors through which Cn^2 enters (null outputs are skipped) — the handle-wide value's and every per-env value's
 void turbulence_factors(int N, int oversampling, double pixel_pitch, double cn_squared, float* amp_high, float* amp_low, float* crop_scale,
                         double* sqrt_cn_squared);

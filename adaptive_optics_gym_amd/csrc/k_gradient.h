@@ -20,16 +20,15 @@
 //       zero C: both contribute exact zeros.  Slab [chunk][A_PAD][Bp].  No atomics, no B x n_ap intermediate.
 //   k_grad_ref_forward / k_grad_ref_backward   float64 validation handles, one workgroup per env, in the style of k_wavefront_ref.
 //   k_grad_finish           one workgroup per env: slabs in chunk order, the scales, grad_act, and the action chain for grad_action.
+//       On the separable observation route with aog_upload_gradient_obs a second slab set (k_gradient_obs.h: the observation's q contracted
+//       with the modes) is added with scales of its own; without it the sum is the first set's alone, bit for bit.
 #pragma once
-#include "k_common.h"
+#include "k_gradient_common.h"
 
 namespace aog {
 
-constexpr int kGradChunkTiles = 64;     // pixel tiles per workgroup (16 per wave)
 constexpr int kGradFwdRows = 66;        // rows of a forward slab of the fast kernels
 constexpr float kGradQScale = 0.0625f;  // q is scaled by 2^-4 x the tables' scale before it is split (|q| <= 2 (28 + 2) x 256: inside the f16 range)
-__host__ __device__ inline int grad_chunks(int n_ptiles) { return (n_ptiles + kGradChunkTiles - 1) / kGradChunkTiles; }
-__host__ __device__ constexpr int grad_blocks(int A_pad) { return (A_pad + 31) / 32; }
 
 // u of this lane's 16 pixels of tile t (register 4 g + r: pixel 8 g + 4 h + r), then cos / sin of 2 pi u and of 2 pi ratio u.  Pad pixels of
 // the last tile read as cos = sin = 0 in both arms.
@@ -61,17 +60,6 @@ __device__ __forceinline__ void grad_tile_trig(const f16x8* __restrict__ ms, con
       cs[j] = real ? __builtin_amdgcn_cosf(ur) : 0.f;
       ss[j] = real ? __builtin_amdgcn_sinf(ur) : 0.f;
     }
-}
-
-// 16 accumulator-order values -> the B operand of a contraction over the tile's pixels (two K steps), hi + lo
-__device__ __forceinline__ void grad_split16(const float (&v)[16], float scale, f16x8 (&hi)[2], f16x8 (&lo)[2]) {
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const float sc = v[j] * scale;
-    const _Float16 h = (_Float16)sc;
-    hi[j >> 3][j & 7] = h;
-    lo[j >> 3][j & 7] = (_Float16)(sc - (float)h);
-  }
 }
 
 #define AOG_GRAD_TILE_LOOP_HEAD                                                                        \
@@ -439,6 +427,11 @@ struct GradFinishArgs {
   int n_chunks, rows, Bp, A;
   double factor;           // 4 pi / lambda_wfs over the operand scales
   double target;           // cfg.surface_rms_target
+  // the observation's part on the separable route (k_gradient_obs.h; all null / 0 otherwise: the sums above are then the whole gradient)
+  const double* slabs2;    // [n_chunks2][rows2][Bp]  nullable
+  const double* cscale2;   // [B]  nullable (1)
+  int n_chunks2, rows2;
+  double factor2;
 };
 
 __global__ __launch_bounds__(256) void k_grad_finish(GradFinishArgs p) {
@@ -452,6 +445,12 @@ __global__ __launch_bounds__(256) void k_grad_finish(GradFinishArgs p) {
     double T = 0;
     for (int c = 0; c < p.n_chunks; ++c) T += p.slabs[c * slab + (size_t)k * p.Bp + env];
     g = (T * p.factor) * p.cscale[env];
+    if (p.slabs2) {
+      const size_t slab2 = (size_t)p.rows2 * p.Bp;
+      double T2 = 0;
+      for (int c = 0; c < p.n_chunks2; ++c) T2 += p.slabs2[c * slab2 + (size_t)k * p.Bp + env];
+      g += (T2 * p.factor2) * (p.cscale2 ? p.cscale2[env] : 1.0);
+    }
     if (p.grad_act) p.grad_act[(size_t)env * p.A + k] = g;
   }
   if (!p.grad_action) return;

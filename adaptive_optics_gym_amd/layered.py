@@ -70,7 +70,8 @@ class LayeredAOEnv(BatchedAOEnv):
     the front's (the atmosphere is observed as it stands, like the reference's dynamic reset); ``step`` / ``step_with_policy`` first evolve
     every layer and install their sum, then step the front.  ``get_screens()`` is the float64 sum, ``layer_screens(l)`` one layer;
     ``velocity_vectors`` is [L, B, 2]; ``set_turbulence`` splits the new r0 by the same fractions; ``get_state`` / ``set_state`` carry the
-    front's state and every layer's.  ``lookahead`` is not available (returns False) and ``set_screens`` raises."""
+    front's state and every layer's.  ``lookahead`` is not available (returns False) and ``set_screens`` raises.  ``obs_gradient`` goes to the
+    front, an ordinary static handle: ``output_gradient`` differentiates the observation of the installed sum."""
 
     def __init__(self, num_envs=1, device=None, atm_layers=None, atm_fried=0.15, act_type="num_actuators", act_dim=64, obs_dim=2,
                  rew_type="strehl_ratio", rew_threshold=None, timesteps_per_episode=20, flat_mirror_start_per_episode=True, SH_operation=False, *,

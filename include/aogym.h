@@ -510,9 +510,32 @@ int aog_upload_gradient(aog_env* env, const aog_tables* tables);
  * validation handles: plain float64 kernels.  Reads the state the last reset or step left and changes nothing a step reads or writes.
  * AOG_ERR_STATE before tables, screens or aog_upload_gradient, while a pipelined or policy-attached step has an action pending, between
  * two steps of a lookahead episode and on a poisoned handle.  On separable-observation handles (cfg.obs_separable = 1) g_obs must be NULL
- * (AOG_ERR_UNSUPPORTED otherwise); power and Strehl gradients work there, because the wfs tables are the fiber modes. */
+ * (AOG_ERR_UNSUPPORTED otherwise) unless aog_upload_gradient_obs was called; power and Strehl gradients work there either way, because the
+ * wfs tables are the fiber modes. */
 int aog_output_gradient(aog_env* env, const double* g_obs_dev, const double* g_power_dev, const double* g_strehl_dev,
                         const float* action_dev, double* grad_act_dev, double* grad_action_dev, double* values_dev, void* stream);
+
+/* The observation gradient on the separable route (obs_dim 6 .. 32 of fast handles, >= 8 of float64 handles; additive in ABI 22).  There the
+ * observation is no row of wfs_coef but the matrix Fourier transform of aog_obs_mft, and its part of the gradient is, per env on the pupil grid,
+ *     E = A o exp(i phi)            phi the sensing-arm phase above, A the aperture
+ *     F = m1 E m2                   o x o; obs_raw[v * o + u] = |F_vu|^2, row v * o + u as in aog_obs_mft
+ *     W = gbar o conj(F)            gbar = g_obs
+ *     H = m1' W m2'                 N x N, ' the plain transpose
+ *     q_yx = 2 Re(i E_yx H_yx)      on aperture pixels
+ * and this q adds to the q_p of power and Strehl before dL/da_k = (4 pi / lambda_wfs) sum_p M_pk q_p; the action chain is unchanged and the
+ * detector does not enter.  Opt-in per handle: after aog_upload_tables, aog_upload_obs_mft and aog_upload_gradient, on handles with
+ * cfg.obs_separable = 1 only (AOG_ERR_STATE otherwise), with the same HOST matrices as aog_upload_obs_mft (the library keeps no host copy); a
+ * later aog_upload_tables clears it.  With it aog_output_gradient accepts g_obs [B][o^2] and writes the float64 obs_raw into values[:, :o^2]
+ * (the forward of the call: K11's pass 1, then float64 sums over the k-steps of pass 2).  With g_obs == NULL grad_act / grad_action and
+ * values[:, o^2:] are bit for bit those of a handle without the upload; a handle without it keeps the refusal, the NaN and its launches.
+ * Fast handles: W is scaled by a power of two per env and split into f16 operands, H = m1' (W m2') runs on the matrix cores one wave per
+ * (env, 32 x 32 tile of the grid) and leaves q in place of the phase, a second kernel gathers q per (env tile, pixel tile) and contracts it
+ * with the modes into partial sums that the finish kernel adds in a fixed order: no atomics, an env's result depends on its own operands
+ * only, and neither a split of the batch over handles nor the round size changes a bit.  The phase grid and T' go through the step's own
+ * observation work buffers (every step rewrites them in full before it reads them); the other buffers are allocated here or by the first
+ * call and counted in device_bytes.  Rounds of whole env tiles: as many envs as those work buffers hold, or fewer with the environment
+ * variable AOG_GRAD_OBS_CHUNK (read here).  Float64 handles: one env at a time, plain float64 products. */
+int aog_upload_gradient_obs(aog_env* env, const aog_obs_mft* mft);
 
 /* ---- policy query of the rollout (Actor.forward + Actor.get_action, network.py:17-69; caller algorithm.py:216-296) ----
  * mean = W_o drop(relu(W_3 drop(relu(W_2 drop(relu(W_1 obs + b_1)) + b_2)) + b_3)) + b_o with nn.Dropout(dropout_p) ACTIVE
