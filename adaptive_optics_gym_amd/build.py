@@ -31,7 +31,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-fno-s
 SHARED = ("aogym_internal.h", "host_common.h", "k_common.h", "fused_layout.h")
 DETECTOR = ("k_poisson.h", "k_detector.h")
 FAMILY = {"aogym": ("k_pack.h", "k_step.h", "k_actor.h", "k_step_act.h") + DETECTOR, "atmosphere": ("k_pack.h", "k_extrude.h", "k_extrude_i8.h"), "screens": ("k_fft.h", "k_screens.h"),
-          "shack": ("k_fft.h", "k_shack.h", "k_poisson.h"), "focal": ("k_focal.h", "k_mft_mma.h", "k_obs.h") + DETECTOR, "actor": ("k_actor.h",), "wavefront": ("k_wavefront.h",), "science": ("k_science.h", "k_mft_mma.h"), "gradient": ("k_gradient.h", "k_gradient_common.h"), "gradient_obs": ("k_gradient_obs.h", "k_gradient_common.h", "k_mft_mma.h"), "layers": ("k_layers.h",), "fused_inst": ("k_fused.h",)}
+          "shack": ("k_fft.h", "k_shack.h", "k_poisson.h"), "focal": ("k_focal.h", "k_mft_mma.h", "k_obs.h") + DETECTOR, "actor": ("k_actor.h",), "wavefront": ("k_wavefront.h", "k_pupil_tile.h"), "science": ("k_science.h", "k_mft_mma.h"), "gradient": ("k_gradient.h", "k_pupil_tile.h"), "gradient_obs": ("k_gradient_obs.h", "k_pupil_tile.h", "k_mft_mma.h"), "layers": ("k_layers.h",), "fused_inst": ("k_fused.h",)}
 
 
 def hipcc_path() -> str:

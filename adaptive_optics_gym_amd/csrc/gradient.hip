@@ -5,25 +5,6 @@
 
 using namespace aog_host;
 
-namespace {
-
-template <int A_PAD>
-void launch_forward(aog_env* e, hipStream_t s, int n_chunks, double ratio) {
-  hipLaunchKernelGGL((aog::k_grad_forward<A_PAD>), dim3(n_chunks, e->n_etiles), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
-                     reinterpret_cast<const aog::f16x8*>(e->grad_ftab16), e->grad_stab, reinterpret_cast<const aog::f32x4*>(e->psi_tile),
-                     reinterpret_cast<const aog::f16x8*>(e->grad_act16), e->grad_fslabs, e->n_ptiles, e->n_ap, e->Bp, ratio);
-}
-template <int A_PAD>
-void launch_backward(aog_env* e, hipStream_t s, int n_chunks, double ratio) {
-  hipLaunchKernelGGL((aog::k_grad_backward<A_PAD>), dim3(n_chunks, e->n_etiles), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
-                     reinterpret_cast<const aog::f16x8*>(e->grad_ttab16), e->grad_stab, reinterpret_cast<const aog::f16x8*>(e->grad_mtab16),
-                     reinterpret_cast<const aog::f32x4*>(e->psi_tile), reinterpret_cast<const aog::f16x8*>(e->grad_act16),
-                     reinterpret_cast<const aog::f16x8*>(e->grad_cop16), e->grad_csci, e->grad_bslabs, e->n_ptiles, e->n_ap, e->Bp, ratio,
-                     e->grad_tscale);
-}
-
-}  // namespace
-
 extern "C" {
 
 int aog_upload_gradient(aog_env* e, const aog_tables* t) {
@@ -49,26 +30,16 @@ int aog_upload_gradient(aog_env* e, const aog_tables* t) {
   const float tscale = std::ldexp(1.f, 7 - std::ilogb(big));
   e->grad_tscale = tscale;
   int rc;
-  // forward: A operand of step s, lane (kg, m = table), element el <-> pixel (el & 3) + 16 s + 8 (el >> 2) + 4 kg of the tile (tab16's order)
-  // backward: A operand of step s, lane (kg, i = pixel of the tile), element el <-> table 16 s + 8 kg + el: the transpose of that role
-  std::vector<_Float16> f16((size_t)np * 2 * 2 * 64 * 8, (_Float16)0.f), t16(f16.size(), (_Float16)0.f);
+  // forward: the wfs tables as one block of rows (pack_tab16_rows); the science table in accumulator order: register j of half-wave h
+  // holds pixel pupil_acc_row(j, h) of the tile
+  const std::vector<_Float16> f16 = pack_tab16_rows(np, n_ap, TW, 1, tscale, [&](int p, int m) { return t->wfs_tables[(size_t)m * n_ap + p]; });
   std::vector<double> st((size_t)np * 32, 0.0);
   for (int pt = 0; pt < np; ++pt)
-    for (int sidx = 0; sidx < 2; ++sidx)
-      for (int kg = 0; kg < 2; ++kg)
-        for (int el = 0; el < 8; ++el) {
-          const int p = pt * 32 + (el & 3) + 16 * sidx + 8 * (el >> 2) + 4 * kg;
-          if (p >= n_ap) continue;
-          for (int m = 0; m < TW; ++m) {
-            _Float16 hi, lo;
-            aog::split_f16((float)t->wfs_tables[(size_t)m * n_ap + p] * tscale, hi, lo);
-            const size_t base = ((((size_t)pt * 2 + sidx) * 2) * 64 + (kg * 32 + m)) * 8 + el;
-            f16[base] = hi;
-            f16[base + (size_t)64 * 8] = lo;
-          }
-          // the science table in accumulator order: register 8 s + el of half-wave kg
-          st[((size_t)pt * 2 + kg) * 16 + 8 * sidx + el] = t->sci_tables[p];
-        }
+    for (int h = 0; h < 2; ++h)
+      for (int j = 0; j < 16; ++j)
+        if (const int p = pt * 32 + aog::pupil_acc_row(j, h); p < n_ap) st[((size_t)pt * 2 + h) * 16 + j] = t->sci_tables[p];
+  // backward: A operand of step s, lane (kg, i = pixel of the tile), element el <-> table 16 s + 8 kg + el: the transpose of that role
+  std::vector<_Float16> t16(f16.size(), (_Float16)0.f);
   for (int p = 0; p < n_ap; ++p)
     for (int m = 0; m < TW; ++m) {
       _Float16 hi, lo;
@@ -78,23 +49,9 @@ int aog_upload_gradient(aog_env* e, const aog_tables* t) {
       t16[base] = hi;
       t16[base + (size_t)64 * 8] = lo;
     }
-  // the modes as table operands (wf_tab16's recipe), so that the call does not depend on aog_upload_wavefront_fit
-  const int nblk = aog::grad_blocks(e->A_pad);
-  std::vector<_Float16> m16((size_t)np * nblk * 2 * 2 * 64 * 8, (_Float16)0.f);
-  for (int pt = 0; pt < np; ++pt)
-    for (int sidx = 0; sidx < 2; ++sidx)
-      for (int kg = 0; kg < 2; ++kg)
-        for (int el = 0; el < 8; ++el) {
-          const int p = pt * 32 + (el & 3) + 16 * sidx + 8 * (el >> 2) + 4 * kg;
-          if (p >= n_ap) continue;
-          for (int k = 0; k < A; ++k) {
-            _Float16 hi, lo;
-            aog::split_f16((float)t->modes[(size_t)p * A + k] * aog::kModeScale, hi, lo);
-            const size_t base = (((((size_t)pt * nblk + (k >> 5)) * 2 + sidx) * 2) * 64 + (kg * 32 + (k & 31))) * 8 + el;
-            m16[base] = hi;
-            m16[base + (size_t)64 * 8] = lo;
-          }
-        }
+  // the modes as table operands: a buffer of the gradient's own, so that the call does not depend on aog_upload_wavefront_fit
+  const std::vector<_Float16> m16 = pack_tab16_rows(np, n_ap, A, aog::pupil_blocks(e->A_pad), aog::kModeScale,
+                                                    [&](int p, int k) { return t->modes[(size_t)p * A + k]; });
   if ((rc = upload(e, &e->grad_ftab16, f16, true)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->grad_ttab16, t16, true)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->grad_mtab16, m16, true)) != AOG_OK) return rc;
@@ -127,7 +84,7 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool fast = e->cfg.precision == AOG_PRECISION_FAST;
-  const int n_chunks = fast ? aog::grad_chunks(e->n_ptiles) : 1, MR = e->MRW_used + e->MRS_used;
+  const int n_chunks = fast ? aog::pupil_chunks(e->n_ptiles) : 1, MR = e->MRW_used + e->MRS_used;
   const int frows = fast ? aog::kGradFwdRows : 2 * MR, brows = fast ? e->A_pad : e->A;
   const double ratio = e->cfg.wavelength_wfs / e->cfg.wavelength_sci;
   int rc;
@@ -141,12 +98,11 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
     // touched); the actuator operands are the call's own copy
     if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
     if ((rc = load_actuators(e, s, {nullptr, e->grad_act16, obs_part ? e->gobs_act_ll : nullptr})) != AOG_OK) return rc;
-    switch (e->A_pad) {
-      case 16: launch_forward<16>(e, s, n_chunks, ratio); break;
-      case 32: launch_forward<32>(e, s, n_chunks, ratio); break;
-      case 64: launch_forward<64>(e, s, n_chunks, ratio); break;
-      default: launch_forward<128>(e, s, n_chunks, ratio); break;
-    }
+    with_apad(e->A_pad, [&](auto apad) {
+      hipLaunchKernelGGL((aog::k_grad_forward<apad()>), dim3(n_chunks, e->n_etiles), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
+                         reinterpret_cast<const aog::f16x8*>(e->grad_ftab16), e->grad_stab, reinterpret_cast<const aog::f32x4*>(e->psi_tile),
+                         reinterpret_cast<const aog::f16x8*>(e->grad_act16), e->grad_fslabs, e->n_ptiles, e->n_ap, e->Bp, ratio);
+    });
   } else {
     if (!e->grad_trig && (rc = dev_alloc(e, &e->grad_trig, (size_t)e->B * e->n_ap * 4, false)) != AOG_OK) return rc;
     hipLaunchKernelGGL(aog::k_grad_ref_forward, dim3(e->B), dim3(256), 0, s, e->modes64, e->tabs64, e->psi64, e->act_dm, e->grad_trig, e->grad_fslabs,
@@ -181,12 +137,13 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
   if (obs_part && (rc = grad_obs_part(e, s, g_obs_dev, values_dev)) != AOG_OK) return rc;   // (behind k_grad_coef: the observation slots of values)
   if (!grad_act_dev && !grad_action_dev) return AOG_OK;   // (the values alone)
   if (fast) {
-    switch (e->A_pad) {
-      case 16: launch_backward<16>(e, s, n_chunks, ratio); break;
-      case 32: launch_backward<32>(e, s, n_chunks, ratio); break;
-      case 64: launch_backward<64>(e, s, n_chunks, ratio); break;
-      default: launch_backward<128>(e, s, n_chunks, ratio); break;
-    }
+    with_apad(e->A_pad, [&](auto apad) {
+      hipLaunchKernelGGL((aog::k_grad_backward<apad()>), dim3(n_chunks, e->n_etiles), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
+                         reinterpret_cast<const aog::f16x8*>(e->grad_ttab16), e->grad_stab, reinterpret_cast<const aog::f16x8*>(e->grad_mtab16),
+                         reinterpret_cast<const aog::f32x4*>(e->psi_tile), reinterpret_cast<const aog::f16x8*>(e->grad_act16),
+                         reinterpret_cast<const aog::f16x8*>(e->grad_cop16), e->grad_csci, e->grad_bslabs, e->n_ptiles, e->n_ap, e->Bp, ratio,
+                         e->grad_tscale);
+    });
   } else {
     hipLaunchKernelGGL(aog::k_grad_ref_backward, dim3(e->B), dim3(256), 0, s, e->modes64, e->tabs64, e->grad_cbuf, e->grad_trig, e->grad_bslabs, e->n_ap,
                        e->A, e->MRW_used, e->MRS_used, e->Bp, ratio);

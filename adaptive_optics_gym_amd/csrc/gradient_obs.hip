@@ -11,12 +11,6 @@ namespace {
 int gobs_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 32); }
 int gobs_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
 
-template <int A_PAD>
-void launch_obs_backward(aog_env* e, hipStream_t s, int n_chunks, int env0, int n, size_t grid_env, int Nxp) {
-  hipLaunchKernelGGL((aog::k_grad_obs_backward<A_PAD>), dim3(n_chunks, (n + 31) / 32), dim3(256), 0, s, e->obs_work.grid, e->focal_ap_yx,
-                     reinterpret_cast<const aog::f16x8*>(e->grad_mtab16), e->gobs_slabs + env0, grid_env, Nxp, n, e->n_ptiles, e->n_ap, e->Bp);
-}
-
 }  // namespace
 
 namespace aog_host {
@@ -43,7 +37,7 @@ int grad_obs_part(aog_env* e, hipStream_t s, const double* g_obs, double* values
     HIP_TRY(hipGetLastError());
     return AOG_OK;
   }
-  const int Nxp = gobs_nxp(e), Nyp = gobs_nyp(e), nxt = Nxp / 32, nyt = (Nyp + 31) / 32, n_chunks = aog::grad_chunks(e->n_ptiles);
+  const int Nxp = gobs_nxp(e), Nyp = gobs_nyp(e), nxt = Nxp / 32, nyt = (Nyp + 31) / 32, n_chunks = aog::pupil_chunks(e->n_ptiles);
   const size_t grid_env = (size_t)Nyp * Nxp;
   // work buffers of the call's own, on first use (never initialised: every element that is read is written by the call first)
   if (g_obs) {
@@ -61,12 +55,10 @@ int grad_obs_part(aog_env* e, hipStream_t s, const double* g_obs, double* values
     if (!g_obs) continue;
     hipLaunchKernelGGL(aog::k_grad_obs_q, dim3((n * nyt * nxt + 3) / 4), dim3(256), 0, s, e->obs_work.grid, reinterpret_cast<const aog::f16x8*>(e->gobs_wop),
                        reinterpret_cast<const aog::f16x8*>(e->gobs_m1t), reinterpret_cast<const aog::f16x8*>(e->gobs_m2t), Nxp, Nyp, n);
-    switch (e->A_pad) {
-      case 16: launch_obs_backward<16>(e, s, n_chunks, env0, n, grid_env, Nxp); break;
-      case 32: launch_obs_backward<32>(e, s, n_chunks, env0, n, grid_env, Nxp); break;
-      case 64: launch_obs_backward<64>(e, s, n_chunks, env0, n, grid_env, Nxp); break;
-      default: launch_obs_backward<128>(e, s, n_chunks, env0, n, grid_env, Nxp); break;
-    }
+    with_apad(e->A_pad, [&](auto apad) {
+      hipLaunchKernelGGL((aog::k_grad_obs_backward<apad()>), dim3(n_chunks, n_et), dim3(256), 0, s, e->obs_work.grid, e->focal_ap_yx,
+                         reinterpret_cast<const aog::f16x8*>(e->grad_mtab16), e->gobs_slabs + env0, grid_env, Nxp, n, e->n_ptiles, e->n_ap, e->Bp);
+    });
   }
   HIP_TRY(hipGetLastError());
   return AOG_OK;

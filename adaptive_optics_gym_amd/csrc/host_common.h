@@ -1,12 +1,14 @@
 // Host-side helpers shared by the translation units of libaogym.so (not part of the C-ABI).
 #pragma once
 #include "aogym_internal.h"
+#include "k_common.h"   // split_f16, for pack_tab16_rows: the host packs operands with the split the kernels use
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace aog {
@@ -119,6 +121,40 @@ struct ActTargets {
   _Float16* act_ll;   // nullable third f16 term of the actuators (K4, K11)
 };
 int load_actuators(aog_env* e, hipStream_t s, ActTargets to);
+// The kernels instantiated per padded mode count outside the step path: f(std::integral_constant<int, 16 | 32 | 64 | 128>) for A_pad (anything
+// else gets 128), e.g. with_apad(e->A_pad, [&](auto apad) { hipLaunchKernelGGL((k<apad()>), ...); }).  (The step path's own table of
+// launchers is launchers_for in aogym.hip.)
+template <typename F>
+void with_apad(int A_pad, F&& f) {
+  switch (A_pad) {
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    default: f(std::integral_constant<int, 128>{}); break;
+  }
+}
+// The A operand of a contraction over the pixels of a tile with accumulator-order values as its B operand (k_pupil_tile.h), per pixel
+// tile and in tab16's pixel order: [pixel tile][block of 32 rows][step 2][hi | lo][lane (kg, row & 31)][el] <-> row `row` at pixel
+// (el & 3) + 16 s + 8 (el >> 2) + 4 kg of the tile; value(p, row) x scale is split like modes16.  Pad pixels and pad rows are zeros.
+template <typename V>
+std::vector<_Float16> pack_tab16_rows(int n_ptiles, int n_ap, int rows, int nblk, float scale, V&& value) {
+  std::vector<_Float16> t16((size_t)n_ptiles * nblk * 2 * 2 * 64 * 8, (_Float16)0.f);
+  for (int pt = 0; pt < n_ptiles; ++pt)
+    for (int sidx = 0; sidx < 2; ++sidx)
+      for (int kg = 0; kg < 2; ++kg)
+        for (int el = 0; el < 8; ++el) {
+          const int p = pt * 32 + (el & 3) + 16 * sidx + 8 * (el >> 2) + 4 * kg;
+          if (p >= n_ap) continue;
+          for (int k = 0; k < rows; ++k) {
+            _Float16 hi, lo;
+            aog::split_f16((float)value(p, k) * scale, hi, lo);
+            const size_t base = (((((size_t)pt * nblk + (k >> 5)) * 2 + sidx) * 2) * 64 + (kg * 32 + (k & 31))) * 8 + el;
+            t16[base] = hi;
+            t16[base + (size_t)64 * 8] = lo;
+          }
+        }
+  return t16;
+}
 // iy << 16 | ix of every aperture pixel, from the host copy of ap_index
 std::vector<int32_t> ap_yx_table(const aog_env* e);
 // Launchers of the kernels instantiated per padded mode count, one translation unit each so the build parallelises (fused_inst.hip compiled

@@ -5,44 +5,37 @@
 // (the science arm alike with E^sci_p = exp(i r phi_p), r = lambda_wfs / lambda_sci):
 //     C_m = sum_j gbar_j conj(Z_j) coef[j][m],  H_p = sum_m C_m g_m(p),  q_p = 2 Re(i E_p H_p) = -2 (cos phi_p Im H_p + sin phi_p Re H_p),
 //     dL/da_k = (4 pi / lambda_wfs) sum_p M_pk q_p            (the science arm's q_p carries the extra factor r).
-//   k_grad_forward<A_PAD>   fast handles: k_wavefront_fit's loop (a wave owns one env tile and every fourth pixel tile of its workgroup's
-//       chunk; u_p = psi_p + (M' a)_p on v_mfma_f32_32x32x16_f16 exactly as the step kernels form it), sin / cos at both wavelengths, and
-//       the cos / sin planes — split into f16 hi + lo as they lie in the accumulator registers — are the B operands of the table contraction
-//       (A = the wfs tables, <= 28 rows in one block of 32, tab16's pixel order).  The one science table is summed on the vector unit in
-//       float64.  fp32 accumulators are added to float64 after every tile; the four waves add in wave order through LDS; slab
-//       [chunk][66][Bp]: rows m = U_m, 32 + m = V_m (scaled by the tables' operand scale), 64 / 65 = U / V of the science arm.
+// The two fast kernels run on the loop, contractions and reduction of k_pupil_tile.h, which explains the register order they rely on.
+//   k_grad_forward<A_PAD>   fast handles: u (pupil_phase_mfma), sin / cos at both wavelengths, and the cos / sin planes, split as they lie, are the
+//       B operands of the table contraction (A = the wfs tables, <= 28 rows in one block of 32: grad_ftab16).  The one science table is
+//       summed on the vector unit in float64.  fp32 accumulators are added to float64 after every tile.  Slab [chunk][66][Bp]: rows
+//       m = U_m, 32 + m = V_m (scaled by the tables' operand scale), 64 / 65 = U / V of the science arm.
 //   k_grad_coef             one workgroup per env, float64, nothing contracted: slabs added in chunk order, Z_j, the values, C_m; C is divided
 //       by its largest component before it is split into f16 operands (its magnitude follows the cotangents and the Strehl over orders);
 //       the divisor goes to k_grad_finish in float64.
-//   k_grad_backward<A_PAD>  fast handles: the same loop; per pixel tile H = g' C on the matrix cores (A = the tables transposed: 32 pixel rows,
-//       K = 32 tables in two steps; B = Re C, Im C of the env tile, resident), q on the vector unit, q split into f16 hi + lo as the B operand
-//       of the modes contraction (wf_tab16's recipe: k_wavefront_fit's second contraction).  Pad pixels have zero table rows and pad envs
-//       zero C: both contribute exact zeros.  Slab [chunk][A_PAD][Bp].  No atomics, no B x n_ap intermediate.
+//   k_grad_backward<A_PAD>  fast handles: per pixel tile H = g' C on the matrix cores (A = the tables transposed: 32 pixel rows, K = 32 tables
+//       in two steps, grad_ttab16; B = Re C, Im C of the env tile, resident), q on the vector unit, q split as the B operand of the modes
+//       contraction (grad_mtab16).  Pad pixels have zero table rows and pad envs zero C: both contribute exact zeros.  Slab
+//       [chunk][A_PAD][Bp].  No atomics, no B x n_ap intermediate.
 //   k_grad_ref_forward / k_grad_ref_backward   float64 validation handles, one workgroup per env, in the style of k_wavefront_ref.
 //   k_grad_finish           one workgroup per env: slabs in chunk order, the scales, grad_act, and the action chain for grad_action.
 //       On the separable observation route with aog_upload_gradient_obs a second slab set (k_gradient_obs.h: the observation's q contracted
 //       with the modes) is added with scales of its own; without it the sum is the first set's alone, bit for bit.
 #pragma once
-#include "k_gradient_common.h"
+#include "k_pupil_tile.h"
 
 namespace aog {
 
 constexpr int kGradFwdRows = 66;        // rows of a forward slab of the fast kernels
 constexpr float kGradQScale = 0.0625f;  // q is scaled by 2^-4 x the tables' scale before it is split (|q| <= 2 (28 + 2) x 256: inside the f16 range)
 
-// u of this lane's 16 pixels of tile t (register 4 g + r: pixel 8 g + 4 h + r), then cos / sin of 2 pi u and of 2 pi ratio u.  Pad pixels of
-// the last tile read as cos = sin = 0 in both arms.
+// cos / sin of 2 pi u and of 2 pi ratio u for the lane's 16 pixels of tile t.  Pad pixels of the last tile read as cos = sin = 0 in both arms.
 template <int NSTEP>
-__device__ __forceinline__ void grad_tile_trig(const f16x8* __restrict__ ms, const f16x8 (&bh)[NSTEP], const f16x8 (&bl)[NSTEP], const f32x4 (&pc)[4],
-                                               int left, double ratio, float (&cw)[16], float (&sw)[16], float (&cs)[16], float (&ss)[16]) {
-  f32x16 d = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < NSTEP; ++s) {
-    const f16x8 mh = ms[(2 * s) * 64], ml = ms[(2 * s + 1) * 64];
-    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(mh, bh[s], d, 0, 0, 0);
-    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(mh, bl[s], d, 0, 0, 0);
-    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ml, bh[s], d, 0, 0, 0);
-  }
+__device__ __forceinline__ void grad_tile_trig(const f16x8* __restrict__ modes16, int t, const f16x8 (&bh)[NSTEP], const f16x8 (&bl)[NSTEP],
+                                               const f32x4 (&pc)[4], int n_ap, double ratio, float (&cw)[16], float (&sw)[16], float (&cs)[16],
+                                               float (&ss)[16]) {
+  const f32x16 d = pupil_phase_mfma<NSTEP>(modes16, t, bh, bl);
+  const int left = pupil_left(n_ap, t);
 #pragma unroll
   for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -62,23 +55,6 @@ __device__ __forceinline__ void grad_tile_trig(const f16x8* __restrict__ ms, con
     }
 }
 
-#define AOG_GRAD_TILE_LOOP_HEAD                                                                        \
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;                           \
-  const int chunk = blockIdx.x, etile = blockIdx.y;                                                    \
-  f16x8 bh[NSTEP], bl[NSTEP];                                                                          \
-  {                                                                                                    \
-    const f16x8* asrc = act16 + ((size_t)etile * NSTEP * 2) * 64 + lane;                               \
-    _Pragma("unroll") for (int s = 0; s < NSTEP; ++s) { bh[s] = asrc[(2 * s) * 64]; bl[s] = asrc[(2 * s + 1) * 64]; } \
-  }                                                                                                    \
-  const int t_end = min((chunk + 1) * kGradChunkTiles, n_ptiles);                                      \
-  int t = chunk * kGradChunkTiles + wave;                                                              \
-  f32x4 pc[4], pn[4];                                                                                  \
-  auto load_psi = [&](int tile, f32x4 (&pp)[4]) {                                                      \
-    const size_t base = (((size_t)etile * n_ptiles + tile) * 4) * 64 + lane;                           \
-    _Pragma("unroll") for (int g = 0; g < 4; ++g) pp[g] = psi_tile[base + g * 64];                     \
-  };                                                                                                   \
-  if (t < t_end) load_psi(t, pc);
-
 template <int A_PAD>
 __global__ __launch_bounds__(256) void k_grad_forward(const f16x8* __restrict__ modes16, const f16x8* __restrict__ ftab16,
                                                       const double* __restrict__ stab, const f32x4* __restrict__ psi_tile,
@@ -86,18 +62,34 @@ __global__ __launch_bounds__(256) void k_grad_forward(const f16x8* __restrict__ 
                                                       double ratio) {
   constexpr int NSTEP = A_PAD / 16;
   __shared__ double red[kGradFwdRows * 32];
-  AOG_GRAD_TILE_LOOP_HEAD
+  const int lane = threadIdx.x & 63, h = pupil_half();
   double aU[16], aV[16];
 #pragma unroll
   for (int j = 0; j < 16; ++j) { aU[j] = 0.0; aV[j] = 0.0; }
   double su = 0.0, sv = 0.0;
-  for (; t < t_end; t += 4) {   // (wave-uniform)
-    if (t + 4 < t_end) load_psi(t + 4, pn);
+  // (pupil_tile_loop written out: through the template this kernel's A_PAD = 64 form needs 10 more accumulator registers and loses a wave)
+  const int etile = blockIdx.y;
+  f16x8 bh[NSTEP], bl[NSTEP];
+  {
+    const f16x8* asrc = act16 + ((size_t)etile * NSTEP * 2) * 64 + lane;
+#pragma unroll
+    for (int s = 0; s < NSTEP; ++s) { bh[s] = asrc[(2 * s) * 64]; bl[s] = asrc[(2 * s + 1) * 64]; }
+  }
+  const PupilTileRange tiles = pupil_tile_range(n_ptiles);
+  f32x4 pc[4], pn[4];
+  auto load_psi = [&](int tile, f32x4 (&pp)[4]) {
+    const size_t base = (((size_t)etile * n_ptiles + tile) * 4) * 64 + lane;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) pp[g] = psi_tile[base + g * 64];
+  };
+  if (tiles.t < tiles.t_end) load_psi(tiles.t, pc);
+  for (int t = tiles.t; t < tiles.t_end; t += kPupilWaves) {   // (wave-uniform)
+    if (t + kPupilWaves < tiles.t_end) load_psi(t + kPupilWaves, pn);
     float cw[16], sw[16], cs[16], ss[16];
-    grad_tile_trig<NSTEP>(modes16 + ((size_t)t * NSTEP * 2) * 64 + lane, bh, bl, pc, n_ap - t * 32 - 4 * h, ratio, cw, sw, cs, ss);
+    grad_tile_trig<NSTEP>(modes16, t, bh, bl, pc, n_ap, ratio, cw, sw, cs, ss);
     f16x8 ch[2], cl[2], sh[2], sl[2];
-    grad_split16(cw, 1.f, ch, cl);
-    grad_split16(sw, 1.f, sh, sl);
+    pupil_split16(cw, 1.f, ch, cl);
+    pupil_split16(sw, 1.f, sh, sl);
     const f16x8* ts = ftab16 + ((size_t)t * 4) * 64 + lane;
     f32x16 U = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, V = U;
 #pragma unroll
@@ -110,7 +102,7 @@ __global__ __launch_bounds__(256) void k_grad_forward(const f16x8* __restrict__ 
       V = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, sl[s], V, 0, 0, 0);
       V = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, sh[s], V, 0, 0, 0);
     }
-    const double* st = stab + ((size_t)t * 2 + h) * 16;
+    const double* st = stab + ((size_t)t * 2 + h) * 16;   // (the science table in accumulator order)
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       aU[j] += (double)U[j];
@@ -124,24 +116,16 @@ __global__ __launch_bounds__(256) void k_grad_forward(const f16x8* __restrict__ 
   }
   su += __shfl_down(su, 32, 64);   // (the two half-waves hold different pixels of the same env)
   sv += __shfl_down(sv, 32, 64);
-  const int col = lane & 31;
-  for (int w = 0; w < 4; ++w) {   // the four waves' sums in wave order (a wave without tiles adds zeros)
-    if (wave == w) {
+  pupil_reduce_store<kGradFwdRows>(red, slabs, Bp, [&](auto put) __attribute__((always_inline)) {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int m = 8 * (j >> 2) + 4 * h + (j & 3);
-        red[m * 32 + col] = w == 0 ? aU[j] : red[m * 32 + col] + aU[j];
-        red[(32 + m) * 32 + col] = w == 0 ? aV[j] : red[(32 + m) * 32 + col] + aV[j];
-      }
-      if (h == 0) {
-        red[64 * 32 + col] = w == 0 ? su : red[64 * 32 + col] + su;
-        red[65 * 32 + col] = w == 0 ? sv : red[65 * 32 + col] + sv;
-      }
+    for (int j = 0; j < 16; ++j) {
+      put(pupil_acc_row(j, h), aU[j]);
+      put(32 + pupil_acc_row(j, h), aV[j]);
     }
-    __syncthreads();
-  }
-  double* out = slabs + (size_t)chunk * kGradFwdRows * Bp + (size_t)etile * 32;
-  for (int i = threadIdx.x; i < kGradFwdRows * 32; i += 256) out[(size_t)(i >> 5) * Bp + (i & 31)] = red[i];
+    if (h != 0) return;
+    put(64, su);
+    put(65, sv);
+  });
 }
 
 template <int A_PAD>
@@ -150,9 +134,9 @@ __global__ __launch_bounds__(256) void k_grad_backward(const f16x8* __restrict__
                                                        const f32x4* __restrict__ psi_tile, const f16x8* __restrict__ act16,
                                                        const f16x8* __restrict__ cop16, const float* __restrict__ csci, double* __restrict__ slabs,
                                                        int n_ptiles, int n_ap, int Bp, double ratio, float tscale) {
-  constexpr int NSTEP = A_PAD / 16, NBLK = grad_blocks(A_PAD);
+  constexpr int NSTEP = A_PAD / 16, NBLK = pupil_blocks(A_PAD);
   __shared__ double red[A_PAD * 32];
-  AOG_GRAD_TILE_LOOP_HEAD
+  const int lane = threadIdx.x & 63, h = pupil_half(), etile = blockIdx.y;
   // Re C, Im C of this env tile (K = 32 tables in two steps, hi | lo) stay in registers
   f16x8 crh[2], crl[2], cih[2], cil[2];
   {
@@ -172,10 +156,10 @@ __global__ __launch_bounds__(256) void k_grad_backward(const f16x8* __restrict__
   for (int b = 0; b < NBLK; ++b)
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[b][j] = 0.0;
-  for (; t < t_end; t += 4) {   // (wave-uniform)
-    if (t + 4 < t_end) load_psi(t + 4, pn);
+  f16x8 bh[NSTEP], bl[NSTEP];
+  pupil_tile_loop<NSTEP>(psi_tile, act16, n_ptiles, bh, bl, [&](int t, const f32x4 (&pc)[4]) {
     float cw[16], sw[16], cs[16], ss[16];
-    grad_tile_trig<NSTEP>(modes16 + ((size_t)t * NSTEP * 2) * 64 + lane, bh, bl, pc, n_ap - t * 32 - 4 * h, ratio, cw, sw, cs, ss);
+    grad_tile_trig<NSTEP>(modes16, t, bh, bl, pc, n_ap, ratio, cw, sw, cs, ss);
     const f16x8* ts = ttab16 + ((size_t)t * 4) * 64 + lane;
     f32x16 Hr = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, Hi = Hr;
 #pragma unroll
@@ -197,40 +181,10 @@ __global__ __launch_bounds__(256) void k_grad_backward(const f16x8* __restrict__
       q[j] = qw + qs;
     }
     f16x8 qh[2], ql[2];
-    grad_split16(q, 1.f, qh, ql);
-    // T += M' q: q is the B operand (K = the tile's 32 pixels in two steps), the modes the A operand in blocks of 32 rows
-    const f16x8* mt = mtab16 + ((size_t)t * NBLK * 4) * 64 + lane;
-#pragma unroll
-    for (int b = 0; b < NBLK; ++b) {
-      f32x16 D = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const f16x8 th = mt[((b * 2 + s) * 2) * 64], tl = mt[((b * 2 + s) * 2 + 1) * 64];
-        D = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh[s], D, 0, 0, 0);
-        D = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql[s], D, 0, 0, 0);
-        D = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh[s], D, 0, 0, 0);
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[b][j] += (double)D[j];
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) pc[g] = pn[g];
-  }
-  const int col = lane & 31;
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w) {
-#pragma unroll
-      for (int b = 0; b < NBLK; ++b)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const int m = 32 * b + 8 * (j >> 2) + 4 * h + (j & 3);
-          if (m < A_PAD) red[m * 32 + col] = w == 0 ? acc[b][j] : red[m * 32 + col] + acc[b][j];
-        }
-    }
-    __syncthreads();
-  }
-  double* out = slabs + (size_t)chunk * A_PAD * Bp + (size_t)etile * 32;
-  for (int i = threadIdx.x; i < A_PAD * 32; i += 256) out[(size_t)(i >> 5) * Bp + (i & 31)] = red[i];
+    pupil_split16(q, 1.f, qh, ql);
+    pupil_modes_mfma<NBLK>(mtab16, t, qh, ql, acc);
+  });
+  pupil_reduce_store<A_PAD>(red, slabs, Bp, [&](auto put) __attribute__((always_inline)) { pupil_mode_rows<A_PAD>(acc, put); });
 }
 
 // ---- per env: Z_j, the values the gradient is taken at, C_m ----
@@ -357,13 +311,10 @@ __global__ __launch_bounds__(256) void k_grad_ref_forward(const double* __restri
   __shared__ double sm[8];
   __shared__ double sa[256];
   const int env = blockIdx.x, MR = MRW + MRS;
-  for (int i = threadIdx.x; i < A; i += blockDim.x) sa[i] = act_dm[(size_t)env * A + i];
-  __syncthreads();
+  pupil64_stage_act(act_dm, env, A, sa);
   double* tg = trig + (size_t)env * n_ap * 4;
   for (int p = threadIdx.x; p < n_ap; p += blockDim.x) {
-    const double* mrow = modes64 + (size_t)p * A;
-    double surf = 0;
-    for (int k = 0; k < A; ++k) surf = fma(mrow[k], sa[k], surf);
+    const double surf = pupil64_surface(modes64, sa, p, A);
     const double rev = (psi64[(size_t)env * n_ap + p] + 4.0 * M_PI * surf) / (2.0 * M_PI * lambda_wfs), revs = rev * ratio;
     double sn, cs;
     sincospi(2.0 * (rev - rint(rev)), &sn, &cs);
@@ -408,12 +359,7 @@ __global__ __launch_bounds__(256) void k_grad_ref_backward(const double* __restr
     tg[4 * p] = -2.0 * (tg[4 * p] * hi + tg[4 * p + 1] * hr) - 2.0 * ratio * (tg[4 * p + 2] * ki + tg[4 * p + 3] * kr);
   }
   __syncthreads();
-  for (int k = 0; k < A; ++k) {
-    double v = 0;
-    for (int p = threadIdx.x; p < n_ap; p += blockDim.x) v = fma(modes64[(size_t)p * A + k], tg[4 * p], v);
-    const double T = block_reduce_sum(v, sm);
-    if (threadIdx.x == 0) slab[(size_t)k * Bp + env] = T;
-  }
+  pupil64_mode_rows(modes64, tg, 4, slab, n_ap, A, Bp, env, sm);
 }
 
 // ---- slabs -> grad_act, and grad_action through action -> actuators (AO_env.py:119-120) ----

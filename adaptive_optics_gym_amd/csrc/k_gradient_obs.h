@@ -13,15 +13,15 @@
 //       of m1' holding v in that register order (what m2s does for pass 2): no LDS, no transposition.  H then has the lanes along x and y in
 //       the registers; the wave reads its tile of the phase grid, takes v_sin_f32 / v_cos_f32 and writes -(sin Re H + cos Im H) over the
 //       phase, on aperture pixels only (the grid's outside and padding keep kShOutside).
-//   k_grad_obs_backward<A_PAD>   k_grad_backward's loop over (env tile, pixel chunk) with q read from the grid instead of formed from tables:
-//       a wave gathers the [32 envs][32 pixels] tile of a pixel tile through focal_ap_yx with the lanes along the pixels into LDS (the
-//       inverse of k_phase_mfma<GRID>'s store; pad pixels and pad envs are exact zeros) and reads it back in accumulator order, splits it
-//       and contracts it with the modes (grad_mtab16).  Slab [chunk][A_PAD][Bp], added by k_grad_finish in chunk order.  No atomics.
+//   k_grad_obs_backward<A_PAD>   the tile range, modes contraction and reduction of k_pupil_tile.h (no screens, no actuators) with q read from
+//       the grid: a wave gathers the [32 envs][32 pixels] tile of a pixel tile through focal_ap_yx with the lanes along the pixels into LDS
+//       (the inverse of k_phase_mfma<GRID>'s store; pad pixels and pad envs are exact zeros) and reads it back in accumulator order, splits
+//       it and contracts it with the modes (grad_mtab16).  Slab [chunk][A_PAD][Bp], added by k_grad_finish in chunk order.  No atomics.
 //   k_grad_obs_w64 / k_grad_obs_q64   float64 validation handles, one env at a time around k_focal_field and k_cgemm_small.
 // Magnitudes: |m1'|, |m2'| < sqrt(2) (largest component in [1/2, 1)), |W| < 8 sqrt(2): |Q| < 2^10 and |H| < 2^15 for every cotangent, inside
 // the f16 range before and after the split.
 #pragma once
-#include "k_gradient_common.h"
+#include "k_pupil_tile.h"
 #include "k_mft_mma.h"
 
 namespace aog {
@@ -153,25 +153,24 @@ __global__ __launch_bounds__(256) void k_grad_obs_q(float* __restrict__ grid, co
   }
 }
 
-// grid dim3(pixel chunks, env tiles of the round), k_grad_backward's geometry.  qgrid [n_env][env_stride] with row stride Nxp: what
+// grid dim3(pixel chunks, env tiles of the round): k_pupil_tile.h's geometry.  qgrid [n_env][env_stride] with row stride Nxp: what
 // k_grad_obs_q left; ap_yx [n_ap] iy << 16 | ix; slabs offset to the round's first env tile.
 template <int A_PAD>
 __global__ __launch_bounds__(256) void k_grad_obs_backward(const float* __restrict__ qgrid, const int32_t* __restrict__ ap_yx, const f16x8* __restrict__ mtab16,
                                                            double* __restrict__ slabs, size_t env_stride, int Nxp, int n_env, int n_ptiles, int n_ap,
                                                            int Bp) {
-  constexpr int NBLK = grad_blocks(A_PAD);
+  constexpr int NBLK = pupil_blocks(A_PAD);
   __shared__ double red[A_PAD * 32];
   __shared__ float qt_lds[4 * 32 * 33];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, col = lane & 31;
-  const int chunk = blockIdx.x, etile = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = pupil_half(), col = lane & 31;
+  const int etile = blockIdx.y;
   float* qt = qt_lds + wave * 32 * 33;   // (private to the wave)
-  const int t_end = min((chunk + 1) * kGradChunkTiles, n_ptiles);
   double acc[NBLK][16];
 #pragma unroll
   for (int b = 0; b < NBLK; ++b)
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[b][j] = 0.0;
-  for (int t = chunk * kGradChunkTiles + wave; t < t_end; t += 4) {   // (wave-uniform)
+  pupil_for_tiles(n_ptiles, [&](int t) {
     // gather: lane = pixel col of the tile, envs 2 j + h of the env tile
     const int pix = t * 32 + col;
     const bool real = pix < n_ap;
@@ -184,43 +183,17 @@ __global__ __launch_bounds__(256) void k_grad_obs_backward(const float* __restri
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
     __builtin_amdgcn_wave_barrier();
-    // accumulator order: lane = env col, register 4 g + r = pixel 8 g + 4 h + r
+    // back in accumulator order: lane = env col, register j = pixel pupil_acc_row(j, h)
     float q[16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) q[j] = qt[col * 33 + 8 * (j >> 2) + 4 * h + (j & 3)];
+    for (int j = 0; j < 16; ++j) q[j] = qt[col * 33 + pupil_acc_row(j, h)];
     __builtin_amdgcn_s_waitcnt(0xc07f);   // (the tile is rewritten by the next pixel tile)
     __builtin_amdgcn_wave_barrier();
     f16x8 qh[2], ql[2];
-    grad_split16(q, 1.f, qh, ql);
-    const f16x8* mt = mtab16 + ((size_t)t * NBLK * 4) * 64 + lane;
-#pragma unroll
-    for (int b = 0; b < NBLK; ++b) {
-      f32x16 D = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const f16x8 th = mt[((b * 2 + s) * 2) * 64], tl = mt[((b * 2 + s) * 2 + 1) * 64];
-        D = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh[s], D, 0, 0, 0);
-        D = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql[s], D, 0, 0, 0);
-        D = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh[s], D, 0, 0, 0);
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[b][j] += (double)D[j];
-    }
-  }
-  for (int w = 0; w < 4; ++w) {   // the four waves' sums in wave order (a wave without tiles adds zeros)
-    if (wave == w) {
-#pragma unroll
-      for (int b = 0; b < NBLK; ++b)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const int m = 32 * b + 8 * (j >> 2) + 4 * h + (j & 3);
-          if (m < A_PAD) red[m * 32 + col] = w == 0 ? acc[b][j] : red[m * 32 + col] + acc[b][j];
-        }
-    }
-    __syncthreads();
-  }
-  double* out = slabs + (size_t)chunk * A_PAD * Bp + (size_t)etile * 32;
-  for (int i = threadIdx.x; i < A_PAD * 32; i += 256) out[(size_t)(i >> 5) * Bp + (i & 31)] = red[i];
+    pupil_split16(q, 1.f, qh, ql);
+    pupil_modes_mfma<NBLK>(mtab16, t, qh, ql, acc);
+  });
+  pupil_reduce_store<A_PAD>(red, slabs, Bp, [&](auto put) __attribute__((always_inline)) { pupil_mode_rows<A_PAD>(acc, put); });
 }
 
 // ---- float64 validation handles, one env at a time ----
@@ -242,12 +215,7 @@ __global__ __launch_bounds__(256) void k_grad_obs_q64(const double2* __restrict_
     q[p] = -2.0 * (e.x * hh.y + e.y * hh.x);
   }
   __syncthreads();
-  for (int k = 0; k < A; ++k) {
-    double v = 0;
-    for (int p = threadIdx.x; p < n_ap; p += blockDim.x) v = fma(modes64[(size_t)p * A + k], q[p], v);
-    const double T = block_reduce_sum(v, sm);
-    if (threadIdx.x == 0) slab[(size_t)k * Bp + env] = T;
-  }
+  pupil64_mode_rows(modes64, q, 1, slab, n_ap, A, Bp, env, sm);
 }
 
 }  // namespace aog

@@ -32,16 +32,6 @@ void release_science(aog_env* e) {
   dev_release(e, &e->sci_frames);
 }
 
-template <int A_PAD>
-void launch_science_phase(aog_env* e, hipStream_t s, int etile0, int n_et, size_t grid_env, int Nxp, const uint8_t* mask) {
-  constexpr int NSTEP = A_PAD / 16;
-  hipLaunchKernelGGL((aog::k_science_phase<A_PAD>), dim3((e->n_ptiles + 3) / 4, n_et), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
-                     reinterpret_cast<const aog::f32x4*>(e->psi_tile) + (size_t)etile0 * e->n_ptiles * 4 * 64,
-                     reinterpret_cast<const aog::f16x8*>(e->sci_act16) + (size_t)etile0 * NSTEP * 2 * 64,
-                     reinterpret_cast<const aog::f16x8*>(e->sci_act_ll) + (size_t)etile0 * NSTEP * 64, e->focal_ap_yx, e->sci_work.grid, grid_env, Nxp, e->n_ptiles,
-                     n_et, e->n_ap, e->B - etile0 * 32, e->sci_ratio, mask ? mask + (size_t)etile0 * 32 : nullptr);
-}
-
 // the checks every call on an uploaded camera shares (aog_focal_images' preconditions)
 int science_ready(aog_env* e, const char* who) {
   if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "%s before aog_upload_tables/aog_set_screens", who);
@@ -135,12 +125,15 @@ int aog_science_integrate(aog_env* e, const uint8_t* mask_dev, void* stream) {
   const size_t grid_env = (size_t)Nyp * Nxp;
   for (int env0 = 0; env0 < e->B; env0 += e->sci_work.chunk) {
     const int n = std::min(e->sci_work.chunk, e->B - env0), n_et = (n + 31) / 32;
-    switch (e->A_pad) {
-      case 16: launch_science_phase<16>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
-      case 32: launch_science_phase<32>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
-      case 64: launch_science_phase<64>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
-      default: launch_science_phase<128>(e, s, env0 / 32, n_et, grid_env, Nxp, mask_dev); break;
-    }
+    const int etile0 = env0 / 32;
+    with_apad(e->A_pad, [&](auto apad) {
+      constexpr int NSTEP = apad() / 16;
+      hipLaunchKernelGGL((aog::k_science_phase<apad()>), dim3((e->n_ptiles + 3) / 4, n_et), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
+                         reinterpret_cast<const aog::f32x4*>(e->psi_tile) + (size_t)etile0 * e->n_ptiles * 4 * 64,
+                         reinterpret_cast<const aog::f16x8*>(e->sci_act16) + (size_t)etile0 * NSTEP * 2 * 64,
+                         reinterpret_cast<const aog::f16x8*>(e->sci_act_ll) + (size_t)etile0 * NSTEP * 64, e->focal_ap_yx, e->sci_work.grid, grid_env, Nxp,
+                         e->n_ptiles, n_et, e->n_ap, e->B - etile0 * 32, e->sci_ratio, mask_dev ? mask_dev + (size_t)etile0 * 32 : nullptr);
+    });
     hipLaunchKernelGGL(aog::k_science_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->sci_work.grid, reinterpret_cast<const aog::f16x8*>(e->sci_m1s),
                        reinterpret_cast<aog::f16x8*>(e->sci_work.T16), Nxp, Nyp, nvb, mask_dev, env0, split);
     hipLaunchKernelGGL(aog::k_science_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->sci_work.T16),

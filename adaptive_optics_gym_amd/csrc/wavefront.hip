@@ -5,17 +5,6 @@
 
 using namespace aog_host;
 
-namespace {
-
-template <int A_PAD>
-void launch_fit(aog_env* e, hipStream_t s, int n_chunks) {
-  hipLaunchKernelGGL((aog::k_wavefront_fit<A_PAD>), dim3(n_chunks, e->n_etiles), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
-                     reinterpret_cast<const aog::f16x8*>(e->wf_tab16), reinterpret_cast<const aog::f32x4*>(e->psi_tile),
-                     reinterpret_cast<const aog::f16x8*>(e->wf_act16), e->wf_slabs, e->n_ptiles, e->n_ap, e->Bp);
-}
-
-}  // namespace
-
 extern "C" {
 
 int aog_upload_wavefront_fit(aog_env* e, const double* modes_host, const double* fit_host) {
@@ -31,24 +20,9 @@ int aog_upload_wavefront_fit(aog_env* e, const double* modes_host, const double*
   if ((rc = upload(e, &e->wf_colsum, colsum, true)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->wf_fit, fit_host, (size_t)A * A, true)) != AOG_OK) return rc;
   if (e->cfg.precision == AOG_PRECISION_FAST) {
-    // the modes as table operands: A operand of block b, step s, lane (kg, m), element el <-> mode 32 b + m at pixel
-    // i = (el & 3) + 16 s + 8 (el >> 2) + 4 kg of the tile (tab16's order), scaled and split like modes16
-    const int nblk = aog::wavefront_blocks(e->A_pad);
-    std::vector<_Float16> t16((size_t)e->n_ptiles * nblk * 2 * 2 * 64 * 8, (_Float16)0.f);
-    for (int pt = 0; pt < e->n_ptiles; ++pt)
-      for (int sidx = 0; sidx < 2; ++sidx)
-        for (int kg = 0; kg < 2; ++kg)
-          for (int el = 0; el < 8; ++el) {
-            const int p = pt * 32 + (el & 3) + 16 * sidx + 8 * (el >> 2) + 4 * kg;
-            if (p >= n_ap) continue;
-            for (int k = 0; k < A; ++k) {
-              _Float16 hi, lo;
-              aog::split_f16((float)modes_host[(size_t)p * A + k] * aog::kModeScale, hi, lo);
-              const size_t base = (((((size_t)pt * nblk + (k >> 5)) * 2 + sidx) * 2) * 64 + (kg * 32 + (k & 31))) * 8 + el;
-              t16[base] = hi;
-              t16[base + (size_t)64 * 8] = lo;
-            }
-          }
+    // the modes as table operands of the second contraction, scaled like modes16
+    const std::vector<_Float16> t16 = pack_tab16_rows(e->n_ptiles, n_ap, A, aog::pupil_blocks(e->A_pad), aog::kModeScale,
+                                                      [&](int p, int k) { return modes_host[(size_t)p * A + k]; });
     if ((rc = upload(e, &e->wf_tab16, t16, true)) != AOG_OK) return rc;
     if (!e->wf_act16 && (rc = dev_alloc(e, &e->wf_act16, (size_t)e->n_etiles * e->A_pad * 32 * 2, true)) != AOG_OK) return rc;
   }
@@ -66,7 +40,7 @@ int aog_wavefront_truth(aog_env* e, double* rms_dev, double* fit_rms_dev, double
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool fast = e->cfg.precision == AOG_PRECISION_FAST;
-  const int n_chunks = fast ? aog::wavefront_chunks(e->n_ptiles) : 1, rows = e->A_pad + 2;
+  const int n_chunks = fast ? aog::pupil_chunks(e->n_ptiles) : 1, rows = e->A_pad + 2;
   int rc;
   // work buffers of the call's own, on first use (never initialised: every element that is read is written by the call first)
   if (!e->wf_slabs && (rc = dev_alloc(e, &e->wf_slabs, (size_t)n_chunks * rows * e->Bp, false)) != AOG_OK) return rc;
@@ -76,12 +50,11 @@ int aog_wavefront_truth(aog_env* e, double* rms_dev, double* fit_rms_dev, double
     // ahead stays, because only what the last step left is read)
     if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
     if ((rc = load_actuators(e, s, {nullptr, e->wf_act16, nullptr})) != AOG_OK) return rc;   // (own copy: act_rev / act16 are not touched)
-    switch (e->A_pad) {
-      case 16: launch_fit<16>(e, s, n_chunks); break;
-      case 32: launch_fit<32>(e, s, n_chunks); break;
-      case 64: launch_fit<64>(e, s, n_chunks); break;
-      default: launch_fit<128>(e, s, n_chunks); break;
-    }
+    with_apad(e->A_pad, [&](auto apad) {
+      hipLaunchKernelGGL((aog::k_wavefront_fit<apad()>), dim3(n_chunks, e->n_etiles), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
+                         reinterpret_cast<const aog::f16x8*>(e->wf_tab16), reinterpret_cast<const aog::f32x4*>(e->psi_tile),
+                         reinterpret_cast<const aog::f16x8*>(e->wf_act16), e->wf_slabs, e->n_ptiles, e->n_ap, e->Bp);
+    });
   } else {
     if (!e->wf_w && (rc = dev_alloc(e, &e->wf_w, (size_t)e->B * e->n_ap, false)) != AOG_OK) return rc;
     hipLaunchKernelGGL(aog::k_wavefront_ref, dim3(e->B), dim3(256), 0, s, e->modes64, e->psi64, e->act_dm, e->wf_w, e->wf_slabs, e->n_ap, e->A, rows,

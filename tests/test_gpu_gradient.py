@@ -12,14 +12,15 @@ import numpy as np
 import pytest
 
 import gradient_reference as gr
-from helpers import actions_for, smooth_screens
-from test_gpu_wavefront_truth import CASES
+from helpers import actions_for, assert_short_last_chunk, smooth_screens
+from test_gpu_wavefront_truth import CASES, EDGE
 
 pytestmark = pytest.mark.gpu
 
 N, B = 32, 40
 FAST, FP64 = 4 * 7.624e-6, 1e-9
 assert FAST <= 1e-3
+assert_short_last_chunk(EDGE[2])   # N = 52: 67 pixel tiles, the second chunk holds three (a wave without tiles), the last tile 16 pixels
 _TABLES = {}
 
 
@@ -131,6 +132,23 @@ def test_parity_with_the_restatement(case, o, precision):
             env.step(torch.from_numpy(actions_for(B, A, t)).cuda())
         w = max(w, _hold(env, bound, f"{case} o={o} {precision} after two steps", seed=2))
         print(f"WORST {case} o={o} {precision}: {w:.3e}")
+    finally:
+        env.close()
+
+
+@pytest.mark.parametrize("precision", ["fast", "fp64"])
+def test_parity_where_a_wave_has_no_tile(precision):
+    torch = _torch()
+    act_type, A, n = EDGE
+    bound = FAST if precision == "fast" else FP64
+    env = _env(B, act_type, A, n, obs_dim=2, screens=smooth_screens(B, n, 31), precision=precision)
+    try:
+        env.reset()
+        w = _hold(env, bound, f"edge52 o=2 {precision} after reset (flat mirror)")
+        for t in range(2):
+            env.step(torch.from_numpy(actions_for(B, A, t)).cuda())
+        w = max(w, _hold(env, bound, f"edge52 o=2 {precision} after two steps", seed=2))
+        print(f"WORST edge52 o=2 {precision}: {w:.3e}")
     finally:
         env.close()
 

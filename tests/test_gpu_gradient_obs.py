@@ -16,14 +16,15 @@ import pytest
 
 import gradient_obs_reference as gor
 import gradient_reference as gr
-from helpers import actions_for, smooth_screens
-from test_gpu_wavefront_truth import CASES
+from helpers import actions_for, assert_short_last_chunk, smooth_screens
+from test_gpu_wavefront_truth import CASES, EDGE
 
 pytestmark = pytest.mark.gpu
 
 B = 40
 FAST, FP64 = 4 * 2.629e-6, 1e-9   # (profiles/output_gradient_separable.md: the worst case is apad16, power after reset)
 assert FAST <= 1e-3
+assert_short_last_chunk(EDGE[2])   # N = 52: 67 pixel tiles, the second chunk holds three (a wave without tiles), the last tile 16 pixels
 _TABLES = {}
 
 
@@ -122,7 +123,7 @@ def _parity(what, precision, act_type, A, n, o):
 
 
 # ---- 1. parity with the restatement --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,o", [(32, 6), (40, 8), (40, 17), (40, 32)])
+@pytest.mark.parametrize("n,o", [(32, 6), (40, 8), (40, 17), (40, 32), (EDGE[2], 8)])
 def test_parity_with_the_restatement(n, o):
     _parity(f"N={n} o={o} fast", "fast", "num_actuators", 20, n, o)
 

@@ -2,6 +2,8 @@
 k_wavefront_finish) against the host restatement tests/wavefront_reference.py, which builds the phase from get_screens(), get_actuators()
 and env.tables.modes.  Shapes: N = 32 has 812 aperture pixels = 26 pixel tiles with 12 pixels in the last; B = 33 is two env tiles, the
 second holding one env; the padded mode counts are 16 (zernike-6), 32 (20 modes), 64 (64 modes) and 128 (100 modes at N = 64, 51 pixel tiles).
+N = 52 (EDGE, B = 40) has 2128 aperture pixels = 67 pixel tiles: the second chunk of 64 holds tiles 64 .. 66, so wave 3 of its workgroups
+has no tile, and the last tile has 16 real pixels.
 PARITY = 1e-5 is the project's standing bound for fast handles against float64, 1e-10 the float64 handles'.
 Each figure is printed before it is asserted (run with -s); the measured maxima are in profiles/wavefront_truth.md."""
 import ctypes as C
@@ -10,7 +12,7 @@ import numpy as np
 import pytest
 
 import wavefront_reference as wr
-from helpers import actions_for, smooth_screens
+from helpers import actions_for, assert_short_last_chunk, smooth_screens
 
 pytestmark = pytest.mark.gpu
 
@@ -18,6 +20,8 @@ N, B = 32, 33
 PARITY, PARITY64 = 1e-5, 1e-10
 KEYS = ("rms", "fit_rms", "coef", "ideal_actuators")
 CASES = {"apad16": ("zernike", 6, 32), "apad32": ("num_actuators", 20, 32), "apad64": ("num_actuators", 64, 32), "apad128": ("num_actuators", 100, 64)}
+EDGE, EDGE_B = ("num_actuators", 20, 52), 40   # a wave without tiles (not in CASES, which other files run in full)
+assert_short_last_chunk(EDGE[2])
 _TABLES = {}
 
 
@@ -67,26 +71,27 @@ def _raw_actions(torch, num_envs, A, seed):
 
 
 # ---- 1. parity with the host restatement ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("case", list(CASES) + ["edge52"])
 @pytest.mark.parametrize("precision", ["fast", "fp64"])
 def test_parity_with_the_host_restatement(case, precision):
     torch = _torch()
-    act_type, A, n = CASES[case]
+    act_type, A, n = CASES.get(case, EDGE)
+    nb = EDGE_B if case == "edge52" else B
     bound = PARITY if precision == "fast" else PARITY64
-    scr = smooth_screens(B, n, 31)
+    scr = smooth_screens(nb, n, 31)
     for raw in (True, False):
         # (the Shack-Hartmann chain, and with it SH_operation=True, is built for fast handles only: a float64 handle gets its raw actuator
         # vectors through set_actuators)
-        env = _env(B, act_type, A, n, screens=scr, SH_operation=raw and precision == "fast", precision=precision)
+        env = _env(nb, act_type, A, n, screens=scr, SH_operation=raw and precision == "fast", precision=precision)
         try:
             env.reset()
             if raw:   # (once per case: the flat mirror)
                 _hold(env, bound, f"{case} {precision} after reset")
             if raw and precision == "fp64":
-                env.set_actuators(_raw_actions(torch, B, A, 1).to(torch.float64))
+                env.set_actuators(_raw_actions(torch, nb, A, 1).to(torch.float64))
             else:
                 for t in range(2):
-                    env.step(_raw_actions(torch, B, A, t) if raw else torch.from_numpy(actions_for(B, A, t)).cuda())
+                    env.step(_raw_actions(torch, nb, A, t) if raw else torch.from_numpy(actions_for(nb, A, t)).cuda())
             _hold(env, bound, f"{case} {precision}, {'raw actuators' if raw else 'two steps of normalised actions'}")
         finally:
             env.close()
