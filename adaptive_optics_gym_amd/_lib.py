@@ -72,6 +72,11 @@ class AogObsMft(C.Structure):  # mirrors aog_obs_mft (ABI 20)
     _fields_ = [("o", C.c_int32), ("reserved0", C.c_int32), ("m1", C.POINTER(C.c_double)), ("m2", C.POINTER(C.c_double))]
 
 
+class AogPyramidTables(C.Structure):  # mirrors aog_pyramid_tables (additive in ABI 22; natural alignment, no aog_struct_size index)
+    _fields_ = [(n, C.c_int32) for n in ("samples", "pixels", "n_mod", "n_valid")] + [(n, C.c_void_p) for n in (
+        "m1", "m2", "b1", "b2", "m1s", "m2s", "b1s", "b2s", "valid")] + [(n, C.c_double) for n in ("fwd_unscale", "back_unscale", "photons")]
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -141,6 +146,11 @@ SYMBOLS = {
     "aog_upload_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_output_gradient": (C.c_int, [C.c_void_p] * 9),
     "aog_upload_gradient_obs": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "aog_upload_pyramid": (C.c_int, [C.c_void_p, C.POINTER(AogPyramidTables)]),
+    "aog_pyramid_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_pyramid_slopes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_upload_pyramid_reconstructor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_pyramid_update": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_selftest_poisson": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
     "aog_selftest_barrier_timeout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -86,6 +86,16 @@ class BatchedAOEnv:
     ``science_clear`` empties, ``science_exposure`` reads the mean PSF, its Strehl and the encircled energy inside ``science_radii``
     (lambda_sci / D; default 1, 2, 3, 5, 8 clipped to the window).  Off the step path: a step computes the same bits with or without it.
 
+    ``pyramid`` (default None: no sensor) switches the modulated pyramid wavefront sensor on: ``dict(samples=w_q, q=2, pixels=n_s, n_mod=8,
+    r_mod=3.0, photons=None, poke=0.01 lambda_wfs, rcond=1e-3, gain=0.4)`` — w_q focal samples per quadrant side at q per lambda_wfs / D, an
+    n_s x n_s image per quadrant, n_mod points on a circle of r_mod lambda / D (``pyramid_host``; ValueError for sizes it is not built for).
+    ``pyramid_frames`` / ``pyramid_slopes`` read the sensor at the state the last reset or step left, ``PYR_step`` runs its integrator
+    (``pyramid_calibrate``, lazily: push-pull pokes of ``poke`` metres through the device sensor on a flat scratch env, Tikhonov inverse with
+    ``rcond``); ``photons`` adds photon noise from a Philox stream keyed by (seed, global env id, pixel, sensor call).  Off the step path.  The response
+    is linear in small tilts only when the modulation points sit closer than a spot width, 2 pi r_mod / n_mod <~ 1 lambda / D: the default 8
+    points at r_mod = 3 close the loop (the integrator converges) but respond quadratically below 1 lambda / D; take n_mod = 32 at r_mod = 3,
+    or 12 at 1.5, for a linear sensor (``profiles/pyramid_wfs.md``).
+
     ``obs_gradient`` (default False) switches the observation gradient of the separable observation route on (``obs_dim`` 6 .. 32; float64
     envs from 8): ``output_gradient`` then takes ``g_obs`` and returns the float64 ``obs_raw`` in its values, and ``autograd.step_outputs``
     differentiates through the observation.  ``ValueError`` on a table-route env, which has that gradient already; ``env.obs_gradient``
@@ -98,7 +108,7 @@ class BatchedAOEnv:
                  num_pupil_pixels=240, seed=None, screen_source="device", screen_oversampling=16, screens=None,
                  precision="fast", kernel="auto", pixel_chunks=0, rng=None, verbose=True, params=None,
                  global_env_offset=0, total_envs=None, sh_fft_precision="single", screen_method="twoband", tables=None, extrusion="auto",
-                 obs_photons=None, obs_read_noise=0.0, obs_background=0.0, science_window=None, science_radii=None, obs_gradient=False):
+                 obs_photons=None, obs_read_noise=0.0, obs_background=0.0, science_window=None, science_radii=None, obs_gradient=False, pyramid=None):
         import torch
 
         self._handle = None   # (first: close() and accumulate_returns() read it on an env whose construction failed below)
@@ -175,6 +185,12 @@ class BatchedAOEnv:
         self._science = None           # optics_host.ScienceTables of the science camera (science_window)
         self._science_uploaded = False
         self.science_window = self.science_radii = None
+        self.pyramid = None            # the sensor's settings (pyramid=dict(...)), its host tables and what was uploaded
+        self._pyramid = None
+        self._pyramid_uploaded = False
+        self._pyramid_calibrated = False
+        self.pyramid_frame_count = 0   # sensor calls since the upload: the frame of the photon stream
+        self._precision, self._kernel, self._pixel_chunks = precision, kernel, pixel_chunks
 
         self.observation_space = make_box(-1, 1, (self.obs_dim ** 2,), np.float16)  # AO_env.py:45
         self.action_space = make_box(-1, 1, (self.num_modes,), np.float16)          # AO_env.py:46
@@ -202,6 +218,21 @@ class BatchedAOEnv:
             self.science_radii = self._science.radii.copy()
         elif science_radii is not None:
             raise ValueError("science_radii without science_window: the science camera is off")
+        if pyramid is not None:
+            from .pyramid_host import pyramid_tables
+
+            cfg = dict(samples=32, q=2, pixels=32, n_mod=8, r_mod=3.0, photons=None, poke=0.01 * self.params.wavelength_wfs, rcond=1e-3, gain=0.4)
+            unknown = set(pyramid) - set(cfg)
+            if unknown:
+                raise ValueError(f"pyramid: unknown keys {sorted(unknown)}")
+            cfg.update(pyramid)
+            if cfg["photons"] is not None and not (np.isfinite(cfg["photons"]) and cfg["photons"] > 0):
+                raise ValueError("pyramid: photons must be None or a positive number")
+            if not (cfg["poke"] > 0 and cfg["rcond"] > 0 and np.isfinite(cfg["gain"])):
+                raise ValueError("pyramid: poke and rcond must be positive, gain finite")
+            self._pyramid = pyramid_tables(self.num_pupil_pixels, self.tables.n_ap, cfg["samples"], cfg["q"], cfg["pixels"], cfg["n_mod"],
+                                           cfg["r_mod"])   # (ValueError before anything is created)
+            self.pyramid = cfg
         self._create_handle(precision, kernel, pixel_chunks)
         self._upload_tables()
         layer = self._draw_wind_and_stencils()
@@ -278,6 +309,8 @@ class BatchedAOEnv:
         self._gradient_uploaded = False        # (and the gradient's operand tables, the observation's among them; output_gradient uploads them again)
         self._upload_keep = (keep, tabs)       # (output_gradient hands the same host tables to aog_upload_gradient)
         self._upload_science()
+        self._pyramid_uploaded = self._pyramid_calibrated = False   # (and the pyramid sensor, with its reconstructor)
+        self._upload_pyramid()
         if self.obs_route == "separable":
             om1 = np.ascontiguousarray(np.stack([t.obs_m1.real, t.obs_m1.imag], axis=-1), dtype=np.float64)
             om2 = np.ascontiguousarray(np.stack([t.obs_m2.real, t.obs_m2.imag], axis=-1), dtype=np.float64)
@@ -1160,6 +1193,111 @@ class BatchedAOEnv:
         _lib.check(self.lib.aog_science_read(self._handle, int(first), count, p(out["psf"].data_ptr()) if image else None, p(out["strehl"].data_ptr()),
                                              p(out["encircled_energy"].data_ptr()), p(out["frames"].data_ptr()), self._stream()))
         return out
+
+    # ------------------------------------------------------------------------------------------------
+    # modulated pyramid wavefront sensor
+    def _upload_pyramid(self):
+        """The sensor's host tables to the handle (``aog_upload_pyramid``); no-op without ``pyramid=`` or when they are there."""
+        t = self._pyramid
+        if t is None or self._pyramid_uploaded:
+            return
+        from .pyramid_host import packed_operands
+
+        c2 = lambda z: np.ascontiguousarray(np.stack([z.real, z.imag], axis=-1), dtype=np.float64)
+        keep = dict(m1=c2(t.m1), m2=c2(t.m2), b1=c2(t.b1), b2=c2(t.b2), valid=np.ascontiguousarray(t.valid, dtype=np.int32))
+        ops = packed_operands(t)
+        keep.update({k: ops[k] for k in ("m1s", "m2s", "b1s", "b2s")})
+        p = lambda a: a.ctypes.data
+        tabs = _lib.AogPyramidTables(t.samples, t.pixels, t.n_mod, t.n_valid, p(keep["m1"]), p(keep["m2"]), p(keep["b1"]), p(keep["b2"]), p(keep["m1s"]),
+                                     p(keep["m2s"]), p(keep["b1s"]), p(keep["b2s"]), p(keep["valid"]), ops["fwd_unscale"], ops["back_unscale"],
+                                     float(self.pyramid["photons"] or 0.0))
+        _lib.check(self.lib.aog_upload_pyramid(self._handle, C.byref(tabs)))
+        self._pyramid_uploaded = True
+        self.pyramid_frame_count = 0
+
+    def _pyramid_mask(self, mask, who):
+        """``who``'s checks, then its mask as a device pointer (None: every env) and the tensor that keeps it alive."""
+        if self._pyramid is None:
+            raise ValueError(f"{who}: this environment was built without a pyramid sensor (pyramid=dict(...))")
+        self._upload_pyramid()
+        if mask is None:
+            return None, None
+        sel = _mask_array(mask, self.num_envs, who)
+        m = self._torch.from_numpy(sel.astype(np.uint8)).to(self.device)
+        return C.c_void_p(m.data_ptr()), m
+
+    def pyramid_frames(self, mask=None, out=None):
+        """The pyramid sensor's frame of every env at the state the last ``reset`` / ``step`` left: [B, 4, n_s, n_s] float64, quadrant
+        2 (k_y > 0) + (k_x > 0).  ``mask``: the rows of the envs it leaves out are not written (``out``: the tensor to write into).
+        Stream-ordered; changes nothing a step reads.  Raises like ``science_integrate`` while an action is pending and between two steps
+        of a lookahead episode."""
+        torch = self._torch
+        ptr, _keep = self._pyramid_mask(mask, "pyramid_frames")
+        ns = self._pyramid.pixels
+        if out is None:
+            out = torch.zeros((self.num_envs, 4, ns, ns), dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (self.num_envs, 4, ns, ns) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("pyramid_frames(out=...): expected a contiguous float64 [B, 4, n_s, n_s] tensor on the env's device")
+        _lib.check(self.lib.aog_pyramid_frames(self._handle, ptr, C.c_void_p(out.data_ptr()), self._stream()))
+        self.pyramid_frame_count += 1
+        return out
+
+    def pyramid_slopes(self, mask=None, out=None):
+        """The sensor's slopes [B, 2 n_valid] float64: s_x over the valid pixels (``env._pyramid.valid``), then s_y.  As ``pyramid_frames``."""
+        torch = self._torch
+        ptr, _keep = self._pyramid_mask(mask, "pyramid_slopes")
+        shape = (self.num_envs, 2 * self._pyramid.n_valid)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("pyramid_slopes(out=...): expected a contiguous float64 [B, 2 n_valid] tensor on the env's device")
+        _lib.check(self.lib.aog_pyramid_slopes(self._handle, ptr, C.c_void_p(out.data_ptr()), self._stream()))
+        self.pyramid_frame_count += 1
+        return out
+
+    def pyramid_calibrate(self):
+        """Calibrate the reconstructor through the device sensor itself: on a scratch env of 2 A + 1 flat wavefronts (same tables, precision
+        and sensor, no photon noise) mode k is pushed and pulled by ``poke`` metres, response[:, k] = (s+ - s-) / (2 poke), the command
+        matrix is ``inverse_tikhonov(response, rcond)`` and the reference slopes are the flat wavefront's.  Returns (command matrix
+        [A, 2 n_valid], reference slopes [2 n_valid]) as numpy arrays (also ``pyramid_response``); ``PYR_step`` calls it when needed."""
+        from .optics_host import inverse_tikhonov
+
+        self._pyramid_mask(None, "pyramid_calibrate")
+        A, N, cfg = self.num_modes, self.num_pupil_pixels, self.pyramid
+        sensor = {k: cfg[k] for k in ("samples", "q", "pixels", "n_mod", "r_mod")}
+        scratch = BatchedAOEnv(2 * A + 1, self.device, act_type=self.act_type, act_dim=A, obs_dim=self.obs_dim, rew_type=self.rew_type,
+                               params=self.params, screens=np.zeros((2 * A + 1, N, N)), precision=self._precision, kernel=self._kernel,
+                               tables=self.tables, pyramid=sensor, verbose=False)
+        try:
+            act = np.zeros((2 * A + 1, A))
+            act[1:A + 1] = cfg["poke"] * np.eye(A)
+            act[A + 1:] = -cfg["poke"] * np.eye(A)
+            scratch.set_actuators(act)
+            s = scratch.pyramid_slopes().cpu().numpy()
+        finally:
+            scratch.close()
+        self.pyramid_response = (s[1:A + 1] - s[A + 1:]).T / (2.0 * cfg["poke"])          # [2 n_valid, A]
+        recon = np.ascontiguousarray(inverse_tikhonov(self.pyramid_response, cfg["rcond"]), dtype=np.float64)
+        ref = np.ascontiguousarray(s[0], dtype=np.float64)
+        _lib.check(self.lib.aog_upload_pyramid_reconstructor(self._handle, recon.ctypes.data_as(C.c_void_p), ref.ctypes.data_as(C.c_void_p)))
+        self.pyramid_reconstructor, self.pyramid_reference_slopes = recon, ref
+        self._pyramid_calibrated = True
+        return recon, ref
+
+    def PYR_step(self):
+        """The pyramid sensor's integrator, the counterpart of ``SH_step``: one sensor call, then a <- a - gain R (s - s_ref) for every env.
+        Returns (actuators [B, A] float64, slopes [B, 2 n_valid] float64); the mirror itself is not touched — step with the actuators
+        (an env built with ``SH_operation=True`` takes them as its action)."""
+        torch = self._torch
+        self._pyramid_mask(None, "PYR_step")
+        if not self._pyramid_calibrated:
+            self.pyramid_calibrate()
+        act = torch.empty((self.num_envs, self.num_modes), dtype=torch.float64, device=self.device)
+        slopes = torch.empty((self.num_envs, 2 * self._pyramid.n_valid), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.aog_pyramid_update(self._handle, float(self.pyramid["gain"]), C.c_void_p(act.data_ptr()), C.c_void_p(slopes.data_ptr()),
+                                               self._stream()))
+        self.pyramid_frame_count += 1
+        return act, slopes
 
     def phase_screen(self, env_index=0):
         """Atmospheric phase at the sensing wavelength [N, N] float32 radians (0 outside the aperture, aperture mean removed) — the

@@ -670,6 +670,7 @@ int aog_upload_tables(aog_env* e, const aog_tables* t) {
   e->wf_ready = false;          // and the wavefront fit belongs to the old mode matrix (aog_upload_wavefront_fit)
   e->sci_ready = false;         // the science camera's aperture table to the old aperture (aog_upload_science)
   e->grad_ready = false;        // the gradient's operand tables to the old tables (aog_upload_gradient)
+  e->pyr_ready = e->pyr_rec_ready = false;   // the pyramid sensor's matrices and mask to the old aperture (aog_upload_pyramid)
   e->gobs_ready = false;        // (and the observation gradient of the separable route with them: aog_upload_gradient_obs)
   const int n_ap = e->n_ap, A = e->A, N2 = e->cfg.n_pupil * e->cfg.n_pupil;
   for (int p = 0; p < n_ap; ++p) {

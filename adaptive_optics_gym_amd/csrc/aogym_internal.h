@@ -183,6 +183,38 @@ struct aog_env {
   int32_t* sci_bin = nullptr;    // [w][w] radial bin of each pixel of the window (-1: outside every radius)
   double* sci_exposure = nullptr;   // [B][w][w] sum of the integrated frames
   int32_t* sci_frames = nullptr;    // [B] frames integrated
+  // pyramid wavefront sensor (aog_upload_pyramid, aog_pyramid_*; pyramid.hip).  Nothing here is read or written by a reset or step, and none
+  // of it is part of the aog_get_state blob.  Every buffer is allocated by aog_upload_pyramid / aog_upload_pyramid_reconstructor.
+  bool pyr_ready = false;        // the sensor is uploaded (aog_upload_tables clears it)
+  bool pyr_rec_ready = false;    // and its reconstructor
+  int pyr_wq = 0, pyr_ns = 0, pyr_nmod = 0, pyr_nvalid = 0;   // samples per quadrant side, detector pixels per side, modulation points, valid pixels
+  double pyr_photons = 0;        // photo-electrons per unit of frame value (0: no photon noise)
+  uint64_t pyr_frame = 0;        // sensor calls since the upload: the frame of the photon stream's counter
+  float pyr_unscale = 1.f;       // what undoes the powers of two of m1s x m2s
+  double pyr_back_unscale = 1.0; // and of the stored field x b1s x b2s
+  _Float16* pyr_m1s = nullptr;   // [n_mod] x the science camera's m1s layout with ceil(w / 32) v blocks
+  _Float16* pyr_m2s = nullptr;   // [n_mod] x its m2s layout
+  _Float16* pyr_b1s = nullptr;   // [2][ceil(n_s / 32)][ceil(w / 32)][2] tiles: column y', K = v in accumulator order
+  _Float16* pyr_b2s = nullptr;   // [2][ceil(n_s / 32)][ceil(w / 32)][2] tiles: column x', K = u in accumulator order
+  MftWork pyr_work;              // phases at lambda_wfs; Nxp = N rounded up to 128, ceil(w / 32) v blocks
+  _Float16* pyr_fop = nullptr;   // [chunk][u block][v block][2][4][64][8]: F_j 2^6, split, k_pyr_back's A operands (row u, K = v)
+  _Float16* pyr_act16 = nullptr; // the calls' own copy of the actuators in act16's layout, and their third f16 term
+  _Float16* pyr_act_ll = nullptr;
+  float* pyr_tile_keep = nullptr;  // dynamic handles whose psi_tile a sensor call refreshes (obs_tiles): psi_tile as the call found it, put back behind the call
+  double* pyr_m1d = nullptr;     // float64 handles: the four tables, E [N][N], T [w][N], F [w][w], X [2][n_s][w], G [4][n_s][n_s] complex
+  double* pyr_m2d = nullptr;
+  double* pyr_b1d = nullptr;
+  double* pyr_b2d = nullptr;
+  double* pyr_E = nullptr;
+  double* pyr_T = nullptr;
+  double* pyr_F = nullptr;
+  double* pyr_X = nullptr;
+  double* pyr_G = nullptr;
+  int32_t* pyr_valid = nullptr;  // [n_valid] y n_s + x of the valid pixels
+  double* pyr_acc = nullptr;     // [B][4][n_s][n_s] sum over the modulation points of the call in flight
+  double* pyr_slopes = nullptr;  // [B][2 n_valid] slopes of the last aog_pyramid_update
+  double* pyr_recon = nullptr;   // [A][2 n_valid]
+  double* pyr_ref = nullptr;     // [2 n_valid]
   // state
   float* psi_rev = nullptr;     // [n_quads][Bp][4]  (handles that run the VALU kernel only)
   double* pack_mean = nullptr;   // [B] aperture means of the screens being installed (k_screen_means -> k_pack_tiles)

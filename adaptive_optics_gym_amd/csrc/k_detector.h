@@ -9,7 +9,7 @@ namespace aog {
 //   {j | kDetTag << 24,  ge,  frame & 0xFFFFFFFF,  (frame >> 32) ^ kDetFrameXor}
 // word 0: the Poisson uniform (small branch) / Box-Muller radius (large branch), word 1: the large branch's angle, words 2, 3: radius and
 // angle of the read-noise normal.  Word 3 of the counter tells the stream from the others under the same key: extrusion normals (0), screen
-// synthesis (0x5C4EE7 / 8), Shack-Hartmann camera (0x50155), policy query (call_hi ^ 0xAC70, tags 1 .. 5 in word 0).
+// synthesis (0x5C4EE7 / 8), Shack-Hartmann camera (0x50155), policy query (call_hi ^ 0xAC70, tags 1 .. 5 in word 0), pyramid sensor (frame_hi ^ 0x9F2A31D, k_pyramid.h).
 constexpr uint32_t kDetTag = 6u;
 constexpr uint32_t kDetFrameXor = 0xDE7EC7u;
 

@@ -141,6 +141,12 @@ def wavefront_fit(modes: np.ndarray) -> np.ndarray:
 # ------------------------------------------------------------------------------------------------
 # step-index fiber LP modes (hcipy StepIndexFiber / make_LP_modes; AO_env.py:393)
 # ------------------------------------------------------------------------------------------------
+def inverse_tikhonov(response, rcond):
+    """hcipy's inverse_tikhonov: pinv with singular values s -> s / (s^2 + (rcond s_max)^2); the command matrix of the Shack-Hartmann baseline and of the pyramid sensor."""
+    U, S, Vt = np.linalg.svd(np.asarray(response, dtype=np.float64), full_matrices=False)
+    return (Vt.T * (S / (S ** 2 + (rcond * S.max()) ** 2))) @ U.T
+
+
 def lp_roots(m: int, V: float):
     """Guided-mode roots u in (0, V) of the LP characteristic equation, written pole-free:
     J_m(u) w K_{m+1}(w) - K_m(w) u J_{m+1}(u) = 0,  w = sqrt(V^2 - u^2)."""

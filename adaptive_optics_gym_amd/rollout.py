@@ -269,7 +269,9 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     Shack-Hartmann integrator on the device; needs an env built with ``SH_operation=True``), ``actor`` may be None and ``log_prob`` holds the
     reference's constant 1.  ``policy="ideal"``: the ideal modal controller — every step's action is ``env.ideal_action()``, the best-fit
     mirror command of the state the last observation saw, applied to the next screen (the one-frame lag every controller has): the ceiling
-    Shack-Hartmann and learnt policies are read against.  Same conditions and ``log_prob`` as ``"shack"``.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
+    Shack-Hartmann and learnt policies are read against.  Same conditions and ``log_prob`` as ``"shack"``.  ``policy="pyramid"``: every
+    step's action is ``env.PYR_step()[0]``, the modulated pyramid sensor's integrator (an env built with ``pyramid=dict(...)`` and
+    ``SH_operation=True``, which makes the action the raw actuators); same ``log_prob``.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
     action before the env sees it (and before it is stored, like the reference's in-place ``action +=``), or a ``DeviceOUNoise``
     (``main.py:218-220``: mu 0, theta 0.3, sigma 0.05), which the HIP policy query advances and adds itself: float64 state, Philox normals keyed
     by the global env id (a split batch reproduces the whole one), no extra launch.  Neither is reset here, as in the reference.
@@ -296,19 +298,21 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     B = env.num_envs
     if gatherer is None:
         gatherer = EpisodeReturnGatherer(B, env.device, False)
-    if policy not in ("actor", "shack", "ideal"):
-        raise ValueError("policy must be 'actor', 'shack' or 'ideal'")
+    if policy not in ("actor", "shack", "ideal", "pyramid"):
+        raise ValueError("policy must be 'actor', 'shack', 'ideal' or 'pyramid'")
     if action_mode not in ("sample", "mean"):
         raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
-    ideal = policy == "ideal"
-    shack = policy == "shack" or ideal   # (no policy query either way: the action is a controller's raw actuator vector)
+    ideal, pyramid = policy == "ideal", policy == "pyramid"
+    shack = policy == "shack" or ideal or pyramid   # (no policy query either way: the action is a controller's raw actuator vector)
     dev_ou = isinstance(ou_noise, DeviceOUNoise)
     if shack and (dev_ou or action_mode != "sample"):
         raise ValueError(f"policy={policy!r} takes neither a DeviceOUNoise nor action_mode='mean' (the "
-                         f"{'ideal modal controller' if ideal else 'Shack-Hartmann integrator'} is not a policy query)")
+                         f"{'ideal modal controller' if ideal else 'pyramid integrator' if pyramid else 'Shack-Hartmann integrator'} is not a policy query)")
     if shack:
         if not getattr(env, "SH_operation", False):
             raise ValueError(f"policy={policy!r} needs an env created with SH_operation=True (AO_env.py:115-116, 254)")
+        if pyramid and getattr(env, "pyramid", None) is None:
+            raise ValueError("policy='pyramid' needs an env created with pyramid=dict(...)")
         actor_impl = "none"
     elif actor_impl == "auto":
         actor_impl = "hip" if actor_layers(actor) is not None and next(actor.parameters()).is_cuda else "torch"
@@ -374,7 +378,7 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                         mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
                     if shack:
                         # (actuators [B, A] float64, the reference's constant log-probability 1; 'ideal': from the state the last observation saw)
-                        sh_act = env.ideal_action() if ideal else env.SH_step()[0]
+                        sh_act = env.ideal_action() if ideal else env.PYR_step()[0] if pyramid else env.SH_step()[0]
                         out["act"][i].copy_(sh_act)
                         out["log_prob"][i].fill_(1.0)
                         action = out["act"][i]

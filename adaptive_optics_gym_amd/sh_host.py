@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .optics_host import HostTables, centred_axis, focal_axis
+from .optics_host import HostTables, centred_axis, focal_axis, inverse_tikhonov
 from .params import OpticalParams
 
 
@@ -88,8 +88,7 @@ class ShackHartmannHost:
                 acc = acc + amp * self.slopes(self.image(field, 1.0)) / probe ** 2          # np.var([-p, p]) = p^2
             response[:, i] = acc
         self.response = response
-        U, S, Vt = np.linalg.svd(response, full_matrices=False)
-        self.reconstruction = (Vt.T * (S / (S ** 2 + (1e-3 * S.max()) ** 2))) @ U.T        # [A, 2 n_sub]
+        self.reconstruction = inverse_tikhonov(response, 1e-3)                              # [A, 2 n_sub]
         # source used by SH_step: Wavefront(aperture, lambda_wfs).total_power = 3.9e10 * 10^(-m/2.5) (AO_env.py:324-326)
         self.amp_wfs = np.sqrt(3.9e10 * 10 ** (-p.stellar_magnitude / 2.5) / (self.n_ap * self.pix_area_pupil))
 

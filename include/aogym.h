@@ -537,6 +537,70 @@ int aog_output_gradient(aog_env* env, const double* g_obs_dev, const double* g_p
  * variable AOG_GRAD_OBS_CHUNK (read here).  Float64 handles: one env at a time, plain float64 products. */
 int aog_upload_gradient_obs(aog_env* env, const aog_obs_mft* mft);
 
+/* ---- modulated pyramid wavefront sensor (additive in ABI 22; no counterpart in the reference) ----
+ * Per env, E = exp(2 pi i u) on the aperture (u = screen + mirror phase in revolutions of lambda_wfs, as the step kernels form it).  For
+ * each of n_mod modulation points j the focal field on a w x w window (w = 2 samples) is the matrix Fourier transform F_j = m1_j E m2_j,
+ * the modulation tilt folded into the matrices; quadrant (s_y, s_x) of F_j is carried back to an n_s x n_s pupil image G = b1_{s_y} F_j
+ * b2_{s_x} (b1 / b2 hold zeros outside their half of the window, so every product runs over the whole window), and the frame is
+ *   I[q][y][x] = (1 / n_mod) sum_j |G_{q,j}[y][x]|^2,   q = 2 (s_y > 0) + (s_x > 0),   float64, j ascending.
+ * With photons > 0 every pixel is replaced by large_poisson(photons x I) / photons from ONE Philox4x32-10 call keyed by the handle's rng_seed
+ * with counter {q n_s^2 + y n_s + x, global env id, frame & 0xFFFFFFFF, (frame >> 32) ^ 0x9F2A31D}, frame = the number of sensor calls
+ * (aog_pyramid_frames / _slopes / _update) made on the handle since the upload: word 0 is the Poisson uniform or the Box-Muller radius, word
+ * 1 the angle.  Slopes over the n_valid pixels of `valid` (indices y n_s + x, ascending):
+ *   s_x[k] = (I[1] + I[3] - I[0] - I[2])[valid k] / Ibar,  s_y[k] = (I[2] + I[3] - I[0] - I[1])[valid k] / Ibar,
+ *   Ibar = mean over the valid pixels of I[0] + I[1] + I[2] + I[3];   slopes [B][2 n_valid] = s_x then s_y.
+ * All host tables are HOST pointers.  float64: m1 [n_mod][w][N][2], m2 [n_mod][N][w][2], b1 [2][n_s][w][2], b2 [2][w][n_s][2] (index 0: the
+ * k < 0 half).  Split-f16 operand tiles for fast handles (IEEE half bits; one tile = [re hi, re lo, im hi, im lo][lane 64][8]): m1s per j
+ * in the science camera's m1s layout [ceil(w/32)][ceil(N/16)] tiles, m2s per j in its m2s layout [ceil(w/32)][Nxp/32][2] tiles (Nxp = N
+ * rounded up to 128), b1s [2][ceil(n_s/32)][ceil(w/32)][2] and b2s likewise in the m2s layout with the window index in the place of x (the
+ * order accumulator registers hold it); fwd_unscale / back_unscale: what undoes the powers of two the forward / back tables were scaled
+ * by (both products of a pair).  Float64 validation handles read the float64 tables, fast handles the operand tiles.  The struct is
+ * four int32, nine pointers and three doubles in natural alignment; it has no index in aog_struct_size. */
+typedef struct aog_pyramid_tables {
+  int32_t samples;      /* w_q: focal samples per quadrant side, 8 .. 64 */
+  int32_t pixels;       /* n_s: detector pixels per image side, 8 .. 64 and <= n_pupil */
+  int32_t n_mod;        /* 1 .. 32 */
+  int32_t n_valid;      /* 1 .. n_s^2 */
+  const double* m1;
+  const double* m2;
+  const double* b1;
+  const double* b2;
+  const uint16_t* m1s;
+  const uint16_t* m2s;
+  const uint16_t* b1s;
+  const uint16_t* b2s;
+  const int32_t* valid; /* [n_valid] */
+  double fwd_unscale;
+  double back_unscale;
+  double photons;       /* expected photo-electrons per frame of a beam that puts 1 into every pixel (0: no photon noise) */
+} aog_pyramid_tables;
+
+/* Install the sensor.  After aog_upload_tables (a later aog_upload_tables clears it); every buffer of the sensor is allocated here, so
+ * handles that never ask keep their device_bytes and their launches.  A second upload replaces the first and restarts the frame count.
+ * Work proceeds in chunks of whole env tiles, capped at ~256 MB per work buffer or at the environment variable AOG_PYRAMID_CHUNK (read
+ * here).  AOG_ERR_INVALID for a size outside the ranges above, a bad valid index or a non-finite / negative photons. */
+int aog_upload_pyramid(aog_env* env, const aog_pyramid_tables* tables);
+
+/* The frame of every env (mask_dev: nullable [B] uint8 device array, non-zero = selected; the rows of the others are not touched) into
+ * frames_dev [B][4][n_s][n_s] float64.  Stream-ordered, no host synchronisation, no atomics: an env's frame depends on its own operands
+ * only, not on how envs are grouped into handles, masks or chunks.  Fast handles: the phase grid once, then per modulation point the
+ * science camera's two matrix-core passes (the second storing the field as split-f16 operands) and one wave per (env, quadrant) for both
+ * back products; float64 handles: plain float64 kernels per env.  Reads the state the last reset or step left and changes nothing a step
+ * reads or writes.  AOG_ERR_STATE before tables, screens or aog_upload_pyramid, while a pipelined or policy-attached step has an action
+ * pending, and between two steps of a lookahead episode. */
+int aog_pyramid_frames(aog_env* env, const uint8_t* mask_dev, double* frames_dev, void* stream);
+
+/* The same call, finished to slopes_dev [B][2 n_valid] float64 (frames stay in a buffer of the sensor). */
+int aog_pyramid_slopes(aog_env* env, const uint8_t* mask_dev, double* slopes_dev, void* stream);
+
+/* Reconstructor R [A][2 n_valid] and reference slopes s_ref [2 n_valid], float64 HOST pointers.  After aog_upload_pyramid. */
+int aog_upload_pyramid_reconstructor(aog_env* env, const double* recon_host, const double* slopes_ref_host);
+
+/* One sensor call, then the integrator act_out[e][k] = a[e][k] - gain sum_i R[k][i] (s[e][i] - s_ref[i]) with a the current actuators, into
+ * act_out_dev [B][A] float64 (float64 sums over i ascending, no fused multiply-add).  The mirror itself is not touched: the caller steps
+ * with act_out.  slopes_dev: nullable [B][2 n_valid], the slopes it used.  AOG_ERR_STATE before aog_upload_pyramid_reconstructor. */
+int aog_pyramid_update(aog_env* env, double gain, double* act_out_dev, double* slopes_dev, void* stream);
+
 /* ---- policy query of the rollout (Actor.forward + Actor.get_action, network.py:17-69; caller algorithm.py:216-296) ----
  * mean = W_o drop(relu(W_3 drop(relu(W_2 drop(relu(W_1 obs + b_1)) + b_2)) + b_3)) + b_o with nn.Dropout(dropout_p) ACTIVE
  * (the reference never leaves training mode while acting), action = mean + sqrt(cov_var) eps, eps ~ N(0, I),
