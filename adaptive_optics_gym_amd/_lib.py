@@ -151,6 +151,7 @@ SYMBOLS = {
     "aog_pyramid_slopes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_upload_pyramid_reconstructor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_pyramid_update": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_pyramid_gradient": (C.c_int, [C.c_void_p] * 9),
     "aog_selftest_poisson": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
     "aog_selftest_barrier_timeout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

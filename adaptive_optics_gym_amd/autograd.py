@@ -1,4 +1,4 @@
-"""``env.step`` as a differentiable function of the action (``torch.autograd``)."""
+"""``env.step`` as a differentiable function of the action, and the pyramid sensor as one of the mirror command (``torch.autograd``)."""
 from __future__ import annotations
 
 import torch
@@ -47,3 +47,34 @@ def step_outputs(env, action):
     ignored, while power and Strehl keep theirs."""
     obs_raw, power, strehl = _StepOutputs.apply(action, env)
     return obs_raw, power, strehl
+
+
+class _PyramidOutput(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, actuators, env, which):
+        a = actuators.detach().to(torch.float64).contiguous()
+        frames, slopes = env.pyramid_clean(actuators=a)   # the gradient call's forward half alone
+        ctx.env, ctx.epoch, ctx.act, ctx.which, ctx.in_dtype = env, env.state_epoch, a, which, actuators.dtype
+        return slopes if which == "slopes" else frames
+
+    @staticmethod
+    def backward(ctx, g):
+        env = ctx.env
+        if env.state_epoch != ctx.epoch:
+            raise RuntimeError("pyramid_" + ctx.which + ": the environment has been stepped, reset or restored since the forward pass; the "
+                               "gradient is that of the state it saw and can only be taken before the state moves on")
+        kw = {"g_slopes": g} if ctx.which == "slopes" else {"g_frames": g}
+        return env.pyramid_gradient(actuators=ctx.act, **kw).to(ctx.in_dtype), None, None
+
+
+def pyramid_slopes(env, actuators):
+    """The clean slopes [B, 2 n_valid] (float64) of ``env``'s pyramid sensor with the mirror at ``actuators`` [B, A] (metres of surface, the
+    units of ``get_actuators()``), differentiable with respect to ``actuators``.  The atmosphere is the state the last reset or step left;
+    the mirror itself is not moved.  Forward is ``env.pyramid_clean``, backward one ``env.pyramid_gradient`` call; backward raises ``RuntimeError`` once
+    the env has been stepped, reset or restored since.  Photon noise is not part of it."""
+    return _PyramidOutput.apply(actuators, env, "slopes")
+
+
+def pyramid_frames(env, actuators):
+    """As ``pyramid_slopes``, for the clean frames [B, 4, n_s, n_s]."""
+    return _PyramidOutput.apply(actuators, env, "frames")

@@ -1085,6 +1085,16 @@ class BatchedAOEnv:
         """True when ``output_gradient`` takes ``g_obs`` on this separable-route env (the ``obs_gradient=True`` keyword; read-only)."""
         return self._obs_gradient
 
+    def _upload_gradient(self):
+        """The output gradient's tables to the handle (``aog_upload_gradient`` and, on ``obs_gradient`` envs, ``aog_upload_gradient_obs``);
+        no-op when they are there."""
+        if self._gradient_uploaded:
+            return
+        _lib.check(self.lib.aog_upload_gradient(self._handle, C.byref(self._upload_keep[1])))
+        if self._obs_gradient:
+            _lib.check(self.lib.aog_upload_gradient_obs(self._handle, C.byref(self._obs_mft_keep[2])))
+        self._gradient_uploaded = True
+
     def output_gradient(self, g_obs=None, g_power=None, g_strehl=None, wrt="actuators", action=None, with_values=False):
         """Vector-Jacobian product of the optical outputs at the state the last reset or step left (``aog_output_gradient``): the gradient of
         ``L = sum(g_obs * obs_raw) + sum(g_power * power) + sum(g_strehl * strehl)`` (cotangents: [B, o^2], [B], [B]; ``None`` = zero, at
@@ -1106,11 +1116,7 @@ class BatchedAOEnv:
             raise ValueError("output_gradient: wrt must be 'actuators' or 'action' (or None with with_values=True: the values alone)")
         if wrt is None and not with_values:
             raise ValueError("output_gradient: wrt=None asks for the values alone and needs with_values=True")
-        if not self._gradient_uploaded:
-            _lib.check(self.lib.aog_upload_gradient(self._handle, C.byref(self._upload_keep[1])))
-            if self._obs_gradient:
-                _lib.check(self.lib.aog_upload_gradient_obs(self._handle, C.byref(self._obs_mft_keep[2])))
-            self._gradient_uploaded = True
+        self._upload_gradient()
         B, A, n = self.num_envs, self.num_modes, self.obs_dim ** 2
 
         def cot(x, shape, name):
@@ -1254,6 +1260,62 @@ class BatchedAOEnv:
         _lib.check(self.lib.aog_pyramid_slopes(self._handle, ptr, C.c_void_p(out.data_ptr()), self._stream()))
         self.pyramid_frame_count += 1
         return out
+
+    def pyramid_gradient(self, g_frames=None, g_slopes=None, actuators=None, mask=None, with_values=False):
+        """Vector-Jacobian product of the sensor's clean frame and slopes (``aog_pyramid_gradient``): the gradient of
+        ``L = sum(g_frames * frame) + sum(g_slopes * slopes)`` (cotangents [B, 4, n_s, n_s] and [B, 2 n_valid]; ``None`` = zero, at least one
+        given) with respect to ``get_actuators()`` (per metre of surface), a float64 device tensor [B, A].  ``actuators`` [B, A]: evaluate
+        there instead of at the mirror's own (the mirror is not written).  ``mask``: the rows of the envs it leaves out are not written
+        (they read as zeros).  ``with_values=True`` returns ``(grad, frames, slopes)`` with the clean frame and slopes at that point.
+        Photon noise is not differentiated: the call draws nothing and leaves ``pyramid_frame_count`` alone.  Fast envs run the backward
+        pass on the matrix cores (built for ``samples`` <= 32); float64 envs a plain float64 chain per env.  Stream-ordered; raises like ``pyramid_frames`` while an action
+        is pending and between two steps of a lookahead episode."""
+        torch = self._torch
+        if g_frames is None and g_slopes is None:
+            raise ValueError("pyramid_gradient: at least one of g_frames and g_slopes must be given")
+        if self._pyramid is None:
+            raise ValueError("pyramid_gradient: this environment was built without a pyramid sensor (pyramid=dict(...))")
+        B, A, ns, nv = self.num_envs, self.num_modes, self._pyramid.pixels, self._pyramid.n_valid
+
+        def arg(x, shape, name):
+            if x is None:
+                return None
+            t = torch.as_tensor(x, device=self.device).to(torch.float64)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"pyramid_gradient: {name} must have shape {shape}, got {tuple(t.shape)}")
+            return t.contiguous()
+
+        gf, gs = arg(g_frames, (B, 4, ns, ns), "g_frames"), arg(g_slopes, (B, 2 * nv), "g_slopes")
+        act = arg(actuators, (B, A), "actuators")
+        mptr, _keep = self._pyramid_mask(mask, "pyramid_gradient")
+        if self._precision != "fp64":
+            self._upload_gradient()   # (fast handles contract with the output gradient's modes operands)
+        grad = torch.zeros((B, A), dtype=torch.float64, device=self.device)
+        frames = torch.zeros((B, 4, ns, ns), dtype=torch.float64, device=self.device) if with_values else None
+        slopes = torch.zeros((B, 2 * nv), dtype=torch.float64, device=self.device) if with_values else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self.lib.aog_pyramid_gradient(self._handle, mptr, ptr(gf), ptr(gs), ptr(act), ptr(grad), ptr(frames), ptr(slopes), self._stream()))
+        return (grad, frames, slopes) if with_values else grad
+
+    def pyramid_clean(self, actuators=None, mask=None):
+        """The CLEAN frames [B, 4, n_s, n_s] and slopes [B, 2 n_valid] (no photon noise, ``pyramid_frame_count`` untouched) at the mirror's
+        actuators or at ``actuators`` [B, A]: the forward half of ``pyramid_gradient`` alone.  Returns (frames, slopes)."""
+        torch = self._torch
+        if self._pyramid is None:
+            raise ValueError("pyramid_clean: this environment was built without a pyramid sensor (pyramid=dict(...))")
+        B, A, ns, nv = self.num_envs, self.num_modes, self._pyramid.pixels, self._pyramid.n_valid
+        act = None
+        if actuators is not None:
+            act = torch.as_tensor(actuators, device=self.device).to(torch.float64).contiguous()
+            if tuple(act.shape) != (B, A):
+                raise ValueError(f"pyramid_clean: actuators must have shape {(B, A)}, got {tuple(act.shape)}")
+        mptr, _keep = self._pyramid_mask(mask, "pyramid_clean")
+        frames = torch.zeros((B, 4, ns, ns), dtype=torch.float64, device=self.device)
+        slopes = torch.zeros((B, 2 * nv), dtype=torch.float64, device=self.device)
+        p = C.c_void_p
+        _lib.check(self.lib.aog_pyramid_gradient(self._handle, mptr, None, None, p(act.data_ptr()) if act is not None else None, None,
+                                                 p(frames.data_ptr()), p(slopes.data_ptr()), self._stream()))
+        return frames, slopes
 
     def pyramid_calibrate(self):
         """Calibrate the reconstructor through the device sensor itself: on a scratch env of 2 A + 1 flat wavefronts (same tables, precision

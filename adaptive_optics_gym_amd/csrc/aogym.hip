@@ -132,10 +132,10 @@ int check_env_range(const char* who, int first, int count, int B) {
   return AOG_OK;
 }
 
-int load_actuators(aog_env* e, hipStream_t s, ActTargets to) {
+int load_actuators(aog_env* e, hipStream_t s, ActTargets to, const double* act_src) {
   const int n = e->B * e->A_pad;
-  hipLaunchKernelGGL(aog::k_load_actuators, dim3((n + 255) / 256), dim3(256), 0, s, e->act_dm, to.act_rev, to.act16, e->B, e->A, e->A_pad, e->Bp,
-                     2.0 / e->cfg.wavelength_wfs, to.act_ll);
+  hipLaunchKernelGGL(aog::k_load_actuators, dim3((n + 255) / 256), dim3(256), 0, s, act_src ? act_src : e->act_dm, to.act_rev, to.act16, e->B, e->A, e->A_pad,
+                     e->Bp, 2.0 / e->cfg.wavelength_wfs, to.act_ll);
   HIP_TRY(hipGetLastError());
   return AOG_OK;
 }

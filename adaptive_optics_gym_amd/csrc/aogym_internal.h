@@ -215,6 +215,30 @@ struct aog_env {
   double* pyr_slopes = nullptr;  // [B][2 n_valid] slopes of the last aog_pyramid_update
   double* pyr_recon = nullptr;   // [A][2 n_valid]
   double* pyr_ref = nullptr;     // [2 n_valid]
+  // its gradient (aog_pyramid_gradient; pyramid_grad.hip).  Every buffer is allocated by the first gradient call and given back by
+  // aog_upload_pyramid; float64 handles only so far.
+  double* pyg_gpix = nullptr;    // [B][4][n_s][n_s] the cotangent on the frame (g_frames + the slopes cotangent pulled back)
+  double* pyg_m1t = nullptr;     // [n_mod] x m1_j' [N][w], m2_j' [w][N] complex
+  double* pyg_m2t = nullptr;
+  double* pyg_b1t = nullptr;     // [w][2 n_s] complex: column (s_y, y') of row v = b1[s_y][y'][v]
+  double* pyg_b2t = nullptr;     // [2 n_s][w] complex: row (s_x, x') = b2[s_x][u][x'] over u
+  double* pyg_W = nullptr;       // [s_y 2][n_s][s_x 2][n_s] complex: W of the four quadrants, rows of one s_y side by side
+  double* pyg_Y = nullptr;       // [s_y 2][n_s][w] complex: W b2'
+  double* pyg_V = nullptr;       // [w][w] complex
+  double* pyg_P = nullptr;       // [N][w] complex: m1' V
+  double* pyg_H = nullptr;       // [N][N] complex
+  double* pyg_q = nullptr;       // [n_ap] the sum over the modulation points of 2 Re(i E H)
+  double* pyg_slabs = nullptr;   // [A][Bp] sum_p M_pk q_p (fast handles: [pixel chunk][A_pad][Bp])
+  double* pyg_gscale = nullptr;  // [B] the power of two of the largest |cotangent| of the env (1 for a zero cotangent)
+  // fast handles: the transposed operand tables (made from the uploaded ones by the first call) and the chunk's work buffers
+  _Float16* pyg_m1s_t = nullptr; // [n_mod][ceil(Nyp / 32)][nvb][2] tiles: row y, K = v in accumulator order
+  _Float16* pyg_m2s_t = nullptr; // [n_mod][Nxp / 32][2 nvb] tiles: column x, K = u
+  _Float16* pyg_b1s_t = nullptr; // [2][nvb][nsb][2] tiles: column v, K = y' in accumulator order
+  _Float16* pyg_b2s_t = nullptr; // [2][nvb][nsb][2] tiles: column u, K = x' in accumulator order
+  _Float16* pyg_vop = nullptr;   // [chunk][nvb][2 nvb] tiles: V_j / scales as A operands (row v, K = u); the pads stay zero
+  double* pyg_wscale = nullptr;  // [chunk] W's power of two over V's, of the modulation point in flight
+  double* pyg_qscale = nullptr;  // [B] the power of two the env's q grid was divided by
+  float* pyg_qgrid = nullptr;    // [chunk][Nyp][Nxp] q summed over the modulation points, on aperture pixels
   // state
   float* psi_rev = nullptr;     // [n_quads][Bp][4]  (handles that run the VALU kernel only)
   double* pack_mean = nullptr;   // [B] aperture means of the screens being installed (k_screen_means -> k_pack_tiles)

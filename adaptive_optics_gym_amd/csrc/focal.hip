@@ -60,11 +60,11 @@ int mft_work_alloc(aog_env* e, MftWork* w, size_t grid_env, size_t t16_env, size
   return AOG_OK;
 }
 
-void launch_focal_field(aog_env* e, hipStream_t s, double* E, int env, double ratio, const uint8_t* mask) {
+void launch_focal_field(aog_env* e, hipStream_t s, double* E, int env, double ratio, const uint8_t* mask, const double* act_src) {
   const bool fast = e->cfg.precision == AOG_PRECISION_FAST;
   hipLaunchKernelGGL(aog::k_focal_field, dim3((e->n_ap + 255) / 256), dim3(256), 0, s, fast ? e->psi_tile : nullptr, fast ? nullptr : e->psi64,
-                     e->modes_f32, e->modes64, e->act_rev, e->act_dm, e->ap_index, reinterpret_cast<double2*>(E), env, e->n_ap, e->n_ptiles, e->A,
-                     e->A_pad, e->Bp, e->cfg.wavelength_wfs, ratio, mask);
+                     e->modes_f32, e->modes64, e->act_rev, act_src ? act_src : e->act_dm, e->ap_index, reinterpret_cast<double2*>(E), env, e->n_ap,
+                     e->n_ptiles, e->A, e->A_pad, e->Bp, e->cfg.wavelength_wfs, ratio, mask);
 }
 void launch_cgemm64(hipStream_t s, const double* a, const double* b, double* out, float* out32, int R, int K, int Cn, const uint8_t* mask, int env) {
   hipLaunchKernelGGL(aog::k_cgemm_small, dim3((R * Cn + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(a),

@@ -15,6 +15,13 @@ int gobs_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
 
 namespace aog_host {
 
+void launch_grad_obs_backward(aog_env* e, hipStream_t s, const float* qgrid, size_t grid_env, int Nxp, int env0, int n, double* slabs) {
+  with_apad(e->A_pad, [&](auto apad) {
+    hipLaunchKernelGGL((aog::k_grad_obs_backward<apad()>), dim3(aog::pupil_chunks(e->n_ptiles), (n + 31) / 32), dim3(256), 0, s, qgrid, e->focal_ap_yx,
+                       reinterpret_cast<const aog::f16x8*>(e->grad_mtab16), slabs + env0, grid_env, Nxp, n, e->n_ptiles, e->n_ap, e->Bp);
+  });
+}
+
 int grad_obs_part(aog_env* e, hipStream_t s, const double* g_obs, double* values) {
   const int N = e->cfg.n_pupil, o = e->cfg.obs_dim, n_obs = e->n_obs;
   int rc;
@@ -55,10 +62,7 @@ int grad_obs_part(aog_env* e, hipStream_t s, const double* g_obs, double* values
     if (!g_obs) continue;
     hipLaunchKernelGGL(aog::k_grad_obs_q, dim3((n * nyt * nxt + 3) / 4), dim3(256), 0, s, e->obs_work.grid, reinterpret_cast<const aog::f16x8*>(e->gobs_wop),
                        reinterpret_cast<const aog::f16x8*>(e->gobs_m1t), reinterpret_cast<const aog::f16x8*>(e->gobs_m2t), Nxp, Nyp, n);
-    with_apad(e->A_pad, [&](auto apad) {
-      hipLaunchKernelGGL((aog::k_grad_obs_backward<apad()>), dim3(n_chunks, n_et), dim3(256), 0, s, e->obs_work.grid, e->focal_ap_yx,
-                         reinterpret_cast<const aog::f16x8*>(e->grad_mtab16), e->gobs_slabs + env0, grid_env, Nxp, n, e->n_ptiles, e->n_ap, e->Bp);
-    });
+    launch_grad_obs_backward(e, s, e->obs_work.grid, grid_env, Nxp, env0, n, e->gobs_slabs);
   }
   HIP_TRY(hipGetLastError());
   return AOG_OK;

@@ -120,7 +120,8 @@ struct ActTargets {
   _Float16* act16;    // split-f16 B operands
   _Float16* act_ll;   // nullable third f16 term of the actuators (K4, K11)
 };
-int load_actuators(aog_env* e, hipStream_t s, ActTargets to);
+// (act_src: nullable [B][A] float64 device actuators to load instead of the mirror's)
+int load_actuators(aog_env* e, hipStream_t s, ActTargets to, const double* act_src = nullptr);
 // The kernels instantiated per padded mode count outside the step path: f(std::integral_constant<int, 16 | 32 | 64 | 128>) for A_pad (anything
 // else gets 128), e.g. with_apad(e->A_pad, [&](auto apad) { hipLaunchKernelGGL((k<apad()>), ...); }).  (The step path's own table of
 // launchers is launchers_for in aogym.hip.)
@@ -190,13 +191,32 @@ int mft_work_alloc(aog_env* e, MftWork* w, size_t grid_env, size_t t16_env, size
 // focal.hip: the steps of the float64 validation forms for one env (K4's single-env export, K11, the science camera).  launch_focal_field:
 // E = exp(2 pi i ratio u_p) on the aperture pixels of the [N][N] complex grid E (the rest is left as it is); launch_cgemm64: out [R][Cn]
 // (and / or its complex64 copy out32) = a [R][K] b [K][Cn], complex row-major.  mask (nullable): nothing happens for an env it leaves out.
-void launch_focal_field(aog_env* e, hipStream_t s, double* E, int env, double ratio = 1.0, const uint8_t* mask = nullptr);
+void launch_focal_field(aog_env* e, hipStream_t s, double* E, int env, double ratio = 1.0, const uint8_t* mask = nullptr,
+                        const double* act_src = nullptr);   // act_src: nullable [B][A] actuators instead of the mirror's
 void launch_cgemm64(hipStream_t s, const double* a, const double* b, double* out, float* out32, int R, int K, int Cn, const uint8_t* mask = nullptr,
                     int env = 0);
 // gradient_obs.hip (K14 on the separable route, after aog_upload_gradient_obs): the observation's part of one aog_output_gradient call, behind
 // its k_grad_coef — the float64 obs_raw into the observation slots of `values` (nullable) and, with g_obs (nullable), the modes contraction of
 // the observation's q into e->gobs_slabs for k_grad_finish.  The actuator operands (grad_act16, gobs_act_ll) are the caller's.
 int grad_obs_part(aog_env* e, hipStream_t s, const double* g_obs_dev, double* values_dev);
+// pyramid.hip: the checks every call on an uploaded sensor shares, and the sum over the modulation points of every selected env into pyr_acc
+// (no division yet) at the mirror's actuators or at act_src (nullable [B][A] device) — the forward launches of aog_pyramid_frames, which
+// aog_pyramid_gradient (pyramid_grad.hip) runs for its clean frame
+int pyramid_ready(aog_env* e, const char* who);
+int pyramid_accumulate(aog_env* e, hipStream_t s, const uint8_t* mask_dev, const double* act_src = nullptr);
+// pyramid.hip, fast handles: the steps of that sum, for the gradient's backward sweep — psi_tile and the call's own actuator operands (and
+// psi_tile put back), the phase grid of a chunk's envs into pyr_work.grid, F_j of the chunk into pyr_fop (the two forward passes), and the
+// 16-row k-steps of the window's two halves
+int pyramid_operands_begin(aog_env* e, hipStream_t s, const double* act_src);
+int pyramid_operands_end(aog_env* e, hipStream_t s);
+void pyramid_phase_grid(aog_env* e, hipStream_t s, int env0, int n);
+void pyramid_forward_point(aog_env* e, hipStream_t s, int j, int env0, int n, const uint8_t* mask_dev);
+int4 pyramid_halves(const aog_env* e);
+// gradient_obs.hip: k_grad_obs_backward on a q grid [n][grid_env] (row stride Nxp) of n envs from env tile env0 / 32 on, into slabs
+// [pupil_chunks][A_pad][Bp] (+ env0 applied here); needs grad_mtab16 (aog_upload_gradient)
+void launch_grad_obs_backward(aog_env* e, hipStream_t s, const float* qgrid, size_t grid_env, int Nxp, int env0, int n, double* slabs);
+// pyramid_grad.hip: gives the gradient's work buffers back (aog_upload_pyramid: they are sized by the sensor)
+void release_pyramid_gradient(aog_env* e);
 // screens.hip: the factors through which Cn^2 enters (null outputs are skipped) — the handle-wide value's and every per-env value's
 void turbulence_factors(int N, int oversampling, double pixel_pitch, double cn_squared, float* amp_high, float* amp_low, float* crop_scale,
                         double* sqrt_cn_squared);

@@ -388,13 +388,11 @@ __global__ __launch_bounds__(256) void k_grad_finish(GradFinishArgs p) {
   const size_t slab = (size_t)p.rows * p.Bp;
   double g = 0;
   if (k < p.A) {
-    double T = 0;
-    for (int c = 0; c < p.n_chunks; ++c) T += p.slabs[c * slab + (size_t)k * p.Bp + env];
+    const double T = pupil_slab_sum(p.slabs, p.n_chunks, slab, k, p.Bp, env);
     g = (T * p.factor) * p.cscale[env];
     if (p.slabs2) {
       const size_t slab2 = (size_t)p.rows2 * p.Bp;
-      double T2 = 0;
-      for (int c = 0; c < p.n_chunks2; ++c) T2 += p.slabs2[c * slab2 + (size_t)k * p.Bp + env];
+      const double T2 = pupil_slab_sum(p.slabs2, p.n_chunks2, slab2, k, p.Bp, env);
       g += (T2 * p.factor2) * (p.cscale2 ? p.cscale2[env] : 1.0);
     }
     if (p.grad_act) p.grad_act[(size_t)env * p.A + k] = g;

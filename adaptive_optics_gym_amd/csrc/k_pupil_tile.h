@@ -149,6 +149,13 @@ __device__ __forceinline__ void pupil_reduce_store(double* red, double* __restri
   for (int i = threadIdx.x; i < ROWS * 32; i += 256) out[(size_t)(i >> 5) * Bp + (i & 31)] = red[i];
 }
 
+// row k of env's column summed over the slabs [n_chunks][rows][Bp] in chunk order (slab = rows * Bp): what every finish kernel starts from
+__device__ __forceinline__ double pupil_slab_sum(const double* __restrict__ slabs, int n_chunks, size_t slab, int k, int Bp, int env) {
+  double T = 0;
+  for (int c = 0; c < n_chunks; ++c) T += slabs[c * slab + (size_t)k * Bp + env];
+  return T;
+}
+
 // ---- float64 validation forms: one workgroup per env, modes64 [n_ap][A] ----
 // the env's actuators (metres of surface) into sa [A] (a barrier follows), then the mirror surface at pixel p
 __device__ __forceinline__ void pupil64_stage_act(const double* __restrict__ act_dm, int env, int A, double* sa) {

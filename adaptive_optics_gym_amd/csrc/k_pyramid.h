@@ -4,6 +4,7 @@
 #include "k_common.h"
 #include "k_mft_mma.h"
 #include "k_poisson.h"
+#include "k_pyramid_back.h"
 
 namespace aog {
 
@@ -65,50 +66,7 @@ __global__ __launch_bounds__(256) void k_pyr_back(const f16x8* __restrict__ fop,
   const int sy = q >> 1, sx = q & 1;
   const int kv0 = sy ? half.z : half.x, kv1 = sy ? half.w : half.y, ku0 = sx ? half.z : half.x, ku1 = sx ? half.w : half.y;
   f32x16 gr[NSB][NSB], gi[NSB][NSB];
-#pragma unroll
-  for (int yb = 0; yb < NSB; ++yb)
-#pragma unroll
-    for (int xb = 0; xb < NSB; ++xb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { gr[yb][xb][r] = 0.f; gi[yb][xb][r] = 0.f; }
-  for (int ub = ku0 >> 1; ub < (ku1 + 1) >> 1; ++ub) {
-    f32x16 xr[NSB], xi[NSB];
-#pragma unroll
-    for (int yb = 0; yb < NSB; ++yb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { xr[yb][r] = 0.f; xi[yb][r] = 0.f; }
-    const f16x8* __restrict__ a = fop + (((size_t)env * nvb + ub) * nvb * 2) * kFocalTile + lane;
-    for (int kv = kv0; kv < kv1; ++kv) {
-      const f16x8* __restrict__ at = a + (size_t)kv * kFocalTile;
-      const f16x8 a0 = at[0], a1 = at[64], a2 = at[128], a3 = at[192];
-#pragma unroll
-      for (int yb = 0; yb < NSB; ++yb) {
-        const f16x8* __restrict__ bt = b1s + (((size_t)(sy * NSB + yb) * nvb * 2) + kv) * kFocalTile + lane;
-        const f16x8 b[4] = {bt[0], bt[64], bt[128], bt[192]};
-        mft_cmul(a0, a1, a2, a3, b, neg8(b[2]), neg8(b[3]), xr[yb], xi[yb]);
-      }
-    }
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      const int ku = 2 * ub + s2;
-      if (ku < ku0 || ku >= ku1) continue;   // (wave-uniform: b2s is zero there)
-#pragma unroll
-      for (int yb = 0; yb < NSB; ++yb) {
-        float vr[8], vi[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { vr[j] = xr[yb][8 * s2 + j]; vi[j] = xi[yb][8 * s2 + j]; }
-        f16x8 rh, rl, ih, il;
-        split8(vr, rh, rl);
-        split8(vi, ih, il);
-#pragma unroll
-        for (int xb = 0; xb < NSB; ++xb) {
-          const f16x8* __restrict__ bt = b2s + (((size_t)(sx * NSB + xb) * nvb * 2) + ku) * kFocalTile + lane;
-          const f16x8 b[4] = {bt[0], bt[64], bt[128], bt[192]};
-          mft_cmul(rh, rl, ih, il, b, neg8(b[2]), neg8(b[3]), gr[yb][xb], gi[yb][xb]);
-        }
-      }
-    }
-  }
+  pyr_back_products<NSB>(fop, b1s, b2s, nvb, env, sy, sx, kv0, kv1, ku0, ku1, gr, gi);
   double* __restrict__ out = acc + ((size_t)(env0 + env) * 4 + q) * ns * ns;
 #pragma unroll
   for (int yb = 0; yb < NSB; ++yb)

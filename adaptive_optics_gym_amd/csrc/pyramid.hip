@@ -42,7 +42,14 @@ void release_pyramid(aog_env* e) {
   dev_release(e, &e->pyr_slopes);
   dev_release(e, &e->pyr_recon);
   dev_release(e, &e->pyr_ref);
+  release_pyramid_gradient(e);
 }
+
+const aog::f16x8* f16x8p(const _Float16* p) { return reinterpret_cast<const aog::f16x8*>(p); }
+
+}  // namespace
+
+namespace aog_host {
 
 // the checks every call on an uploaded sensor shares (aog_science_integrate's preconditions)
 int pyramid_ready(aog_env* e, const char* who) {
@@ -52,16 +59,14 @@ int pyramid_ready(aog_env* e, const char* who) {
   return refuse_pre_evolved(e, who);
 }
 
-const aog::f16x8* f16x8p(const _Float16* p) { return reinterpret_cast<const aog::f16x8*>(p); }
-
 // The sum over the modulation points of every selected env into pyr_acc (no division yet: k_pyr_finish).
-int pyramid_accumulate(aog_env* e, hipStream_t s, const uint8_t* mask_dev) {
+int pyramid_accumulate(aog_env* e, hipStream_t s, const uint8_t* mask_dev, const double* act_src) {
   const int N = e->cfg.n_pupil, wq = e->pyr_wq, w = 2 * wq, ns = e->pyr_ns, n_mod = e->pyr_nmod;
   if (e->cfg.precision == AOG_PRECISION_FP64) {
     const int nG = 4 * ns * ns;
     const size_t m_el = (size_t)w * N * 2, b_el = (size_t)ns * w * 2;
     for (int env = 0; env < e->B; ++env) {
-      launch_focal_field(e, s, e->pyr_E, env, 1.0, mask_dev);
+      launch_focal_field(e, s, e->pyr_E, env, 1.0, mask_dev, act_src);
       for (int j = 0; j < n_mod; ++j) {
         launch_cgemm64(s, e->pyr_m1d + j * m_el, e->pyr_E, e->pyr_T, nullptr, w, N, N, mask_dev, env);
         launch_cgemm64(s, e->pyr_T, e->pyr_m2d + j * m_el, e->pyr_F, nullptr, w, N, w, mask_dev, env);
@@ -75,28 +80,15 @@ int pyramid_accumulate(aog_env* e, hipStream_t s, const uint8_t* mask_dev) {
     HIP_TRY(hipGetLastError());
     return AOG_OK;
   }
-  int rc;
-  // psi_tile holding the screens the last step read (psi_tile alone: nothing a step reads is touched); the actuator operands are the call's own
-  // (a dynamic handle that steps with the VALU kernel keeps a psi_tile nobody reads between its screen installations, but the state blob
-  // carries it: the call leaves it as it found it, so that aog_get_state does not depend on whether the sensor was called)
-  const size_t tile_bytes = sizeof(float) * (size_t)e->n_etiles * e->n_ptiles * 1024;
-  const bool keep = e->pyr_tile_keep && e->kernel != AOG_KERNEL_MFMA && !e->sh_ready;
-  if (keep) HIP_TRY(hipMemcpyAsync(e->pyr_tile_keep, e->psi_tile, tile_bytes, hipMemcpyDeviceToDevice, s));
-  if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
-  if ((rc = load_actuators(e, s, {nullptr, e->pyr_act16, e->pyr_act_ll})) != AOG_OK) return rc;
-  const int Nxp = pyr_nxp(e), Nyp = pyr_nyp(e), nvb = pyr_nvb(e), nsb = pyr_nsb(e), nwg = (nvb + 3) / 4, split = nvb <= 2;
-  const size_t grid_env = (size_t)Nyp * Nxp;
-  const size_t m1_el = (size_t)nvb * (Nyp / 16) * 4 * 64 * 8, m2_el = (size_t)nvb * (Nxp / 32) * 2 * 4 * 64 * 8;
+  if (int rc = pyramid_operands_begin(e, s, act_src)) return rc;
+  const int nsb = pyr_nsb(e), nvb = pyr_nvb(e);
   // 16-row k-steps of the two halves of the window
-  const int4 half = make_int4(0, (wq + 15) / 16, wq / 16, (w + 15) / 16);
+  const int4 half = pyramid_halves(e);
   for (int env0 = 0; env0 < e->B; env0 += e->pyr_work.chunk) {
-    const int n = std::min(e->pyr_work.chunk, e->B - env0), n_et = (n + 31) / 32;
-    launch_phase_grid(e, s, e->pyr_act16, e->pyr_act_ll, e->pyr_work.grid, grid_env, Nxp, env0 / 32, n_et);   // once: the grid is read n_mod times
+    const int n = std::min(e->pyr_work.chunk, e->B - env0);
+    pyramid_phase_grid(e, s, env0, n);   // once: the grid is read n_mod times
     for (int j = 0; j < n_mod; ++j) {
-      hipLaunchKernelGGL(aog::k_pyr_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->pyr_work.grid, f16x8p(e->pyr_m1s + j * m1_el),
-                         reinterpret_cast<aog::f16x8*>(e->pyr_work.T16), Nxp, Nyp, nvb, mask_dev, env0, split);
-      hipLaunchKernelGGL(aog::k_pyr_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, f16x8p(e->pyr_work.T16), f16x8p(e->pyr_m2s + j * m2_el), e->pyr_fop, Nxp,
-                         nvb, w, e->pyr_unscale * aog::kPyrFieldScale, mask_dev, env0);
+      pyramid_forward_point(e, s, j, env0, n, mask_dev);
       if (nsb == 1)
         hipLaunchKernelGGL(aog::k_pyr_back<1>, dim3(n), dim3(256), 0, s, f16x8p(e->pyr_fop), f16x8p(e->pyr_b1s), f16x8p(e->pyr_b2s), e->pyr_acc, nvb, ns,
                            half, e->pyr_back_unscale, j == 0, mask_dev, env0);
@@ -106,9 +98,49 @@ int pyramid_accumulate(aog_env* e, hipStream_t s, const uint8_t* mask_dev) {
     }
     HIP_TRY(hipGetLastError());
   }
-  if (keep) HIP_TRY(hipMemcpyAsync(e->psi_tile, e->pyr_tile_keep, tile_bytes, hipMemcpyDeviceToDevice, s));
+  return pyramid_operands_end(e, s);
+}
+
+int4 pyramid_halves(const aog_env* e) {
+  const int wq = e->pyr_wq, w = 2 * wq;
+  return make_int4(0, (wq + 15) / 16, wq / 16, (w + 15) / 16);
+}
+
+static bool pyr_keeps_tiles(const aog_env* e) { return e->pyr_tile_keep && e->kernel != AOG_KERNEL_MFMA && !e->sh_ready; }
+static size_t pyr_tile_bytes(const aog_env* e) { return sizeof(float) * (size_t)e->n_etiles * e->n_ptiles * 1024; }
+
+int pyramid_operands_begin(aog_env* e, hipStream_t s, const double* act_src) {
+  int rc;
+  // psi_tile holding the screens the last step read (psi_tile alone: nothing a step reads is touched); the actuator operands are the call's own
+  // (a dynamic handle that steps with the VALU kernel keeps a psi_tile nobody reads between its screen installations, but the state blob
+  // carries it: the call leaves it as it found it, so that aog_get_state does not depend on whether the sensor was called)
+  if (pyr_keeps_tiles(e)) HIP_TRY(hipMemcpyAsync(e->pyr_tile_keep, e->psi_tile, pyr_tile_bytes(e), hipMemcpyDeviceToDevice, s));
+  if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
+  return load_actuators(e, s, {nullptr, e->pyr_act16, e->pyr_act_ll}, act_src);
+}
+
+int pyramid_operands_end(aog_env* e, hipStream_t s) {
+  if (pyr_keeps_tiles(e)) HIP_TRY(hipMemcpyAsync(e->psi_tile, e->pyr_tile_keep, pyr_tile_bytes(e), hipMemcpyDeviceToDevice, s));
   return AOG_OK;
 }
+
+void pyramid_phase_grid(aog_env* e, hipStream_t s, int env0, int n) {
+  launch_phase_grid(e, s, e->pyr_act16, e->pyr_act_ll, e->pyr_work.grid, (size_t)pyr_nyp(e) * pyr_nxp(e), pyr_nxp(e), env0 / 32, (n + 31) / 32);
+}
+
+// F_j of the chunk's envs into pyr_fop: the two forward passes
+void pyramid_forward_point(aog_env* e, hipStream_t s, int j, int env0, int n, const uint8_t* mask_dev) {
+  const int Nxp = pyr_nxp(e), Nyp = pyr_nyp(e), nvb = pyr_nvb(e), nwg = (nvb + 3) / 4, split = nvb <= 2, w = 2 * e->pyr_wq;
+  const size_t m1_el = (size_t)nvb * (Nyp / 16) * 4 * 64 * 8, m2_el = (size_t)nvb * (Nxp / 32) * 2 * 4 * 64 * 8;
+  hipLaunchKernelGGL(aog::k_pyr_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->pyr_work.grid, f16x8p(e->pyr_m1s + j * m1_el),
+                     reinterpret_cast<aog::f16x8*>(e->pyr_work.T16), Nxp, Nyp, nvb, mask_dev, env0, split);
+  hipLaunchKernelGGL(aog::k_pyr_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, f16x8p(e->pyr_work.T16), f16x8p(e->pyr_m2s + j * m2_el), e->pyr_fop, Nxp,
+                     nvb, w, e->pyr_unscale * aog::kPyrFieldScale, mask_dev, env0);
+}
+
+}  // namespace aog_host
+
+namespace {
 
 // accumulate + finish: the shared body of the three sensor calls
 int pyramid_sense(aog_env* e, hipStream_t s, const uint8_t* mask_dev, double* frames_dev, double* slopes_dev) {

@@ -601,6 +601,27 @@ int aog_upload_pyramid_reconstructor(aog_env* env, const double* recon_host, con
  * with act_out.  slopes_dev: nullable [B][2 n_valid], the slopes it used.  AOG_ERR_STATE before aog_upload_pyramid_reconstructor. */
 int aog_pyramid_update(aog_env* env, double gain, double* act_out_dev, double* slopes_dev, void* stream);
 
+/* The vector-Jacobian product of the sensor's CLEAN frame and slopes with respect to the mirror's actuators (per metre of surface, the
+ * units of aog_get_actuators): grad_dev [B][A] float64 = d/da of sum(g_frames * frame) + sum(g_slopes * slopes).  g_frames_dev: nullable
+ * [B][4][n_s][n_s]; g_slopes_dev: nullable [B][2 n_valid]; at least one (AOG_ERR_INVALID), both add.  A slopes cotangent is pulled back to
+ * the frame in float64 through s_x = (I1 + I3 - I0 - I2) / Ibar, s_y = (I2 + I3 - I0 - I1) / Ibar, the dependence on Ibar included.
+ * act_dev: nullable [B][A], the point of evaluation instead of the mirror's actuators (the mirror is never written).  frames_dev /
+ * slopes_dev: nullable, the clean frame and slopes at that point, from the launches of aog_pyramid_frames (the same bits as that call
+ * gives without photons).  With W_{q,j} = g_q o conj(G_{q,j}) / n_mod, V_j the window whose quadrant block q is b1' W_{q,j} b2', and
+ * H_j = m1_j' V_j m2_j' (' = the plain transpose): q_p = sum_j 2 Re(2 pi i E_p H_{j,p}) on the aperture, j ascending, and
+ * grad_k = (2 / lambda_wfs) sum_p M_pk q_p.  Photon noise is not differentiated: the call draws no random number and leaves the sensor's
+ * frame count alone.  mask_dev as above: the rows of the envs it leaves out are not touched, in any output.  Stream-ordered, no host
+ * synchronisation, no atomics; an env's result depends on its own operands only.  The work buffers are allocated by the first call (which
+ * blocks for that): a handle that never asks keeps its device_bytes.  grad_dev may be NULL when both cotangents are NULL and frames_dev or
+ * slopes_dev is given: the clean values alone.  Fast handles: per chunk the phase grid once, per modulation point the two forward passes,
+ * k_pyr_grad_back (one wave per (env, quadrant): G again, W, back through b1' and b2' on the matrix cores) and k_pyr_grad_q (back through
+ * m2_j' and m1_j', added into an fp32 q grid; every split operand first brought into a fixed binade by a measured power of two), then
+ * the modes contraction of aog_output_gradient's separable route; they need
+ * aog_upload_gradient (AOG_ERR_STATE without) and are built for w_q <= 32, n_s <= 64 (AOG_ERR_UNSUPPORTED beyond, the sizes named).
+ * Float64 handles: plain float64 kernels per env.  Refusals as aog_pyramid_frames. */
+int aog_pyramid_gradient(aog_env* env, const uint8_t* mask_dev, const double* g_frames_dev, const double* g_slopes_dev, const double* act_dev,
+                         double* grad_dev, double* frames_dev, double* slopes_dev, void* stream);
+
 /* ---- policy query of the rollout (Actor.forward + Actor.get_action, network.py:17-69; caller algorithm.py:216-296) ----
  * mean = W_o drop(relu(W_3 drop(relu(W_2 drop(relu(W_1 obs + b_1)) + b_2)) + b_3)) + b_o with nn.Dropout(dropout_p) ACTIVE
  * (the reference never leaves training mode while acting), action = mean + sqrt(cov_var) eps, eps ~ N(0, I),
