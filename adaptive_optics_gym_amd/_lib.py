@@ -77,6 +77,11 @@ class AogPyramidTables(C.Structure):  # mirrors aog_pyramid_tables (additive in 
         "m1", "m2", "b1", "b2", "m1s", "m2s", "b1s", "b2s", "valid")] + [(n, C.c_double) for n in ("fwd_unscale", "back_unscale", "photons")]
 
 
+class AogPredictorConfig(C.Structure):  # mirrors aog_predictor_config (additive in ABI 22; no aog_struct_size index)
+    _fields_ = [(n, C.c_int32) for n in ("batch", "act_dim", "order", "env_id_base", "reserved0", "reserved1")] + [(n, C.c_double) for n in (
+        "forgetting", "p0", "scale")]
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -152,6 +157,13 @@ SYMBOLS = {
     "aog_upload_pyramid_reconstructor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_pyramid_update": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_pyramid_gradient": (C.c_int, [C.c_void_p] * 9),
+    "aog_predictor_create": (C.c_int, [C.POINTER(AogPredictorConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "aog_predictor_destroy": (None, [C.c_void_p]),
+    "aog_predictor_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_predictor_update": (C.c_int, [C.c_void_p] * 6),
+    "aog_predictor_state_bytes": (C.c_int64, [C.c_void_p]),
+    "aog_predictor_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_predictor_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_selftest_poisson": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
     "aog_selftest_barrier_timeout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

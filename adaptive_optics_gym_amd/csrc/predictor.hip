@@ -1,0 +1,130 @@
+// K17: the predictive linear controller's per-env recursive-least-squares state (aog_predictor_*).  Independent of any aog_env.
+#include "host_common.h"
+#include "k_predictor.h"
+
+using namespace aog_host;
+
+struct aog_predictor {
+  aog_predictor_config cfg{};
+  int device = 0;
+  int n = 0;
+  size_t rec_bytes = 0;
+  char* state = nullptr;   // [batch] records (k_predictor.h)
+};
+
+namespace {
+
+// the checks of a configuration, before any device work
+int predictor_check(const aog_predictor_config* c) {
+  if (c->reserved0 != 0 || c->reserved1 != 0) return fail(AOG_ERR_INVALID, "aog_predictor_create: reserved fields must be 0");
+  if (c->batch < 1 || c->act_dim < 1 || c->act_dim > aog::kPredMaxN || c->order < 1)
+    return fail(AOG_ERR_INVALID, "aog_predictor_create: bad dimensions (batch %d, act_dim %d, order %d; act_dim <= %d)", c->batch, c->act_dim, c->order,
+                aog::kPredMaxN);
+  if (!(c->forgetting > 0.0 && c->forgetting <= 1.0)) return fail(AOG_ERR_INVALID, "aog_predictor_create: forgetting %g outside (0, 1]", c->forgetting);
+  if (!std::isfinite(c->p0) || !(c->p0 > 0.0)) return fail(AOG_ERR_INVALID, "aog_predictor_create: p0 %g must be finite and > 0", c->p0);
+  if (!std::isfinite(c->scale) || !(c->scale > 0.0)) return fail(AOG_ERR_INVALID, "aog_predictor_create: scale %g must be finite and > 0", c->scale);
+  if ((int64_t)c->act_dim * c->order > aog::kPredMaxN)
+    return fail(AOG_ERR_UNSUPPORTED, "aog_predictor_create: n = act_dim %d x order %d = %lld regressor entries; built for n <= %d", c->act_dim, c->order,
+                (long long)c->act_dim * c->order, aog::kPredMaxN);
+  return AOG_OK;
+}
+
+aog::PredictorArgs predictor_args(const aog_predictor* p, const uint8_t* mask) {
+  aog::PredictorArgs a{};
+  a.state = p->state;
+  a.rec_bytes = p->rec_bytes;
+  a.mask = mask;
+  a.A = p->cfg.act_dim;
+  a.order = p->cfg.order;
+  a.n = p->n;
+  a.lam = p->cfg.forgetting;
+  a.scale = p->cfg.scale;
+  a.p0 = p->cfg.p0;
+  return a;
+}
+
+template <int NW, int RPW, int CB, int CBW, bool KEEP>
+void launch_update(const aog::PredictorArgs& a, int batch, hipStream_t s) {
+  const size_t lds = aog::predictor_lds_words(a.A, a.n, NW) * sizeof(double);   // <= 46 KB at n = A = 256
+  hipLaunchKernelGGL((aog::k_predictor_update<NW, RPW, CB, CBW, KEEP>), dim3(batch), dim3(NW * 64), lds, s, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int aog_predictor_create(const aog_predictor_config* cfg, int device, aog_predictor** out) {
+  if (!cfg || !out) return fail(AOG_ERR_INVALID, "aog_predictor_create: null argument");
+  *out = nullptr;
+  if (int rc = predictor_check(cfg)) return rc;
+  HIP_TRY(hipSetDevice(device));
+  aog_predictor* p = new aog_predictor;
+  p->cfg = *cfg;
+  p->device = device;
+  p->n = cfg->act_dim * cfg->order;
+  p->rec_bytes = aog::predictor_record_words(cfg->act_dim, p->n) * sizeof(double);
+  hipError_t err = hipMalloc(reinterpret_cast<void**>(&p->state), p->rec_bytes * (size_t)cfg->batch);
+  if (err == hipSuccess) {
+    hipLaunchKernelGGL(aog::k_predictor_reset, dim3(cfg->batch), dim3(256), 0, nullptr, predictor_args(p, nullptr));
+    err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+  }
+  if (err != hipSuccess) {
+    if (p->state) (void)hipFree(p->state);
+    delete p;
+    return fail(AOG_ERR_HIP, "aog_predictor_create: %s", hipGetErrorString(err));
+  }
+  *out = p;
+  return AOG_OK;
+}
+
+void aog_predictor_destroy(aog_predictor* p) {
+  if (!p) return;
+  (void)hipSetDevice(p->device);
+  if (p->state) (void)hipFree(p->state);
+  delete p;
+}
+
+int aog_predictor_reset(aog_predictor* p, const uint8_t* mask_dev, void* stream) {
+  if (!p) return fail(AOG_ERR_INVALID, "aog_predictor_reset: null argument");
+  HIP_TRY(hipSetDevice(p->device));
+  hipLaunchKernelGGL(aog::k_predictor_reset, dim3(p->cfg.batch), dim3(256), 0, static_cast<hipStream_t>(stream), predictor_args(p, mask_dev));
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
+int aog_predictor_update(aog_predictor* p, const double* y_dev, const uint8_t* mask_dev, double* pred_dev, double* innov_dev, void* stream) {
+  if (!p || !y_dev || !pred_dev) return fail(AOG_ERR_INVALID, "aog_predictor_update: null argument");
+  HIP_TRY(hipSetDevice(p->device));
+  aog::PredictorArgs a = predictor_args(p, mask_dev);
+  a.y = y_dev;
+  a.pred = pred_dev;
+  a.innov = innov_dev;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int B = p->cfg.batch;
+  // the register forms hold the wave's rows of P and W (k_predictor.h); above kPredKeepN the two-read form
+  if (p->n <= 64) launch_update<4, 16, 1, 1, true>(a, B, s);
+  else if (p->n <= aog::kPredKeepN && a.A <= 64) launch_update<8, 16, 2, 1, true>(a, B, s);
+  else if (p->n <= aog::kPredKeepN) launch_update<8, 16, 2, 2, true>(a, B, s);
+  else launch_update<8, 0, 4, 4, false>(a, B, s);
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
+int64_t aog_predictor_state_bytes(const aog_predictor* p) { return p ? (int64_t)(p->rec_bytes * (size_t)p->cfg.batch) : 0; }
+
+int aog_predictor_get_state(aog_predictor* p, void* blob_dev, void* stream) {
+  if (!p || !blob_dev) return fail(AOG_ERR_INVALID, "aog_predictor_get_state: null argument");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpyAsync(blob_dev, p->state, p->rec_bytes * (size_t)p->cfg.batch, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  return AOG_OK;
+}
+
+int aog_predictor_set_state(aog_predictor* p, const void* blob_dev, void* stream) {
+  if (!p || !blob_dev) return fail(AOG_ERR_INVALID, "aog_predictor_set_state: null argument");
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipMemcpyAsync(p->state, blob_dev, p->rec_bytes * (size_t)p->cfg.batch, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  return AOG_OK;
+}
+
+}  // extern "C"

@@ -253,7 +253,7 @@ class DeviceActor:
 
 def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, generator=None, actor_impl: str = "auto", seed: int = 0,
             dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None, fused_policy: bool = False, action_mode: str = "sample",
-            science: bool = False):
+            science: bool = False, predictor=None):
     """Collect ``episodes`` lock-step episodes from ``env`` (a ``BatchedAOEnv``).
 
     ``actor_impl``: "hip" = the fused policy-query kernel (``DeviceActor``), "torch" = the module's own forward +
@@ -271,7 +271,11 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     mirror command of the state the last observation saw, applied to the next screen (the one-frame lag every controller has): the ceiling
     Shack-Hartmann and learnt policies are read against.  Same conditions and ``log_prob`` as ``"shack"``.  ``policy="pyramid"``: every
     step's action is ``env.PYR_step()[0]``, the modulated pyramid sensor's integrator (an env built with ``pyramid=dict(...)`` and
-    ``SH_operation=True``, which makes the action the raw actuators); same ``log_prob``.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
+    ``SH_operation=True``, which makes the action the raw actuators); same ``log_prob``.  ``policy="predictive"``: every step's action is
+    ``predictor.action()`` of the ``predictor.PredictiveController`` passed as ``predictor`` (built for this env): a linear predictor of the
+    next best-fit command, learnt on the device by recursive least squares from the measurements the loop takes — what recovers the one-frame
+    lag ``"ideal"`` commits.  Same conditions and ``log_prob`` as ``"shack"``; the predictor is NOT reset at episode ends (the atmosphere is
+    not reset either); not with ``lookahead``.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
     action before the env sees it (and before it is stored, like the reference's in-place ``action +=``), or a ``DeviceOUNoise``
     (``main.py:218-220``: mu 0, theta 0.3, sigma 0.05), which the HIP policy query advances and adds itself: float64 state, Philox normals keyed
     by the global env id (a split batch reproduces the whole one), no extra launch.  Neither is reset here, as in the reference.
@@ -298,21 +302,28 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     B = env.num_envs
     if gatherer is None:
         gatherer = EpisodeReturnGatherer(B, env.device, False)
-    if policy not in ("actor", "shack", "ideal", "pyramid"):
-        raise ValueError("policy must be 'actor', 'shack', 'ideal' or 'pyramid'")
+    if policy not in ("actor", "shack", "ideal", "pyramid", "predictive"):
+        raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid' or 'predictive'")
     if action_mode not in ("sample", "mean"):
         raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
-    ideal, pyramid = policy == "ideal", policy == "pyramid"
-    shack = policy == "shack" or ideal or pyramid   # (no policy query either way: the action is a controller's raw actuator vector)
+    ideal, pyramid, predictive = policy == "ideal", policy == "pyramid", policy == "predictive"
+    shack = policy == "shack" or ideal or pyramid or predictive   # (no policy query either way: the action is a controller's raw actuator vector)
+    if predictive != (predictor is not None):
+        raise ValueError("policy='predictive' takes its controller as predictor=PredictiveController(env, ...), and no other policy takes one")
+    if predictive and predictor.env is not env:
+        raise ValueError("policy='predictive': the predictor was built for another env")
     dev_ou = isinstance(ou_noise, DeviceOUNoise)
     if shack and (dev_ou or action_mode != "sample"):
         raise ValueError(f"policy={policy!r} takes neither a DeviceOUNoise nor action_mode='mean' (the "
-                         f"{'ideal modal controller' if ideal else 'pyramid integrator' if pyramid else 'Shack-Hartmann integrator'} is not a policy query)")
+                         f"{'ideal modal controller' if ideal else 'pyramid integrator' if pyramid else 'predictive controller' if predictive else 'Shack-Hartmann integrator'} is not a policy query)")
     if shack:
         if not getattr(env, "SH_operation", False):
             raise ValueError(f"policy={policy!r} needs an env created with SH_operation=True (AO_env.py:115-116, 254)")
         if pyramid and getattr(env, "pyramid", None) is None:
             raise ValueError("policy='pyramid' needs an env created with pyramid=dict(...)")
+        if predictive and (lookahead or fused_policy):
+            raise ValueError("policy='predictive' goes with neither lookahead nor fused_policy: its measurement is refused while the next screens or "
+                             "the next action are already in place")
         actor_impl = "none"
     elif actor_impl == "auto":
         actor_impl = "hip" if actor_layers(actor) is not None and next(actor.parameters()).is_cuda else "torch"
@@ -378,7 +389,8 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                         mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
                     if shack:
                         # (actuators [B, A] float64, the reference's constant log-probability 1; 'ideal': from the state the last observation saw)
-                        sh_act = env.ideal_action() if ideal else env.PYR_step()[0] if pyramid else env.SH_step()[0]
+                        sh_act = (env.ideal_action() if ideal else env.PYR_step()[0] if pyramid else predictor.action() if predictive
+                                  else env.SH_step()[0])
                         out["act"][i].copy_(sh_act)
                         out["log_prob"][i].fill_(1.0)
                         action = out["act"][i]

@@ -704,6 +704,51 @@ int aog_step_act_noise(aog_env* env, const aog_actor* net, const float* action_d
                        uint8_t* done_dev, float* power_dev, float* strehl_dev, float* action_out, float* log_prob_out, float* mean_out,
                        int* queried /* host int, nullable */, const aog_action_noise* noise /* nullable */, void* stream);
 
+/* ---- predictive linear controller: a per-env recursive-least-squares predictor learnt on the device (additive in ABI 22; no counterpart in
+ * the reference) ----
+ * The data-driven linear predictor learnt controllers are read against.  It depends on no sensor and on no aog_env: it is fed a
+ * pseudo-open-loop measurement y_t [B][A] float64, the actuator vector (metres) that would have flattened the wavefront at step t —
+ * aog_wavefront_truth's act_ideal, or aog_pyramid_update with gain = 1 — and returns its prediction of y_{t+1}.  Per env, n = act_dim x
+ * order, everything float64 without fused multiply-add: W [n][A], P [n][n], a history of the last `order` measurements divided by
+ * `scale` (the regressor x: newest measurement first), `count` (measurements taken) and `skipped`.  After create or reset: W = the
+ * persistence predictor (rows 0 .. A - 1 the identity, the rest 0), P = p0 I, an empty history, both counters 0.
+ *
+ * One update of a selected env (mask_dev: nullable [B] uint8 device array, non-zero = selected), with c = count as the call finds it:
+ *   1. if c >= order a previous regressor x_ exists:  e = y / scale - W' x_,  g = P x_,  d = forgetting + x_' g,
+ *      W[i][j] += (g[i] / d) e[j],  P[i][j] = (P[i][j] - (g[i] g[j]) / d) / forgetting  (g[i] g[j] is formed first: P stays symmetric bit
+ *      for bit; the blob handed to the set_state call must hold a symmetric P, as every blob of the get_state call does);
+ *   2. y / scale is pushed into the history, count = c + 1;
+ *   3. if c >= order (step 1 ran): pred = scale W' x with the new W and the new x; otherwise pred = y, the same bits (persistence).  So the
+ *      first `order` predictions are the measurements themselves and the first prediction through W is made by a W that has learnt once;
+ *   4. innov (nullable) = scale e, zero while no regressor exists.
+ * An env whose row of y holds a non-finite value keeps its whole state; its pred row is a copy of its y row, its innov row zero, and
+ * `skipped` counts it.  Envs the mask leaves out are touched nowhere, and neither are their rows of pred and innov.
+ * One workgroup per env, every sum in an order fixed by (act_dim, order) alone (csrc/k_predictor.h): any split of a batch over handles
+ * reproduces the whole batch bit for bit.  P and W are read once and written once per update up to n = 128 (16 n^2 + 16 n A bytes per env);
+ * from n = 129 to the limit n = 256 they are read twice (24 n^2 + 24 n A).  Plain vector stores, no atomics, no host synchronisation.
+ * AOG_ERR_INVALID, before any device work: batch < 1, act_dim outside [1, 256], order < 1, forgetting outside (0, 1], a non-finite or
+ * non-positive p0 or scale, a nonzero reserved field.  AOG_ERR_UNSUPPORTED, naming the sizes: n > 256.  env_id_base is carried for the
+ * caller (the global id of row 0) and enters no arithmetic.  The struct is six int32 and three doubles; it has no index in aog_struct_size. */
+typedef struct aog_predictor aog_predictor;
+typedef struct aog_predictor_config {
+  int32_t batch, act_dim, order, env_id_base;
+  int32_t reserved0, reserved1;         /* = 0 */
+  double forgetting;                    /* lambda in (0, 1] */
+  double p0;                            /* P = p0 I after create / reset */
+  double scale;                         /* metres per unit of the regressor (BatchedAOEnv: wavelength_wfs / 2 pi) */
+} aog_predictor_config;
+int aog_predictor_create(const aog_predictor_config* cfg, int device, aog_predictor** out);
+void aog_predictor_destroy(aog_predictor* p);
+/* The selected envs (mask_dev as above) back to the state after create, `skipped` included.  Stream-ordered. */
+int aog_predictor_reset(aog_predictor* p, const uint8_t* mask_dev, void* stream);
+/* y_dev, pred_dev [B][A] float64 device pointers, innov_dev likewise or NULL.  Stream-ordered; pred_dev may be y_dev. */
+int aog_predictor_update(aog_predictor* p, const double* y_dev, const uint8_t* mask_dev, double* pred_dev, double* innov_dev, void* stream);
+/* Checkpointing: per env, one after the other, W [n][A], P [n][n], the history [n] (float64), count and skipped (int64) — so the blob of
+ * a whole batch is the blobs of its parts in a row.  A handle of the same configuration that takes the blob resumes bit-identically. */
+int64_t aog_predictor_state_bytes(const aog_predictor* p);
+int aog_predictor_get_state(aog_predictor* p, void* blob_dev, void* stream);
+int aog_predictor_set_state(aog_predictor* p, const void* blob_dev, void* stream);
+
 /* Self-test hook: sin(2 pi u), cos(2 pi u) for n float32 revolutions u_dev with the fused kernels' device code.
  * flavour 0 = polynomial, 1 = v_sin_f32/v_cos_f32 after the exact reduction, 2 = v_sin_f32/v_cos_f32 on raw input. */
 int aog_selftest_sincos(const float* u_dev, float* sin_dev, float* cos_dev, int n, int flavour, void* stream);
