@@ -117,6 +117,8 @@ SYMBOLS = {
     "aog_turbulence_factors": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     "aog_fused_plan": (C.c_int, [C.c_int] * 7 + [C.c_void_p]),
+    "aog_pack_operand_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "aog_reorder_operand_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "aog_set_screen_method": (C.c_int, [C.c_void_p, C.c_int]),
     "aog_upload_sh": (C.c_int, [C.c_void_p, C.POINTER(AogShTables)]),
     "aog_sh_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -233,3 +235,43 @@ def fused_plan(num_envs, n_ap, n_modes, n_wfs_tables, atm_dynamic=False, pixel_c
     check(load().aog_fused_plan(int(num_envs), int(n_ap), int(n_modes), int(n_wfs_tables), int(bool(atm_dynamic)), int(pixel_chunks),
                                 int(bool(four_wave)), out))
     return dict(zip(FUSED_PLAN_FIELDS, out))
+
+
+TILE_ORDERS = {"natural": 0, "accumulator": 1}   # AOG_TILE_*
+
+
+def _tile_array(n_blocks, k_pad, out):
+    import numpy as np
+
+    shape = (int(n_blocks), int(k_pad) // 16, 4, 64, 8)
+    if out is None:
+        return np.empty(shape, dtype=np.uint16)
+    if out.shape != shape or out.dtype != np.uint16 or not out.flags.c_contiguous:
+        raise ValueError(f"operand tiles: out must be a C-contiguous uint16 array of shape {shape}")
+    return out
+
+
+def pack_operand_tiles(m, scale, order, n_blocks, k_pad, out=None):
+    """complex m [rows, K] x scale as split-f16 operand tiles [n_blocks, k_pad / 16, 4, 64, 8] uint16 (IEEE half bits) in ``order``
+    ('natural' | 'accumulator'), by the library's own packer (aog_pack_operand_tiles: host arithmetic only, no device).  Every element of
+    ``out`` (default: a new array) is written."""
+    import numpy as np
+
+    m = np.asarray(m, dtype=np.complex128)
+    ri = np.ascontiguousarray(np.stack([m.real, m.imag], axis=-1))
+    out = _tile_array(n_blocks, k_pad, out)
+    check(load().aog_pack_operand_tiles(ri.ctypes.data_as(C.c_void_p), m.shape[0], m.shape[1], float(scale), TILE_ORDERS[order], int(n_blocks), int(k_pad),
+                                        out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def reorder_operand_tiles(src, src_order, dst_order, dst_blocks, dst_k_pad, out=None):
+    """The tiles of the transposed matrix of the packed table ``src`` [n_blocks, k_pad / 16, 4, 64, 8] uint16, in ``dst_order`` and the
+    given shape (aog_reorder_operand_tiles: the halves are copied, nothing is rounded again)."""
+    import numpy as np
+
+    src = np.ascontiguousarray(src, dtype=np.uint16)
+    out = _tile_array(dst_blocks, dst_k_pad, out)
+    check(load().aog_reorder_operand_tiles(src.ctypes.data_as(C.c_void_p), TILE_ORDERS[src_order], src.shape[0], 16 * src.shape[1], TILE_ORDERS[dst_order],
+                                           int(dst_blocks), int(dst_k_pad), out.ctypes.data_as(C.c_void_p)))
+    return out

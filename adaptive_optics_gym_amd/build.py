@@ -30,8 +30,8 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-fno-s
 # headers each unit includes besides the shared ones (an edit of a family header recompiles that family only)
 SHARED = ("aogym_internal.h", "host_common.h", "k_common.h", "fused_layout.h")
 DETECTOR = ("k_poisson.h", "k_detector.h")
-FAMILY = {"aogym": ("k_pack.h", "k_step.h", "k_actor.h", "k_step_act.h") + DETECTOR, "atmosphere": ("k_pack.h", "k_extrude.h", "k_extrude_i8.h"), "screens": ("k_fft.h", "k_screens.h"),
-          "shack": ("k_fft.h", "k_shack.h", "k_poisson.h"), "focal": ("k_focal.h", "k_mft_mma.h", "k_obs.h") + DETECTOR, "actor": ("k_actor.h",), "wavefront": ("k_wavefront.h", "k_pupil_tile.h"), "science": ("k_science.h", "k_mft_mma.h"), "gradient": ("k_gradient.h", "k_pupil_tile.h"), "gradient_obs": ("k_gradient_obs.h", "k_pupil_tile.h", "k_mft_mma.h"), "layers": ("k_layers.h",), "pyramid": ("k_pyramid.h", "k_mft_mma.h", "k_poisson.h"), "pyramid_grad": ("k_pyramid_grad.h", "k_pupil_tile.h"), "predictor": ("k_predictor.h",), "fused_inst": ("k_fused.h",)}
+FAMILY = {"aogym": ("mft_host.h", "k_pack.h", "k_step.h", "k_actor.h", "k_step_act.h") + DETECTOR, "atmosphere": ("k_pack.h", "k_extrude.h", "k_extrude_i8.h"), "screens": ("k_fft.h", "k_screens.h"),
+          "shack": ("k_fft.h", "k_shack.h", "k_poisson.h"), "focal": ("mft_host.h", "k_focal.h", "k_mft_mma.h", "k_obs.h") + DETECTOR, "actor": ("k_actor.h",), "wavefront": ("k_wavefront.h", "k_pupil_tile.h"), "science": ("mft_host.h", "k_science.h", "k_mft_mma.h"), "gradient": ("k_gradient.h", "k_pupil_tile.h"), "gradient_obs": ("mft_host.h", "k_gradient_obs.h", "k_pupil_tile.h", "k_mft_mma.h"), "layers": ("k_layers.h",), "pyramid": ("mft_host.h", "k_pyramid.h", "k_mft_mma.h", "k_poisson.h"), "pyramid_grad": ("mft_host.h", "k_pyramid_grad.h", "k_pupil_tile.h"), "predictor": ("k_predictor.h",), "fused_inst": ("k_fused.h",)}
 
 
 def hipcc_path() -> str:

@@ -1,6 +1,6 @@
 // libaogym.so — C-ABI (include/aogym.h) over the gfx950 kernels in the k_*.h headers.
 // Host side only: argument checking, table conversion/upload, launch geometry, stream-ordered launches.
-#include "host_common.h"
+#include "mft_host.h"
 #include "k_pack.h"
 #include "k_step.h"
 #include "k_step_act.h"
@@ -800,9 +800,8 @@ int aog_upload_tables(aog_env* e, const aog_tables* t) {
     if ((rc = dev_alloc(e, &e->focal_E, (size_t)N * N * 2)) != AOG_OK) return rc;
     if ((rc = dev_alloc(e, &e->focal_T, (size_t)nf * N * 2)) != AOG_OK) return rc;
     if (e->cfg.precision == AOG_PRECISION_FAST) {   // split-f16 operand tables of the batched matrix-core path (k_focal_pass1 / k_focal_pass2)
-      const int Nxp = round_up(N, 128), Nyp = round_up(N, 16), nfp = round_up(nf, 128);
       std::vector<_Float16> m1s, m2s;
-      e->focal_unscale = mft_operand_tables(t->focal_m1, t->focal_m2, N, nf, nfp, Nxp, Nyp, m1s, m2s);
+      e->focal_unscale = mft_operand_tables(t->focal_m1, t->focal_m2, N, nf, mft_geom_wide(N, round_up(nf, 128)), m1s, m2s);
       if ((rc = upload(e, &e->focal_m1s, m1s)) != AOG_OK) return rc;
       if ((rc = upload(e, &e->focal_m2s, m2s)) != AOG_OK) return rc;
       if ((rc = upload(e, &e->focal_ap_yx, ap_yx_table(e), true)) != AOG_OK) return rc;

@@ -13,10 +13,12 @@ namespace aog {
 struct X8Table;
 }
 
-// Work buffers of a split-f16 Fraunhofer transform (K4, K11, the science camera) for a chunk of whole env tiles (focal.hip: mft_work_alloc)
+// Work buffers of a split-f16 Fraunhofer transform (K4, K11, the science camera, the pyramid) for a chunk of whole env tiles (mft_host.h:
+// mft_work_alloc).  "Tiles", "natural" and "accumulator" in the comments of this file are DESIGN.md §5's ("Operand tiles of the MFT family"):
+// a matrix [i][k] as [i >> 5][k >> 4] tiles of [4][64][8] f16, lane = i, K = k in one of the two orders; sizes are MftGeom's (mft_host.h).
 struct MftWork {
   float* grid = nullptr;      // [chunk][Nyp][Nxp] reduced phases (revolutions), kShOutside outside the aperture and in the padding
-  _Float16* T16 = nullptr;    // [chunk][Nxp / 32][v blocks][2][4][64][8]: T' = m1' E, split, pass 2's operand order
+  _Float16* T16 = nullptr;    // [chunk][Nxp / 32][v blocks][2] tiles: T' = m1' E, split, as pass 1's accumulators hold it (lane v, K = x accumulator)
   int chunk = 0;              // envs per round of phase grid + pass 1 + pass 2
 };
 
@@ -102,8 +104,8 @@ struct aog_env {
   double* focal_m2 = nullptr;    // [N][n_focal] complex
   double* focal_E = nullptr;     // [N][N] complex scratch
   double* focal_T = nullptr;     // [n_focal][N] complex scratch
-  _Float16* focal_m1s = nullptr; // split-f16 operand tiles of the batched matrix-core path (aog_focal_images): m1 2^e1, [v block][k-step][4][64][8]
-  _Float16* focal_m2s = nullptr; // m2 2^e2, [u block][x tile][2][4][64][8] (x in the order pass 1's accumulators hold it)
+  _Float16* focal_m1s = nullptr; // the batched matrix-core path (aog_focal_images): m1 2^e1, [nfp / 32][Nyp / 16] tiles, lane v, K = y natural
+  _Float16* focal_m2s = nullptr; // m2 2^e2, [nfp / 32][Nxp / 16] tiles, lane u, K = x accumulator
   float focal_unscale = 1.f;     // 2^-(e1 + e2)
   int32_t* focal_ap_yx = nullptr;  // [n_ap] iy << 16 | ix of aperture pixel p (K4, K11 and the science camera: whoever comes first uploads it)
   MftWork focal_work;            // allocated by the first aog_focal_images; Nxp = N rounded up to 128, nfp / 32 v blocks
@@ -111,8 +113,8 @@ struct aog_env {
   // separable observation route (cfg.obs_separable, aog_upload_obs_mft; K11, k_obs.h)
   bool obs_sep = false;
   bool obs_ready = false;        // aog_upload_obs_mft done
-  _Float16* obs_m1s = nullptr;   // m1 2^e1, K4's m1s layout with one v block: [Nyp / 16][4][64][8]
-  _Float16* obs_m2s = nullptr;   // m2 2^e2, K4's m2s layout with one u block: [Nxp / 32][2][4][64][8]
+  _Float16* obs_m1s = nullptr;   // m1 2^e1, K4's m1s layout with one v block
+  _Float16* obs_m2s = nullptr;   // m2 2^e2, K4's m2s layout with one u block
   float obs_unscale = 1.f;
   MftWork obs_work;              // Nxp = N rounded up to 32, one v block
   _Float16* obs_act16 = nullptr; // actuators of the step being observed in the phase kernel's operand layouts (hi | lo, third term):
@@ -151,8 +153,8 @@ struct aog_env {
   bool gobs_ready = false;         // the transposed operand tables are uploaded (aog_upload_tables clears it)
   int gobs_chunk = 0;              // envs per round: obs_work.chunk, or less through AOG_GRAD_OBS_CHUNK (whole env tiles)
   double gobs_unscale = 1.0;       // 2^-(e1 + e2) of the two tables below
-  _Float16* gobs_m1t = nullptr;    // m1' 2^e1 as A operands: [ceil(Nyp / 32)][step 2][4][64][8], row y, K = v in the order accumulators hold it
-  _Float16* gobs_m2t = nullptr;    // m2' 2^e2 as B operands: [Nxp / 32][step 2][4][64][8], column x, K = u
+  _Float16* gobs_m1t = nullptr;    // m1' 2^e1 as A operands: [ceil(Nyp / 32)][2] tiles, lane y, K = v accumulator
+  _Float16* gobs_m2t = nullptr;    // m2' 2^e2 as B operands: [Nxp / 32][2] tiles, lane x, K = u natural
   _Float16* gobs_act_ll = nullptr; // the call's own third f16 term of the actuators (grad_act16 holds the first two)
   _Float16* gobs_wop = nullptr;    // [chunk][step 2][4][64][8] W / wscale of every env as A operands (row v, K = u)
   double* gobs_wscale = nullptr;   // [B] the power of two W was divided by
@@ -194,10 +196,10 @@ struct aog_env {
   double pyr_back_unscale = 1.0; // and of the stored field x b1s x b2s
   _Float16* pyr_m1s = nullptr;   // [n_mod] x the science camera's m1s layout with ceil(w / 32) v blocks
   _Float16* pyr_m2s = nullptr;   // [n_mod] x its m2s layout
-  _Float16* pyr_b1s = nullptr;   // [2][ceil(n_s / 32)][ceil(w / 32)][2] tiles: column y', K = v in accumulator order
-  _Float16* pyr_b2s = nullptr;   // [2][ceil(n_s / 32)][ceil(w / 32)][2] tiles: column x', K = u in accumulator order
+  _Float16* pyr_b1s = nullptr;   // [2][ceil(n_s / 32)][2 ceil(w / 32)] tiles: lane y', K = v accumulator
+  _Float16* pyr_b2s = nullptr;   // [2][ceil(n_s / 32)][2 ceil(w / 32)] tiles: lane x', K = u accumulator
   MftWork pyr_work;              // phases at lambda_wfs; Nxp = N rounded up to 128, ceil(w / 32) v blocks
-  _Float16* pyr_fop = nullptr;   // [chunk][u block][v block][2][4][64][8]: F_j 2^6, split, k_pyr_back's A operands (row u, K = v)
+  _Float16* pyr_fop = nullptr;   // [chunk][nvb][2 nvb] tiles: F_j 2^6, split, k_pyr_back's A operands (lane u, K = v accumulator)
   _Float16* pyr_act16 = nullptr; // the calls' own copy of the actuators in act16's layout, and their third f16 term
   _Float16* pyr_act_ll = nullptr;
   float* pyr_tile_keep = nullptr;  // dynamic handles whose psi_tile a sensor call refreshes (obs_tiles): psi_tile as the call found it, put back behind the call
@@ -231,11 +233,11 @@ struct aog_env {
   double* pyg_slabs = nullptr;   // [A][Bp] sum_p M_pk q_p (fast handles: [pixel chunk][A_pad][Bp])
   double* pyg_gscale = nullptr;  // [B] the power of two of the largest |cotangent| of the env (1 for a zero cotangent)
   // fast handles: the transposed operand tables (made from the uploaded ones by the first call) and the chunk's work buffers
-  _Float16* pyg_m1s_t = nullptr; // [n_mod][ceil(Nyp / 32)][nvb][2] tiles: row y, K = v in accumulator order
-  _Float16* pyg_m2s_t = nullptr; // [n_mod][Nxp / 32][2 nvb] tiles: column x, K = u
-  _Float16* pyg_b1s_t = nullptr; // [2][nvb][nsb][2] tiles: column v, K = y' in accumulator order
-  _Float16* pyg_b2s_t = nullptr; // [2][nvb][nsb][2] tiles: column u, K = x' in accumulator order
-  _Float16* pyg_vop = nullptr;   // [chunk][nvb][2 nvb] tiles: V_j / scales as A operands (row v, K = u); the pads stay zero
+  _Float16* pyg_m1s_t = nullptr; // [n_mod][ceil(Nyp / 32)][2 nvb] tiles: lane y, K = v accumulator
+  _Float16* pyg_m2s_t = nullptr; // [n_mod][Nxp / 32][2 nvb] tiles: lane x, K = u natural
+  _Float16* pyg_b1s_t = nullptr; // [2][nvb][2 nsb] tiles: lane v, K = y' accumulator
+  _Float16* pyg_b2s_t = nullptr; // [2][nvb][2 nsb] tiles: lane u, K = x' accumulator
+  _Float16* pyg_vop = nullptr;   // [chunk][nvb][2 nvb] tiles: V_j / scales as A operands (lane v, K = u natural); the pads stay zero
   double* pyg_wscale = nullptr;  // [chunk] W's power of two over V's, of the modulation point in flight
   double* pyg_qscale = nullptr;  // [B] the power of two the env's q grid was divided by
   float* pyg_qgrid = nullptr;    // [chunk][Nyp][Nxp] q summed over the modulation points, on aperture pixels

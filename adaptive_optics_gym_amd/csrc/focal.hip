@@ -1,5 +1,5 @@
 // K4: focal-plane field export (aog_focal_image / aog_focal_images); K11: the observation of the separable route (aog_upload_obs_mft, launch_obs).
-#include "host_common.h"
+#include "mft_host.h"
 #include "k_focal.h"
 #include "k_obs.h"
 
@@ -7,44 +7,29 @@ using namespace aog_host;
 
 namespace aog_host {
 
-float mft_operand_tables(const double* m1, const double* m2, int N, int nf, int nfp, int Nxp, int Nyp, std::vector<_Float16>& m1s,
-                         std::vector<_Float16>& m2s) {
-  // power-of-two scales: the largest component of a table lands in [1/2, 1)
-  auto scale_of = [](const double* v, size_t n) {
-    double mx = 0.0;
-    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(v[i]));
-    return mx > 0.0 ? std::ldexp(1.0, -(std::ilogb(mx) + 1)) : 1.0;
-  };
+static_assert(kTileF16 == (size_t)aog::kFocalTile * 8, "an operand tile on the host is the kFocalTile f16x8 the kernels step by");
+
+double scale_of(const double* v, size_t n) {
+  double mx = 0.0;
+  for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(v[i]));
+  return mx > 0.0 && std::isfinite(mx) ? std::ldexp(1.0, -(std::ilogb(mx) + 1)) : 1.0;
+}
+
+void reorder_tiles(_Float16* dst, int dst_order, int dst_blocks, int dst_k_pad, const _Float16* src, int src_order, int src_blocks, int src_k_pad) {
+  pack_tiles(dst, dst_order, dst_blocks, dst_k_pad, src_k_pad, 32 * src_blocks, [&](int i, int k) {
+    const _Float16* p = src + tile_offset(src_order, src_k_pad, k, i);
+    return TileParts{{p[0], p[kTilePartF16], p[2 * kTilePartF16], p[3 * kTilePartF16]}};
+  });
+}
+
+float mft_operand_tables(const double* m1, const double* m2, int N, int nf, const MftGeom& g, std::vector<_Float16>& m1s, std::vector<_Float16>& m2s) {
   const double s1 = scale_of(m1, (size_t)nf * N * 2), s2 = scale_of(m2, (size_t)nf * N * 2);
-  auto put = [](std::vector<_Float16>& tab, size_t tile, int lane, int slot, double re, double im) {
-    const double c[2] = {re, im};
-    for (int q = 0; q < 2; ++q) {
-      const _Float16 hi = (_Float16)(float)c[q];   // round to nearest, like the kernels' split8
-      tab[((tile * 4 + 2 * q) * 64 + lane) * 8 + slot] = hi;
-      tab[((tile * 4 + 2 * q + 1) * 64 + lane) * 8 + slot] = (_Float16)(float)(c[q] - (double)(float)hi);
-    }
-  };
-  // m1s [v block][k-step over y]: lane l = column v = 32 vb + (l & 31), slot j = y = 16 ks + 8 (l >> 5) + j
-  m1s.assign((size_t)(nfp / 32) * (Nyp / 16) * 4 * 64 * 8, (_Float16)0.f);
-  for (int vb = 0; vb < nfp / 32; ++vb)
-    for (int ks = 0; ks < Nyp / 16; ++ks)
-      for (int l = 0; l < 64; ++l)
-        for (int j = 0; j < 8; ++j) {
-          const int v = 32 * vb + (l & 31), y = 16 * ks + 8 * (l >> 5) + j;
-          if (v < nf && y < N) put(m1s, (size_t)vb * (Nyp / 16) + ks, l, j, m1[((size_t)v * N + y) * 2] * s1, m1[((size_t)v * N + y) * 2 + 1] * s1);
-        }
-  // m2s [u block][x tile][s]: lane l = column u = 32 ub + (l & 31), slot j = x = 32 xt + (r & 3) + 8 (r >> 2) + 4 (l >> 5), r = 8 s + j
-  // (the order in which pass 1's accumulator registers hold x)
-  m2s.assign((size_t)(nfp / 32) * (Nxp / 32) * 2 * 4 * 64 * 8, (_Float16)0.f);
-  for (int ub = 0; ub < nfp / 32; ++ub)
-    for (int xt = 0; xt < Nxp / 32; ++xt)
-      for (int s2i = 0; s2i < 2; ++s2i)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 8; ++j) {
-            const int r = 8 * s2i + j, x = 32 * xt + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), u = 32 * ub + (l & 31);
-            if (u < nf && x < N)
-              put(m2s, ((size_t)ub * (Nxp / 32) + xt) * 2 + s2i, l, j, m2[((size_t)x * nf + u) * 2] * s2, m2[((size_t)x * nf + u) * 2 + 1] * s2);
-          }
+  m1s.resize(g.m1_f16());
+  pack_tiles(m1s.data(), AOG_TILE_NATURAL, g.nvb, g.Nyp, nf, N,
+             [&](int v, int y) { return std::complex<double>(m1[((size_t)v * N + y) * 2] * s1, m1[((size_t)v * N + y) * 2 + 1] * s1); });
+  m2s.resize(g.m2_f16());
+  pack_tiles(m2s.data(), AOG_TILE_ACCUMULATOR, g.nvb, g.Nxp, nf, N,
+             [&](int u, int x) { return std::complex<double>(m2[((size_t)x * nf + u) * 2] * s2, m2[((size_t)x * nf + u) * 2 + 1] * s2); });
   return (float)(1.0 / (s1 * s2));
 }
 
@@ -71,28 +56,33 @@ void launch_cgemm64(hipStream_t s, const double* a, const double* b, double* out
                      reinterpret_cast<const double2*>(b), reinterpret_cast<double2*>(out), reinterpret_cast<float2*>(out32), R, K, Cn, mask, env);
 }
 
-// K11 geometry: x padded to whole 32-column tiles (one wave each), y to whole 16-row k-steps
-static int obs_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 32); }
-static int obs_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
+void launch_mft64(aog_env* e, hipStream_t s, const Mft64& t, double* F, float* F32, int env, bool field, double ratio, const uint8_t* mask, const double* act_src) {
+  const int N = e->cfg.n_pupil;
+  if (field) launch_focal_field(e, s, t.E, env, ratio, mask, act_src);
+  launch_cgemm64(s, t.m1, t.E, t.T, nullptr, t.w, N, N, mask, env);
+  launch_cgemm64(s, t.T, t.m2, F, F32, t.w, N, t.w, mask, env);
+}
+
+int alloc_act_operands(aog_env* e, _Float16** act16, _Float16** act_ll) {
+  const size_t n = (size_t)e->n_etiles * 32 * e->A_pad;
+  if (int rc = act16 ? need(e, act16, 2 * n, true) : AOG_OK) return rc;
+  return need(e, act_ll, n, true);
+}
 
 void launch_obs_pass1(aog_env* e, hipStream_t s, int n) {
-  const int Nxp = obs_nxp(e), Nyp = obs_nyp(e);
-  hipLaunchKernelGGL(aog::k_obs_pass1, dim3((n * (Nxp / 32) + 3) / 4), dim3(256), 0, s, e->obs_work.grid, reinterpret_cast<const aog::f16x8*>(e->obs_m1s),
-                     reinterpret_cast<aog::f16x8*>(e->obs_work.T16), Nxp, Nyp, n);
+  const MftGeom g = mft_geom_narrow(e->cfg.n_pupil);
+  hipLaunchKernelGGL(aog::k_obs_pass1, dim3((n * (g.Nxp / 32) + 3) / 4), dim3(256), 0, s, e->obs_work.grid, f16x8p(e->obs_m1s), f16x8p(e->obs_work.T16),
+                     g.Nxp, g.Nyp, n);
 }
 
 int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const uint8_t* mask) {
   if (!e->obs_sep) return AOG_OK;
-  const int N = e->cfg.n_pupil, o = e->cfg.obs_dim, n_obs = e->n_obs;
+  const int o = e->cfg.obs_dim, n_obs = e->n_obs;
   if (e->cfg.precision == AOG_PRECISION_FP64) {
     // validation form: per env, E on the pupil grid (k_focal_field writes the aperture pixels; the rest of obs_E stays 0), then the two
     // products in float64
     const double2* F = reinterpret_cast<const double2*>(e->obs_F);
-    for (int env = 0; env < e->B; ++env) {
-      launch_focal_field(e, s, e->obs_E, env);
-      launch_cgemm64(s, e->obs_m1d, e->obs_E, e->obs_T, nullptr, o, N, N);
-      launch_cgemm64(s, e->obs_T, e->obs_m2d, e->obs_F + (size_t)env * n_obs * 2, nullptr, o, N, o);
-    }
+    for (int env = 0; env < e->B; ++env) launch_mft64(e, s, {e->obs_m1d, e->obs_m2d, e->obs_E, e->obs_T, o}, e->obs_F + (size_t)env * n_obs * 2, nullptr, env);
     const int n = e->B * n_obs;
     if (e->det_on)
       hipLaunchKernelGGL(aog::k_obs_finish64_det, dim3((n + 255) / 256), dim3(256), 0, s, F, n, n_obs, e->obs_pw, obs_raw, obs, detector_args(e, mask));
@@ -103,21 +93,19 @@ int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const u
   }
   if (int rc = obs_tiles(e, s)) return rc;
   if (int rc = load_actuators(e, s, {nullptr, e->obs_act16, e->obs_act_ll})) return rc;   // (own copies: act_rev / act16 are not touched)
-  const int Nxp = obs_nxp(e), Nyp = obs_nyp(e), nxt = Nxp / 32;
-  const size_t grid_env = (size_t)Nyp * Nxp;
+  const MftGeom g = mft_geom_narrow(e->cfg.n_pupil);
+  const int nxt = g.Nxp / 32;
   for (int env0 = 0; env0 < e->B; env0 += e->obs_work.chunk) {
     const int n = std::min(e->obs_work.chunk, e->B - env0), n_et = (n + 31) / 32;
-    aog_host::launch_phase_grid(e, s, e->obs_act16, e->obs_act_ll, e->obs_work.grid, grid_env, Nxp, env0 / 32, n_et);
+    aog_host::launch_phase_grid(e, s, e->obs_act16, e->obs_act_ll, e->obs_work.grid, g.grid_env(), g.Nxp, env0 / 32, n_et);
     launch_obs_pass1(e, s, n);
     const size_t off = (size_t)env0 * n_obs;
     if (e->det_on)
-      hipLaunchKernelGGL(aog::k_obs_pass2_det, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_work.T16),
-                         reinterpret_cast<const aog::f16x8*>(e->obs_m2s), nxt, n, o, e->obs_unscale, e->obs_pw + off, obs_raw ? obs_raw + off : nullptr,
-                         obs ? obs + off : nullptr, detector_args(e, mask), env0);
+      hipLaunchKernelGGL(aog::k_obs_pass2_det, dim3((n + 3) / 4), dim3(256), 0, s, f16x8p(e->obs_work.T16), f16x8p(e->obs_m2s), nxt, n, o, e->obs_unscale,
+                         e->obs_pw + off, obs_raw ? obs_raw + off : nullptr, obs ? obs + off : nullptr, detector_args(e, mask), env0);
     else
-      hipLaunchKernelGGL(aog::k_obs_pass2, dim3((n + 3) / 4), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->obs_work.T16),
-                         reinterpret_cast<const aog::f16x8*>(e->obs_m2s), nxt, n, o, e->obs_unscale, e->obs_pw + off, obs_raw ? obs_raw + off : nullptr,
-                         obs ? obs + off : nullptr);
+      hipLaunchKernelGGL(aog::k_obs_pass2, dim3((n + 3) / 4), dim3(256), 0, s, f16x8p(e->obs_work.T16), f16x8p(e->obs_m2s), nxt, n, o, e->obs_unscale,
+                         e->obs_pw + off, obs_raw ? obs_raw + off : nullptr, obs ? obs + off : nullptr);
   }
   HIP_TRY(hipGetLastError());
   return AOG_OK;
@@ -146,19 +134,43 @@ int aog_upload_obs_mft(aog_env* e, const aog_obs_mft* t) {
     e->obs_ready = true;
     return AOG_OK;
   }
-  const int Nxp = obs_nxp(e), Nyp = obs_nyp(e);
+  const MftGeom g = mft_geom_narrow(N);
   std::vector<_Float16> m1s, m2s;
-  e->obs_unscale = mft_operand_tables(t->m1, t->m2, N, o, 32, Nxp, Nyp, m1s, m2s);
+  e->obs_unscale = mft_operand_tables(t->m1, t->m2, N, o, g, m1s, m2s);
   if ((rc = upload(e, &e->obs_m1s, m1s)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->obs_m2s, m2s)) != AOG_OK) return rc;
   // (shared with K4: where each packed aperture pixel lies on the pupil grid)
   if (!e->focal_ap_yx && (rc = upload(e, &e->focal_ap_yx, ap_yx_table(e))) != AOG_OK) return rc;
   // work buffers for whole env tiles, at most ~512 MB together
-  const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * 2 * 4 * 64 * 8;
+  const size_t grid_env = g.grid_env(), t16_env = g.t16_env();
   if ((rc = mft_work_alloc(e, &e->obs_work, grid_env, t16_env, ((size_t)512 << 20) / (grid_env * 4 + t16_env * 2), nullptr)) != AOG_OK) return rc;
-  if ((rc = dev_alloc(e, &e->obs_act16, (size_t)e->n_etiles * 32 * e->A_pad * 2, true)) != AOG_OK) return rc;
-  if ((rc = dev_alloc(e, &e->obs_act_ll, (size_t)e->n_etiles * 32 * e->A_pad, true)) != AOG_OK) return rc;
+  if ((rc = alloc_act_operands(e, &e->obs_act16, &e->obs_act_ll)) != AOG_OK) return rc;
   e->obs_ready = true;
+  return AOG_OK;
+}
+
+static int check_tile_shape(const char* who, int order, int n_blocks, int k_pad) {
+  if ((order != AOG_TILE_NATURAL && order != AOG_TILE_ACCUMULATOR) || n_blocks < 1 || k_pad < 16 || k_pad % 16)
+    return fail(AOG_ERR_INVALID, "%s: order %d, %d blocks, k_pad = %d (an AOG_TILE_* order, at least one block, k_pad a positive multiple of 16)", who,
+                order, n_blocks, k_pad);
+  return AOG_OK;
+}
+
+int aog_pack_operand_tiles(const double* m, int rows, int K, double scale, int order, int n_blocks, int k_pad, uint16_t* tiles_out) {
+  if (!m || !tiles_out || rows < 1 || K < 1) return fail(AOG_ERR_INVALID, "aog_pack_operand_tiles: null argument or empty matrix");
+  if (int rc = check_tile_shape("aog_pack_operand_tiles", order, n_blocks, k_pad)) return rc;
+  if (rows > 32 * n_blocks || K > k_pad) return fail(AOG_ERR_INVALID, "aog_pack_operand_tiles: [%d][%d] does not fit %d blocks x %d", rows, K, n_blocks, k_pad);
+  pack_tiles(reinterpret_cast<_Float16*>(tiles_out), order, n_blocks, k_pad, rows, K,
+             [&](int i, int k) { return std::complex<double>(m[((size_t)i * K + k) * 2] * scale, m[((size_t)i * K + k) * 2 + 1] * scale); });
+  return AOG_OK;
+}
+
+int aog_reorder_operand_tiles(const uint16_t* src, int src_order, int src_blocks, int src_k_pad, int dst_order, int dst_blocks, int dst_k_pad,
+                              uint16_t* dst) {
+  if (!src || !dst) return fail(AOG_ERR_INVALID, "aog_reorder_operand_tiles: null argument");
+  if (int rc = check_tile_shape("aog_reorder_operand_tiles (source)", src_order, src_blocks, src_k_pad)) return rc;
+  if (int rc = check_tile_shape("aog_reorder_operand_tiles (destination)", dst_order, dst_blocks, dst_k_pad)) return rc;
+  reorder_tiles(reinterpret_cast<_Float16*>(dst), dst_order, dst_blocks, dst_k_pad, reinterpret_cast<const _Float16*>(src), src_order, src_blocks, src_k_pad);
   return AOG_OK;
 }
 
@@ -174,9 +186,7 @@ int aog_focal_image(aog_env* e, int env_index, float* field_dev, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int N = e->cfg.n_pupil, nf = e->n_focal;
   HIP_TRY(hipMemsetAsync(e->focal_E, 0, sizeof(double) * 2 * N * N, s));
-  launch_focal_field(e, s, e->focal_E, env_index);
-  launch_cgemm64(s, e->focal_m1, e->focal_E, e->focal_T, nullptr, nf, N, N);
-  launch_cgemm64(s, e->focal_T, e->focal_m2, nullptr, field_dev, nf, N, nf);
+  launch_mft64(e, s, {e->focal_m1, e->focal_m2, e->focal_E, e->focal_T, nf}, nullptr, field_dev, env_index);
   HIP_TRY(hipGetLastError());
   return AOG_OK;
 }
@@ -194,12 +204,13 @@ int aog_focal_images(aog_env* e, int first, int count, float* field_dev, void* s
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int N = e->cfg.n_pupil, nf = e->n_focal;
   int rc;
-  const int Nxp = round_up(N, 128), Nyp = round_up(N, 16), nfp = round_up(nf, 128);
-  const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * (nfp / 32) * 2 * 4 * 64 * 8;
+  const MftGeom g = mft_geom_wide(N, round_up(nf, 128));
+  const int Nxp = g.Nxp, Nyp = g.Nyp, nfp = 32 * g.nvb;
+  const size_t grid_env = g.grid_env(), t16_env = g.t16_env();
   if (!e->focal_work.grid) {   // work buffers on first use, at most ~256 MB each
     if ((rc = mft_work_alloc(e, &e->focal_work, grid_env, t16_env, ((size_t)256 << 20) / std::max(grid_env * 4, t16_env * 2), "AOG_FOCAL_CHUNK")) != AOG_OK)
       return rc;
-    if ((rc = dev_alloc(e, &e->focal_act_ll, (size_t)e->n_etiles * 32 * e->A_pad, true)) != AOG_OK) return rc;
+    if ((rc = alloc_act_operands(e, nullptr, &e->focal_act_ll)) != AOG_OK) return rc;
   }
   // psi_tile is always current for quasi_static / semi_dynamic handles; dynamic ones refresh it here when the step kernel does not use it
   if ((rc = ensure_tiles(e, s)) != AOG_OK) return rc;
@@ -212,10 +223,9 @@ int aog_focal_images(aog_env* e, int first, int count, float* field_dev, void* s
     aog_host::launch_phase_grid(e, s, e->act16, e->focal_act_ll, e->focal_work.grid, grid_env, Nxp, env0 / 32, n_et);
     const size_t skip = (size_t)(lo - env0);
     hipLaunchKernelGGL(aog::k_focal_pass1, dim3(Nxp / 128, nfp / 128, env1 - lo), dim3(256), 0, s, e->focal_work.grid + skip * grid_env,
-                       reinterpret_cast<const aog::f16x8*>(e->focal_m1s), reinterpret_cast<aog::f16x8*>(e->focal_work.T16), Nxp, Nyp, nfp);
-    hipLaunchKernelGGL(aog::k_focal_pass2, dim3(nfp / 128, nfp / 128, env1 - lo), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->focal_work.T16),
-                       reinterpret_cast<const aog::f16x8*>(e->focal_m2s), reinterpret_cast<float2*>(field_dev) + (size_t)(lo - first) * nf * nf, Nxp, nfp,
-                       nf, e->focal_unscale);
+                       f16x8p(e->focal_m1s), f16x8p(e->focal_work.T16), Nxp, Nyp, nfp);
+    hipLaunchKernelGGL(aog::k_focal_pass2, dim3(nfp / 128, nfp / 128, env1 - lo), dim3(256), 0, s, f16x8p(e->focal_work.T16), f16x8p(e->focal_m2s),
+                       reinterpret_cast<float2*>(field_dev) + (size_t)(lo - first) * nf * nf, Nxp, nfp, nf, e->focal_unscale);
     HIP_TRY(hipGetLastError());
   }
   return AOG_OK;

@@ -41,6 +41,11 @@ int dev_alloc(aog_env* e, T** out, size_t count, bool zero = true) {
   if (rc == AOG_OK) *out = static_cast<T*>(p);
   return rc;
 }
+// a buffer made on first use: allocated unless it is there already
+template <typename T>
+int need(aog_env* e, T** ptr, size_t count, bool zero = false) {
+  return *ptr ? AOG_OK : dev_alloc(e, ptr, count, zero);
+}
 // give a work buffer of the handle back (workspaces that are re-sized when the caller changes the synthesis method or oversampling:
 // without this every change would keep the old gigabytes until aog_destroy)
 template <typename T>
@@ -180,21 +185,6 @@ int launch_obs(aog_env* e, hipStream_t s, float* obs_raw, uint16_t* obs, const u
 void launch_obs_pass1(aog_env* e, hipStream_t s, int n);
 // the detector's kernel arguments for the observation this call writes (e->det_on): frame = e->obs_frame
 aog::DetectorArgs detector_args(const aog_env* e, const uint8_t* mask);
-// split-f16 operand tables of a Fraunhofer matrix Fourier transform m1 [nf][N] . E . m2 [N][nf] (K4's layouts: m1s [nfp / 32][Nyp / 16] tiles,
-// m2s [nfp / 32][Nxp / 32][2] tiles), each matrix scaled by a power of two; returns the unscale factor 2^-(e1 + e2)
-float mft_operand_tables(const double* m1, const double* m2, int N, int nf, int nfp, int Nxp, int Nyp, std::vector<_Float16>& m1s,
-                         std::vector<_Float16>& m2s);
-// focal.hip: the work buffers of such a transform.  The chunk is the handle's whole env tiles, capped at cap_envs (the caller's memory rule)
-// rounded down to whole tiles, at least one, and at the value of the environment variable chunk_env (nullable; tests: several chunks at small
-// sizes); the grid starts out as "outside the aperture" everywhere (only aperture pixels are ever written).  Blocking.
-int mft_work_alloc(aog_env* e, MftWork* w, size_t grid_env, size_t t16_env, size_t cap_envs, const char* chunk_env);
-// focal.hip: the steps of the float64 validation forms for one env (K4's single-env export, K11, the science camera).  launch_focal_field:
-// E = exp(2 pi i ratio u_p) on the aperture pixels of the [N][N] complex grid E (the rest is left as it is); launch_cgemm64: out [R][Cn]
-// (and / or its complex64 copy out32) = a [R][K] b [K][Cn], complex row-major.  mask (nullable): nothing happens for an env it leaves out.
-void launch_focal_field(aog_env* e, hipStream_t s, double* E, int env, double ratio = 1.0, const uint8_t* mask = nullptr,
-                        const double* act_src = nullptr);   // act_src: nullable [B][A] actuators instead of the mirror's
-void launch_cgemm64(hipStream_t s, const double* a, const double* b, double* out, float* out32, int R, int K, int Cn, const uint8_t* mask = nullptr,
-                    int env = 0);
 // gradient_obs.hip (K14 on the separable route, after aog_upload_gradient_obs): the observation's part of one aog_output_gradient call, behind
 // its k_grad_coef — the float64 obs_raw into the observation slots of `values` (nullable) and, with g_obs (nullable), the modes contraction of
 // the observation's q into e->gobs_slabs for k_grad_finish.  The actuator operands (grad_act16, gobs_act_ll) are the caller's.
@@ -204,6 +194,8 @@ int grad_obs_part(aog_env* e, hipStream_t s, const double* g_obs_dev, double* va
 // aog_pyramid_gradient (pyramid_grad.hip) runs for its clean frame
 int pyramid_ready(aog_env* e, const char* who);
 int pyramid_accumulate(aog_env* e, hipStream_t s, const uint8_t* mask_dev, const double* act_src = nullptr);
+// pyramid.hip, float64 handles: modulation point j of one env — F_j (launch_mft64; the field with j = 0), X = b1 F_j, the quadrants G = X b2
+void launch_pyramid_point64(aog_env* e, hipStream_t s, int j, int env, const uint8_t* mask_dev, const double* act_src);
 // pyramid.hip, fast handles: the steps of that sum, for the gradient's backward sweep — psi_tile and the call's own actuator operands (and
 // psi_tile put back), the phase grid of a chunk's envs into pyr_work.grid, F_j of the chunk into pyr_fop (the two forward passes), and the
 // 16-row k-steps of the window's two halves

@@ -1,6 +1,6 @@
 // K15: the modulated pyramid wavefront sensor (aog_upload_pyramid, aog_pyramid_frames, aog_pyramid_slopes, aog_upload_pyramid_reconstructor,
 // aog_pyramid_update).  A translation unit of its own: the kernels a step launches keep their code objects as they are.
-#include "host_common.h"
+#include "mft_host.h"
 #include "k_pyramid.h"
 
 using namespace aog_host;
@@ -10,11 +10,8 @@ namespace {
 constexpr int kPyrMinSide = 8, kPyrMaxSide = 64, kPyrMaxMod = 32;
 static_assert(sizeof(aog_pyramid_tables) == 4 * 4 + 9 * 8 + 3 * 8, "aog_pyramid_tables: four int32, nine pointers, three doubles, no padding (the ctypes mirror relies on it)");
 
-// x padded to pass 1's 128-column spans, y to whole k-steps, the window to whole 32-column blocks (the science camera's geometry)
-int pyr_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 128); }
-int pyr_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
-int pyr_nvb(const aog_env* e) { return (2 * e->pyr_wq + 31) / 32; }
-int pyr_nsb(const aog_env* e) { return (e->pyr_ns + 31) / 32; }
+// the science camera's geometry, for the window of both halves
+MftGeom pyr_geom(const aog_env* e) { return mft_geom_wide(e->cfg.n_pupil, 2 * e->pyr_wq); }
 
 void release_pyramid(aog_env* e) {
   e->pyr_ready = e->pyr_rec_ready = false;
@@ -45,8 +42,6 @@ void release_pyramid(aog_env* e) {
   release_pyramid_gradient(e);
 }
 
-const aog::f16x8* f16x8p(const _Float16* p) { return reinterpret_cast<const aog::f16x8*>(p); }
-
 }  // namespace
 
 namespace aog_host {
@@ -61,27 +56,20 @@ int pyramid_ready(aog_env* e, const char* who) {
 
 // The sum over the modulation points of every selected env into pyr_acc (no division yet: k_pyr_finish).
 int pyramid_accumulate(aog_env* e, hipStream_t s, const uint8_t* mask_dev, const double* act_src) {
-  const int N = e->cfg.n_pupil, wq = e->pyr_wq, w = 2 * wq, ns = e->pyr_ns, n_mod = e->pyr_nmod;
+  const int ns = e->pyr_ns, n_mod = e->pyr_nmod;
   if (e->cfg.precision == AOG_PRECISION_FP64) {
     const int nG = 4 * ns * ns;
-    const size_t m_el = (size_t)w * N * 2, b_el = (size_t)ns * w * 2;
-    for (int env = 0; env < e->B; ++env) {
-      launch_focal_field(e, s, e->pyr_E, env, 1.0, mask_dev, act_src);
+    for (int env = 0; env < e->B; ++env)
       for (int j = 0; j < n_mod; ++j) {
-        launch_cgemm64(s, e->pyr_m1d + j * m_el, e->pyr_E, e->pyr_T, nullptr, w, N, N, mask_dev, env);
-        launch_cgemm64(s, e->pyr_T, e->pyr_m2d + j * m_el, e->pyr_F, nullptr, w, N, w, mask_dev, env);
-        for (int sy = 0; sy < 2; ++sy) launch_cgemm64(s, e->pyr_b1d + sy * b_el, e->pyr_F, e->pyr_X + sy * b_el, nullptr, ns, w, w, mask_dev, env);
-        for (int q = 0; q < 4; ++q)
-          launch_cgemm64(s, e->pyr_X + (q >> 1) * b_el, e->pyr_b2d + (q & 1) * b_el, e->pyr_G + (size_t)q * ns * ns * 2, nullptr, ns, w, ns, mask_dev, env);
+        launch_pyramid_point64(e, s, j, env, mask_dev, act_src);
         hipLaunchKernelGGL(aog::k_pyr_accum64, dim3((nG + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->pyr_G), e->pyr_acc, nG, env,
                            j == 0, mask_dev);
       }
-    }
     HIP_TRY(hipGetLastError());
     return AOG_OK;
   }
   if (int rc = pyramid_operands_begin(e, s, act_src)) return rc;
-  const int nsb = pyr_nsb(e), nvb = pyr_nvb(e);
+  const int nsb = blocks32(ns), nvb = pyr_geom(e).nvb;
   // 16-row k-steps of the two halves of the window
   const int4 half = pyramid_halves(e);
   for (int env0 = 0; env0 < e->B; env0 += e->pyr_work.chunk) {
@@ -89,16 +77,21 @@ int pyramid_accumulate(aog_env* e, hipStream_t s, const uint8_t* mask_dev, const
     pyramid_phase_grid(e, s, env0, n);   // once: the grid is read n_mod times
     for (int j = 0; j < n_mod; ++j) {
       pyramid_forward_point(e, s, j, env0, n, mask_dev);
-      if (nsb == 1)
-        hipLaunchKernelGGL(aog::k_pyr_back<1>, dim3(n), dim3(256), 0, s, f16x8p(e->pyr_fop), f16x8p(e->pyr_b1s), f16x8p(e->pyr_b2s), e->pyr_acc, nvb, ns,
-                           half, e->pyr_back_unscale, j == 0, mask_dev, env0);
-      else
-        hipLaunchKernelGGL(aog::k_pyr_back<2>, dim3(n), dim3(256), 0, s, f16x8p(e->pyr_fop), f16x8p(e->pyr_b1s), f16x8p(e->pyr_b2s), e->pyr_acc, nvb, ns,
-                           half, e->pyr_back_unscale, j == 0, mask_dev, env0);
+      hipLaunchKernelGGL(nsb == 1 ? aog::k_pyr_back<1> : aog::k_pyr_back<2>, dim3(n), dim3(256), 0, s, f16x8p(e->pyr_fop), f16x8p(e->pyr_b1s),
+                         f16x8p(e->pyr_b2s), e->pyr_acc, nvb, ns, half, e->pyr_back_unscale, j == 0, mask_dev, env0);
     }
     HIP_TRY(hipGetLastError());
   }
   return pyramid_operands_end(e, s);
+}
+
+void launch_pyramid_point64(aog_env* e, hipStream_t s, int j, int env, const uint8_t* mask_dev, const double* act_src) {
+  const int N = e->cfg.n_pupil, w = 2 * e->pyr_wq, ns = e->pyr_ns;
+  const size_t m_el = (size_t)w * N * 2, b_el = (size_t)ns * w * 2;
+  launch_mft64(e, s, {e->pyr_m1d + j * m_el, e->pyr_m2d + j * m_el, e->pyr_E, e->pyr_T, w}, e->pyr_F, nullptr, env, j == 0, 1.0, mask_dev, act_src);
+  for (int sy = 0; sy < 2; ++sy) launch_cgemm64(s, e->pyr_b1d + sy * b_el, e->pyr_F, e->pyr_X + sy * b_el, nullptr, ns, w, w, mask_dev, env);
+  for (int q = 0; q < 4; ++q)
+    launch_cgemm64(s, e->pyr_X + (q >> 1) * b_el, e->pyr_b2d + (q & 1) * b_el, e->pyr_G + (size_t)q * ns * ns * 2, nullptr, ns, w, ns, mask_dev, env);
 }
 
 int4 pyramid_halves(const aog_env* e) {
@@ -125,16 +118,17 @@ int pyramid_operands_end(aog_env* e, hipStream_t s) {
 }
 
 void pyramid_phase_grid(aog_env* e, hipStream_t s, int env0, int n) {
-  launch_phase_grid(e, s, e->pyr_act16, e->pyr_act_ll, e->pyr_work.grid, (size_t)pyr_nyp(e) * pyr_nxp(e), pyr_nxp(e), env0 / 32, (n + 31) / 32);
+  const MftGeom g = pyr_geom(e);
+  launch_phase_grid(e, s, e->pyr_act16, e->pyr_act_ll, e->pyr_work.grid, g.grid_env(), g.Nxp, env0 / 32, (n + 31) / 32);
 }
 
 // F_j of the chunk's envs into pyr_fop: the two forward passes
 void pyramid_forward_point(aog_env* e, hipStream_t s, int j, int env0, int n, const uint8_t* mask_dev) {
-  const int Nxp = pyr_nxp(e), Nyp = pyr_nyp(e), nvb = pyr_nvb(e), nwg = (nvb + 3) / 4, split = nvb <= 2, w = 2 * e->pyr_wq;
-  const size_t m1_el = (size_t)nvb * (Nyp / 16) * 4 * 64 * 8, m2_el = (size_t)nvb * (Nxp / 32) * 2 * 4 * 64 * 8;
-  hipLaunchKernelGGL(aog::k_pyr_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->pyr_work.grid, f16x8p(e->pyr_m1s + j * m1_el),
-                     reinterpret_cast<aog::f16x8*>(e->pyr_work.T16), Nxp, Nyp, nvb, mask_dev, env0, split);
-  hipLaunchKernelGGL(aog::k_pyr_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, f16x8p(e->pyr_work.T16), f16x8p(e->pyr_m2s + j * m2_el), e->pyr_fop, Nxp,
+  const MftGeom g = pyr_geom(e);
+  const int Nxp = g.Nxp, nvb = g.nvb, nwg = (nvb + 3) / 4, split = nvb <= 2, w = 2 * e->pyr_wq;
+  hipLaunchKernelGGL(aog::k_pyr_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->pyr_work.grid, f16x8p(e->pyr_m1s + j * g.m1_f16()),
+                     f16x8p(e->pyr_work.T16), Nxp, g.Nyp, nvb, mask_dev, env0, split);
+  hipLaunchKernelGGL(aog::k_pyr_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, f16x8p(e->pyr_work.T16), f16x8p(e->pyr_m2s + j * g.m2_f16()), e->pyr_fop, Nxp,
                      nvb, w, e->pyr_unscale * aog::kPyrFieldScale, mask_dev, env0);
 }
 
@@ -215,26 +209,24 @@ int aog_upload_pyramid(aog_env* e, const aog_pyramid_tables* t) {
     e->pyr_ready = true;
     return AOG_OK;
   }
-  const int Nxp = pyr_nxp(e), Nyp = pyr_nyp(e), nvb = pyr_nvb(e), nsb = pyr_nsb(e);
-  const size_t tile = (size_t)4 * 64 * 8;
-  const size_t m1_el = (size_t)nvb * (Nyp / 16) * tile, m2_el = (size_t)nvb * (Nxp / 32) * 2 * tile, b_el = (size_t)2 * nsb * nvb * 2 * tile;
+  const MftGeom g = pyr_geom(e);
+  const size_t b_el = 2 * operand_f16(blocks32(ns), 32 * g.nvb), fop_env = operand_f16(g.nvb, 32 * g.nvb);   // (both halves' b tables; F_j of one env)
   e->pyr_unscale = (float)t->fwd_unscale;
   e->pyr_back_unscale = t->back_unscale / (double)aog::kPyrFieldScale;
   static_assert(sizeof(_Float16) == sizeof(uint16_t), "the operand tables arrive as IEEE half bits");
-  if ((rc = upload(e, &e->pyr_m1s, reinterpret_cast<const _Float16*>(t->m1s), m1_el * n_mod)) != AOG_OK) return rc;
-  if ((rc = upload(e, &e->pyr_m2s, reinterpret_cast<const _Float16*>(t->m2s), m2_el * n_mod)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->pyr_m1s, reinterpret_cast<const _Float16*>(t->m1s), g.m1_f16() * n_mod)) != AOG_OK) return rc;
+  if ((rc = upload(e, &e->pyr_m2s, reinterpret_cast<const _Float16*>(t->m2s), g.m2_f16() * n_mod)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->pyr_b1s, reinterpret_cast<const _Float16*>(t->b1s), b_el)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->pyr_b2s, reinterpret_cast<const _Float16*>(t->b2s), b_el)) != AOG_OK) return rc;
   // (shared with K4, K11 and the science camera; written again in place, since aog_upload_tables may have changed the aperture since it was made)
   if ((rc = upload(e, &e->focal_ap_yx, ap_yx_table(e), true)) != AOG_OK) return rc;
   // work buffers as the science camera's, at most ~256 MB each
-  const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * nvb * 2 * tile, fop_env = (size_t)nvb * nvb * 2 * tile;
+  const size_t grid_env = g.grid_env(), t16_env = g.t16_env();
   if ((rc = mft_work_alloc(e, &e->pyr_work, grid_env, t16_env, ((size_t)256 << 20) / std::max(grid_env * 4, std::max(t16_env, fop_env) * 2),
                            "AOG_PYRAMID_CHUNK")) != AOG_OK)
     return rc;
   if ((rc = dev_alloc(e, &e->pyr_fop, (size_t)e->pyr_work.chunk * fop_env, true)) != AOG_OK) return rc;   // (the pads stay zero)
-  if ((rc = dev_alloc(e, &e->pyr_act16, (size_t)e->n_etiles * 32 * e->A_pad * 2, true)) != AOG_OK) return rc;
-  if ((rc = dev_alloc(e, &e->pyr_act_ll, (size_t)e->n_etiles * 32 * e->A_pad, true)) != AOG_OK) return rc;
+  if ((rc = alloc_act_operands(e, &e->pyr_act16, &e->pyr_act_ll)) != AOG_OK) return rc;
   if (e->cfg.atm_dynamic && !e->ring_direct && (rc = dev_alloc(e, &e->pyr_tile_keep, (size_t)e->n_etiles * e->n_ptiles * 1024, false)) != AOG_OK) return rc;
   e->pyr_ready = true;
   return AOG_OK;

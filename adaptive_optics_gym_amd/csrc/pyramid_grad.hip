@@ -1,6 +1,6 @@
 // K15's gradient (aog_pyramid_gradient).  A translation unit of its own: the kernels a step or a sensor call launches keep their code
 // objects as they are.
-#include "host_common.h"
+#include "mft_host.h"
 #include "k_pyramid_grad.h"
 
 using namespace aog_host;
@@ -9,11 +9,6 @@ namespace {
 
 // the shapes the matrix-core backward passes are built for (fast handles): two 32-blocks along every axis of the window and the detector
 constexpr int kPyrGradMaxWq = 32, kPyrGradMaxNs = 64;
-
-template <typename T>
-int need(aog_env* e, T** ptr, size_t count, bool zero = false) {
-  return *ptr ? AOG_OK : dev_alloc(e, ptr, count, zero);
-}
 
 // Work buffers of the float64 form, on the first call: the transposed tables (made on the device from the uploaded ones, in stream order)
 // and the per-env scratch.
@@ -48,94 +43,55 @@ int grad_buffers64(aog_env* e, hipStream_t s) {
 }
 
 // ---- fast handles ----
-int fg_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 128); }
-int fg_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
-int fg_nvb(const aog_env* e) { return (2 * e->pyr_wq + 31) / 32; }
-int fg_nsb(const aog_env* e) { return (e->pyr_ns + 31) / 32; }
-constexpr size_t kTile = 4 * 64 * 8;   // f16 per operand tile
-
-// where element (row i, column c) of a 32 x 32 block sits in a tile pair packed with K = the rows in accumulator order (pack_columns_accumulator):
-// step s, lane, slot
-struct AccPos { int s, lane, slot; };
-AccPos acc_pos(int i, int c) {
-  const int r = (i & 3) + 4 * (i >> 3), h = (i >> 2) & 1;
-  return {r >> 3, c + 32 * h, r & 7};
-}
-int acc_row(int s, int slot, int lane) {
-  const int r = 8 * s + slot;
-  return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-}
-void copy_parts(std::vector<_Float16>& dst, size_t dt, int dl, int dsl, const std::vector<_Float16>& src, size_t st, int sl, int ssl) {
-  for (int part = 0; part < 4; ++part) dst[((dt * 4 + part) * 64 + dl) * 8 + dsl] = src[((st * 4 + part) * 64 + sl) * 8 + ssl];
+// the sensor's geometry (pyramid.hip) with the 32-blocks of the detector (nsb), of the padded pupil rows (nyt) and columns (nxt); kw: the
+// padded window as a K axis
+struct GradGeom : MftGeom {
+  int nsb, nyt, nxt, kw;
+};
+GradGeom grad_geom(const aog_env* e) {
+  const MftGeom g = mft_geom_wide(e->cfg.n_pupil, 2 * e->pyr_wq);
+  return {g, blocks32(e->pyr_ns), blocks32(g.Nyp), g.Nxp / 32, 32 * g.nvb};
 }
 
 // The transposed operand tables, from the uploaded ones (the same split values in another order: nothing is rounded again), and the chunk's
 // work buffers.  First call only; blocks for the copies.
 int grad_buffers_fast(aog_env* e, bool values_only) {
-  const int Nxp = fg_nxp(e), Nyp = fg_nyp(e), nvb = fg_nvb(e), nsb = fg_nsb(e), n_mod = e->pyr_nmod, ns = e->pyr_ns;
-  const int nyt = (Nyp + 31) / 32, nxt = Nxp / 32, nku = 2 * nvb, chunk = e->pyr_work.chunk;
+  const GradGeom g = grad_geom(e);
+  const int n_mod = e->pyr_nmod, ns = e->pyr_ns, chunk = e->pyr_work.chunk;
   int rc;
   if ((rc = need(e, &e->pyg_gpix, (size_t)e->B * 4 * ns * ns)) != AOG_OK) return rc;
   if ((rc = need(e, &e->pyg_gscale, (size_t)e->B)) != AOG_OK) return rc;
   if (values_only) return AOG_OK;
   if ((rc = need(e, &e->pyg_qscale, (size_t)e->B)) != AOG_OK) return rc;
-  if ((rc = need(e, &e->pyg_vop, (size_t)chunk * nvb * nku * kTile, true)) != AOG_OK) return rc;   // (the pads stay zero)
+  if ((rc = need(e, &e->pyg_vop, (size_t)chunk * operand_f16(g.nvb, g.kw), true)) != AOG_OK) return rc;   // (the pads stay zero)
   if ((rc = need(e, &e->pyg_wscale, (size_t)chunk)) != AOG_OK) return rc;
-  if ((rc = need(e, &e->pyg_qgrid, (size_t)chunk * Nyp * Nxp)) != AOG_OK) return rc;
+  if ((rc = need(e, &e->pyg_qgrid, (size_t)chunk * g.grid_env())) != AOG_OK) return rc;
   if ((rc = need(e, &e->pyg_slabs, (size_t)aog::pupil_chunks(e->n_ptiles) * e->A_pad * e->Bp)) != AOG_OK) return rc;
   if (e->pyg_m1s_t && e->pyg_m2s_t && e->pyg_b1s_t && e->pyg_b2s_t) return AOG_OK;
-  const size_t m1_tiles = (size_t)n_mod * nvb * (Nyp / 16), m2_tiles = (size_t)n_mod * nvb * nxt * 2, b_tiles = (size_t)2 * nsb * nvb * 2;
-  std::vector<_Float16> m1s(m1_tiles * kTile), m2s(m2_tiles * kTile), b1s(b_tiles * kTile), b2s(b_tiles * kTile);
+  // f16 of one modulation point's m1s / m2s and their transposes, and of one half of b1s / b2s (and of their transposes)
+  const size_t m1_el = g.m1_f16(), m2_el = g.m2_f16(), m1t_el = operand_f16(g.nyt, g.kw), m2t_el = operand_f16(g.nxt, g.kw), b_el = operand_f16(g.nsb, g.kw);
+  std::vector<_Float16> m1s(n_mod * m1_el), m2s(n_mod * m2_el), b1s(2 * b_el), b2s(2 * b_el);
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(m1s.data(), e->pyr_m1s, m1s.size() * 2, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(m2s.data(), e->pyr_m2s, m2s.size() * 2, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(b1s.data(), e->pyr_b1s, b1s.size() * 2, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(b2s.data(), e->pyr_b2s, b2s.size() * 2, hipMemcpyDeviceToHost));
-  std::vector<_Float16> m1t((size_t)n_mod * nyt * nvb * 2 * kTile, (_Float16)0.f), m2t((size_t)n_mod * nxt * nku * kTile, (_Float16)0.f);
-  std::vector<_Float16> b1t(b_tiles * kTile, (_Float16)0.f), b2t(b_tiles * kTile, (_Float16)0.f);
+  std::vector<_Float16> m1t(n_mod * m1t_el), m2t(n_mod * m2t_el), b1t(2 * b_el), b2t(2 * b_el);
+  // m1t (lane y, K = v accumulator) <- m1s (lane v, K = y natural); m2t (lane x, K = u natural) <- m2s (lane u, K = x accumulator)
   for (int j = 0; j < n_mod; ++j) {
-    // m1t [j][y tile][vb][s]: lane = row y, slot = v in accumulator order  <-  m1s [j][vb][y >> 4]: lane = v & 31 + 32 (bit 3 of y), slot = y & 7
-    for (int yt = 0; yt < nyt; ++yt)
-      for (int vb = 0; vb < nvb; ++vb)
-        for (int sidx = 0; sidx < 2; ++sidx)
-          for (int l = 0; l < 64; ++l)
-            for (int sl = 0; sl < 8; ++sl) {
-              const int y = 32 * yt + (l & 31), vl = acc_row(sidx, sl, l);
-              if (y >= Nyp) continue;
-              copy_parts(m1t, (((size_t)j * nyt + yt) * nvb + vb) * 2 + sidx, l, sl, m1s, ((size_t)j * nvb + vb) * (Nyp / 16) + (y >> 4),
-                         vl + 32 * ((y >> 3) & 1), y & 7);
-            }
-    // m2t [j][x tile][ku]: lane = column x, slot = u = 16 ku + 8 (lane >> 5) + slot  <-  m2s [j][ub][x tile][s]: lane = u & 31 (+ 32 h), K = x in
-    // accumulator order
-    for (int xt = 0; xt < nxt; ++xt)
-      for (int ku = 0; ku < nku; ++ku)
-        for (int l = 0; l < 64; ++l)
-          for (int sl = 0; sl < 8; ++sl) {
-            const int u = 16 * ku + 8 * (l >> 5) + sl;
-            const AccPos sp = acc_pos(l & 31, u & 31);
-            copy_parts(m2t, ((size_t)j * nxt + xt) * nku + ku, l, sl, m2s, (((size_t)j * nvb + (u >> 5)) * nxt + xt) * 2 + sp.s, sp.lane, sp.slot);
-          }
+    reorder_tiles(m1t.data() + j * m1t_el, AOG_TILE_ACCUMULATOR, g.nyt, g.kw, m1s.data() + j * m1_el, AOG_TILE_NATURAL, g.nvb, g.Nyp);
+    reorder_tiles(m2t.data() + j * m2t_el, AOG_TILE_NATURAL, g.nxt, g.kw, m2s.data() + j * m2_el, AOG_TILE_ACCUMULATOR, g.nvb, g.Nxp);
   }
-  // b1t [h][vb][yb][s]: lane = column v, slot = y' in accumulator order  <-  b1s [h][yb][vb][s]: lane = column y', K = v in accumulator order
-  // (b2t from b2s the same way, with u for v and x' for y')
-  for (int hh = 0; hh < 2; ++hh)
-    for (int vb = 0; vb < nvb; ++vb)
-      for (int yb = 0; yb < nsb; ++yb)
-        for (int sidx = 0; sidx < 2; ++sidx)
-          for (int l = 0; l < 64; ++l)
-            for (int sl = 0; sl < 8; ++sl) {
-              const AccPos sp = acc_pos(l & 31, acc_row(sidx, sl, l));   // source: row (K) = v & 31, column = y' & 31
-              const size_t dt = (((size_t)hh * nvb + vb) * nsb + yb) * 2 + sidx, st = (((size_t)hh * nsb + yb) * nvb + vb) * 2 + sp.s;
-              copy_parts(b1t, dt, l, sl, b1s, st, sp.lane, sp.slot);
-              copy_parts(b2t, dt, l, sl, b2s, st, sp.lane, sp.slot);
-            }
+  // b1t (lane v, K = y' accumulator) <- b1s (lane y', K = v accumulator), each half; b2t from b2s the same way, with u for v and x' for y'
+  for (int hh = 0; hh < 2; ++hh) {
+    reorder_tiles(b1t.data() + hh * b_el, AOG_TILE_ACCUMULATOR, g.nvb, 32 * g.nsb, b1s.data() + hh * b_el, AOG_TILE_ACCUMULATOR, g.nsb, g.kw);
+    reorder_tiles(b2t.data() + hh * b_el, AOG_TILE_ACCUMULATOR, g.nvb, 32 * g.nsb, b2s.data() + hh * b_el, AOG_TILE_ACCUMULATOR, g.nsb, g.kw);
+  }
   if ((rc = upload(e, &e->pyg_m1s_t, m1t, true)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->pyg_m2s_t, m2t, true)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->pyg_b1s_t, b1t, true)) != AOG_OK) return rc;
   return upload(e, &e->pyg_b2s_t, b2t, true);
 }
-
-const aog::f16x8* f16x8p(const _Float16* p) { return reinterpret_cast<const aog::f16x8*>(p); }
 
 template <int NSB, int NVB>
 void launch_back(aog_env* e, hipStream_t s, int env0, int n, const uint8_t* mask_dev) {
@@ -147,9 +103,9 @@ void launch_back(aog_env* e, hipStream_t s, int env0, int n, const uint8_t* mask
 // per chunk of whole env tiles: the phase grid once, per modulation point the two forward passes and the two backward kernels, then the
 // modes contraction of the chunk's q grid into the slabs
 int backward_fast(aog_env* e, hipStream_t s, const uint8_t* mask_dev, const double* act_src) {
-  const int Nxp = fg_nxp(e), Nyp = fg_nyp(e), nvb = fg_nvb(e), nsb = fg_nsb(e), n_mod = e->pyr_nmod;
-  const int nyt = (Nyp + 31) / 32, nxt = Nxp / 32, nku = 2 * nvb, nku_used = (2 * e->pyr_wq + 15) / 16;
-  const size_t m1t_el = (size_t)nyt * nvb * 2 * kTile, m2t_el = (size_t)nxt * nku * kTile;
+  const GradGeom g = grad_geom(e);
+  const int Nxp = g.Nxp, Nyp = g.Nyp, nvb = g.nvb, nsb = g.nsb, n_mod = e->pyr_nmod, nku_used = (2 * e->pyr_wq + 15) / 16;
+  const size_t m1t_el = operand_f16(g.nyt, g.kw), m2t_el = operand_f16(g.nxt, g.kw);
   if (int rc = pyramid_operands_begin(e, s, act_src)) return rc;
   for (int env0 = 0; env0 < e->B; env0 += e->pyr_work.chunk) {
     const int n = std::min(e->pyr_work.chunk, e->B - env0);
@@ -160,17 +116,13 @@ int backward_fast(aog_env* e, hipStream_t s, const uint8_t* mask_dev, const doub
       else if (nsb == 1) launch_back<1, 2>(e, s, env0, n, mask_dev);
       else if (nvb == 1) launch_back<2, 1>(e, s, env0, n, mask_dev);
       else launch_back<2, 2>(e, s, env0, n, mask_dev);
-      const dim3 grid((n * nyt * nxt + 3) / 4);
-      if (nvb == 1)
-        hipLaunchKernelGGL(aog::k_pyr_grad_q<1>, grid, dim3(256), 0, s, e->pyr_work.grid, e->pyg_qgrid, f16x8p(e->pyg_vop), f16x8p(e->pyg_m1s_t + j * m1t_el),
-                           f16x8p(e->pyg_m2s_t + j * m2t_el), e->pyg_wscale, Nxp, Nyp, n, nku_used, j == 0, mask_dev, env0);
-      else
-        hipLaunchKernelGGL(aog::k_pyr_grad_q<2>, grid, dim3(256), 0, s, e->pyr_work.grid, e->pyg_qgrid, f16x8p(e->pyg_vop), f16x8p(e->pyg_m1s_t + j * m1t_el),
-                           f16x8p(e->pyg_m2s_t + j * m2t_el), e->pyg_wscale, Nxp, Nyp, n, nku_used, j == 0, mask_dev, env0);
+      hipLaunchKernelGGL(nvb == 1 ? aog::k_pyr_grad_q<1> : aog::k_pyr_grad_q<2>, dim3((n * g.nyt * g.nxt + 3) / 4), dim3(256), 0, s, e->pyr_work.grid,
+                         e->pyg_qgrid, f16x8p(e->pyg_vop), f16x8p(e->pyg_m1s_t + j * m1t_el), f16x8p(e->pyg_m2s_t + j * m2t_el), e->pyg_wscale, Nxp, Nyp, n,
+                         nku_used, j == 0, mask_dev, env0);
     }
-    hipLaunchKernelGGL(aog::k_pyr_grad_qnorm, dim3(n), dim3(256), 0, s, e->pyg_qgrid, e->focal_ap_yx, e->pyg_qscale, (size_t)Nyp * Nxp, Nxp, e->n_ap,
+    hipLaunchKernelGGL(aog::k_pyr_grad_qnorm, dim3(n), dim3(256), 0, s, e->pyg_qgrid, e->focal_ap_yx, e->pyg_qscale, g.grid_env(), Nxp, e->n_ap,
                        mask_dev, env0);
-    launch_grad_obs_backward(e, s, e->pyg_qgrid, (size_t)Nyp * Nxp, Nxp, env0, n, e->pyg_slabs);
+    launch_grad_obs_backward(e, s, e->pyg_qgrid, g.grid_env(), Nxp, env0, n, e->pyg_slabs);
     HIP_TRY(hipGetLastError());
   }
   return pyramid_operands_end(e, s);
@@ -182,13 +134,8 @@ void backward64(aog_env* e, hipStream_t s, const uint8_t* mask_dev, const double
   const int N = e->cfg.n_pupil, w = 2 * e->pyr_wq, ns = e->pyr_ns, n_mod = e->pyr_nmod, nG = 4 * ns * ns;
   const size_t m_el = (size_t)w * N * 2, b_el = (size_t)ns * w * 2;
   for (int env = 0; env < e->B; ++env) {
-    launch_focal_field(e, s, e->pyr_E, env, 1.0, mask_dev, act_src);
     for (int j = 0; j < n_mod; ++j) {
-      launch_cgemm64(s, e->pyr_m1d + j * m_el, e->pyr_E, e->pyr_T, nullptr, w, N, N, mask_dev, env);
-      launch_cgemm64(s, e->pyr_T, e->pyr_m2d + j * m_el, e->pyr_F, nullptr, w, N, w, mask_dev, env);
-      for (int sy = 0; sy < 2; ++sy) launch_cgemm64(s, e->pyr_b1d + sy * b_el, e->pyr_F, e->pyr_X + sy * b_el, nullptr, ns, w, w, mask_dev, env);
-      for (int q = 0; q < 4; ++q)
-        launch_cgemm64(s, e->pyr_X + (q >> 1) * b_el, e->pyr_b2d + (q & 1) * b_el, e->pyr_G + (size_t)q * ns * ns * 2, nullptr, ns, w, ns, mask_dev, env);
+      launch_pyramid_point64(e, s, j, env, mask_dev, act_src);
       hipLaunchKernelGGL(aog::k_pyr_grad_w64, dim3((nG + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->pyr_G), e->pyg_gpix,
                          reinterpret_cast<double2*>(e->pyg_W), ns, n_mod, env, mask_dev);
       // Y_{sy} [n_s][w] = (W_{sy,0} | W_{sy,1}) [n_s][2 n_s] x the stacked b2' [2 n_s][w]; V [w][w] = b1' [w][2 n_s] x (Y_0 ; Y_1) [2 n_s][w]: the

@@ -1,6 +1,6 @@
 // K13: the science camera (aog_upload_science, aog_science_integrate, aog_science_clear, aog_science_read).  A translation unit of its
 // own: the kernels a step launches keep their code objects as they are.
-#include "host_common.h"
+#include "mft_host.h"
 #include "k_science.h"
 
 using namespace aog_host;
@@ -9,10 +9,7 @@ namespace {
 
 constexpr int kScienceMaxRadii = 32, kScienceMaxWindow = 4096;
 
-// x padded to pass 1's 128-column spans, y to whole k-steps, the window to whole 32-column blocks
-int sci_nxp(const aog_env* e) { return round_up(e->cfg.n_pupil, 128); }
-int sci_nyp(const aog_env* e) { return round_up(e->cfg.n_pupil, 16); }
-int sci_nvb(const aog_env* e) { return (e->sci_w + 31) / 32; }
+MftGeom sci_geom(const aog_env* e) { return mft_geom_wide(e->cfg.n_pupil, e->sci_w); }
 
 void release_science(aog_env* e) {
   e->sci_ready = false;
@@ -78,19 +75,18 @@ int aog_upload_science(aog_env* e, const double* m1_host, const double* m2_host,
     e->sci_ready = true;
     return AOG_OK;
   }
-  const int Nxp = sci_nxp(e), Nyp = sci_nyp(e), nvb = sci_nvb(e);
+  const MftGeom g = sci_geom(e);
   std::vector<_Float16> m1s, m2s;
-  e->sci_unscale = mft_operand_tables(m1_host, m2_host, N, w, nvb * 32, Nxp, Nyp, m1s, m2s);
+  e->sci_unscale = mft_operand_tables(m1_host, m2_host, N, w, g, m1s, m2s);
   if ((rc = upload(e, &e->sci_m1s, m1s)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->sci_m2s, m2s)) != AOG_OK) return rc;
   // (shared with K4 and K11; written again in place, since aog_upload_tables may have changed the aperture since it was made)
   if ((rc = upload(e, &e->focal_ap_yx, ap_yx_table(e), true)) != AOG_OK) return rc;
   // work buffers as K4's, at most ~256 MB each
-  const size_t grid_env = (size_t)Nyp * Nxp, t16_env = (size_t)(Nxp / 32) * nvb * 2 * 4 * 64 * 8;
+  const size_t grid_env = g.grid_env(), t16_env = g.t16_env();
   if ((rc = mft_work_alloc(e, &e->sci_work, grid_env, t16_env, ((size_t)256 << 20) / std::max(grid_env * 4, t16_env * 2), "AOG_SCIENCE_CHUNK")) != AOG_OK)
     return rc;
-  if ((rc = dev_alloc(e, &e->sci_act16, (size_t)e->n_etiles * 32 * e->A_pad * 2, true)) != AOG_OK) return rc;
-  if ((rc = dev_alloc(e, &e->sci_act_ll, (size_t)e->n_etiles * 32 * e->A_pad, true)) != AOG_OK) return rc;
+  if ((rc = alloc_act_operands(e, &e->sci_act16, &e->sci_act_ll)) != AOG_OK) return rc;
   e->sci_ready = true;
   return AOG_OK;
 }
@@ -100,12 +96,10 @@ int aog_science_integrate(aog_env* e, const uint8_t* mask_dev, void* stream) {
   if (int rc = science_ready(e, "aog_science_integrate")) return rc;
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int N = e->cfg.n_pupil, w = e->sci_w, w2 = w * w;
+  const int w = e->sci_w, w2 = w * w;
   if (e->cfg.precision == AOG_PRECISION_FP64) {
     for (int env = 0; env < e->B; ++env) {
-      launch_focal_field(e, s, e->sci_E, env, e->sci_ratio, mask_dev);
-      launch_cgemm64(s, e->sci_m1d, e->sci_E, e->sci_T, nullptr, w, N, N, mask_dev, env);
-      launch_cgemm64(s, e->sci_T, e->sci_m2d, e->sci_F, nullptr, w, N, w, mask_dev, env);
+      launch_mft64(e, s, {e->sci_m1d, e->sci_m2d, e->sci_E, e->sci_T, w}, e->sci_F, nullptr, env, true, e->sci_ratio, mask_dev);
       hipLaunchKernelGGL(aog::k_science_accum64, dim3((w2 + 255) / 256), dim3(256), 0, s, reinterpret_cast<const double2*>(e->sci_F), e->sci_exposure,
                          e->sci_frames, w2, env, mask_dev);
     }
@@ -117,27 +111,28 @@ int aog_science_integrate(aog_env* e, const uint8_t* mask_dev, void* stream) {
   // touched); the actuator operands are the call's own copy
   if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
   if ((rc = load_actuators(e, s, {nullptr, e->sci_act16, e->sci_act_ll})) != AOG_OK) return rc;
-  const int Nxp = sci_nxp(e), Nyp = sci_nyp(e), nvb = sci_nvb(e), nwg = (nvb + 3) / 4;
+  const MftGeom g = sci_geom(e);
+  const int Nxp = g.Nxp, Nyp = g.Nyp, nvb = g.nvb, nwg = (nvb + 3) / 4;
   // windows of at most two 32-column blocks: the four waves of a workgroup share the two blocks (k_science_pass1); AOG_SCIENCE_SPLIT=0
   // keeps the one-block-per-wave form with idle waves (same bits; tests and measurements)
   int split = nvb <= 2;
   if (const char* v = getenv("AOG_SCIENCE_SPLIT")) split = split && atoi(v) != 0;
-  const size_t grid_env = (size_t)Nyp * Nxp;
+  const size_t grid_env = g.grid_env();
   for (int env0 = 0; env0 < e->B; env0 += e->sci_work.chunk) {
     const int n = std::min(e->sci_work.chunk, e->B - env0), n_et = (n + 31) / 32;
     const int etile0 = env0 / 32;
     with_apad(e->A_pad, [&](auto apad) {
       constexpr int NSTEP = apad() / 16;
-      hipLaunchKernelGGL((aog::k_science_phase<apad()>), dim3((e->n_ptiles + 3) / 4, n_et), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
+      hipLaunchKernelGGL((aog::k_science_phase<apad()>), dim3((e->n_ptiles + 3) / 4, n_et), dim3(256), 0, s, f16x8p(e->modes16),
                          reinterpret_cast<const aog::f32x4*>(e->psi_tile) + (size_t)etile0 * e->n_ptiles * 4 * 64,
-                         reinterpret_cast<const aog::f16x8*>(e->sci_act16) + (size_t)etile0 * NSTEP * 2 * 64,
-                         reinterpret_cast<const aog::f16x8*>(e->sci_act_ll) + (size_t)etile0 * NSTEP * 64, e->focal_ap_yx, e->sci_work.grid, grid_env, Nxp,
+                         f16x8p(e->sci_act16) + (size_t)etile0 * NSTEP * 2 * 64,
+                         f16x8p(e->sci_act_ll) + (size_t)etile0 * NSTEP * 64, e->focal_ap_yx, e->sci_work.grid, grid_env, Nxp,
                          e->n_ptiles, n_et, e->n_ap, e->B - etile0 * 32, e->sci_ratio, mask_dev ? mask_dev + (size_t)etile0 * 32 : nullptr);
     });
-    hipLaunchKernelGGL(aog::k_science_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->sci_work.grid, reinterpret_cast<const aog::f16x8*>(e->sci_m1s),
-                       reinterpret_cast<aog::f16x8*>(e->sci_work.T16), Nxp, Nyp, nvb, mask_dev, env0, split);
-    hipLaunchKernelGGL(aog::k_science_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->sci_work.T16),
-                       reinterpret_cast<const aog::f16x8*>(e->sci_m2s), e->sci_exposure, e->sci_frames, Nxp, nvb, w, e->sci_unscale, mask_dev, env0, split);
+    hipLaunchKernelGGL(aog::k_science_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->sci_work.grid, f16x8p(e->sci_m1s), f16x8p(e->sci_work.T16), Nxp,
+                       Nyp, nvb, mask_dev, env0, split);
+    hipLaunchKernelGGL(aog::k_science_pass2, dim3(nwg, nwg, n), dim3(256), 0, s, f16x8p(e->sci_work.T16), f16x8p(e->sci_m2s), e->sci_exposure, e->sci_frames,
+                       Nxp, nvb, w, e->sci_unscale, mask_dev, env0, split);
     HIP_TRY(hipGetLastError());
   }
   return AOG_OK;

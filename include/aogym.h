@@ -300,6 +300,22 @@ int aog_turbulence_factors(int n_pupil, int oversampling, double pixel_pitch, co
 #define AOG_FUSED_PLAN_FIELDS 16
 int aog_fused_plan(int num_envs, int n_ap, int n_modes, int n_wfs_tables, int atm_dynamic, int pixel_chunks, int four_wave, int32_t* out);
 
+/* The split-f16 operand tiles of the matrix Fourier transform family (K4, K11, K13, K14, K15), as the library's one host packer lays them out
+ * (pure host functions, no handle or device; ABI stays 22, no new struct; tests/test_operand_tiles_cpu.py holds them to the numpy packers of
+ * pyramid_host.py).  One tile = [re hi, re lo, im hi, im lo][lane 64][8] IEEE halves; a table holds a matrix m [i][k] as [n_blocks][k_pad / 16]
+ * tiles, tile (i >> 5, k >> 4), with k in one of two orders:
+ *   AOG_TILE_NATURAL      lane (i & 31) + 32 ((k >> 3) & 1), slot k & 7
+ *   AOG_TILE_ACCUMULATOR  lane (i & 31) + 32 ((k >> 2) & 1), slot (k & 3) + 4 ((k >> 3) & 1)   (the order a matrix-core accumulator holds rows)
+ * aog_pack_operand_tiles: tiles_out [n_blocks][k_pad / 16][4][64][8] <- m [rows][K] complex float64 (re, im interleaved) x scale; hi = the value
+ * rounded to half through float, lo = the float64 remainder rounded the same way; the pads (i >= rows, k >= K) are zero.
+ * aog_reorder_operand_tiles: dst <- the tiles of the TRANSPOSED matrix of the packed table src, in another order and shape: element (i, k) of
+ * dst is element (k, i) of src, halves copied as they are (what aog_pyramid_gradient does to the uploaded tables), zero where src has none.
+ * AOG_ERR_INVALID for an unknown order, k_pad no positive multiple of 16, or a matrix that does not fit. */
+enum { AOG_TILE_NATURAL = 0, AOG_TILE_ACCUMULATOR = 1 };
+int aog_pack_operand_tiles(const double* m, int rows, int K, double scale, int order, int n_blocks, int k_pad, uint16_t* tiles_out);
+int aog_reorder_operand_tiles(const uint16_t* src, int src_order, int src_blocks, int src_k_pad, int dst_order, int dst_blocks, int dst_k_pad,
+                              uint16_t* dst);
+
 /* How aog_generate_screens draws a screen.  Both methods draw the same zero-mean stationary Gaussian field on the N x N pupil up to
  * max |dC(r)| < 1e-4 C(0) over every lag r of the pupil (tests/test_screen_twoband.py evaluates both covariance functions exactly on
  * the host in float64), i.e. they are statistically equivalent to hcipy's layer.reset() (AO_env.py:77), not draw-for-draw.
