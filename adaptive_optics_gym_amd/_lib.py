@@ -82,6 +82,10 @@ class AogPredictorConfig(C.Structure):  # mirrors aog_predictor_config (additive
         "forgetting", "p0", "scale")]
 
 
+class AogTelemetryConfig(C.Structure):  # mirrors aog_telemetry_config (additive in ABI 22; no aog_struct_size index)
+    _fields_ = [(n, C.c_int32) for n in ("batch", "act_dim", "length", "env_id_base")]
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -166,7 +170,16 @@ SYMBOLS = {
     "aog_predictor_state_bytes": (C.c_int64, [C.c_void_p]),
     "aog_predictor_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_predictor_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_selftest_poisson": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "aog_telemetry_create": (C.c_int, [C.POINTER(AogTelemetryConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "aog_telemetry_destroy": (None, [C.c_void_p]),
+    "aog_telemetry_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_telemetry_push": (C.c_int, [C.c_void_p] * 4),
+    "aog_telemetry_psd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_telemetry_gains": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int] + [C.c_void_p] * 5),
+    "aog_telemetry_state_bytes": (C.c_int64, [C.c_void_p]),
+    "aog_telemetry_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_telemetry_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_selftest_poisson":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
     "aog_selftest_barrier_timeout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "aog_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -69,6 +69,15 @@ int upload(aog_env* e, T** dst, const std::vector<T>& src, bool keep = false) {
   return upload(e, dst, src.data(), src.size(), keep);
 }
 
+// one launch with `lds` bytes of dynamic LDS on `device`, for handles that are no aog_env: the request for it, the launch and its error check
+template <typename... Params, typename... Args>
+int launch_with_lds(int device, hipStream_t s, void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, const Args&... args) {
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds, device)) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  HIP_TRY(hipGetLastError());
+  return AOG_OK;
+}
+
 // zero `n_words` 32-bit words at p on stream s with a kernel of the library (see k_zero_words for why not hipMemsetAsync)
 void zero_words(void* p, size_t n_words, hipStream_t s);
 

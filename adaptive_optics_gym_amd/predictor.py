@@ -116,6 +116,28 @@ def alloc_like(alloc, t):
     return alloc(t.shape, dtype=t.dtype, device=t.device)
 
 
+def pseudo_open_loop(env, measurement, who):
+    """The pseudo-open-loop measurement of ``env`` at the state the last ``reset`` / ``step`` left, [B, A] float64 actuators:
+    ``"truth"``: ``env.ideal_action()``; ``"pyramid"``: the pyramid sensor's integrator with gain 1, ``a - R (s - s_ref)``."""
+    if getattr(env, "_next_actions_keepalive", None) is not None:
+        raise ValueError(f"{who}: a pipelined step has an action pending (the mirror already belongs to the next step)")
+    try:
+        if measurement == "truth":
+            return env.ideal_action()
+        torch = env._torch
+        env._pyramid_mask(None, who)
+        if not env._pyramid_calibrated:
+            env.pyramid_calibrate()
+        y = torch.empty((env.num_envs, env.num_modes), dtype=torch.float64, device=env.device)
+        _lib.check(env.lib.aog_pyramid_update(env._handle, 1.0, C.c_void_p(y.data_ptr()), None, env._stream()))
+        env.pyramid_frame_count += 1
+        return y
+    except _lib.AogError as err:
+        if "NEXT action" in str(err) or "advanced to the next step" in str(err):
+            raise ValueError(f"{who}: {err}") from None
+        raise
+
+
 class PredictiveController:
     """The predictive controller of an env (``BatchedAOEnv`` or ``LayeredAOEnv``).
 
@@ -153,24 +175,7 @@ class PredictiveController:
         self.measurement_value = None
 
     def _measure(self):
-        env = self.env
-        if getattr(env, "_next_actions_keepalive", None) is not None:
-            raise ValueError("PredictiveController.action: a pipelined step has an action pending (the mirror already belongs to the next step)")
-        try:
-            if self.measurement == "truth":
-                return env.ideal_action()
-            torch = env._torch
-            env._pyramid_mask(None, "PredictiveController.action")
-            if not env._pyramid_calibrated:
-                env.pyramid_calibrate()
-            y = torch.empty((env.num_envs, env.num_modes), dtype=torch.float64, device=env.device)
-            _lib.check(env.lib.aog_pyramid_update(env._handle, 1.0, C.c_void_p(y.data_ptr()), None, env._stream()))
-            env.pyramid_frame_count += 1
-            return y
-        except _lib.AogError as err:
-            if "NEXT action" in str(err) or "advanced to the next step" in str(err):
-                raise ValueError(f"PredictiveController.action: {err}") from None
-            raise
+        return pseudo_open_loop(self.env, self.measurement, "PredictiveController.action")
 
     def action(self):
         return self.update(self._measure())

@@ -253,7 +253,7 @@ class DeviceActor:
 
 def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, generator=None, actor_impl: str = "auto", seed: int = 0,
             dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None, fused_policy: bool = False, action_mode: str = "sample",
-            science: bool = False, predictor=None):
+            science: bool = False, predictor=None, controller=None):
     """Collect ``episodes`` lock-step episodes from ``env`` (a ``BatchedAOEnv``).
 
     ``actor_impl``: "hip" = the fused policy-query kernel (``DeviceActor``), "torch" = the module's own forward +
@@ -275,7 +275,10 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     ``predictor.action()`` of the ``predictor.PredictiveController`` passed as ``predictor`` (built for this env): a linear predictor of the
     next best-fit command, learnt on the device by recursive least squares from the measurements the loop takes — what recovers the one-frame
     lag ``"ideal"`` commits.  Same conditions and ``log_prob`` as ``"shack"``; the predictor is NOT reset at episode ends (the atmosphere is
-    not reset either); not with ``lookahead``.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
+    not reset either); not with ``lookahead``.  ``policy="modal"``: every step's action is ``controller.action()`` of the
+    ``telemetry.ModalIntegrator`` passed as ``controller`` (built for this env): the integrator with one gain per (env, mode), which also
+    records the measurements it takes (``controller.retune()`` then sets the optimised modal gains); same conditions as ``"predictive"``,
+    and neither its command nor its telemetry is reset at episode ends.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
     action before the env sees it (and before it is stored, like the reference's in-place ``action +=``), or a ``DeviceOUNoise``
     (``main.py:218-220``: mu 0, theta 0.3, sigma 0.05), which the HIP policy query advances and adds itself: float64 state, Philox normals keyed
     by the global env id (a split batch reproduces the whole one), no extra launch.  Neither is reset here, as in the reference.
@@ -302,27 +305,31 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     B = env.num_envs
     if gatherer is None:
         gatherer = EpisodeReturnGatherer(B, env.device, False)
-    if policy not in ("actor", "shack", "ideal", "pyramid", "predictive"):
-        raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid' or 'predictive'")
+    if policy not in ("actor", "shack", "ideal", "pyramid", "predictive", "modal"):
+        raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive' or 'modal'")
     if action_mode not in ("sample", "mean"):
         raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
-    ideal, pyramid, predictive = policy == "ideal", policy == "pyramid", policy == "predictive"
-    shack = policy == "shack" or ideal or pyramid or predictive   # (no policy query either way: the action is a controller's raw actuator vector)
+    ideal, pyramid, predictive, modal = policy == "ideal", policy == "pyramid", policy == "predictive", policy == "modal"
+    shack = policy == "shack" or ideal or pyramid or predictive or modal   # (no policy query either way: the action is a controller's raw actuator vector)
     if predictive != (predictor is not None):
         raise ValueError("policy='predictive' takes its controller as predictor=PredictiveController(env, ...), and no other policy takes one")
     if predictive and predictor.env is not env:
         raise ValueError("policy='predictive': the predictor was built for another env")
+    if modal != (controller is not None):
+        raise ValueError("policy='modal' takes its controller as controller=ModalIntegrator(env, ...), and no other policy takes one")
+    if modal and controller.env is not env:
+        raise ValueError("policy='modal': the controller was built for another env")
     dev_ou = isinstance(ou_noise, DeviceOUNoise)
     if shack and (dev_ou or action_mode != "sample"):
         raise ValueError(f"policy={policy!r} takes neither a DeviceOUNoise nor action_mode='mean' (the "
-                         f"{'ideal modal controller' if ideal else 'pyramid integrator' if pyramid else 'predictive controller' if predictive else 'Shack-Hartmann integrator'} is not a policy query)")
+                         f"{'ideal modal controller' if ideal else 'pyramid integrator' if pyramid else 'predictive controller' if predictive else 'modal integrator' if modal else 'Shack-Hartmann integrator'} is not a policy query)")
     if shack:
         if not getattr(env, "SH_operation", False):
             raise ValueError(f"policy={policy!r} needs an env created with SH_operation=True (AO_env.py:115-116, 254)")
         if pyramid and getattr(env, "pyramid", None) is None:
             raise ValueError("policy='pyramid' needs an env created with pyramid=dict(...)")
-        if predictive and (lookahead or fused_policy):
-            raise ValueError("policy='predictive' goes with neither lookahead nor fused_policy: its measurement is refused while the next screens or "
+        if (predictive or modal) and (lookahead or fused_policy):
+            raise ValueError(f"policy={policy!r} goes with neither lookahead nor fused_policy: its measurement is refused while the next screens or "
                              "the next action are already in place")
         actor_impl = "none"
     elif actor_impl == "auto":
@@ -390,7 +397,7 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                     if shack:
                         # (actuators [B, A] float64, the reference's constant log-probability 1; 'ideal': from the state the last observation saw)
                         sh_act = (env.ideal_action() if ideal else env.PYR_step()[0] if pyramid else predictor.action() if predictive
-                                  else env.SH_step()[0])
+                                  else controller.action() if modal else env.SH_step()[0])
                         out["act"][i].copy_(sh_act)
                         out["log_prob"][i].fill_(1.0)
                         action = out["act"][i]

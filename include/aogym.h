@@ -765,6 +765,52 @@ int64_t aog_predictor_state_bytes(const aog_predictor* p);
 int aog_predictor_get_state(aog_predictor* p, void* blob_dev, void* stream);
 int aog_predictor_set_state(aog_predictor* p, const void* blob_dev, void* stream);
 
+/* ---- closed-loop modal telemetry: per-env rings of measurements, their power spectral densities and the optimised integrator gains
+ * (additive in ABI 22; no counterpart in the reference) ----
+ * Independent of any aog_env and of any sensor, like aog_predictor.  Per env: hist [length][act_dim] float64, a ring in which sample
+ * number c lies in row c mod length; `count` (samples stored) and `skipped`, int64.  length T is a power of two in [64, 1024], act_dim A
+ * in [1, 128].  Everything float64 without fused multiply-add, every sum in an order that (A, T, S) alone fix (csrc/k_telemetry.h): any
+ * split of a batch over handles, and any mask, reproduces the whole batch bit for bit.  Plain vector stores, no atomics, no host
+ * synchronisation; the calls on one handle are ordered by the one stream they are given.  mask_dev: nullable [B] uint8 device array,
+ * non-zero = selected; envs it leaves out are touched nowhere, and neither are their rows of any output.
+ *
+ * aog_telemetry_push stores the row y [b] of every selected env at row count mod T and adds 1 to count; a row that holds a non-finite
+ * value is not stored: `skipped` counts it and count stays.
+ *
+ * aog_telemetry_psd is Welch's estimate over what the ring holds.  `segment` S is a power of two with 32 <= S <= T, the hop S / 2.  With
+ * n = min(count, T): segments = floor((n - S) / (S / 2)) + 1, the last one ends at the newest sample, they are summed oldest first.  Per
+ * segment and mode: subtract the segment's mean, multiply by the periodic Hann window w_n = (1 - cos(2 pi n / S)) / 2,
+ * X_k = sum_n w_n (y_n - mean) exp(-2 pi i k n / S), and Phi[k] = m_k (mean over the segments of |X_k|^2) / (S sum_n w_n^2), m_k = 1 at
+ * k = 0 and k = S / 2 and 2 between: the variance per bin (S sum w^2 is taken as its exact value 3 S^2 / 8).  psd_dev [B][A][S/2+1]
+ * float64, segments_dev (nullable) [B] int32.  An env with n < S gets NaN rows and 0 segments.  The ring is read once.
+ *
+ * aog_telemetry_gains computes the same Phi and from it, per env and mode, the gain of the integrator a <- a + g m that minimises
+ *   J(g) = sum_{k=1}^{S/2} |R_k(g)|^2 Phi[k],   R_k(g) = 1 / (1 + g z^-d / (1 - z^-1)),   z = exp(2 pi i k / S),   d = delay in {1, 2, 3, 4}
+ * over the n_grid <= 64 ascending candidates grid_host (a HOST array), each in (0, g_max(d)), g_max(d) = 2 sin(pi / (2 (2 d - 1))), the
+ * stability limit of z^d - z^(d-1) + g = 0 (2 at d = 1, 1 at d = 2).  gain_dev [B][A] = the first minimiser in grid order, cost_dev
+ * [B][A] its J, cost_all_dev (nullable) [B][A][n_grid] every J; NaN for an env with n < S.  |R_k(g)|^2 depends on (k, g) alone: it is
+ * BUILT ON THE DEVICE once per call (k_telemetry_rk, float64, into a buffer of the handle), not uploaded.
+ * AOG_ERR_INVALID, before any device work: batch < 1, act_dim outside [1, 128], a length or segment that is not such a power of two, a
+ * delay outside [1, 4], n_grid outside [1, 64], a candidate outside (0, g_max(d)) or not above the one before it.  env_id_base is
+ * carried for the caller and enters no arithmetic.  The struct is four int32; it has no index in aog_struct_size. */
+typedef struct aog_telemetry aog_telemetry;
+typedef struct aog_telemetry_config {
+  int32_t batch, act_dim, length, env_id_base;
+} aog_telemetry_config;
+int aog_telemetry_create(const aog_telemetry_config* cfg, int device, aog_telemetry** out);
+void aog_telemetry_destroy(aog_telemetry* t);
+/* The selected envs back to the state after create: a ring of zeros, both counters 0.  Stream-ordered. */
+int aog_telemetry_reset(aog_telemetry* t, const uint8_t* mask_dev, void* stream);
+int aog_telemetry_push(aog_telemetry* t, const double* y_dev, const uint8_t* mask_dev, void* stream);
+int aog_telemetry_psd(aog_telemetry* t, int segment, double* psd_dev, int32_t* segments_dev, const uint8_t* mask_dev, void* stream);
+int aog_telemetry_gains(aog_telemetry* t, int segment, int delay, const double* grid_host, int n_grid, double* gain_dev, double* cost_dev,
+                        double* cost_all_dev, const uint8_t* mask_dev, void* stream);
+/* Checkpointing: per env, one after the other, hist [T][A] (float64), count and skipped (int64) — the blob of a whole batch is the blobs of
+ * its parts in a row.  A handle of the same configuration that takes the blob resumes bit-identically. */
+int64_t aog_telemetry_state_bytes(const aog_telemetry* t);
+int aog_telemetry_get_state(aog_telemetry* t, void* blob_dev, void* stream);
+int aog_telemetry_set_state(aog_telemetry* t, const void* blob_dev, void* stream);
+
 /* Self-test hook: sin(2 pi u), cos(2 pi u) for n float32 revolutions u_dev with the fused kernels' device code.
  * flavour 0 = polynomial, 1 = v_sin_f32/v_cos_f32 after the exact reduction, 2 = v_sin_f32/v_cos_f32 on raw input. */
 int aog_selftest_sincos(const float* u_dev, float* sin_dev, float* cos_dev, int n, int flavour, void* stream);
