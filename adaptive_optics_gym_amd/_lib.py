@@ -86,6 +86,14 @@ class AogTelemetryConfig(C.Structure):  # mirrors aog_telemetry_config (additive
     _fields_ = [(n, C.c_int32) for n in ("batch", "act_dim", "length", "env_id_base")]
 
 
+class AogSpgdConfig(C.Structure):  # mirrors aog_spgd_config (additive in ABI 22; no aog_struct_size index)
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "num_envs", "act_dim", "env_id_base")] + [("seed", C.c_uint64), ("metric", C.c_int32),
+                                                                                                  ("reserved0", C.c_int32), ("clip", C.c_double)]
+
+
+AOG_SPGD_METRIC = {"power": 0, "strehl": 1, "reward": 2}
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -179,6 +187,16 @@ SYMBOLS = {
     "aog_telemetry_state_bytes": (C.c_int64, [C.c_void_p]),
     "aog_telemetry_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_telemetry_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_spgd_create": (C.c_int, [C.POINTER(AogSpgdConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "aog_spgd_destroy": (None, [C.c_void_p]),
+    "aog_spgd_set_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_spgd_reset": (C.c_int, [C.c_void_p] * 5),
+    "aog_spgd_update": (C.c_int, [C.c_void_p] * 5),
+    "aog_spgd_state_bytes": (C.c_int64, [C.c_void_p]),
+    "aog_spgd_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_spgd_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_reset_spgd": (C.c_int, [C.c_void_p] * 6),
+    "aog_step_spgd": (C.c_int, [C.c_void_p] * 10 + [C.POINTER(C.c_int), C.c_void_p]),
     "aog_selftest_poisson":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
     "aog_selftest_barrier_timeout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aog_selftest_sincos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

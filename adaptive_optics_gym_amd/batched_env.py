@@ -798,6 +798,7 @@ class BatchedAOEnv:
     # refuses a backward pass once it has moved
     state_epoch = 0
     _last_action = None
+    _last_step = None   # the last step's return tuple; None after a reset
     _gradient_uploaded = False
 
     def step(self, actions, out=None, next_actions=_PIPELINE_END):
@@ -825,6 +826,7 @@ class BatchedAOEnv:
                 self._step_cache = (ret, ptrs)
         self._launch_step(a, next_actions, ptrs)
         self._last_action = a   # (output_gradient(wrt="action") differentiates through it)
+        self._last_step = ret   # (SPGDController.action reads its metric)
         self._observed(ret[0], ret[4]["obs_raw"], step=True)
         return ret
 
@@ -838,6 +840,7 @@ class BatchedAOEnv:
         self.state_epoch += 1
         if not step:
             self._last_action = None
+            self._last_step = None
         if step:
             self.timestep += 1
 
@@ -956,6 +959,57 @@ class BatchedAOEnv:
             return ret, None
         policy.calls += 1
         return ret, pol
+
+    # SPGD stepping: the sensorless baseline's query (sensorless.SPGDController) in the policy's place
+    def _spgd_checked(self, ctrl, action_out, who):
+        torch = self._torch
+        if getattr(ctrl, "env", None) is not self:
+            raise ValueError(f"{who}: the controller was built for another env")
+        B, A = self.num_envs, self.num_modes
+        if action_out is None:
+            return torch.empty((B, A), dtype=torch.float32, device=self.device)
+        if (action_out.dtype != torch.float32 or tuple(action_out.shape) != (B, A) or not action_out.is_contiguous() or action_out.device != self.device):
+            raise ValueError(f"{who}: action_out must be a contiguous float32 [B, A] tensor on the env's device")
+        return action_out
+
+    def reset_with_spgd(self, ctrl, mask=None, action_out=None):
+        """``reset()`` of the whole batch with ``ctrl`` (a ``sensorless.SPGDController`` of this env) attached (``aog_reset_spgd``): the
+        reset's last launch also resets the controller (``ctrl.reset()``: flat start or the env's actuators, iteration counters kept) and
+        loads its first command into the mirror, so the next ``step_with_spgd`` steps it (pass no ``action`` there).  Returns
+        ``((obs, info), action)``.  Masked resets are not fused: use ``reset(mask)`` + ``ctrl.reset(mask)`` and pass the action."""
+        if mask is not None:
+            raise ValueError("reset_with_spgd resets the whole batch; reset some envs with reset(mask) + ctrl.reset(mask) and step with an explicit action")
+        action = self._spgd_checked(ctrl, action_out, "reset_with_spgd")
+        if self.atm_type == "semi_dynamic":
+            self._generate_screens(mask=None)  # layer.reset() (AO_env.py:76-77)
+        obs, obs_raw = self._obs_buffers(False)
+        p = C.c_void_p
+        _lib.check(self.lib.aog_reset_spgd(self._handle, ctrl._handle, p(obs_raw.data_ptr()), p(obs.data_ptr()), p(action.data_ptr()), self._stream()))
+        self._observed(obs, obs_raw)
+        return (obs, {}), action
+
+    def step_with_spgd(self, ctrl, out=None, action=None, action_out=None):
+        """``step()`` with ``ctrl`` attached (``aog_step_spgd``): steps the action left pending by ``reset_with_spgd`` or the previous call
+        (``action=None``), or ``action`` (first step after a plain ``reset``).  Unless this is the episode's last step, the step's last launch
+        also runs the SPGD query on the metric it has just stored and loads the next command into the mirror: one launch where ``step`` +
+        ``ctrl.action()`` + the next ``step``'s prologue take three, bit-identical to that unfused loop.  Returns ``(step tuple, action)``, or
+        ``(step tuple, None)`` on the episode's last step (no query, controller and ``action_out`` untouched).  ``out`` as in ``step``, or a
+        dict ``{"obs", "reward", "done"}`` of those tensors that may also carry ``"action"`` (= ``action_out``)."""
+        if isinstance(out, dict):
+            action_out = out.get("action", action_out)
+            out = (out["obs"], out["reward"], out["done"])
+        a = self._as_actions(action) if action is not None else None
+        nxt = self._spgd_checked(ctrl, action_out, "step_with_spgd")
+        if self.atm_type == "dynamic" and self._host_rng:
+            self._host_extrusion_noise()
+        ret, ptrs = self._step_outputs(out)
+        p = C.c_void_p
+        queried = C.c_int(0)
+        _lib.check(self.lib.aog_step_spgd(self._handle, ctrl._handle, p(a.data_ptr() if a is not None else None), p(ptrs[0]), p(ptrs[1]), p(ptrs[2]),
+                                          p(ptrs[3]), p(ptrs[4]), p(ptrs[5]), p(nxt.data_ptr()), C.byref(queried), self._stream()))
+        self._last_step = ret
+        self._observed(ret[0], ret[4]["obs_raw"], step=True)
+        return ret, (nxt if queried.value else None)
 
     def _as_actions(self, actions):
         """[B, A] float32 contiguous device tensor (as is when it already is one)."""

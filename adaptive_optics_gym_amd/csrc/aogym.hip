@@ -4,6 +4,8 @@
 #include "k_pack.h"
 #include "k_step.h"
 #include "k_step_act.h"
+#include "k_step_spgd.h"
+#include "spgd_host.h"
 
 #include <hipfft/hipfft.h>
 
@@ -279,6 +281,8 @@ struct ActTail {
   size_t lds = 0;      // the query's own dynamic LDS
   aog::ActorNoise nz{};
   bool noisy = false;  // nz needs k_epilogue_act_prologue_noise (aog_action_noise: mean mode / OU term)
+  bool spgd = false;   // aog_reset_spgd / aog_step_spgd: the SPGD query `sp` rides in the policy's place (k_epilogue_spgd_prologue), `a` is unused
+  aog::SpgdArgs sp{};
 };
 
 // the prologue of a step from `action` (k_prologue, k_epilogue_prologue, k_epilogue_act_prologue)
@@ -349,6 +353,7 @@ int launch_with_lds(const aog_env* e, hipStream_t s, void (*kernel)(Params...), 
 //                                                                      its own behind the epilogue's
 //   tail (aog_reset_act / aog_step_act)       k_epilogue_act_prologue  the policy query on this epilogue's observation and the prologue of the next
 //                                             (_noise: tail->noisy)    step from its action ride in the same launch, per workgroup of 16 envs
+//   tail->spgd (aog_reset_spgd / aog_step_spgd) k_epilogue_spgd_prologue the same with the SPGD query on this epilogue's metric in the policy's place
 // Handles with a detector (e->det_on) launch the same form through the _det kernel of that name, which draws the detector's noise: the same
 // grid, block and arguments, its LDS from epilogue_lds, and DetectorArgs appended.
 // mask (masked aog_reset): handles with a detector draw for the masked envs only
@@ -361,6 +366,9 @@ int launch_epilogue(aog_env* e, bool is_step, float* obs_raw, uint16_t* obs, flo
     return e->det_on ? launch_with_lds(e, s, det, grid, block, bytes, p, args..., detector_args(e, mask))
                      : launch_with_lds(e, s, plain, grid, block, bytes, p, args...);
   };
+  if (tail && tail->spgd)
+    return launch(aog::k_epilogue_spgd_prologue, aog::k_epilogue_spgd_prologue_det, dim3(n_epi), dim3(aog::kStepSpgdThreads),
+                  aog::step_spgd_lds_bytes(lds), tail->sp, prologue_args(e, tail->sp.action));
   if (tail) {
     aog::ActorArgs a = tail->a;
     a.obs = obs;
@@ -1263,6 +1271,48 @@ int aog_step_act_noise(aog_env* e, const aog_actor* net, const float* action, fl
 int aog_step_act(aog_env* e, const aog_actor* net, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
                  float* strehl, float* action_out, float* log_prob_out, float* mean_out, int* queried, void* stream) {
   return aog_step_act_noise(e, net, action, obs_raw, obs, reward, done, power, strehl, action_out, log_prob_out, mean_out, queried, nullptr, stream);
+}
+// the checks of aog_reset_spgd / aog_step_spgd that concern the controller, made before the call changes anything
+static int step_spgd_tail(const aog_env* e, const aog_spgd* g, const char* who, const float* action_out) {
+  if (!e || !g || !action_out) return fail(AOG_ERR_INVALID, "%s: null argument", who);
+  if (!e->cfg.sh_operation)
+    return fail(AOG_ERR_INVALID, "%s: the handle was created without sh_operation: its action is rescaled to a fixed surface rms, so a perturbation "
+                "amplitude means nothing there", who);
+  if (g->cfg.act_dim != e->A) return fail(AOG_ERR_INVALID, "%s: the controller's act_dim %d is not the handle's n_modes %d", who, g->cfg.act_dim, e->A);
+  if (g->cfg.num_envs != e->B) return fail(AOG_ERR_INVALID, "%s: the controller's num_envs %d is not the handle's %d", who, g->cfg.num_envs, e->B);
+  if (g->cfg.env_id_base != e->cfg.env_id_base || g->device != e->device)
+    return fail(AOG_ERR_INVALID, "%s: the controller (env_id_base %d, device %d) does not belong to the handle (env_id_base %d, device %d)", who,
+                g->cfg.env_id_base, g->device, e->cfg.env_id_base, e->device);
+  const size_t lds = aog::step_spgd_lds_bytes(epilogue_lds(e));
+  if (lds > kLdsBytes) return fail(AOG_ERR_UNSUPPORTED, "%s: the fused tail needs %zu bytes of LDS > %zu", who, lds, kLdsBytes);
+  return AOG_OK;
+}
+int aog_reset_spgd(aog_env* e, aog_spgd* g, float* obs_raw, uint16_t* obs, float* action_out, void* stream) {
+  if (!e) return fail(AOG_ERR_INVALID, "aog_reset_spgd: null handle");
+  if (int rc = refuse_pre_evolved(e, "aog_reset_spgd")) return rc;
+  if (int rc = step_spgd_tail(e, g, "aog_reset_spgd", action_out)) return rc;
+  ActTail t{};
+  t.spgd = true;
+  // (the reset's k_reset_state has flattened the mirror, or left it: the query starts u from what the prologue would replace)
+  t.sp = spgd_args(g, true, nullptr, nullptr, e->cfg.flat_mirror_start ? nullptr : e->act_dm, action_out);
+  return reset_impl(e, nullptr, obs_raw, obs, stream, &t);
+}
+int aog_step_spgd(aog_env* e, aog_spgd* g, const float* action, float* obs_raw, uint16_t* obs, float* reward, uint8_t* done, float* power,
+                  float* strehl, float* action_out, int* queried, void* stream) {
+  if (queried) *queried = 0;
+  if (!e) return fail(AOG_ERR_INVALID, "aog_step_spgd: null handle");
+  if (!action && !e->pro_pending)
+    return fail(AOG_ERR_INVALID, "aog_step_spgd: action = NULL but no action is pending (the first step after a plain aog_reset needs its action)");
+  if (action && e->pro_pending)
+    return fail(AOG_ERR_INVALID, "aog_step_spgd: an action is pending (from aog_reset_spgd / aog_step_spgd / aog_step_pipelined): pass action = NULL");
+  if (int rc = step_spgd_tail(e, g, "aog_step_spgd", action_out)) return rc;
+  // the query reads the float32 the epilogue stores: an output the caller leaves out goes to the controller's own buffer
+  float** sel = g->cfg.metric == AOG_SPGD_POWER ? &power : g->cfg.metric == AOG_SPGD_STREHL ? &strehl : &reward;
+  if (!*sel) *sel = g->metric;
+  ActTail t{};
+  t.spgd = true;
+  t.sp = spgd_args(g, false, *sel, nullptr, nullptr, action_out);
+  return step_impl(e, action, nullptr, false, obs_raw, obs, reward, done, power, strehl, stream, &t, queried);
 }
 int aog_selftest_sincos(const float* u_dev, float* sin_dev, float* cos_dev, int n, int flavour, void* stream) {
   if (!u_dev || !sin_dev || !cos_dev || n < 0 || flavour < 0 || flavour > 2) return fail(AOG_ERR_INVALID, "aog_selftest_sincos: bad argument");

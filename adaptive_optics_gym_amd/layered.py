@@ -5,7 +5,7 @@ their sum is what makes a one-frame control lag cost Strehl.  On axis and conjug
 independent screens, so every layer here is an ordinary dynamic ``BatchedAOEnv`` that only evolves (``evolve_atmosphere``), one kernel
 sums the layers' float64 master screens into the screen tiles of a quasi-static FRONT handle (``install_layer_sum``), and the front
 steps with the static fused kernel it already has.  Everything that reads the front's screens — reset, step, the separable observation
-route, Shack-Hartmann, ``wavefront_truth``, the science camera, ``output_gradient``, ``step_with_policy``, pipelined steps — works on it
+route, Shack-Hartmann, ``wavefront_truth``, the science camera, ``output_gradient``, ``step_with_policy``, ``step_with_spgd``, pipelined steps — works on it
 unchanged.
 """
 from __future__ import annotations
@@ -139,6 +139,10 @@ class LayeredAOEnv(BatchedAOEnv):
     def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None, ou_noise=None, action_mode="sample"):
         self._advance()
         return super().step_with_policy(policy, cov_var, out=out, policy_out=policy_out, action=action, ou_noise=ou_noise, action_mode=action_mode)
+
+    def step_with_spgd(self, ctrl, out=None, action=None, action_out=None):
+        self._advance()
+        return super().step_with_spgd(ctrl, out=out, action=action, action_out=action_out)
 
     def evolve_atmosphere(self):
         raise RuntimeError("LayeredAOEnv: the layers evolve inside step()")

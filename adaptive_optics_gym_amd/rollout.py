@@ -278,7 +278,12 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     not reset either); not with ``lookahead``.  ``policy="modal"``: every step's action is ``controller.action()`` of the
     ``telemetry.ModalIntegrator`` passed as ``controller`` (built for this env): the integrator with one gain per (env, mode), which also
     records the measurements it takes (``controller.retune()`` then sets the optimised modal gains); same conditions as ``"predictive"``,
-    and neither its command nor its telemetry is reset at episode ends.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
+    and neither its command nor its telemetry is reset at episode ends.  ``policy="spgd"``: the sensorless baseline — every step's action
+    comes from the ``sensorless.SPGDController`` passed as ``controller`` (built for this env, ``SH_operation=True``), which sees only the scalar
+    metric of the last step; it is reset with the env at every episode start (all envs; its iteration counters go on) and ``log_prob`` is the
+    constant 1.  Not with ``lookahead``, ``science``, ``ou_noise`` or ``action_mode="mean"``: ValueError before anything runs.  With
+    ``fused_policy=True`` it goes through ``env.reset_with_spgd`` / ``env.step_with_spgd`` (the query rides in the step's last launch) and
+    returns the same dict, bit for bit, as the unfused loop from the same controller state.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
     action before the env sees it (and before it is stored, like the reference's in-place ``action +=``), or a ``DeviceOUNoise``
     (``main.py:218-220``: mu 0, theta 0.3, sigma 0.05), which the HIP policy query advances and adds itself: float64 state, Philox normals keyed
     by the global env id (a split batch reproduces the whole one), no extra launch.  Neither is reset here, as in the reference.
@@ -305,24 +310,28 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     B = env.num_envs
     if gatherer is None:
         gatherer = EpisodeReturnGatherer(B, env.device, False)
-    if policy not in ("actor", "shack", "ideal", "pyramid", "predictive", "modal"):
-        raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive' or 'modal'")
+    if policy not in ("actor", "shack", "ideal", "pyramid", "predictive", "modal", "spgd"):
+        raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive', 'modal' or 'spgd'")
     if action_mode not in ("sample", "mean"):
         raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
-    ideal, pyramid, predictive, modal = policy == "ideal", policy == "pyramid", policy == "predictive", policy == "modal"
-    shack = policy == "shack" or ideal or pyramid or predictive or modal   # (no policy query either way: the action is a controller's raw actuator vector)
+    ideal, pyramid, predictive, modal, spgd = policy == "ideal", policy == "pyramid", policy == "predictive", policy == "modal", policy == "spgd"
+    shack = policy == "shack" or ideal or pyramid or predictive or modal or spgd   # (no policy query either way: the action is a controller's raw actuator vector)
     if predictive != (predictor is not None):
         raise ValueError("policy='predictive' takes its controller as predictor=PredictiveController(env, ...), and no other policy takes one")
     if predictive and predictor.env is not env:
         raise ValueError("policy='predictive': the predictor was built for another env")
-    if modal != (controller is not None):
-        raise ValueError("policy='modal' takes its controller as controller=ModalIntegrator(env, ...), and no other policy takes one")
-    if modal and controller.env is not env:
-        raise ValueError("policy='modal': the controller was built for another env")
+    if (modal or spgd) != (controller is not None):
+        raise ValueError("policy='modal' takes its controller as controller=ModalIntegrator(env, ...), policy='spgd' as "
+                         "controller=SPGDController(env, ...), and no other policy takes one")
+    if (modal or spgd) and controller.env is not env:
+        raise ValueError(f"policy={policy!r}: the controller was built for another env")
+    if spgd and (lookahead or science or ou_noise is not None or action_mode != "sample"):
+        raise ValueError("policy='spgd' goes with none of lookahead, science, ou_noise and action_mode='mean': the controller's commands are the "
+                         "experiment (a noise term or another mirror command between two of its queries would enter its metric differences)")
     dev_ou = isinstance(ou_noise, DeviceOUNoise)
     if shack and (dev_ou or action_mode != "sample"):
         raise ValueError(f"policy={policy!r} takes neither a DeviceOUNoise nor action_mode='mean' (the "
-                         f"{'ideal modal controller' if ideal else 'pyramid integrator' if pyramid else 'predictive controller' if predictive else 'modal integrator' if modal else 'Shack-Hartmann integrator'} is not a policy query)")
+                         f"{'ideal modal controller' if ideal else 'pyramid integrator' if pyramid else 'predictive controller' if predictive else 'modal integrator' if modal else 'SPGD controller' if spgd else 'Shack-Hartmann integrator'} is not a policy query)")
     if shack:
         if not getattr(env, "SH_operation", False):
             raise ValueError(f"policy={policy!r} needs an env created with SH_operation=True (AO_env.py:115-116, 254)")
@@ -350,7 +359,7 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         pkw["ou_noise"] = ou_noise
     if action_mode != "sample":
         pkw["action_mode"] = action_mode
-    if fused_policy:
+    if fused_policy and not spgd:
         if shack:
             raise ValueError("fused_policy=True needs policy='actor' (neither the Shack-Hartmann integrator nor the ideal controller is a policy query)")
         if dev_actor is None:
@@ -375,7 +384,10 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     n = T * episodes
     out = None
     ep_returns = []
-    if fused_policy:
+    if fused_policy and spgd:
+        with torch.no_grad():
+            out = _rollout_fused_spgd(env, controller, T, episodes, gatherer, ep_returns)
+    elif fused_policy:
         with torch.no_grad():
             out = _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns, pkw)
     else:
@@ -394,7 +406,10 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                                "log_prob": torch.empty((n, B), dtype=torch.float32, device=dev), "rew": torch.empty((n, B), dtype=torch.float32, device=dev),
                                "next_obs": torch.empty((n, B, S), dtype=obs.dtype, device=dev), "done": torch.empty((n, B), dtype=torch.bool, device=dev)}
                         mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
-                    if shack:
+                    if spgd:   # (the controller is reset with the env; every later step queries it on the last step's metric)
+                        action = controller.reset(out=out["act"][i]) if _t == 0 else controller.action(out=out["act"][i])
+                        out["log_prob"][i].fill_(1.0)
+                    elif shack:
                         # (actuators [B, A] float64, the reference's constant log-probability 1; 'ideal': from the state the last observation saw)
                         sh_act = (env.ideal_action() if ideal else env.PYR_step()[0] if pyramid else predictor.action() if predictive
                                   else controller.action() if modal else env.SH_step()[0])
@@ -465,6 +480,36 @@ def _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns, p
             _, pol = env.step_with_policy(dev_actor, cov_var, out=(out["next_obs"][i], out["rew"][i], out["done"][i]), policy_out=pol_out, **pkw)
             if (pol is None) != last:
                 raise RuntimeError(f"step_with_policy {'did not query' if pol is None else 'queried'} the policy at step {t + 1} of {T}: the env's "
+                                   "episode length differs from timesteps_per_episode")
+        if T > 1:
+            out["obs"][i0 + 1:i0 + T].copy_(out["next_obs"][i0:i0 + T - 1])   # obs of step t+1 = next_obs of step t
+        gatherer.add(out["rew"][i0:i0 + T].sum(0))
+        ep_returns.append(gatherer.finish_episode().clone())
+    return out
+
+
+def _rollout_fused_spgd(env, controller, T, episodes, gatherer, ep_returns):
+    """rollout(policy='spgd', fused_policy=True)'s loop: reset_with_spgd writes row i0's command, step i the command of row i + 1 (none on the
+    last step)."""
+    import torch
+
+    B, S, A, dev = env.num_envs, int(env.obs_dim) ** 2, int(env.num_modes), env.device
+    n = T * episodes
+    out = {"obs": torch.empty((n, B, S), dtype=torch.float16, device=dev), "act": torch.empty((n, B, A), dtype=torch.float32, device=dev),
+           "log_prob": torch.ones((n, B), dtype=torch.float32, device=dev), "rew": torch.empty((n, B), dtype=torch.float32, device=dev),
+           "next_obs": torch.empty((n, B, S), dtype=torch.float16, device=dev), "done": torch.empty((n, B), dtype=torch.bool, device=dev)}
+    spare = torch.empty((B, A), dtype=torch.float32, device=dev)   # (the last step of an episode writes no command)
+    for e in range(episodes):
+        i0 = e * T
+        (obs, _), _ = env.reset_with_spgd(controller, action_out=out["act"][i0])
+        gatherer.start_episode()
+        out["obs"][i0].copy_(obs)
+        for t in range(T):
+            i = i0 + t
+            last = t == T - 1
+            _, nxt = env.step_with_spgd(controller, out=(out["next_obs"][i], out["rew"][i], out["done"][i]), action_out=spare if last else out["act"][i + 1])
+            if (nxt is None) != last:
+                raise RuntimeError(f"step_with_spgd {'did not query' if nxt is None else 'queried'} the controller at step {t + 1} of {T}: the env's "
                                    "episode length differs from timesteps_per_episode")
         if T > 1:
             out["obs"][i0 + 1:i0 + T].copy_(out["next_obs"][i0:i0 + T - 1])   # obs of step t+1 = next_obs of step t

@@ -811,6 +811,59 @@ int64_t aog_telemetry_state_bytes(const aog_telemetry* t);
 int aog_telemetry_get_state(aog_telemetry* t, void* blob_dev, void* stream);
 int aog_telemetry_set_state(aog_telemetry* t, const void* blob_dev, void* stream);
 
+/* ---- stochastic parallel gradient descent (SPGD): the sensorless baseline, as a controller on the device (additive in ABI 22; no
+ * counterpart in the reference) ----
+ * The one classical controller that sees only what a learnt policy sees: a scalar quality of the last command.  Two-sided SPGD with
+ * Bernoulli perturbations, per env.  State: the centre command u [A] float64, the iteration k (uint32), the half h in {0, 1} and J_plus
+ * (float64).  Per-env hyper-parameters gain [B] and amplitude [B] (float64, 0 until aog_spgd_set_params), one bound clip on |u_i| (0: none).
+ *   delta_k in {-1, +1}^A: actuator i takes bit i & 31 of word (i >> 5) & 3 of the Philox4x32-10 call keyed by `seed` (low word, high word)
+ *   with counter (env_id_base + env, k, i >> 7, 0x53504744); a set bit is +1.  Keyed by the GLOBAL env id: a split batch reproduces the whole.
+ *   query, h = 0: the command in place gave the metric J:  J_plus = J,  emit u - amplitude delta_k,  h = 1;
+ *   query, h = 1: u = clip(u + (gain (J_plus - J)) delta_k),  k = k + 1,  h = 0,  emit u + amplitude delta_k  (the new k's delta);
+ *   reset of an env: u = 0 (or its row of act_dev),  h = 0,  k KEPT (no stream is replayed),  emit u + amplitude delta_k.
+ * J is a float32 (what aog_step stores as power, Strehl or reward) widened to float64; every product and sum above is one rounded float64
+ * operation in the order written, nothing fused; the emitted command is the float32 of the float64 sum, [B][A], raw actuators: the action
+ * of an sh_operation handle.  A host replay from the recorded metrics is therefore bit-exact.  One wave per env, one Philox evaluation per
+ * wave and 2048 actuators; plain vector stores, no atomics, no host synchronisation.  mask_dev: nullable [B] uint8 device array, non-zero =
+ * selected; envs it leaves out are touched nowhere, and neither are their rows of action_out.
+ * AOG_ERR_INVALID, before any device work: a wrong abi_version, num_envs < 1, act_dim < 1, a metric outside AOG_SPGD_*, a nonzero reserved
+ * field, a NaN, infinite or negative clip, gain or amplitude.  The struct is four int32, a uint64, two int32 and a double; it has no index in
+ * aog_struct_size. */
+enum { AOG_SPGD_POWER = 0, AOG_SPGD_STREHL = 1, AOG_SPGD_REWARD = 2 };
+typedef struct aog_spgd aog_spgd;
+typedef struct aog_spgd_config {
+  int32_t abi_version;                  /* = AOG_ABI_VERSION */
+  int32_t num_envs, act_dim, env_id_base;
+  uint64_t seed;
+  int32_t metric;                       /* AOG_SPGD_*: which of the step's outputs aog_step_spgd descends on */
+  int32_t reserved0;                    /* = 0 */
+  double clip;                          /* bound on |u_i|; 0 = none */
+} aog_spgd_config;
+int aog_spgd_create(const aog_spgd_config* cfg, int device, aog_spgd** out);
+void aog_spgd_destroy(aog_spgd* spgd);
+/* gain_host, amplitude_host: HOST arrays [B].  Blocking copy. */
+int aog_spgd_set_params(aog_spgd* spgd, const double* gain_host, const double* amplitude_host);
+/* Reset of the selected envs.  act_dev: nullable [B][A] float64 device array to start u from (aog_get_actuators' form); action_out: nullable. */
+int aog_spgd_reset(aog_spgd* spgd, const uint8_t* mask_dev, const double* act_dev, float* action_out, void* stream);
+/* One query of the selected envs on metric_dev [B] float32. */
+int aog_spgd_update(aog_spgd* spgd, const float* metric_dev, const uint8_t* mask_dev, float* action_out, void* stream);
+/* Checkpointing: per env, one after the other, u [A] and J_plus (float64), then k and h (uint32) — the blob of a whole batch is the blobs
+ * of its parts in a row.  A handle of the same configuration and parameters that takes the blob resumes bit-identically. */
+int64_t aog_spgd_state_bytes(const aog_spgd* spgd);
+int aog_spgd_get_state(aog_spgd* spgd, void* blob_dev, void* stream);
+int aog_spgd_set_state(aog_spgd* spgd, const void* blob_dev, void* stream);
+/* aog_reset_act / aog_step_act with the SPGD query in the policy's place (k_epilogue_spgd_prologue: the epilogue of step t, the query on
+ * the metric it has just stored and the prologue of step t + 1 as one launch, 16 envs per workgroup).  Results bit-identical to aog_reset +
+ * aog_spgd_reset (act_dev = the handle's actuators unless cfg.flat_mirror_start) resp. aog_step + aog_spgd_update on that step's output +
+ * the next aog_step's prologue.  Argument rules, pending-action rules and the unusable-handle rule after a late failure as aog_reset_act /
+ * aog_step_act; action_out [B][A] float32 required.  On the episode's last step aog_step_spgd is a plain epilogue: no query, action_out and
+ * the controller untouched, *queried = 0.  The step's output that cfg.metric names may be NULL (the controller then keeps the metric in a
+ * buffer of its own).  AOG_ERR_INVALID: a handle without cfg.sh_operation (its action is rescaled to a fixed surface rms, so a perturbation
+ * amplitude means nothing there), act_dim != n_modes, num_envs != the handle's, another env_id_base or device. */
+int aog_reset_spgd(aog_env* env, aog_spgd* spgd, float* obs_raw_dev, uint16_t* obs_dev, float* action_out, void* stream);
+int aog_step_spgd(aog_env* env, aog_spgd* spgd, const float* action_dev, float* obs_raw_dev, uint16_t* obs_dev, float* reward_dev,
+                  uint8_t* done_dev, float* power_dev, float* strehl_dev, float* action_out, int* queried /* host int, nullable */, void* stream);
+
 /* Self-test hook: sin(2 pi u), cos(2 pi u) for n float32 revolutions u_dev with the fused kernels' device code.
  * flavour 0 = polynomial, 1 = v_sin_f32/v_cos_f32 after the exact reduction, 2 = v_sin_f32/v_cos_f32 on raw input. */
 int aog_selftest_sincos(const float* u_dev, float* sin_dev, float* cos_dev, int n, int flavour, void* stream);
