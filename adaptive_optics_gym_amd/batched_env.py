@@ -910,6 +910,41 @@ class BatchedAOEnv:
                 raise ValueError("policy_out: expected contiguous float32 (action [B, A], log_prob [B], mean [B, A] or None) tensors on the env's device")
         return policy.net(B, cov_var, layers), (action, log_prob, mean), noise
 
+    def _reset_with_tail(self, fn, first, rest):
+        """The launches and bookkeeping of a whole-batch ``reset()`` whose last launch also runs a tail (a policy query, an SPGD reset) that
+        loads the first action into the mirror: ``fn(handle, first, obs_raw, obs, *rest, stream)``.  The caller has refused a mask and
+        checked the tail's arguments.  Returns ``(obs, info)``."""
+        if self.atm_type == "semi_dynamic":
+            self._generate_screens(mask=None)  # layer.reset() (AO_env.py:76-77)
+        obs, obs_raw = self._obs_buffers(False)
+        _lib.check(fn(self._handle, first, C.c_void_p(obs_raw.data_ptr()), C.c_void_p(obs.data_ptr()), *rest, self._stream()))
+        self._observed(obs, obs_raw)
+        return obs, {}
+
+    def _step_with_tail(self, fn, first, a, out, mid, last, keep_last_step):
+        """The launches and bookkeeping of a ``step()`` of the pending action (``a`` = None) or of ``a`` whose last launch also runs a tail on
+        the new observation, unless the episode ends: ``fn(handle, first, action, the six outputs of aog_step, *mid, &queried, *last, stream)``.
+        The caller has checked the tail's arguments.  ``keep_last_step``: the step tuple becomes ``_last_step`` (``SPGDController.action`` reads
+        it).  Returns ``(step tuple, whether the tail ran)``."""
+        if self.atm_type == "dynamic" and self._host_rng:
+            self._host_extrusion_noise()
+        ret, ptrs = self._step_outputs(out)
+        p = C.c_void_p
+        queried = C.c_int(0)
+        _lib.check(fn(self._handle, first, p(a.data_ptr() if a is not None else None), p(ptrs[0]), p(ptrs[1]), p(ptrs[2]), p(ptrs[3]), p(ptrs[4]),
+                      p(ptrs[5]), *mid, C.byref(queried), *last, self._stream()))
+        if keep_last_step:
+            self._last_step = ret
+        self._observed(ret[0], ret[4]["obs_raw"], step=True)
+        return ret, queried.value
+
+    @staticmethod
+    def _policy_ptrs(pol, noise):
+        """``_policy_net``'s outputs and noise as the library's arguments: ((action, log_prob, mean), (noise,)); noise = NULL is the plain form."""
+        p = C.c_void_p
+        return ((p(pol[0].data_ptr()), p(pol[1].data_ptr()), p(pol[2].data_ptr() if pol[2] is not None else None)),
+                (C.byref(noise) if noise is not None else None,))
+
     def reset_with_policy(self, policy, cov_var=0.5, policy_out=None, mask=None, ou_noise=None, action_mode="sample"):
         """``reset()`` of the whole batch with ``policy`` (a ``rollout.DeviceActor``) attached (``aog_reset_act``): the reset's last launch
         also queries the policy on the reset observation and loads the resulting action into the mirror, so the next ``step_with_policy``
@@ -920,18 +955,11 @@ class BatchedAOEnv:
         (``aog_reset_act_noise``)."""
         if mask is not None:
             raise ValueError("reset_with_policy resets the whole batch; reset some envs with reset(mask) and step with an explicit action")
-        net, (action, log_prob, mean), noise = self._policy_net(policy, cov_var, policy_out, ou_noise, action_mode)
-        if self.atm_type == "semi_dynamic":
-            self._generate_screens(mask=None)  # layer.reset() (AO_env.py:76-77)
-        obs, obs_raw = self._obs_buffers(False)
-        p = C.c_void_p
-        # (noise = NULL is the library's aog_reset_act)
-        _lib.check(self.lib.aog_reset_act_noise(self._handle, C.byref(net), p(obs_raw.data_ptr()), p(obs.data_ptr()), p(action.data_ptr()),
-                                                p(log_prob.data_ptr()), p(mean.data_ptr() if mean is not None else None),
-                                                C.byref(noise) if noise is not None else None, self._stream()))
+        net, pol, noise = self._policy_net(policy, cov_var, policy_out, ou_noise, action_mode)
+        ptrs, noise = self._policy_ptrs(pol, noise)
+        ret = self._reset_with_tail(self.lib.aog_reset_act_noise, C.byref(net), ptrs + noise)
         policy.calls += 1
-        self._observed(obs, obs_raw)
-        return (obs, {}), (action, log_prob, mean)
+        return ret, pol
 
     def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None, ou_noise=None, action_mode="sample"):
         """``step()`` with ``policy`` (a ``rollout.DeviceActor``) attached (``aog_step_act``): steps the action left pending by
@@ -944,18 +972,9 @@ class BatchedAOEnv:
         queried)."""
         a = self._as_actions(action) if action is not None else None
         net, pol, noise = self._policy_net(policy, cov_var, policy_out, ou_noise, action_mode)
-        if self.atm_type == "dynamic" and self._host_rng:
-            self._host_extrusion_noise()
-        ret, ptrs = self._step_outputs(out)
-        p = C.c_void_p
-        queried = C.c_int(0)
-        # (noise = NULL is the library's aog_step_act)
-        _lib.check(self.lib.aog_step_act_noise(self._handle, C.byref(net), p(a.data_ptr() if a is not None else None), p(ptrs[0]), p(ptrs[1]),
-                                               p(ptrs[2]), p(ptrs[3]), p(ptrs[4]), p(ptrs[5]), p(pol[0].data_ptr()), p(pol[1].data_ptr()),
-                                               p(pol[2].data_ptr() if pol[2] is not None else None), C.byref(queried),
-                                               C.byref(noise) if noise is not None else None, self._stream()))
-        self._observed(ret[0], ret[4]["obs_raw"], step=True)
-        if not queried.value:
+        ptrs, noise = self._policy_ptrs(pol, noise)
+        ret, queried = self._step_with_tail(self.lib.aog_step_act_noise, C.byref(net), a, out, ptrs, noise, keep_last_step=False)
+        if not queried:
             return ret, None
         policy.calls += 1
         return ret, pol
@@ -980,13 +999,7 @@ class BatchedAOEnv:
         if mask is not None:
             raise ValueError("reset_with_spgd resets the whole batch; reset some envs with reset(mask) + ctrl.reset(mask) and step with an explicit action")
         action = self._spgd_checked(ctrl, action_out, "reset_with_spgd")
-        if self.atm_type == "semi_dynamic":
-            self._generate_screens(mask=None)  # layer.reset() (AO_env.py:76-77)
-        obs, obs_raw = self._obs_buffers(False)
-        p = C.c_void_p
-        _lib.check(self.lib.aog_reset_spgd(self._handle, ctrl._handle, p(obs_raw.data_ptr()), p(obs.data_ptr()), p(action.data_ptr()), self._stream()))
-        self._observed(obs, obs_raw)
-        return (obs, {}), action
+        return self._reset_with_tail(self.lib.aog_reset_spgd, ctrl._handle, (C.c_void_p(action.data_ptr()),)), action
 
     def step_with_spgd(self, ctrl, out=None, action=None, action_out=None):
         """``step()`` with ``ctrl`` attached (``aog_step_spgd``): steps the action left pending by ``reset_with_spgd`` or the previous call
@@ -1000,16 +1013,8 @@ class BatchedAOEnv:
             out = (out["obs"], out["reward"], out["done"])
         a = self._as_actions(action) if action is not None else None
         nxt = self._spgd_checked(ctrl, action_out, "step_with_spgd")
-        if self.atm_type == "dynamic" and self._host_rng:
-            self._host_extrusion_noise()
-        ret, ptrs = self._step_outputs(out)
-        p = C.c_void_p
-        queried = C.c_int(0)
-        _lib.check(self.lib.aog_step_spgd(self._handle, ctrl._handle, p(a.data_ptr() if a is not None else None), p(ptrs[0]), p(ptrs[1]), p(ptrs[2]),
-                                          p(ptrs[3]), p(ptrs[4]), p(ptrs[5]), p(nxt.data_ptr()), C.byref(queried), self._stream()))
-        self._last_step = ret
-        self._observed(ret[0], ret[4]["obs_raw"], step=True)
-        return ret, (nxt if queried.value else None)
+        ret, queried = self._step_with_tail(self.lib.aog_step_spgd, ctrl._handle, a, out, (C.c_void_p(nxt.data_ptr()),), (), keep_last_step=True)
+        return ret, (nxt if queried else None)
 
     def _as_actions(self, actions):
         """[B, A] float32 contiguous device tensor (as is when it already is one)."""

@@ -77,6 +77,39 @@ int launch_with_lds(int device, hipStream_t s, void (*kernel)(Params...), dim3 g
   HIP_TRY(hipGetLastError());
   return AOG_OK;
 }
+// an entry point's one launch of a kernel without dynamic LDS on `stream` (void*): makes `device` current, launches, checks — and returns
+// from the entry point on failure, with the entry point's own file and line in aog_last_error as HIP_TRY gives them
+#define LAUNCH_PLAIN(device, stream, kernel, grid, block, ...)                                      \
+  do {                                                                                             \
+    HIP_TRY(hipSetDevice(device));                                                                 \
+    hipLaunchKernelGGL(kernel, grid, block, 0, static_cast<hipStream_t>(stream), __VA_ARGS__);     \
+    HIP_TRY(hipGetLastError());                                                                    \
+  } while (0)
+
+// The per-env records of a handle that is no aog_env (aog_predictor, aog_telemetry, aog_spgd): one device buffer, and the stream-ordered
+// copies of its checkpoint (*_get_state / *_set_state: `blob` is a device buffer of `bytes` bytes)
+struct RecordStore {
+  int device = 0;
+  size_t bytes = 0;
+  char* ptr = nullptr;
+  // (the caller has made `dev` current; what the records hold at first is the handle's own business)
+  hipError_t alloc(int dev, size_t n) {
+    device = dev;
+    bytes = n;
+    return hipMalloc(reinterpret_cast<void**>(&ptr), n);
+  }
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+  }
+  int copy(void* dst, const void* src, void* stream) const {
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return AOG_OK;
+  }
+  int copy_out(void* blob, void* stream) const { return copy(blob, ptr, stream); }
+  int copy_in(const void* blob, void* stream) const { return copy(ptr, blob, stream); }
+};
 
 // zero `n_words` 32-bit words at p on stream s with a kernel of the library (see k_zero_words for why not hipMemsetAsync)
 void zero_words(void* p, size_t n_words, hipStream_t s);

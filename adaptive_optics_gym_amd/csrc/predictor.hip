@@ -6,10 +6,9 @@ using namespace aog_host;
 
 struct aog_predictor {
   aog_predictor_config cfg{};
-  int device = 0;
   int n = 0;
   size_t rec_bytes = 0;
-  char* state = nullptr;   // [batch] records (k_predictor.h)
+  RecordStore state;   // [batch] records (k_predictor.h)
 };
 
 namespace {
@@ -31,7 +30,7 @@ int predictor_check(const aog_predictor_config* c) {
 
 aog::PredictorArgs predictor_args(const aog_predictor* p, const uint8_t* mask) {
   aog::PredictorArgs a{};
-  a.state = p->state;
+  a.state = p->state.ptr;
   a.rec_bytes = p->rec_bytes;
   a.mask = mask;
   a.A = p->cfg.act_dim;
@@ -44,9 +43,14 @@ aog::PredictorArgs predictor_args(const aog_predictor* p, const uint8_t* mask) {
 }
 
 template <int NW, int RPW, int CB, int CBW, bool KEEP>
-void launch_update(const aog::PredictorArgs& a, int batch, hipStream_t s) {
+int launch_update(const aog_predictor* p, const aog::PredictorArgs& a, hipStream_t s) {
   const size_t lds = aog::predictor_lds_words(a.A, a.n, NW) * sizeof(double);   // <= 46 KB at n = A = 256
-  hipLaunchKernelGGL((aog::k_predictor_update<NW, RPW, CB, CBW, KEEP>), dim3(batch), dim3(NW * 64), lds, s, a);
+  return launch_with_lds(p->state.device, s, aog::k_predictor_update<NW, RPW, CB, CBW, KEEP>, dim3(p->cfg.batch), dim3(NW * 64), lds, a);
+}
+
+void release(aog_predictor* p) {
+  p->state.release();
+  delete p;
 }
 
 }  // namespace
@@ -60,18 +64,16 @@ int aog_predictor_create(const aog_predictor_config* cfg, int device, aog_predic
   HIP_TRY(hipSetDevice(device));
   aog_predictor* p = new aog_predictor;
   p->cfg = *cfg;
-  p->device = device;
   p->n = cfg->act_dim * cfg->order;
   p->rec_bytes = aog::predictor_record_words(cfg->act_dim, p->n) * sizeof(double);
-  hipError_t err = hipMalloc(reinterpret_cast<void**>(&p->state), p->rec_bytes * (size_t)cfg->batch);
+  hipError_t err = p->state.alloc(device, p->rec_bytes * (size_t)cfg->batch);
   if (err == hipSuccess) {
     hipLaunchKernelGGL(aog::k_predictor_reset, dim3(cfg->batch), dim3(256), 0, nullptr, predictor_args(p, nullptr));
     err = hipGetLastError();
     if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
   }
   if (err != hipSuccess) {
-    if (p->state) (void)hipFree(p->state);
-    delete p;
+    release(p);
     return fail(AOG_ERR_HIP, "aog_predictor_create: %s", hipGetErrorString(err));
   }
   *out = p;
@@ -80,51 +82,41 @@ int aog_predictor_create(const aog_predictor_config* cfg, int device, aog_predic
 
 void aog_predictor_destroy(aog_predictor* p) {
   if (!p) return;
-  (void)hipSetDevice(p->device);
-  if (p->state) (void)hipFree(p->state);
-  delete p;
+  (void)hipSetDevice(p->state.device);
+  release(p);
 }
 
 int aog_predictor_reset(aog_predictor* p, const uint8_t* mask_dev, void* stream) {
   if (!p) return fail(AOG_ERR_INVALID, "aog_predictor_reset: null argument");
-  HIP_TRY(hipSetDevice(p->device));
-  hipLaunchKernelGGL(aog::k_predictor_reset, dim3(p->cfg.batch), dim3(256), 0, static_cast<hipStream_t>(stream), predictor_args(p, mask_dev));
-  HIP_TRY(hipGetLastError());
+  LAUNCH_PLAIN(p->state.device, stream, aog::k_predictor_reset, dim3(p->cfg.batch), dim3(256), predictor_args(p, mask_dev));
   return AOG_OK;
 }
 
 int aog_predictor_update(aog_predictor* p, const double* y_dev, const uint8_t* mask_dev, double* pred_dev, double* innov_dev, void* stream) {
   if (!p || !y_dev || !pred_dev) return fail(AOG_ERR_INVALID, "aog_predictor_update: null argument");
-  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipSetDevice(p->state.device));
   aog::PredictorArgs a = predictor_args(p, mask_dev);
   a.y = y_dev;
   a.pred = pred_dev;
   a.innov = innov_dev;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int B = p->cfg.batch;
   // the register forms hold the wave's rows of P and W (k_predictor.h); above kPredKeepN the two-read form
-  if (p->n <= 64) launch_update<4, 16, 1, 1, true>(a, B, s);
-  else if (p->n <= aog::kPredKeepN && a.A <= 64) launch_update<8, 16, 2, 1, true>(a, B, s);
-  else if (p->n <= aog::kPredKeepN) launch_update<8, 16, 2, 2, true>(a, B, s);
-  else launch_update<8, 0, 4, 4, false>(a, B, s);
-  HIP_TRY(hipGetLastError());
-  return AOG_OK;
+  if (p->n <= 64) return launch_update<4, 16, 1, 1, true>(p, a, s);
+  if (p->n <= aog::kPredKeepN && a.A <= 64) return launch_update<8, 16, 2, 1, true>(p, a, s);
+  if (p->n <= aog::kPredKeepN) return launch_update<8, 16, 2, 2, true>(p, a, s);
+  return launch_update<8, 0, 4, 4, false>(p, a, s);
 }
 
-int64_t aog_predictor_state_bytes(const aog_predictor* p) { return p ? (int64_t)(p->rec_bytes * (size_t)p->cfg.batch) : 0; }
+int64_t aog_predictor_state_bytes(const aog_predictor* p) { return p ? (int64_t)p->state.bytes : 0; }
 
 int aog_predictor_get_state(aog_predictor* p, void* blob_dev, void* stream) {
   if (!p || !blob_dev) return fail(AOG_ERR_INVALID, "aog_predictor_get_state: null argument");
-  HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(hipMemcpyAsync(blob_dev, p->state, p->rec_bytes * (size_t)p->cfg.batch, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return AOG_OK;
+  return p->state.copy_out(blob_dev, stream);
 }
 
 int aog_predictor_set_state(aog_predictor* p, const void* blob_dev, void* stream) {
   if (!p || !blob_dev) return fail(AOG_ERR_INVALID, "aog_predictor_set_state: null argument");
-  HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(hipMemcpyAsync(p->state, blob_dev, p->rec_bytes * (size_t)p->cfg.batch, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return AOG_OK;
+  return p->state.copy_in(blob_dev, stream);
 }
 
 }  // extern "C"

@@ -16,17 +16,13 @@ __global__ __launch_bounds__(64 * kSpgdEnvs) void k_spgd_update(SpgdArgs s) {
 namespace {
 
 int launch_query(const aog_spgd* g, const aog::SpgdArgs& s, void* stream) {
-  HIP_TRY(hipSetDevice(g->device));
   const int B = g->cfg.num_envs;
-  hipLaunchKernelGGL(aog::k_spgd_update, dim3((B + aog::kSpgdEnvs - 1) / aog::kSpgdEnvs), dim3(64 * aog::kSpgdEnvs), 0, static_cast<hipStream_t>(stream), s);
-  HIP_TRY(hipGetLastError());
+  LAUNCH_PLAIN(g->device, stream, aog::k_spgd_update, dim3((B + aog::kSpgdEnvs - 1) / aog::kSpgdEnvs), dim3(64 * aog::kSpgdEnvs), s);
   return AOG_OK;
 }
 
-size_t state_bytes(const aog_spgd* g) { return aog::spgd_record_doubles(g->cfg.act_dim) * sizeof(double) * (size_t)g->cfg.num_envs; }
-
 void release(aog_spgd* g) {
-  if (g->state) (void)hipFree(g->state);
+  g->state.release();
   if (g->gain) (void)hipFree(g->gain);
   if (g->amplitude) (void)hipFree(g->amplitude);
   if (g->metric) (void)hipFree(g->metric);
@@ -51,12 +47,12 @@ int aog_spgd_create(const aog_spgd_config* cfg, int device, aog_spgd** out) {
   g->cfg = *cfg;
   g->device = device;
   const size_t B = (size_t)cfg->num_envs;
-  hipError_t err = hipMalloc(reinterpret_cast<void**>(&g->state), state_bytes(g));
+  hipError_t err = g->state.alloc(device, aog::spgd_record_doubles(cfg->act_dim) * sizeof(double) * B);
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&g->gain), B * sizeof(double));
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&g->amplitude), B * sizeof(double));
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&g->metric), B * sizeof(float));
   // u = 0, J_plus = 0, k = 0, h = 0; gain = amplitude = 0 until aog_spgd_set_params
-  if (err == hipSuccess) err = hipMemset(g->state, 0, state_bytes(g));
+  if (err == hipSuccess) err = hipMemset(g->state.ptr, 0, g->state.bytes);
   if (err == hipSuccess) err = hipMemset(g->gain, 0, B * sizeof(double));
   if (err == hipSuccess) err = hipMemset(g->amplitude, 0, B * sizeof(double));
   if (err == hipSuccess) err = hipMemset(g->metric, 0, B * sizeof(float));
@@ -97,20 +93,16 @@ int aog_spgd_update(aog_spgd* g, const float* metric_dev, const uint8_t* mask_de
   return launch_query(g, spgd_args(g, false, metric_dev, mask_dev, nullptr, action_out), stream);
 }
 
-int64_t aog_spgd_state_bytes(const aog_spgd* g) { return g ? (int64_t)state_bytes(g) : 0; }
+int64_t aog_spgd_state_bytes(const aog_spgd* g) { return g ? (int64_t)g->state.bytes : 0; }
 
 int aog_spgd_get_state(aog_spgd* g, void* blob_dev, void* stream) {
   if (!g || !blob_dev) return fail(AOG_ERR_INVALID, "aog_spgd_get_state: null argument");
-  HIP_TRY(hipSetDevice(g->device));
-  HIP_TRY(hipMemcpyAsync(blob_dev, g->state, state_bytes(g), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return AOG_OK;
+  return g->state.copy_out(blob_dev, stream);
 }
 
 int aog_spgd_set_state(aog_spgd* g, const void* blob_dev, void* stream) {
   if (!g || !blob_dev) return fail(AOG_ERR_INVALID, "aog_spgd_set_state: null argument");
-  HIP_TRY(hipSetDevice(g->device));
-  HIP_TRY(hipMemcpyAsync(g->state, blob_dev, state_bytes(g), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return AOG_OK;
+  return g->state.copy_in(blob_dev, stream);
 }
 
 }  // extern "C"

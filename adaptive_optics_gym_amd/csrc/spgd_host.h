@@ -6,7 +6,7 @@
 struct aog_spgd {
   aog_spgd_config cfg{};
   int device = 0;
-  double* state = nullptr;       // [B] records (k_spgd.h)
+  aog_host::RecordStore state;   // [B] records (k_spgd.h)
   double* gain = nullptr;        // [B]
   double* amplitude = nullptr;   // [B]
   float* metric = nullptr;       // [B] where a fused step stores the metric when the caller passes no output for it
@@ -16,7 +16,7 @@ namespace aog_host {
 // the arguments of one query (reset = false: on `metric`) or reset (from `start`, nullable) writing the commands to `action`
 inline aog::SpgdArgs spgd_args(const aog_spgd* g, bool reset, const float* metric, const uint8_t* mask, const double* start, float* action) {
   aog::SpgdArgs s{};
-  s.state = g->state;
+  s.state = reinterpret_cast<double*>(g->state.ptr);
   s.gain = g->gain;
   s.amplitude = g->amplitude;
   s.metric = metric;

@@ -7,9 +7,8 @@ using namespace aog_host;
 
 struct aog_telemetry {
   aog_telemetry_config cfg{};
-  int device = 0;
   size_t rec_bytes = 0;
-  char* state = nullptr;   // [batch] records (k_telemetry.h)
+  RecordStore state;       // [batch] records (k_telemetry.h)
   double* r2 = nullptr;    // |R_k(g)|^2 of the last aog_telemetry_gains and its grid: kTelMaxG (kTelMaxT / 2 + 1) float64
 };
 
@@ -33,7 +32,7 @@ int segment_check(const aog_telemetry* t, const char* who, int S) {
 
 aog::TelemetryArgs telemetry_args(const aog_telemetry* t, const uint8_t* mask) {
   aog::TelemetryArgs a{};
-  a.state = t->state;
+  a.state = t->state.ptr;
   a.rec_bytes = t->rec_bytes;
   a.mask = mask;
   a.A = t->cfg.act_dim;
@@ -45,7 +44,7 @@ template <int S>
 int launch_psd(const aog_telemetry* t, const aog::TelemetryArgs& a, hipStream_t s) {
   using Geo = aog::TelGeom<S>;
   const int nmb = (a.A + Geo::M - 1) / Geo::M;
-  return launch_with_lds(t->device, s, aog::k_telemetry_psd<S>, dim3((unsigned)t->cfg.batch * nmb), dim3(aog::kTelThreads), Geo::kLdsWords * sizeof(double), a);
+  return launch_with_lds(t->state.device, s, aog::k_telemetry_psd<S>, dim3((unsigned)t->cfg.batch * nmb), dim3(aog::kTelThreads), Geo::kLdsWords * sizeof(double), a);
 }
 
 int launch_psd_for(const aog_telemetry* t, int S, const aog::TelemetryArgs& a, hipStream_t s) {
@@ -57,6 +56,12 @@ int launch_psd_for(const aog_telemetry* t, int S, const aog::TelemetryArgs& a, h
     case 512: return launch_psd<512>(t, a, s);
     default: return launch_psd<1024>(t, a, s);
   }
+}
+
+void release(aog_telemetry* t) {
+  t->state.release();
+  if (t->r2) (void)hipFree(t->r2);
+  delete t;
 }
 
 // the stability limit of z^d - z^(d-1) + g = 0: 2 at d = 1, 1 at d = 2
@@ -73,9 +78,8 @@ int aog_telemetry_create(const aog_telemetry_config* cfg, int device, aog_teleme
   HIP_TRY(hipSetDevice(device));
   aog_telemetry* t = new aog_telemetry;
   t->cfg = *cfg;
-  t->device = device;
   t->rec_bytes = aog::telemetry_record_words(cfg->act_dim, cfg->length) * sizeof(double);
-  hipError_t err = hipMalloc(reinterpret_cast<void**>(&t->state), t->rec_bytes * (size_t)cfg->batch);
+  hipError_t err = t->state.alloc(device, t->rec_bytes * (size_t)cfg->batch);
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&t->r2), sizeof(double) * aog::kTelMaxG * (aog::kTelMaxT / 2 + 1));
   if (err == hipSuccess) {
     hipLaunchKernelGGL(aog::k_telemetry_reset, dim3(cfg->batch), dim3(256), 0, nullptr, telemetry_args(t, nullptr));
@@ -83,9 +87,7 @@ int aog_telemetry_create(const aog_telemetry_config* cfg, int device, aog_teleme
     if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
   }
   if (err != hipSuccess) {
-    if (t->state) (void)hipFree(t->state);
-    if (t->r2) (void)hipFree(t->r2);
-    delete t;
+    release(t);
     return fail(AOG_ERR_HIP, "aog_telemetry_create: %s", hipGetErrorString(err));
   }
   *out = t;
@@ -94,34 +96,28 @@ int aog_telemetry_create(const aog_telemetry_config* cfg, int device, aog_teleme
 
 void aog_telemetry_destroy(aog_telemetry* t) {
   if (!t) return;
-  (void)hipSetDevice(t->device);
-  if (t->state) (void)hipFree(t->state);
-  if (t->r2) (void)hipFree(t->r2);
-  delete t;
+  (void)hipSetDevice(t->state.device);
+  release(t);
 }
 
 int aog_telemetry_reset(aog_telemetry* t, const uint8_t* mask_dev, void* stream) {
   if (!t) return fail(AOG_ERR_INVALID, "aog_telemetry_reset: null argument");
-  HIP_TRY(hipSetDevice(t->device));
-  hipLaunchKernelGGL(aog::k_telemetry_reset, dim3(t->cfg.batch), dim3(256), 0, static_cast<hipStream_t>(stream), telemetry_args(t, mask_dev));
-  HIP_TRY(hipGetLastError());
+  LAUNCH_PLAIN(t->state.device, stream, aog::k_telemetry_reset, dim3(t->cfg.batch), dim3(256), telemetry_args(t, mask_dev));
   return AOG_OK;
 }
 
 int aog_telemetry_push(aog_telemetry* t, const double* y_dev, const uint8_t* mask_dev, void* stream) {
   if (!t || !y_dev) return fail(AOG_ERR_INVALID, "aog_telemetry_push: null argument");
-  HIP_TRY(hipSetDevice(t->device));
   aog::TelemetryArgs a = telemetry_args(t, mask_dev);
   a.y = y_dev;
-  hipLaunchKernelGGL(aog::k_telemetry_push, dim3(t->cfg.batch), dim3(aog::kTelMaxA), 0, static_cast<hipStream_t>(stream), a);
-  HIP_TRY(hipGetLastError());
+  LAUNCH_PLAIN(t->state.device, stream, aog::k_telemetry_push, dim3(t->cfg.batch), dim3(aog::kTelMaxA), a);
   return AOG_OK;
 }
 
 int aog_telemetry_psd(aog_telemetry* t, int segment, double* psd_dev, int32_t* segments_dev, const uint8_t* mask_dev, void* stream) {
   if (!t || !psd_dev) return fail(AOG_ERR_INVALID, "aog_telemetry_psd: null argument");
   if (int rc = segment_check(t, "aog_telemetry_psd", segment)) return rc;
-  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(hipSetDevice(t->state.device));
   aog::TelemetryArgs a = telemetry_args(t, mask_dev);
   a.psd = psd_dev;
   a.segments = segments_dev;
@@ -143,37 +139,30 @@ int aog_telemetry_gains(aog_telemetry* t, int segment, int delay, const double* 
     if (i && !(g > grid_host[i - 1])) return fail(AOG_ERR_INVALID, "aog_telemetry_gains: the grid must ascend (candidate %d = %g after %g)", i, g, grid_host[i - 1]);
     rk.grid[i] = g;
   }
-  HIP_TRY(hipSetDevice(t->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
   rk.r2 = t->r2;
   rk.S = segment;
   rk.G = n_grid;
   rk.delay = delay;
-  hipLaunchKernelGGL(aog::k_telemetry_rk, dim3((segment / 2 + 255) / 256, n_grid), dim3(256), 0, s, rk);
-  HIP_TRY(hipGetLastError());
+  LAUNCH_PLAIN(t->state.device, stream, aog::k_telemetry_rk, dim3((segment / 2 + 255) / 256, n_grid), dim3(256), rk);
   aog::TelemetryArgs a = telemetry_args(t, mask_dev);
   a.r2 = t->r2;
   a.gain = gain_dev;
   a.cost = cost_dev;
   a.cost_all = cost_all_dev;
   a.G = n_grid;
-  return launch_psd_for(t, segment, a, s);
+  return launch_psd_for(t, segment, a, static_cast<hipStream_t>(stream));
 }
 
-int64_t aog_telemetry_state_bytes(const aog_telemetry* t) { return t ? (int64_t)(t->rec_bytes * (size_t)t->cfg.batch) : 0; }
+int64_t aog_telemetry_state_bytes(const aog_telemetry* t) { return t ? (int64_t)t->state.bytes : 0; }
 
 int aog_telemetry_get_state(aog_telemetry* t, void* blob_dev, void* stream) {
   if (!t || !blob_dev) return fail(AOG_ERR_INVALID, "aog_telemetry_get_state: null argument");
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipMemcpyAsync(blob_dev, t->state, t->rec_bytes * (size_t)t->cfg.batch, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return AOG_OK;
+  return t->state.copy_out(blob_dev, stream);
 }
 
 int aog_telemetry_set_state(aog_telemetry* t, const void* blob_dev, void* stream) {
   if (!t || !blob_dev) return fail(AOG_ERR_INVALID, "aog_telemetry_set_state: null argument");
-  HIP_TRY(hipSetDevice(t->device));
-  HIP_TRY(hipMemcpyAsync(t->state, blob_dev, t->rec_bytes * (size_t)t->cfg.batch, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return AOG_OK;
+  return t->state.copy_in(blob_dev, stream);
 }
 
 }  // extern "C"

@@ -14,44 +14,30 @@ import ctypes as C
 import math
 
 from . import _lib
+from .device_handle import DeviceHandle, check_measurement, ptr
 
 
-class DevicePredictor:
+class DevicePredictor(DeviceHandle):
     """The library handle (``aog_predictor``) alone: ``batch`` independent RLS predictors of ``act_dim`` outputs and ``order`` past
-    measurements, float64 on ``device``.  ``update(y, mask=None)`` -> (prediction, innovation), both [batch, act_dim] float64."""
+    measurements, float64 on ``device``.  ``update(y, mask=None)`` -> (prediction, innovation), both [batch, act_dim] float64.
+    The state blob of ``get_state`` / ``set_state`` holds per env W [n, A], P [n, n], history [n] float64, count and skipped int64."""
+
+    prefix, noun = "aog_predictor", "predictor"
 
     def __init__(self, batch, act_dim, order=2, forgetting=0.999, p0=1e3, scale=1.0, env_id_base=0, device=None):
         import torch
 
-        self._torch = torch
-        self.lib = _lib.load()
         self.batch, self.act_dim, self.order = int(batch), int(act_dim), int(order)
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
-        cfg = _lib.AogPredictorConfig(self.batch, self.act_dim, self.order, int(env_id_base), 0, 0, float(forgetting), float(p0), float(scale))
-        self._handle = C.c_void_p()
-        _lib.check(self.lib.aog_predictor_create(C.byref(cfg), self.device.index or 0, C.byref(self._handle)))
-        self.config = cfg
+        self._bind(torch, device, self.batch)
+        self.config = _lib.AogPredictorConfig(self.batch, self.act_dim, self.order, int(env_id_base), 0, 0, float(forgetting), float(p0), float(scale))
+        self._create()
 
-    def _stream(self):
-        return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+    def _config(self):
+        return self.config
 
     def _rows(self, t, who, name):
-        torch = self._torch
-        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != (self.batch, self.act_dim)
-                or t.device != self.device):
-            raise ValueError(f"{who}: {name} must be a contiguous float64 [{self.batch}, {self.act_dim}] tensor on {self.device}")
-        return t
-
-    def _mask(self, mask, who):
-        if mask is None:
-            return None
-        torch = self._torch
-        m = torch.as_tensor(mask, device=self.device)
-        if m.dtype not in (torch.bool, torch.uint8) or tuple(m.shape) != (self.batch,):
-            raise ValueError(f"{who}: mask must be a bool vector of {self.batch} entries")
-        return m.to(torch.uint8).contiguous()
+        return self._tensor(t, (self.batch, self.act_dim), self._torch.float64,
+                            f"{who}: {name} must be a contiguous float64 [{self.batch}, {self.act_dim}] tensor on {self.device}")
 
     def update(self, y, mask=None, out=None):
         """One RLS update and prediction per selected env.  ``out`` = (pred, innov) tensors to write into (rows of unselected envs are not
@@ -64,31 +50,11 @@ class DevicePredictor:
             pred, innov = alloc_like(alloc, y), alloc_like(alloc, y)
         else:
             pred, innov = self._rows(out[0], "update", "out[0]"), self._rows(out[1], "update", "out[1]")
-        p = C.c_void_p
-        _lib.check(self.lib.aog_predictor_update(self._handle, p(y.data_ptr()), p(m.data_ptr() if m is not None else None), p(pred.data_ptr()),
-                                                 p(innov.data_ptr()), self._stream()))
+        self._call("update", ptr(y), ptr(m), ptr(pred), ptr(innov), self._stream())
         return pred, innov
 
     def reset(self, mask=None):
-        m = self._mask(mask, "reset")
-        _lib.check(self.lib.aog_predictor_reset(self._handle, C.c_void_p(m.data_ptr() if m is not None else None), self._stream()))
-
-    def get_state(self):
-        """The state blob (uint8 device tensor): per env W [n, A], P [n, n], history [n] float64, count and skipped int64."""
-        torch = self._torch
-        blob = torch.empty((int(self.lib.aog_predictor_state_bytes(self._handle)),), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.aog_predictor_get_state(self._handle, C.c_void_p(blob.data_ptr()), self._stream()))
-        return blob
-
-    def set_state(self, blob):
-        torch = self._torch
-        n = int(self.lib.aog_predictor_state_bytes(self._handle))
-        b = torch.as_tensor(blob)
-        if b.dtype != torch.uint8 or tuple(b.shape) != (n,):
-            raise ValueError(f"set_state: the blob of this predictor is a uint8 vector of {n} bytes")
-        b = b.to(self.device).contiguous()
-        _lib.check(self.lib.aog_predictor_set_state(self._handle, C.c_void_p(b.data_ptr()), self._stream()))
-        self._torch.cuda.current_stream(self.device).synchronize()   # (b may be a temporary)
+        self._call("reset", ptr(self._mask(mask, "reset")), self._stream())
 
     def unpack(self, blob=None):
         """A blob as a dict of tensors: W [B, n, A], P [B, n, n], history [B, n] float64, count [B], skipped [B] int64 (copies)."""
@@ -99,17 +65,6 @@ class DevicePredictor:
         ints = blob.view(torch.int64).reshape(B, -1)
         return {"W": words[:, :n * A].reshape(B, n, A).clone(), "P": words[:, n * A:n * A + n * n].reshape(B, n, n).clone(),
                 "history": words[:, n * A + n * n:n * A + n * n + n].clone(), "count": ints[:, -2].clone(), "skipped": ints[:, -1].clone()}
-
-    def close(self):
-        h, self._handle = self._handle, None
-        if h:
-            self.lib.aog_predictor_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def alloc_like(alloc, t):
@@ -152,10 +107,7 @@ class PredictiveController:
     across episodes (the atmosphere is not reset either): ``reset(mask)`` is the caller's.  ``state_dict`` / ``load_state_dict`` resume bit-identically."""
 
     def __init__(self, env, order=2, forgetting=0.999, p0=1e3, scale=None, measurement="truth"):
-        if measurement not in ("truth", "pyramid"):
-            raise ValueError(f"measurement must be 'truth' or 'pyramid' (got {measurement!r})")
-        if measurement == "pyramid" and getattr(env, "pyramid", None) is None:
-            raise ValueError("measurement='pyramid' needs an env created with pyramid=dict(...)")
+        check_measurement(env, measurement)
         order = int(order)
         A = int(env.num_modes)
         if order < 1:

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import math
 import weakref
+from collections import namedtuple
 
 
 def make_actor(state_dim: int, act_dim: int, hidden_dim: int, init_w: float = 3e-3, device=None):
@@ -251,56 +252,147 @@ class DeviceActor:
         return action, log_prob, mean
 
 
+# One row of rollout's policy table.  noun: what the messages call the source of the action; act(env, ctrl, row, first): writes the step's
+# [B, A] action into ``row`` (None: the policy query); sh: needs an env built with SH_operation=True, the action being a controller's raw
+# actuator vector; pyramid: needs env.pyramid; keyword: the rollout keyword that carries its controller (``ctrl``); refuses: reason -> the
+# options it refuses for that reason (keys of ``given`` in rollout), the reasons being checked in the order of _REFUSALS; fused: which of the
+# env's fused forms runs it under fused_policy=True ("policy": reset_with_policy / step_with_policy, "spgd": reset_with_spgd / step_with_spgd)
+_NOT_A_QUERY = {"query": ("dev_ou", "mean"), "fused": ("fused_policy",)}
+_MEASURES = {"query": ("dev_ou", "mean"), "measurement": ("lookahead", "fused_policy")}
+_Policy = namedtuple("_Policy", "noun act sh pyramid keyword refuses fused", defaults=(None, True, False, None, _NOT_A_QUERY, None))
+
+# the message of each reason for refusing an option, in the order they are checked (the env's own conditions come after "query")
+_REFUSALS = {
+    "experiment": "policy='spgd' goes with none of lookahead, science, ou_noise and action_mode='mean': the controller's commands are the "
+                  "experiment (a noise term or another mirror command between two of its queries would enter its metric differences)",
+    "query": "policy={policy!r} takes neither a DeviceOUNoise nor action_mode='mean' (the {noun} is not a policy query)",
+    "measurement": "policy={policy!r} goes with neither lookahead nor fused_policy: its measurement is refused while the next screens or "
+                   "the next action are already in place",
+    "fused": "fused_policy=True needs policy='actor' (neither the Shack-Hartmann integrator nor the ideal controller is a policy query)",
+}
+_POLICIES = {
+    "actor": _Policy("policy query", sh=False, refuses={}, fused="policy"),
+    "shack": _Policy("Shack-Hartmann integrator", lambda env, ctrl, row, first: row.copy_(env.SH_step()[0])),
+    "ideal": _Policy("ideal modal controller", lambda env, ctrl, row, first: row.copy_(env.ideal_action())),
+    "pyramid": _Policy("pyramid integrator", lambda env, ctrl, row, first: row.copy_(env.PYR_step()[0]), pyramid=True),
+    "predictive": _Policy("predictive controller", lambda env, ctrl, row, first: row.copy_(ctrl.action()), keyword="predictor", refuses=_MEASURES),
+    "modal": _Policy("modal integrator", lambda env, ctrl, row, first: row.copy_(ctrl.action()), keyword="controller", refuses=_MEASURES),
+    # (the controller is reset with the env; every later step queries it on the last step's metric)
+    "spgd": _Policy("SPGD controller", lambda env, ctrl, row, first: ctrl.reset(out=row) if first else ctrl.action(out=row), keyword="controller",
+                    refuses={"experiment": ("lookahead", "science", "ou_noise", "mean")}, fused="spgd"),
+}
+_CONTROLLER_KEYWORDS = {
+    "predictor": "policy='predictive' takes its controller as predictor=PredictiveController(env, ...), and no other policy takes one",
+    "controller": "policy='modal' takes its controller as controller=ModalIntegrator(env, ...), policy='spgd' as "
+                  "controller=SPGDController(env, ...), and no other policy takes one",
+}
+
+
+def _transition_buffers(n, B, S, A, obs_dtype, dev):
+    """rollout's six ``[n = T*E, B, ...]`` tensors, written in place, and one spare ``[B, A]`` float32 row (the policy query's mean; the
+    command the last step of a fused SPGD episode does not write)."""
+    import torch
+
+    def rows(*shape, dtype=torch.float32):
+        return torch.empty((n, B) + shape, dtype=dtype, device=dev)
+
+    return ({"obs": rows(S, dtype=obs_dtype), "act": rows(A), "log_prob": rows(), "rew": rows(), "next_obs": rows(S, dtype=obs_dtype),
+             "done": rows(dtype=torch.bool)}, torch.empty((B, A), dtype=torch.float32, device=dev))
+
+
+def _run_episodes(T, episodes, gatherer, reset, step):
+    """rollout's episode skeleton.  ``reset(i0)`` -> (the buffers, the reset observation): starts an episode whose rows begin at ``i0``
+    (the buffers may be made at the first call, once the shapes are known); ``step(i, t, obs)`` -> the next observation (None where the
+    form has no use for it): step ``t`` of the episode, which fills ``act`` / ``log_prob`` (unless the form did so earlier) and ``next_obs`` / ``rew`` / ``done`` of row ``i``.
+    All envs run in lock-step: ``done`` is identical for every env (AO_env.py:147), so no host sync is needed to end an episode."""
+    ep_returns = []
+    for e in range(episodes):
+        i0 = e * T
+        out, obs = reset(i0)
+        gatherer.start_episode()
+        out["obs"][i0].copy_(obs)
+        for t in range(T):
+            obs = step(i0 + t, t, obs)
+        if T > 1:
+            out["obs"][i0 + 1:i0 + T].copy_(out["next_obs"][i0:i0 + T - 1])   # obs of step t+1 = next_obs of step t
+        gatherer.add(out["rew"][i0:i0 + T].sum(0))
+        ep_returns.append(gatherer.finish_episode().clone())
+    return out, ep_returns
+
+
+def _out_of_step(who, what, queried, t, T):
+    return RuntimeError(f"{who} {'did not query' if queried is None else 'queried'} the {what} at step {t + 1} of {T}: the env's "
+                        "episode length differs from timesteps_per_episode")
+
+
 def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, generator=None, actor_impl: str = "auto", seed: int = 0,
             dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None, fused_policy: bool = False, action_mode: str = "sample",
             science: bool = False, predictor=None, controller=None):
     """Collect ``episodes`` lock-step episodes from ``env`` (a ``BatchedAOEnv``).
 
-    ``actor_impl``: "hip" = the fused policy-query kernel (``DeviceActor``), "torch" = the module's own forward +
-    ``sample_action``, "auto" = "hip" for CUDA modules with the ``make_actor`` structure.  The ``DeviceActor`` (and with it the
-    call counter of its random streams) persists across calls: pass one in as ``dev_actor``, or let this function cache it (in a
-    module-level weak dictionary keyed by the actor: the caller's module stays deep-copyable and picklable) — a training loop that calls ``rollout`` once per iteration (algorithm.py:156) then explores with fresh
-    dropout masks and noise in every iteration, like the reference's torch generator does.  Returns a dict of device tensors
-    shaped ``[T*E, B, ...]`` (obs, act, log_prob, rew, next_obs, done), ``ep_returns`` ``[E, B_global]`` (gathered over ranks
-    when ``gatherer`` is distributed), ``avg_ep_rew`` (the reference's logged scalar) and ``batch_lens`` (``algorithm.py:226,283``: a numpy
-    array of T*E zeros whose first E entries hold the length of each episode — always T here: ``done`` depends on the step counter only).
+    Returns a dict of device tensors shaped ``[T*E, B, ...]`` (obs, act, log_prob, rew, next_obs, done), ``ep_returns`` ``[E, B_global]``
+    (gathered over ranks when ``gatherer`` is distributed), ``avg_ep_rew`` (the reference's logged scalar) and ``batch_lens``
+    (``algorithm.py:226,283``: a numpy array of T*E zeros whose first E entries hold the length of each episode — always T here: ``done``
+    depends on the step counter only).  Every condition below is checked before anything runs: ValueError.
 
-    ``policy="shack"`` (``algorithm.py:252-253``, the 'SHACK' algorithm): the action of every step comes from ``env.SH_step()`` (the
-    Shack-Hartmann integrator on the device; needs an env built with ``SH_operation=True``), ``actor`` may be None and ``log_prob`` holds the
-    reference's constant 1.  ``policy="ideal"``: the ideal modal controller — every step's action is ``env.ideal_action()``, the best-fit
-    mirror command of the state the last observation saw, applied to the next screen (the one-frame lag every controller has): the ceiling
-    Shack-Hartmann and learnt policies are read against.  Same conditions and ``log_prob`` as ``"shack"``.  ``policy="pyramid"``: every
-    step's action is ``env.PYR_step()[0]``, the modulated pyramid sensor's integrator (an env built with ``pyramid=dict(...)`` and
-    ``SH_operation=True``, which makes the action the raw actuators); same ``log_prob``.  ``policy="predictive"``: every step's action is
-    ``predictor.action()`` of the ``predictor.PredictiveController`` passed as ``predictor`` (built for this env): a linear predictor of the
-    next best-fit command, learnt on the device by recursive least squares from the measurements the loop takes — what recovers the one-frame
-    lag ``"ideal"`` commits.  Same conditions and ``log_prob`` as ``"shack"``; the predictor is NOT reset at episode ends (the atmosphere is
-    not reset either); not with ``lookahead``.  ``policy="modal"``: every step's action is ``controller.action()`` of the
-    ``telemetry.ModalIntegrator`` passed as ``controller`` (built for this env): the integrator with one gain per (env, mode), which also
-    records the measurements it takes (``controller.retune()`` then sets the optimised modal gains); same conditions as ``"predictive"``,
-    and neither its command nor its telemetry is reset at episode ends.  ``policy="spgd"``: the sensorless baseline — every step's action
-    comes from the ``sensorless.SPGDController`` passed as ``controller`` (built for this env, ``SH_operation=True``), which sees only the scalar
-    metric of the last step; it is reset with the env at every episode start (all envs; its iteration counters go on) and ``log_prob`` is the
-    constant 1.  Not with ``lookahead``, ``science``, ``ou_noise`` or ``action_mode="mean"``: ValueError before anything runs.  With
-    ``fused_policy=True`` it goes through ``env.reset_with_spgd`` / ``env.step_with_spgd`` (the query rides in the step's last launch) and
-    returns the same dict, bit for bit, as the unfused loop from the same controller state.  ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every
-    action before the env sees it (and before it is stored, like the reference's in-place ``action +=``), or a ``DeviceOUNoise``
-    (``main.py:218-220``: mu 0, theta 0.3, sigma 0.05), which the HIP policy query advances and adds itself: float64 state, Philox normals keyed
-    by the global env id (a split batch reproduces the whole one), no extra launch.  Neither is reset here, as in the reference.
+    ``policy="actor"``: the action is the policy query on the last observation.  ``actor_impl``: "hip" = the fused policy-query kernel
+    (``DeviceActor``), "torch" = the module's own forward + ``sample_action``, "auto" = "hip" for CUDA modules with the ``make_actor``
+    structure.  The ``DeviceActor`` (and with it the call counter of its random streams) persists across calls: pass one in as ``dev_actor``,
+    or let this function cache it (in a module-level weak dictionary keyed by the actor: the caller's module stays deep-copyable and
+    picklable) — a training loop that calls ``rollout`` once per iteration (algorithm.py:156) then explores with fresh dropout masks and
+    noise in every iteration, like the reference's torch generator does.
+
+    The other policies take no query: the action is a controller's raw actuator vector, so they need an env built with
+    ``SH_operation=True``, ``actor`` may be None, ``log_prob`` holds the reference's constant 1, and they take neither a ``DeviceOUNoise``
+    nor ``action_mode="mean"``.
+
+    ``policy="shack"`` (``algorithm.py:252-253``, the 'SHACK' algorithm): ``env.SH_step()``, the Shack-Hartmann integrator on the device.
+
+    ``policy="ideal"``: the ideal modal controller — ``env.ideal_action()``, the best-fit mirror command of the state the last
+    observation saw, applied to the next screen (the one-frame lag every controller has): the ceiling Shack-Hartmann and learnt policies
+    are read against.
+
+    ``policy="pyramid"``: ``env.PYR_step()[0]``, the modulated pyramid sensor's integrator (an env built with ``pyramid=dict(...)``).
+
+    ``policy="predictive"``: ``predictor.action()`` of the ``predictor.PredictiveController`` passed as ``predictor`` (built for this env):
+    a linear predictor of the next best-fit command, learnt on the device by recursive least squares from the measurements the loop
+    takes — what recovers the one-frame lag ``"ideal"`` commits.  The predictor is NOT reset at episode ends (the atmosphere is not reset
+    either); not with ``lookahead`` or ``fused_policy``.
+
+    ``policy="modal"``: ``controller.action()`` of the ``telemetry.ModalIntegrator`` passed as ``controller`` (built for this env): the
+    integrator with one gain per (env, mode), which also records the measurements it takes (``controller.retune()`` then sets the
+    optimised modal gains).  Same conditions as ``"predictive"``; neither its command nor its telemetry is reset at episode ends.
+
+    ``policy="spgd"``: the sensorless baseline — the ``sensorless.SPGDController`` passed as ``controller`` (built for this env), which
+    sees only the scalar metric of the last step; it is reset with the env at every episode start (all envs; its iteration counters go
+    on).  Not with ``lookahead``, ``science``, ``ou_noise`` or ``action_mode="mean"``.  With ``fused_policy=True`` it goes through
+    ``env.reset_with_spgd`` / ``env.step_with_spgd`` (the query rides in the step's last launch) and returns the same dict, bit for bit, as
+    the unfused loop from the same controller state.
+
+    ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every action before the env sees
+    it (and before it is stored, like the reference's in-place ``action +=``), or a ``DeviceOUNoise`` (``main.py:218-220``: mu 0, theta
+    0.3, sigma 0.05), which the HIP policy query advances and adds itself: float64 state, Philox normals keyed by the global env id (a
+    split batch reproduces the whole one), no extra launch; it needs the HIP query.  Neither is reset here, as in the reference.
 
     ``action_mode="mean"`` (evaluation, ``eval_policy.py:31``): the action is the policy's mean with dropout still active, ``log_prob`` the
-    density of ``N(mean, cov_var I)`` there; with ``actor_impl="torch"`` the action is ``actor(obs)``.  A ``DeviceOUNoise`` needs the HIP
-    query, and neither a ``DeviceOUNoise`` nor ``action_mode="mean"`` goes with ``policy="shack"`` or ``"ideal"``: ValueError.
+    density of ``N(mean, cov_var I)`` there; with ``actor_impl="torch"`` the action is ``actor(obs)``.
 
     ``fused_policy=True``: the policy query rides with the env step (``env.reset_with_policy`` / ``env.step_with_policy``, one launch where
     the epilogue of step t, the query on its observation and the prologue of step t + 1 take three): needs ``policy="actor"`` resolved to
-    ``actor_impl="hip"``, and takes a ``DeviceOUNoise`` and ``action_mode`` but not the torch ``OrnsteinUhlenbeckNoise`` (that noise would have
-    to be added between the query and the prologue); ValueError otherwise.  Returns the same dict, bit for bit, as the unfused loop with the
-    same ``DeviceActor`` (seed and call counter) and, if any, an OU state equal to the unfused loop's.
+    ``actor_impl="hip"`` (or ``policy="spgd"``, above), and takes a ``DeviceOUNoise`` and ``action_mode`` but not the torch
+    ``OrnsteinUhlenbeckNoise`` (that noise would have to be added between the query and the prologue).  Returns the same dict, bit for
+    bit, as the unfused loop with the same ``DeviceActor`` (seed and call counter) and, if any, an OU state equal to the unfused loop's.
+
+    ``lookahead=True`` (dynamic atmosphere on the device stream): the next step's wind extrusion is launched on the library's own stream
+    beside this step's epilogue and the policy query — bit-identical results; the screens are off limits between two steps of an
+    episode, which this loop never touches.  Off by default: on ROCm 7.2 the two cross-stream event hand-offs it needs cost what the
+    overlap saves.
 
     ``science=True`` (an env built with ``science_window``): ``env.science_integrate()`` after every step, never cleared here — read the
     long exposure with ``env.science_exposure()`` afterwards.  The transitions are those of ``science=False`` bit for bit.  Not with
-    ``fused_policy`` or ``lookahead`` (the camera is refused while the next action or the next screens are already in place): ValueError."""
+    ``fused_policy`` or ``lookahead`` (the camera is refused while the next action or the next screens are already in place)."""
+    import inspect
+
     import numpy as np
     import torch
 
@@ -310,36 +402,35 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     B = env.num_envs
     if gatherer is None:
         gatherer = EpisodeReturnGatherer(B, env.device, False)
-    if policy not in ("actor", "shack", "ideal", "pyramid", "predictive", "modal", "spgd"):
+    if policy not in _POLICIES:
         raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive', 'modal' or 'spgd'")
     if action_mode not in ("sample", "mean"):
         raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
-    ideal, pyramid, predictive, modal, spgd = policy == "ideal", policy == "pyramid", policy == "predictive", policy == "modal", policy == "spgd"
-    shack = policy == "shack" or ideal or pyramid or predictive or modal or spgd   # (no policy query either way: the action is a controller's raw actuator vector)
-    if predictive != (predictor is not None):
-        raise ValueError("policy='predictive' takes its controller as predictor=PredictiveController(env, ...), and no other policy takes one")
-    if predictive and predictor.env is not env:
-        raise ValueError("policy='predictive': the predictor was built for another env")
-    if (modal or spgd) != (controller is not None):
-        raise ValueError("policy='modal' takes its controller as controller=ModalIntegrator(env, ...), policy='spgd' as "
-                         "controller=SPGDController(env, ...), and no other policy takes one")
-    if (modal or spgd) and controller.env is not env:
-        raise ValueError(f"policy={policy!r}: the controller was built for another env")
-    if spgd and (lookahead or science or ou_noise is not None or action_mode != "sample"):
-        raise ValueError("policy='spgd' goes with none of lookahead, science, ou_noise and action_mode='mean': the controller's commands are the "
-                         "experiment (a noise term or another mirror command between two of its queries would enter its metric differences)")
+    pol, ctrl = _POLICIES[policy], None
+    for keyword, message in _CONTROLLER_KEYWORDS.items():
+        passed = predictor if keyword == "predictor" else controller
+        if (pol.keyword == keyword) != (passed is not None):
+            raise ValueError(message)
+        if pol.keyword == keyword:
+            if passed.env is not env:
+                raise ValueError(f"policy={policy!r}: the {keyword} was built for another env")
+            ctrl = passed
     dev_ou = isinstance(ou_noise, DeviceOUNoise)
-    if shack and (dev_ou or action_mode != "sample"):
-        raise ValueError(f"policy={policy!r} takes neither a DeviceOUNoise nor action_mode='mean' (the "
-                         f"{'ideal modal controller' if ideal else 'pyramid integrator' if pyramid else 'predictive controller' if predictive else 'modal integrator' if modal else 'SPGD controller' if spgd else 'Shack-Hartmann integrator'} is not a policy query)")
-    if shack:
+    given = {"lookahead": lookahead, "fused_policy": fused_policy, "science": science, "ou_noise": ou_noise is not None, "dev_ou": dev_ou,
+             "mean": action_mode != "sample"}
+
+    def refuse(reason):
+        if any(given[option] for option in pol.refuses.get(reason, ())):
+            raise ValueError(_REFUSALS[reason].format(policy=policy, noun=pol.noun))
+
+    refuse("experiment")
+    refuse("query")
+    if pol.sh:
         if not getattr(env, "SH_operation", False):
             raise ValueError(f"policy={policy!r} needs an env created with SH_operation=True (AO_env.py:115-116, 254)")
-        if pyramid and getattr(env, "pyramid", None) is None:
+        if pol.pyramid and getattr(env, "pyramid", None) is None:
             raise ValueError("policy='pyramid' needs an env created with pyramid=dict(...)")
-        if (predictive or modal) and (lookahead or fused_policy):
-            raise ValueError(f"policy={policy!r} goes with neither lookahead nor fused_policy: its measurement is refused while the next screens or "
-                             "the next action are already in place")
+        refuse("measurement")
         actor_impl = "none"
     elif actor_impl == "auto":
         actor_impl = "hip" if actor_layers(actor) is not None and next(actor.parameters()).is_cuda else "torch"
@@ -351,7 +442,7 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         if dev_actor is None or dev_actor.seed != int(seed) or dev_actor.env_id_base != base or dev_actor.actor is not actor:
             dev_actor = DeviceActor(actor, seed=seed, env_id_base=base)
             _DEVICE_ACTORS[actor] = dev_actor
-    if dev_ou and not shack and dev_actor is None:
+    if dev_ou and not pol.sh and dev_actor is None:
         raise ValueError("a DeviceOUNoise is advanced by the HIP policy query (actor_impl='hip'); the torch query takes an OrnsteinUhlenbeckNoise")
     # the query's action-form keywords, passed only when they differ from the defaults
     pkw = {}
@@ -359,9 +450,8 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         pkw["ou_noise"] = ou_noise
     if action_mode != "sample":
         pkw["action_mode"] = action_mode
-    if fused_policy and not spgd:
-        if shack:
-            raise ValueError("fused_policy=True needs policy='actor' (neither the Shack-Hartmann integrator nor the ideal controller is a policy query)")
+    refuse("fused")
+    if fused_policy and not pol.sh:
         if dev_actor is None:
             raise ValueError("fused_policy=True needs the HIP policy query (actor_impl='hip': a make_actor / reference Actor module with CUDA weights)")
         if ou_noise is not None and not dev_ou:
@@ -373,80 +463,77 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         if fused_policy or lookahead:
             raise ValueError("science=True goes with neither fused_policy nor lookahead: between two such steps the mirror or the screens already "
                              "belong to the next step and the camera is refused")
-    import inspect
-
     step_takes_out = "out" in inspect.signature(env.step).parameters
-    # lookahead=True (dynamic atmosphere on the device stream): the next step's wind extrusion is launched on the library's own stream
-    # beside this step's epilogue and the policy query — bit-identical results; the screens are off limits between two steps of an
-    # episode, which this loop never touches.  Off by default: on ROCm 7.2 the two cross-stream event hand-offs it needs cost what the
-    # overlap saves.
     looking_ahead = bool(env.lookahead(True)) if (lookahead and callable(getattr(env, "lookahead", None))) else False
     n = T * episodes
-    out = None
-    ep_returns = []
-    if fused_policy and spgd:
-        with torch.no_grad():
-            out = _rollout_fused_spgd(env, controller, T, episodes, gatherer, ep_returns)
-    elif fused_policy:
-        with torch.no_grad():
-            out = _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns, pkw)
+    out = spare = None
+
+    def buffers(S, A, obs_dtype, dev):
+        nonlocal out, spare
+        out, spare = _transition_buffers(n, B, S, A, obs_dtype, dev)
+        if pol.sh:
+            out["log_prob"].fill_(1.0)   # the reference's constant log-probability 1
+
+    if fused_policy:
+        # the env's reset writes row i0's action, step i the action of row i + 1 (none on the last step: the spare row stands in)
+        buffers(int(env.obs_dim) ** 2, int(env.num_modes), torch.float16, env.device)
+        act, logp, nobs, rew, done = (out[k] for k in ("act", "log_prob", "next_obs", "rew", "done"))
+        end = T - 1
+        if pol.fused == "spgd":
+            def reset(i0):
+                return out, env.reset_with_spgd(ctrl, action_out=act[i0])[0][0]
+
+            def step(i, t, obs):
+                nxt = env.step_with_spgd(ctrl, out=(nobs[i], rew[i], done[i]), action_out=spare if t == end else act[i + 1])[1]
+                if (nxt is None) != (t == end):
+                    raise _out_of_step("step_with_spgd", "controller", nxt, t, T)
+        else:
+            def reset(i0):
+                return out, env.reset_with_policy(dev_actor, cov_var, policy_out=(act[i0], logp[i0], spare), **pkw)[0][0]
+
+            def step(i, t, obs):
+                nxt = env.step_with_policy(dev_actor, cov_var, out=(nobs[i], rew[i], done[i]),
+                                           policy_out=None if t == end else (act[i + 1], logp[i + 1], spare), **pkw)[1]
+                if (nxt is None) != (t == end):
+                    raise _out_of_step("step_with_policy", "policy", nxt, t, T)
     else:
-        with torch.no_grad():
-            i = 0
-            for _ in range(episodes):
-                obs, _ = env.reset()
-                gatherer.start_episode()
-                i0 = i
-                for _t in range(T):
-                    if out is None:   # buffers are laid out once the shapes are known: [T*E, B, ...], written in place
-                        S = obs.shape[1]
-                        A = int(env.num_modes) if shack else int(list(actor.parameters())[-1].shape[0])   # width of the output layer's bias
-                        dev = obs.device
-                        out = {"obs": torch.empty((n, B, S), dtype=obs.dtype, device=dev), "act": torch.empty((n, B, A), dtype=torch.float32, device=dev),
-                               "log_prob": torch.empty((n, B), dtype=torch.float32, device=dev), "rew": torch.empty((n, B), dtype=torch.float32, device=dev),
-                               "next_obs": torch.empty((n, B, S), dtype=obs.dtype, device=dev), "done": torch.empty((n, B), dtype=torch.bool, device=dev)}
-                        mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
-                    if spgd:   # (the controller is reset with the env; every later step queries it on the last step's metric)
-                        action = controller.reset(out=out["act"][i]) if _t == 0 else controller.action(out=out["act"][i])
-                        out["log_prob"][i].fill_(1.0)
-                    elif shack:
-                        # (actuators [B, A] float64, the reference's constant log-probability 1; 'ideal': from the state the last observation saw)
-                        sh_act = (env.ideal_action() if ideal else env.PYR_step()[0] if pyramid else predictor.action() if predictive
-                                  else controller.action() if modal else env.SH_step()[0])
-                        out["act"][i].copy_(sh_act)
-                        out["log_prob"][i].fill_(1.0)
-                        action = out["act"][i]
-                    elif dev_actor is not None:
-                        action, _, _ = dev_actor(obs, cov_var, out=(out["act"][i], out["log_prob"][i], mean_buf), **pkw)
-                    elif action_mode == "mean":   # eval_policy.py:31: the mean, dropout still active; log_prob = the density at the mean
-                        out["act"][i].copy_(actor(obs))
-                        out["log_prob"][i].fill_(-0.5 * A * math.log(2 * math.pi * cov_var))
-                        action = out["act"][i]
-                    else:
-                        action, log_prob = sample_action(actor(obs), cov_var, generator)
-                        out["act"][i].copy_(action)
-                        out["log_prob"][i].copy_(log_prob)
-                    if ou_noise is not None and not dev_ou:
-                        out["act"][i].add_(ou_noise.sample())           # algorithm.py:258-259
-                        action = out["act"][i]
-                    if step_takes_out:   # the env writes the transition straight into this step's slices
-                        next_obs = env.step(action, out=(out["next_obs"][i], out["rew"][i], out["done"][i]))[0]
-                    else:
-                        next_obs, rew, done, _, _ = env.step(action)
-                        out["rew"][i].copy_(rew)
-                        out["next_obs"][i].copy_(next_obs)
-                        out["done"][i].copy_(done)
-                    if science:
-                        env.science_integrate()
-                    if _t == 0:
-                        out["obs"][i].copy_(obs)
-                    obs = next_obs
-                    i += 1
-                    # lock-step: done is identical for every env (AO_env.py:147), so no host sync is needed to break
-                if T > 1:
-                    out["obs"][i0 + 1:i0 + T].copy_(out["next_obs"][i0:i0 + T - 1])   # obs of step t+1 = next_obs of step t
-                gatherer.add(out["rew"][i0:i0 + T].sum(0))
-                ep_returns.append(gatherer.finish_episode().clone())
+        def reset(i0):
+            obs = env.reset()[0]
+            if out is None:   # the buffers are laid out once the shapes are known
+                A = int(env.num_modes) if pol.sh else int(list(actor.parameters())[-1].shape[0])   # width of the output layer's bias
+                buffers(obs.shape[1], A, obs.dtype, obs.device)
+            return out, obs
+
+        def step(i, t, obs):
+            action = row = out["act"][i]   # (action: what the env is handed)
+            log_prob = out["log_prob"][i]
+            if pol.sh:
+                pol.act(env, ctrl, row, t == 0)
+            elif dev_actor is not None:
+                dev_actor(obs, cov_var, out=(row, log_prob, spare), **pkw)
+            elif action_mode == "mean":   # eval_policy.py:31: the mean, dropout still active; log_prob = the density at the mean
+                row.copy_(actor(obs))
+                log_prob.fill_(-0.5 * row.shape[-1] * math.log(2 * math.pi * cov_var))
+            else:
+                action, lp = sample_action(actor(obs), cov_var, generator)
+                row.copy_(action)
+                log_prob.copy_(lp)
+            if ou_noise is not None and not dev_ou:
+                row.add_(ou_noise.sample())           # algorithm.py:258-259
+                action = row
+            transition = (out["next_obs"][i], out["rew"][i], out["done"][i])
+            if step_takes_out:   # the env writes the transition straight into this step's slices
+                next_obs = env.step(action, out=transition)[0]
+            else:
+                next_obs, rew, done, _, _ = env.step(action)
+                for dst, src in zip(transition, (next_obs, rew, done)):
+                    dst.copy_(src)
+            if science:
+                env.science_integrate()
+            return next_obs
+
+    with torch.no_grad():
+        out, ep_returns = _run_episodes(T, episodes, gatherer, reset, step)
     if looking_ahead:
         env.lookahead(False)
     out["ep_returns"] = torch.stack(ep_returns)
@@ -454,67 +541,6 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     lens = np.zeros(n)
     lens[:episodes] = T
     out["batch_lens"] = lens
-    return out
-
-
-def _rollout_fused(env, dev_actor, T, episodes, cov_var, gatherer, ep_returns, pkw):
-    """rollout(fused_policy=True)'s loop: reset_with_policy writes row i0's action, step i the action of row i + 1 (none on the last step).
-    ``pkw``: the query's action-form keywords (ou_noise, action_mode) that differ from the defaults."""
-    import torch
-
-    B, S, A, dev = env.num_envs, int(env.obs_dim) ** 2, int(env.num_modes), env.device
-    n = T * episodes
-    out = {"obs": torch.empty((n, B, S), dtype=torch.float16, device=dev), "act": torch.empty((n, B, A), dtype=torch.float32, device=dev),
-           "log_prob": torch.empty((n, B), dtype=torch.float32, device=dev), "rew": torch.empty((n, B), dtype=torch.float32, device=dev),
-           "next_obs": torch.empty((n, B, S), dtype=torch.float16, device=dev), "done": torch.empty((n, B), dtype=torch.bool, device=dev)}
-    mean_buf = torch.empty((B, A), dtype=torch.float32, device=dev)
-    for e in range(episodes):
-        i0 = e * T
-        (obs, _), _ = env.reset_with_policy(dev_actor, cov_var, policy_out=(out["act"][i0], out["log_prob"][i0], mean_buf), **pkw)
-        gatherer.start_episode()
-        out["obs"][i0].copy_(obs)
-        for t in range(T):
-            i = i0 + t
-            last = t == T - 1
-            pol_out = None if last else (out["act"][i + 1], out["log_prob"][i + 1], mean_buf)
-            _, pol = env.step_with_policy(dev_actor, cov_var, out=(out["next_obs"][i], out["rew"][i], out["done"][i]), policy_out=pol_out, **pkw)
-            if (pol is None) != last:
-                raise RuntimeError(f"step_with_policy {'did not query' if pol is None else 'queried'} the policy at step {t + 1} of {T}: the env's "
-                                   "episode length differs from timesteps_per_episode")
-        if T > 1:
-            out["obs"][i0 + 1:i0 + T].copy_(out["next_obs"][i0:i0 + T - 1])   # obs of step t+1 = next_obs of step t
-        gatherer.add(out["rew"][i0:i0 + T].sum(0))
-        ep_returns.append(gatherer.finish_episode().clone())
-    return out
-
-
-def _rollout_fused_spgd(env, controller, T, episodes, gatherer, ep_returns):
-    """rollout(policy='spgd', fused_policy=True)'s loop: reset_with_spgd writes row i0's command, step i the command of row i + 1 (none on the
-    last step)."""
-    import torch
-
-    B, S, A, dev = env.num_envs, int(env.obs_dim) ** 2, int(env.num_modes), env.device
-    n = T * episodes
-    out = {"obs": torch.empty((n, B, S), dtype=torch.float16, device=dev), "act": torch.empty((n, B, A), dtype=torch.float32, device=dev),
-           "log_prob": torch.ones((n, B), dtype=torch.float32, device=dev), "rew": torch.empty((n, B), dtype=torch.float32, device=dev),
-           "next_obs": torch.empty((n, B, S), dtype=torch.float16, device=dev), "done": torch.empty((n, B), dtype=torch.bool, device=dev)}
-    spare = torch.empty((B, A), dtype=torch.float32, device=dev)   # (the last step of an episode writes no command)
-    for e in range(episodes):
-        i0 = e * T
-        (obs, _), _ = env.reset_with_spgd(controller, action_out=out["act"][i0])
-        gatherer.start_episode()
-        out["obs"][i0].copy_(obs)
-        for t in range(T):
-            i = i0 + t
-            last = t == T - 1
-            _, nxt = env.step_with_spgd(controller, out=(out["next_obs"][i], out["rew"][i], out["done"][i]), action_out=spare if last else out["act"][i + 1])
-            if (nxt is None) != last:
-                raise RuntimeError(f"step_with_spgd {'did not query' if nxt is None else 'queried'} the controller at step {t + 1} of {T}: the env's "
-                                   "episode length differs from timesteps_per_episode")
-        if T > 1:
-            out["obs"][i0 + 1:i0 + T].copy_(out["next_obs"][i0:i0 + T - 1])   # obs of step t+1 = next_obs of step t
-        gatherer.add(out["rew"][i0:i0 + T].sum(0))
-        ep_returns.append(gatherer.finish_episode().clone())
     return out
 
 

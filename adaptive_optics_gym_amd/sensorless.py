@@ -13,6 +13,7 @@ import ctypes as C
 import math
 
 from . import _lib
+from .device_handle import DeviceHandle, ptr
 
 METRICS = ("power", "strehl", "reward")
 
@@ -31,7 +32,7 @@ def _per_env(name, value, num_envs):
     return np.ascontiguousarray(v)
 
 
-class SPGDController:
+class SPGDController(DeviceHandle):
     """SPGD for an env built with ``SH_operation=True`` (``BatchedAOEnv`` or ``LayeredAOEnv``), whose action is the raw actuator vector.
 
     ``gain`` and ``amplitude`` are scalars or per-env values (a batch can sweep them); ``metric`` names the step output it climbs
@@ -43,7 +44,10 @@ class SPGDController:
     ``flat_mirror_start_per_episode=False`` — keeps their iteration counters and returns the first command.  ``action()`` is one query on
     the metric of the env's last step, ``update(metric)`` the same on a caller's own float32 ``[B]`` tensor; both return the next command,
     ``[B, A]`` float32.  ``env.reset_with_spgd(ctrl)`` / ``env.step_with_spgd(ctrl)`` run the same query inside the step's last launch.
-    ``centre()`` is ``u``; ``get_state`` / ``set_state`` resume bit-identically."""
+    ``centre()`` is ``u``; ``get_state`` / ``set_state`` resume bit-identically (the state blob holds per env u [A] and J_plus float64, then
+    k and h uint32)."""
+
+    prefix, noun = "aog_spgd", "controller"
 
     def __init__(self, env, gain=1.0, amplitude=0.05, metric="power", clip=0.0, seed=None):
         if metric not in METRICS:
@@ -62,40 +66,26 @@ class SPGDController:
         self.seed = int(env._base_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
         self.num_envs, self.act_dim = B, A
         self.env_id_base = int(getattr(env, "global_env_offset", 0))
-        self._torch = env._torch
-        self.device = env.device
-        self.lib = _lib.load()
-        cfg = _lib.AogSpgdConfig(_lib.ABI_VERSION, B, A, self.env_id_base, self.seed, _lib.AOG_SPGD_METRIC[metric], 0, clip)
-        self._handle = C.c_void_p()
-        _lib.check(self.lib.aog_spgd_create(C.byref(cfg), self.device.index or 0, C.byref(self._handle)))
+        self._bind(env._torch, env.device, B)
+        self._create()
         self.set_params(gain, amplitude)
 
-    def _stream(self):
-        return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _mask(self, mask, who):
-        if mask is None:
-            return None
-        torch = self._torch
-        m = torch.as_tensor(mask, device=self.device)
-        if m.dtype not in (torch.bool, torch.uint8) or tuple(m.shape) != (self.num_envs,):
-            raise ValueError(f"{who}: mask must be a bool vector of {self.num_envs} entries")
-        return m.to(torch.uint8).contiguous()
+    def _config(self):
+        return _lib.AogSpgdConfig(_lib.ABI_VERSION, self.num_envs, self.act_dim, self.env_id_base, self.seed, _lib.AOG_SPGD_METRIC[self.metric], 0, self.clip)
 
     def _out(self, out, masked, who):
         torch = self._torch
         if out is None:
             return (torch.zeros if masked else torch.empty)((self.num_envs, self.act_dim), dtype=torch.float32, device=self.device)
-        if (out.dtype != torch.float32 or tuple(out.shape) != (self.num_envs, self.act_dim) or not out.is_contiguous() or out.device != self.device):
-            raise ValueError(f"{who}: out must be a contiguous float32 [{self.num_envs}, {self.act_dim}] tensor on {self.device}")
-        return out
+        return self._tensor(out, (self.num_envs, self.act_dim), torch.float32,
+                            f"{who}: out must be a contiguous float32 [{self.num_envs}, {self.act_dim}] tensor on {self.device}")
 
     def set_params(self, gain=None, amplitude=None):
         """New per-env ``gain`` / ``amplitude`` (scalars or ``[B]`` values; None keeps the current ones)."""
         gain = self.gain if gain is None else _per_env("gain", gain, self.num_envs)
         amplitude = self.amplitude if amplitude is None else _per_env("amplitude", amplitude, self.num_envs)
         self._torch.cuda.current_stream(self.device).synchronize()   # (the copy is blocking but not ordered behind this stream's queries)
-        _lib.check(self.lib.aog_spgd_set_params(self._handle, gain.ctypes.data_as(C.c_void_p), amplitude.ctypes.data_as(C.c_void_p)))
+        self._call("set_params", gain.ctypes.data_as(C.c_void_p), amplitude.ctypes.data_as(C.c_void_p))
         self.gain, self.amplitude = gain, amplitude
 
     def reset(self, mask=None, out=None):
@@ -104,22 +94,15 @@ class SPGDController:
         m = self._mask(mask, "reset")
         out = self._out(out, m is not None, "reset")
         start = None if self.env.flat_mirror_start_per_episode else self.env.get_actuators()
-        p = C.c_void_p
-        _lib.check(self.lib.aog_spgd_reset(self._handle, p(m.data_ptr() if m is not None else None), p(start.data_ptr() if start is not None else None),
-                                           p(out.data_ptr()), self._stream()))
+        self._call("reset", ptr(m), ptr(start), ptr(out), self._stream())
         return out
 
     def update(self, metric, mask=None, out=None):
         """One query on ``metric`` (float32 ``[B]`` device tensor): the next command."""
-        torch = self._torch
-        if (not isinstance(metric, torch.Tensor) or metric.dtype != torch.float32 or tuple(metric.shape) != (self.num_envs,)
-                or not metric.is_contiguous() or metric.device != self.device):
-            raise ValueError(f"update: metric must be a contiguous float32 [{self.num_envs}] tensor on {self.device}")
+        self._tensor(metric, (self.num_envs,), self._torch.float32, f"update: metric must be a contiguous float32 [{self.num_envs}] tensor on {self.device}")
         m = self._mask(mask, "update")
         out = self._out(out, m is not None, "update")
-        p = C.c_void_p
-        _lib.check(self.lib.aog_spgd_update(self._handle, p(metric.data_ptr()), p(m.data_ptr() if m is not None else None), p(out.data_ptr()),
-                                            self._stream()))
+        self._call("update", ptr(metric), ptr(m), ptr(out), self._stream())
         return out
 
     def action(self, out=None):
@@ -133,23 +116,6 @@ class SPGDController:
         """The tensor of a step tuple this controller descends on."""
         return step_ret[1] if self.metric == "reward" else step_ret[4][self.metric]
 
-    def get_state(self):
-        """The state blob (uint8 device tensor): per env u [A] and J_plus float64, then k and h uint32."""
-        torch = self._torch
-        blob = torch.empty((int(self.lib.aog_spgd_state_bytes(self._handle)),), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.aog_spgd_get_state(self._handle, C.c_void_p(blob.data_ptr()), self._stream()))
-        return blob
-
-    def set_state(self, blob):
-        torch = self._torch
-        n = int(self.lib.aog_spgd_state_bytes(self._handle))
-        b = torch.as_tensor(blob)
-        if b.dtype != torch.uint8 or tuple(b.shape) != (n,):
-            raise ValueError(f"set_state: the blob of this controller is a uint8 vector of {n} bytes")
-        b = b.to(self.device).contiguous()
-        _lib.check(self.lib.aog_spgd_set_state(self._handle, C.c_void_p(b.data_ptr()), self._stream()))
-        torch.cuda.current_stream(self.device).synchronize()   # (b may be a temporary)
-
     def unpack(self, blob=None):
         """A blob as a dict of tensors: u [B, A] float64, J_plus [B] float64, k [B] and h [B] int64 (copies)."""
         torch = self._torch
@@ -162,14 +128,3 @@ class SPGDController:
     def centre(self):
         """The centre command u, [B, A] float64."""
         return self.unpack()["u"]
-
-    def close(self):
-        h, self._handle = self._handle, None
-        if h:
-            self.lib.aog_spgd_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -13,6 +13,7 @@ import ctypes as C
 import math
 
 from . import _lib
+from .device_handle import DeviceHandle, check_measurement, ptr
 
 MAX_MODES, MIN_LENGTH, MAX_LENGTH, MIN_SEGMENT, MAX_GRID, MAX_DELAY = 128, 64, 1024, 32, 64, 4
 
@@ -60,7 +61,7 @@ def check_grid(grid, delay):
     return g
 
 
-class ModalTelemetry:
+class ModalTelemetry(DeviceHandle):
     """``num_envs`` rings of ``length`` measurements of ``act_dim`` modes, float64 on ``device`` (the library handle ``aog_telemetry``; it is
     made on first use).  ``push(y, mask=None)`` stores one row per selected env (a row with a non-finite value is skipped and counted);
     ``psd(segment=None)`` -> (freq_bins [S/2+1] in cycles per frame, psd [B, A, S/2+1], segments [B] int32): Welch's estimate, periodic Hann
@@ -68,12 +69,14 @@ class ModalTelemetry:
     ``optimise_gains(delay=1, grid=None, segment=None, with_costs=False)`` -> (gain [B, A], cost [B, A][, cost_all [B, A, G]]): per mode the
     first candidate of ``grid`` (default ``default_grid(delay)``) that minimises J(g) = sum_k |R_k(g)|^2 Phi[k].  ``segment`` defaults to
     ``length // 4`` (32 at length 64).  Rows of envs a ``mask`` leaves out are NaN (0 segments) in fresh outputs.  ``state_dict`` / ``load_state_dict``
-    resume bit-identically; a batch split over several instances reproduces the whole one bit for bit."""
+    resume bit-identically; a batch split over several instances reproduces the whole one bit for bit.  The state blob of ``get_state`` /
+    ``set_state`` holds per env hist [T, A] float64, count and skipped int64."""
+
+    prefix, noun, lazy = "aog_telemetry", "telemetry", True
 
     def __init__(self, num_envs, act_dim, length=512, device=None, global_env_offset=0):
         import torch
 
-        self._torch = torch
         self.num_envs, self.act_dim, self.length = int(num_envs), int(act_dim), int(length)
         if self.num_envs < 1:
             raise ValueError(f"num_envs must be >= 1 (got {num_envs})")
@@ -82,34 +85,11 @@ class ModalTelemetry:
         if not _is_pow2(self.length) or not MIN_LENGTH <= self.length <= MAX_LENGTH:
             raise ValueError(f"length must be a power of two in [{MIN_LENGTH}, {MAX_LENGTH}] (got {length})")
         self.global_env_offset = int(global_env_offset)
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self._bind(torch, device, self.num_envs)
         self.default_segment = max(MIN_SEGMENT, self.length // 4)
-        self.lib = None
-        self._handle = None
 
-    # -- plumbing
-    def _h(self):
-        if self._handle is None:
-            self.lib = _lib.load()
-            cfg = _lib.AogTelemetryConfig(self.num_envs, self.act_dim, self.length, self.global_env_offset)
-            h = C.c_void_p()
-            _lib.check(self.lib.aog_telemetry_create(C.byref(cfg), self.device.index or 0, C.byref(h)))
-            self._handle = h
-        return self._handle
-
-    def _stream(self):
-        return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _mask(self, mask, who):
-        if mask is None:
-            return None
-        torch = self._torch
-        m = torch.as_tensor(mask, device=self.device)
-        if m.dtype not in (torch.bool, torch.uint8) or tuple(m.shape) != (self.num_envs,):
-            raise ValueError(f"{who}: mask must be a bool vector of {self.num_envs} entries")
-        return m.to(torch.uint8).contiguous()
+    def _config(self):
+        return _lib.AogTelemetryConfig(self.num_envs, self.act_dim, self.length, self.global_env_offset)
 
     def _out(self, shape, m, dtype=None):
         torch = self._torch
@@ -118,22 +98,11 @@ class ModalTelemetry:
             return torch.empty(shape, dtype=dtype, device=self.device)
         return torch.full(shape, float("nan") if dtype == torch.float64 else 0, dtype=dtype, device=self.device)
 
-    @staticmethod
-    def _p(t):
-        return C.c_void_p(t.data_ptr() if t is not None else None)
-
-    def _call(self, name, *args):
-        h = self._h()
-        _lib.check(getattr(self.lib, name)(h, *args))
-
     # -- the calls
     def push(self, y, mask=None):
-        torch = self._torch
-        if (not isinstance(y, torch.Tensor) or y.dtype != torch.float64 or not y.is_contiguous() or tuple(y.shape) != (self.num_envs, self.act_dim)
-                or y.device != self.device):
-            raise ValueError(f"push: y must be a contiguous float64 [{self.num_envs}, {self.act_dim}] tensor on {self.device}")
-        m = self._mask(mask, "push")
-        self._call("aog_telemetry_push", self._p(y), self._p(m), self._stream())
+        self._tensor(y, (self.num_envs, self.act_dim), self._torch.float64,
+                     f"push: y must be a contiguous float64 [{self.num_envs}, {self.act_dim}] tensor on {self.device}")
+        self._call("push", ptr(y), ptr(self._mask(mask, "push")), self._stream())
 
     def psd(self, segment=None, mask=None):
         torch = self._torch
@@ -141,7 +110,7 @@ class ModalTelemetry:
         m = self._mask(mask, "psd")
         psd = self._out((self.num_envs, self.act_dim, S // 2 + 1), m)
         seg = self._out((self.num_envs,), m, torch.int32)
-        self._call("aog_telemetry_psd", S, self._p(psd), self._p(seg), self._p(m), self._stream())
+        self._call("psd", S, ptr(psd), ptr(seg), ptr(m), self._stream())
         freq = torch.arange(S // 2 + 1, dtype=torch.float64, device=self.device) / S
         return freq, psd, seg
 
@@ -152,32 +121,17 @@ class ModalTelemetry:
         B, A = self.num_envs, self.act_dim
         gain, cost = self._out((B, A), m), self._out((B, A), m)
         cost_all = self._out((B, A, g.size), m) if with_costs else None
-        self._call("aog_telemetry_gains", S, int(delay), g.ctypes.data_as(C.POINTER(C.c_double)), int(g.size), self._p(gain), self._p(cost),
-                   self._p(cost_all), self._p(m), self._stream())
+        self._call("gains", S, int(delay), g.ctypes.data_as(C.POINTER(C.c_double)), int(g.size), ptr(gain), ptr(cost), ptr(cost_all), ptr(m),
+                   self._stream())
         return (gain, cost, cost_all) if with_costs else (gain, cost)
 
     def reset(self, mask=None):
-        m = self._mask(mask, "reset")
-        self._call("aog_telemetry_reset", self._p(m), self._stream())
+        self._call("reset", ptr(self._mask(mask, "reset")), self._stream())
 
     def state_bytes(self):
         return 8 * self.num_envs * (self.length * self.act_dim + 2)
 
-    def get_state(self):
-        """The state blob (uint8 device tensor): per env hist [T, A] float64, count and skipped int64."""
-        blob = self._torch.empty((self.state_bytes(),), dtype=self._torch.uint8, device=self.device)
-        self._call("aog_telemetry_get_state", self._p(blob), self._stream())
-        return blob
-
-    def set_state(self, blob):
-        torch = self._torch
-        n = self.state_bytes()
-        b = torch.as_tensor(blob)
-        if b.dtype != torch.uint8 or tuple(b.shape) != (n,):
-            raise ValueError(f"set_state: the blob of this telemetry is a uint8 vector of {n} bytes")
-        b = b.to(self.device).contiguous()
-        self._call("aog_telemetry_set_state", self._p(b), self._stream())
-        torch.cuda.current_stream(self.device).synchronize()   # (b may be a temporary)
+    _state_bytes = state_bytes   # (no handle needed)
 
     def unpack(self, blob=None):
         """A blob as a dict of tensors: hist [B, T, A] float64, count [B], skipped [B] int64 (copies)."""
@@ -197,17 +151,6 @@ class ModalTelemetry:
                 raise ValueError(f"load_state_dict: the state was taken with {k} = {state[k]}, this telemetry has {getattr(self, k)}")
         self.set_state(state["blob"])
 
-    def close(self):
-        h, self._handle = self._handle, None
-        if h:
-            self.lib.aog_telemetry_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class ModalIntegrator:
     """The modal integrator of an env (``BatchedAOEnv`` or ``LayeredAOEnv``) with one gain per (env, mode): ``gains`` [B, A] float64 on the
@@ -223,10 +166,7 @@ class ModalIntegrator:
     ``rollout``'s loop."""
 
     def __init__(self, env, measurement="truth", delay=1, gain=0.4, leak=1.0, telemetry=None):
-        if measurement not in ("truth", "pyramid"):
-            raise ValueError(f"measurement must be 'truth' or 'pyramid' (got {measurement!r})")
-        if measurement == "pyramid" and getattr(env, "pyramid", None) is None:
-            raise ValueError("measurement='pyramid' needs an env created with pyramid=dict(...)")
+        check_measurement(env, measurement)
         g_max = gain_limit(delay)
         gain, leak = float(gain), float(leak)
         if not 0.0 < gain < g_max:
