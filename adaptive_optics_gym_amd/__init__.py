@@ -4,14 +4,16 @@
     from adaptive_optics_gym_amd import LayeredAOEnv      # the same over several frozen-flow wind layers per env
     from adaptive_optics_gym_amd.envs import AOEnv        # the reference's single-env gym API
     from adaptive_optics_gym_amd import ModalTelemetry, ModalIntegrator   # loop telemetry (PSDs) and the optimised modal integrator
+    from adaptive_optics_gym_amd import LinkTelemetry     # the optical link's read-out: fades, power histogram, bit-error rate
     import gym_AO                                         # registers 'AO-v0' like the reference (needs gymnasium)
 """
 from .batched_env import BatchedAOEnv  # noqa: F401
 from .layered import LayeredAOEnv  # noqa: F401
+from .link import LinkTelemetry  # noqa: F401
 from .params import OpticalParams  # noqa: F401
 from .telemetry import ModalIntegrator, ModalTelemetry  # noqa: F401
 
-__all__ = ["BatchedAOEnv", "LayeredAOEnv", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "register"]
+__all__ = ["BatchedAOEnv", "LayeredAOEnv", "LinkTelemetry", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "register"]
 
 
 def register():

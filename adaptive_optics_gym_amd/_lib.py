@@ -94,6 +94,13 @@ class AogSpgdConfig(C.Structure):  # mirrors aog_spgd_config (additive in ABI 22
 AOG_SPGD_METRIC = {"power": 0, "strehl": 1, "reward": 2}
 
 
+class AogLinkConfig(C.Structure):  # mirrors aog_link_config (additive in ABI 22; no aog_struct_size index)
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "num_envs", "length", "env_id_base", "reserved")]
+
+
+AOG_LINK_REF = {"absolute": 0, "mean": 1}
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -195,6 +202,15 @@ SYMBOLS = {
     "aog_spgd_state_bytes": (C.c_int64, [C.c_void_p]),
     "aog_spgd_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_spgd_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_link_create": (C.c_int, [C.POINTER(AogLinkConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "aog_link_destroy": (None, [C.c_void_p]),
+    "aog_link_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_link_push": (C.c_int, [C.c_void_p] * 4),
+    "aog_link_statistics": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int,
+                                      C.POINTER(C.c_double), C.c_int] + [C.c_void_p] * 13),
+    "aog_link_state_bytes": (C.c_int64, [C.c_void_p]),
+    "aog_link_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_link_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_reset_spgd": (C.c_int, [C.c_void_p] * 6),
     "aog_step_spgd": (C.c_int, [C.c_void_p] * 10 + [C.POINTER(C.c_int), C.c_void_p]),
     "aog_selftest_poisson":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),

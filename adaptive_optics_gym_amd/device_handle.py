@@ -1,4 +1,4 @@
-"""What the wrappers of the library's stand-alone handles share (``aog_predictor``, ``aog_telemetry``, ``aog_spgd``: per-env records on one
+"""What the wrappers of the library's stand-alone handles share (``aog_predictor``, ``aog_telemetry``, ``aog_spgd``, ``aog_link``: per-env records on one
 device, independent of any ``aog_env``): the handle's life, the stream, the argument checks and the checkpoint calls."""
 from __future__ import annotations
 

@@ -327,7 +327,7 @@ def _out_of_step(who, what, queried, t, T):
 
 def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, generator=None, actor_impl: str = "auto", seed: int = 0,
             dev_actor=None, lookahead: bool = False, policy: str = "actor", ou_noise=None, fused_policy: bool = False, action_mode: str = "sample",
-            science: bool = False, predictor=None, controller=None):
+            science: bool = False, predictor=None, controller=None, link=None):
     """Collect ``episodes`` lock-step episodes from ``env`` (a ``BatchedAOEnv``).
 
     Returns a dict of device tensors shaped ``[T*E, B, ...]`` (obs, act, log_prob, rew, next_obs, done), ``ep_returns`` ``[E, B_global]``
@@ -390,7 +390,11 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
 
     ``science=True`` (an env built with ``science_window``): ``env.science_integrate()`` after every step, never cleared here — read the
     long exposure with ``env.science_exposure()`` afterwards.  The transitions are those of ``science=False`` bit for bit.  Not with
-    ``fused_policy`` or ``lookahead`` (the camera is refused while the next action or the next screens are already in place)."""
+    ``fused_policy`` or ``lookahead`` (the camera is refused while the next action or the next screens are already in place).
+
+    ``link`` (a ``link.LinkTelemetry`` built for the env's ``num_envs`` and device): ``link.push(info["power"])`` after every step of every
+    policy, the fused and look-ahead forms included; never reset here — read ``link.statistics()`` afterwards.  The transitions are those
+    of ``link=None`` bit for bit."""
     import inspect
 
     import numpy as np
@@ -463,6 +467,10 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         if fused_policy or lookahead:
             raise ValueError("science=True goes with neither fused_policy nor lookahead: between two such steps the mirror or the screens already "
                              "belong to the next step and the camera is refused")
+    if link is not None:
+        from .link import check_link
+
+        check_link(link, env)
     step_takes_out = "out" in inspect.signature(env.step).parameters
     looking_ahead = bool(env.lookahead(True)) if (lookahead and callable(getattr(env, "lookahead", None))) else False
     n = T * episodes
@@ -484,18 +492,22 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                 return out, env.reset_with_spgd(ctrl, action_out=act[i0])[0][0]
 
             def step(i, t, obs):
-                nxt = env.step_with_spgd(ctrl, out=(nobs[i], rew[i], done[i]), action_out=spare if t == end else act[i + 1])[1]
+                ret, nxt = env.step_with_spgd(ctrl, out=(nobs[i], rew[i], done[i]), action_out=spare if t == end else act[i + 1])
                 if (nxt is None) != (t == end):
                     raise _out_of_step("step_with_spgd", "controller", nxt, t, T)
+                if link is not None:
+                    link.push(ret[4]["power"])
         else:
             def reset(i0):
                 return out, env.reset_with_policy(dev_actor, cov_var, policy_out=(act[i0], logp[i0], spare), **pkw)[0][0]
 
             def step(i, t, obs):
-                nxt = env.step_with_policy(dev_actor, cov_var, out=(nobs[i], rew[i], done[i]),
-                                           policy_out=None if t == end else (act[i + 1], logp[i + 1], spare), **pkw)[1]
+                ret, nxt = env.step_with_policy(dev_actor, cov_var, out=(nobs[i], rew[i], done[i]),
+                                                policy_out=None if t == end else (act[i + 1], logp[i + 1], spare), **pkw)
                 if (nxt is None) != (t == end):
                     raise _out_of_step("step_with_policy", "policy", nxt, t, T)
+                if link is not None:
+                    link.push(ret[4]["power"])
     else:
         def reset(i0):
             obs = env.reset()[0]
@@ -523,13 +535,15 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                 action = row
             transition = (out["next_obs"][i], out["rew"][i], out["done"][i])
             if step_takes_out:   # the env writes the transition straight into this step's slices
-                next_obs = env.step(action, out=transition)[0]
+                next_obs, _, _, _, info = env.step(action, out=transition)
             else:
-                next_obs, rew, done, _, _ = env.step(action)
+                next_obs, rew, done, _, info = env.step(action)
                 for dst, src in zip(transition, (next_obs, rew, done)):
                     dst.copy_(src)
             if science:
                 env.science_integrate()
+            if link is not None:
+                link.push(info["power"])
             return next_obs
 
     with torch.no_grad():

@@ -864,6 +864,62 @@ int aog_reset_spgd(aog_env* env, aog_spgd* spgd, float* obs_raw_dev, uint16_t* o
 int aog_step_spgd(aog_env* env, aog_spgd* spgd, const float* action_dev, float* obs_raw_dev, uint16_t* obs_dev, float* reward_dev,
                   uint8_t* done_dev, float* power_dev, float* strehl_dev, float* action_out, int* queried /* host int, nullable */, void* stream);
 
+/* ---- link telemetry: per-env rings of the fibre-coupled power, their fade statistics, histogram and bit-error rate (additive in ABI 22;
+ * no counterpart in the reference) ----
+ * Independent of any aog_env, like aog_telemetry.  Per env one record, which is also the checkpoint blob: ring [length] float32 (sample
+ * number c lies at c mod length), then `count` (samples stored) and `skipped`, int64.  length T is a power of two in [64, 4096].  Plain
+ * vector stores, no atomics on floats, no host synchronisation; the calls on one handle are ordered by the one stream they are given.
+ * mask_dev: nullable [B] uint8 device array, non-zero = selected; envs it leaves out are touched nowhere, and neither are their rows of
+ * any output.
+ *
+ * aog_link_push stores power_dev [b] (float32 [B] on the device: what a step writes as power) of every selected env at count mod T and
+ * adds 1 to count; a non-finite sample is not stored: `skipped` counts it and count stays.
+ *
+ * aog_link_statistics works, per env, over its window: the last n = min(count, T) samples p_0 .. p_{n-1}, oldest first.  One launch covers
+ * every env, threshold, bin and Q factor; the ring is read once.
+ *   mean_dev, mean_square_dev [B] float64: sum p / n and sum p^2 / n, float64 sums of the float32 samples, each square exact in float64;
+ *   minimum_dev, maximum_dev [B] float32, exact; samples_dev [B] int32 = n.
+ *   Reference level P: the caller's `reference` (positive, finite) under AOG_LINK_REF_ABSOLUTE, the env's own mean under
+ *   AOG_LINK_REF_MEAN (`reference` is then ignored); reference_dev [B] float64 receives it.
+ *   Thresholds: n_edges = K <= 16 ascending positive factors edges_rel (a HOST array); the edge is the float64 product P f_k, sample i
+ *   is in fade k when (double) p_i < P f_k.  below_dev, fades_dev, longest_dev [B][K] int32: the samples in fade, the maximal runs of
+ *   consecutive in-fade samples (a run cut by either end of the window counts as one) and the longest run in frames.
+ *   Histogram: n_hist = E <= 64 ascending positive factors hist_edges_rel (HOST) give hist_dev [B][E + 1] int32: bin 0 counts p < P g_0,
+ *   bin j counts P g_{j-1} <= p < P g_j, bin E counts p >= P g_{E-1}; every row sums to n.
+ *   Bit-error rate of on-off keying at the receiver Q factors q (HOST, n_q = Q <= 8, each positive and finite), at the reference level:
+ *   ber_dev [B][Q] float64 = (1 / n) sum_i erfc(q_m p_i / (P sqrt 2)) / 2.
+ *   An env with n = 0 gets 0 in every integer output and NaN in every float output.  K, E or Q may be 0; the outputs of a zero size
+ *   may be NULL, all others are required.
+ * Every float64 sum is taken in an order that (T, n) alone fix (csrc/k_link.h): any split of a batch over handles, and any mask,
+ * reproduces the whole batch bit for bit.
+ * AOG_ERR_INVALID, before any device work, with aog_last_error naming the field: a wrong abi_version, num_envs < 1, a length that is
+ * not such a power of two, a nonzero reserved field; a reference_mode outside AOG_LINK_REF_*, an absolute reference that is not
+ * positive and finite, K, E or Q beyond its limit, factors that are not positive, finite and strictly ascending, a q that is not
+ * positive and finite.  env_id_base is carried for the caller and enters no arithmetic.  The struct is five int32; it has no index in
+ * aog_struct_size. */
+enum { AOG_LINK_REF_ABSOLUTE = 0, AOG_LINK_REF_MEAN = 1 };
+enum { AOG_LINK_MAX_EDGES = 16, AOG_LINK_MAX_HIST = 64, AOG_LINK_MAX_Q = 8 };
+typedef struct aog_link aog_link;
+typedef struct aog_link_config {
+  int32_t abi_version;                  /* = AOG_ABI_VERSION */
+  int32_t num_envs, length, env_id_base;
+  int32_t reserved;                     /* = 0 */
+} aog_link_config;
+int aog_link_create(const aog_link_config* cfg, int device, aog_link** out);
+void aog_link_destroy(aog_link* link);
+/* The selected envs back to the state after create: a ring of zeros, both counters 0.  Stream-ordered. */
+int aog_link_reset(aog_link* link, const uint8_t* mask_dev, void* stream);
+int aog_link_push(aog_link* link, const float* power_dev, const uint8_t* mask_dev, void* stream);
+int aog_link_statistics(aog_link* link, int reference_mode, double reference, const double* edges_rel, int n_edges,
+                        const double* hist_edges_rel, int n_hist, const double* q, int n_q, int32_t* samples_dev, double* mean_dev,
+                        double* mean_square_dev, float* minimum_dev, float* maximum_dev, double* reference_dev, int32_t* below_dev,
+                        int32_t* fades_dev, int32_t* longest_dev, int32_t* hist_dev, double* ber_dev, const uint8_t* mask_dev, void* stream);
+/* Checkpointing: per env, one after the other, ring [T] (float32), count and skipped (int64) — the blob of a whole batch is the blobs of
+ * its parts in a row.  A handle of the same configuration that takes the blob resumes bit-identically. */
+int64_t aog_link_state_bytes(const aog_link* link);
+int aog_link_get_state(aog_link* link, void* blob_dev, void* stream);
+int aog_link_set_state(aog_link* link, const void* blob_dev, void* stream);
+
 /* Self-test hook: sin(2 pi u), cos(2 pi u) for n float32 revolutions u_dev with the fused kernels' device code.
  * flavour 0 = polynomial, 1 = v_sin_f32/v_cos_f32 after the exact reduction, 2 = v_sin_f32/v_cos_f32 on raw input. */
 int aog_selftest_sincos(const float* u_dev, float* sin_dev, float* cos_dev, int n, int flavour, void* stream);
