@@ -1104,7 +1104,6 @@ class BatchedAOEnv:
         ``get_actuators() - coef / 2``).  Stream-ordered, no host synchronisation, nothing a step reads is changed.  ``out``: such a dict to
         write into.  The fit's host table (``optics_host.wavefront_fit``) is uploaded by the first call.  Raises like ``focal_images`` while a
         pipelined or policy-attached step has an action pending and between two steps of a lookahead episode."""
-        torch = self._torch
         if not self._wavefront_fit_uploaded:
             from .optics_host import wavefront_fit
 
@@ -1114,14 +1113,12 @@ class BatchedAOEnv:
             self._wavefront_fit_uploaded = True
         B, A = self.num_envs, self.num_modes
         shapes = {"rms": (B,), "fit_rms": (B,), "coef": (B, A), "ideal_actuators": (B, A)}
+        text = "contiguous float64 device tensors rms [B], fit_rms [B], coef [B, A], ideal_actuators [B, A]"
         if out is None:
-            out = {k: torch.empty(s, dtype=torch.float64, device=self.device) for k, s in shapes.items()}
+            out = {k: self._f64_out(None, s, "wavefront_truth", text, zero=False) for k, s in shapes.items()}
         else:
-            for k, s in shapes.items():
-                t = out.get(k)
-                if t is None or t.dtype != torch.float64 or tuple(t.shape) != s or not t.is_contiguous() or t.device != self.device:
-                    raise ValueError("wavefront_truth(out=...): expected contiguous float64 device tensors rms [B], fit_rms [B], coef [B, A], "
-                                     "ideal_actuators [B, A]")
+            for k, s in shapes.items():   # (every entry must be there: a missing one is not made here)
+                self._f64_out(False if out.get(k) is None else out[k], s, "wavefront_truth", text)
         p = C.c_void_p
         _lib.check(self.lib.aog_wavefront_truth(self._handle, p(out["rms"].data_ptr()), p(out["fit_rms"].data_ptr()), p(out["coef"].data_ptr()),
                                                 p(out["ideal_actuators"].data_ptr()), self._stream()))
@@ -1136,6 +1133,46 @@ class BatchedAOEnv:
         act = torch.empty((self.num_envs, self.num_modes), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.aog_wavefront_truth(self._handle, None, None, None, C.c_void_p(act.data_ptr()), self._stream()))
         return act
+
+    # ------------------------------------------------------------------------------------------------
+    # what the off-step instruments' wrappers share
+    # instrument -> (the attribute holding its host tables, what an env without it was built without, its upload method)
+    _INSTRUMENTS = {"science": ("_science", "a science camera (science_window=...)", "_upload_science"),
+                    "pyramid": ("_pyramid", "a pyramid sensor (pyramid=dict(...))", "_upload_pyramid")}
+
+    def _instrument_mask(self, instrument, mask, who):
+        """``who``'s checks on ``instrument`` (built with it; its tables uploaded, on demand), then its mask as a device pointer (None: every
+        env) and the tensor that keeps it alive."""
+        tables, without, upload = self._INSTRUMENTS[instrument]
+        if getattr(self, tables) is None:
+            raise ValueError(f"{who}: this environment was built without {without}")
+        getattr(self, upload)()
+        if mask is None:
+            return None, None
+        sel = _mask_array(mask, self.num_envs, who)
+        m = self._torch.from_numpy(sel.astype(np.uint8)).to(self.device)
+        return C.c_void_p(m.data_ptr()), m
+
+    def _f64_arg(self, x, shape, who, name):
+        """An input ``x`` (None stays None; numpy, torch on any device, any dtype) as a contiguous float64 tensor on the env's device;
+        ValueError unless it has ``shape``."""
+        if x is None:
+            return None
+        t = self._torch.as_tensor(x, device=self.device).to(self._torch.float64)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t.contiguous()
+
+    def _f64_out(self, out, shape, who, text, zero=True):
+        """An ``out=`` tensor: ``out`` itself if it is a contiguous float64 tensor of ``shape`` on the env's device, a new one (zeros, or
+        uninitialised with ``zero=False``) for None, and ``ValueError(f"{who}(out=...): expected {text}")`` for anything else."""
+        torch = self._torch
+        if out is None:
+            return (torch.zeros if zero else torch.empty)(tuple(shape), dtype=torch.float64, device=self.device)
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != tuple(shape) or not out.is_contiguous()
+                or out.device != self.device):
+            raise ValueError(f"{who}(out=...): expected {text}")
+        return out
 
     # ------------------------------------------------------------------------------------------------
     # analytic gradient
@@ -1177,15 +1214,7 @@ class BatchedAOEnv:
             raise ValueError("output_gradient: wrt=None asks for the values alone and needs with_values=True")
         self._upload_gradient()
         B, A, n = self.num_envs, self.num_modes, self.obs_dim ** 2
-
-        def cot(x, shape, name):
-            if x is None:
-                return None
-            t = torch.as_tensor(x, device=self.device).to(torch.float64)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"output_gradient: {name} must have shape {shape}")
-            return t.contiguous()
-
+        cot = lambda x, shape, name: self._f64_arg(x, shape, "output_gradient", name)
         go, gp, gs = cot(g_obs, (B, n), "g_obs"), cot(g_power, (B,), "g_power"), cot(g_strehl, (B,), "g_strehl")
         a = None
         if wrt == "action":
@@ -1214,27 +1243,16 @@ class BatchedAOEnv:
                                                float(t.phase_ratio), float(t.peak_fraction), bins.ctypes.data_as(C.c_void_p), int(t.radii.size)))
         self._science_uploaded = True
 
-    def _science_mask(self, mask, who):
-        """``who``'s checks, then its mask as a device pointer (None: every env) and the tensor that keeps it alive."""
-        if self._science is None:
-            raise ValueError(f"{who}: this environment was built without a science camera (science_window=...)")
-        self._upload_science()
-        if mask is None:
-            return None, None
-        sel = _mask_array(mask, self.num_envs, who)
-        m = self._torch.from_numpy(sel.astype(np.uint8)).to(self.device)
-        return C.c_void_p(m.data_ptr()), m
-
     def science_integrate(self, mask=None):
         """Add the current science-arm frame of every env (or those ``mask`` selects) to its long exposure (``aog_science_integrate``).
         Stream-ordered; reads the state the last ``reset`` / ``step`` left and changes nothing a step reads.  Raises like ``focal_images``
         while a pipelined or policy-attached step has an action pending and between two steps of a lookahead episode."""
-        ptr, _keep = self._science_mask(mask, "science_integrate")   # (the mask lives until the launches are queued: torch frees in stream order)
+        ptr, _keep = self._instrument_mask("science", mask, "science_integrate")   # (the mask lives until the launches are queued: torch frees in stream order)
         _lib.check(self.lib.aog_science_integrate(self._handle, ptr, self._stream()))
 
     def science_clear(self, mask=None):
         """Empty the long exposure (and frame count) of every env, or of those ``mask`` selects."""
-        ptr, _keep = self._science_mask(mask, "science_clear")
+        ptr, _keep = self._instrument_mask("science", mask, "science_clear")
         _lib.check(self.lib.aog_science_clear(self._handle, ptr, self._stream()))
 
     def science_exposure(self, first=0, count=None, image=True):
@@ -1243,7 +1261,7 @@ class BatchedAOEnv:
         ``encircled_energy`` [count, len(science_radii)] the share of the beam's power inside each of ``science_radii`` (lambda_sci / D),
         ``frames`` [count] int32.  An env with no frames reads as zeros.  A range outside the batch raises ``ValueError``."""
         torch = self._torch
-        self._science_mask(None, "science_exposure")
+        self._instrument_mask("science", None, "science_exposure")
         first = int(first)
         count = self.num_envs - first if count is None else int(count)
         if first < 0 or count < 0 or first + count > self.num_envs:
@@ -1280,42 +1298,23 @@ class BatchedAOEnv:
         self._pyramid_uploaded = True
         self.pyramid_frame_count = 0
 
-    def _pyramid_mask(self, mask, who):
-        """``who``'s checks, then its mask as a device pointer (None: every env) and the tensor that keeps it alive."""
-        if self._pyramid is None:
-            raise ValueError(f"{who}: this environment was built without a pyramid sensor (pyramid=dict(...))")
-        self._upload_pyramid()
-        if mask is None:
-            return None, None
-        sel = _mask_array(mask, self.num_envs, who)
-        m = self._torch.from_numpy(sel.astype(np.uint8)).to(self.device)
-        return C.c_void_p(m.data_ptr()), m
-
     def pyramid_frames(self, mask=None, out=None):
         """The pyramid sensor's frame of every env at the state the last ``reset`` / ``step`` left: [B, 4, n_s, n_s] float64, quadrant
         2 (k_y > 0) + (k_x > 0).  ``mask``: the rows of the envs it leaves out are not written (``out``: the tensor to write into).
         Stream-ordered; changes nothing a step reads.  Raises like ``science_integrate`` while an action is pending and between two steps
         of a lookahead episode."""
-        torch = self._torch
-        ptr, _keep = self._pyramid_mask(mask, "pyramid_frames")
+        ptr, _keep = self._instrument_mask("pyramid", mask, "pyramid_frames")
         ns = self._pyramid.pixels
-        if out is None:
-            out = torch.zeros((self.num_envs, 4, ns, ns), dtype=torch.float64, device=self.device)
-        elif out.dtype != torch.float64 or tuple(out.shape) != (self.num_envs, 4, ns, ns) or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("pyramid_frames(out=...): expected a contiguous float64 [B, 4, n_s, n_s] tensor on the env's device")
+        out = self._f64_out(out, (self.num_envs, 4, ns, ns), "pyramid_frames", "a contiguous float64 [B, 4, n_s, n_s] tensor on the env's device")
         _lib.check(self.lib.aog_pyramid_frames(self._handle, ptr, C.c_void_p(out.data_ptr()), self._stream()))
         self.pyramid_frame_count += 1
         return out
 
     def pyramid_slopes(self, mask=None, out=None):
         """The sensor's slopes [B, 2 n_valid] float64: s_x over the valid pixels (``env._pyramid.valid``), then s_y.  As ``pyramid_frames``."""
-        torch = self._torch
-        ptr, _keep = self._pyramid_mask(mask, "pyramid_slopes")
-        shape = (self.num_envs, 2 * self._pyramid.n_valid)
-        if out is None:
-            out = torch.zeros(shape, dtype=torch.float64, device=self.device)
-        elif out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("pyramid_slopes(out=...): expected a contiguous float64 [B, 2 n_valid] tensor on the env's device")
+        ptr, _keep = self._instrument_mask("pyramid", mask, "pyramid_slopes")
+        out = self._f64_out(out, (self.num_envs, 2 * self._pyramid.n_valid), "pyramid_slopes",
+                            "a contiguous float64 [B, 2 n_valid] tensor on the env's device")
         _lib.check(self.lib.aog_pyramid_slopes(self._handle, ptr, C.c_void_p(out.data_ptr()), self._stream()))
         self.pyramid_frame_count += 1
         return out
@@ -1335,18 +1334,10 @@ class BatchedAOEnv:
         if self._pyramid is None:
             raise ValueError("pyramid_gradient: this environment was built without a pyramid sensor (pyramid=dict(...))")
         B, A, ns, nv = self.num_envs, self.num_modes, self._pyramid.pixels, self._pyramid.n_valid
-
-        def arg(x, shape, name):
-            if x is None:
-                return None
-            t = torch.as_tensor(x, device=self.device).to(torch.float64)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"pyramid_gradient: {name} must have shape {shape}, got {tuple(t.shape)}")
-            return t.contiguous()
-
+        arg = lambda x, shape, name: self._f64_arg(x, shape, "pyramid_gradient", name)
         gf, gs = arg(g_frames, (B, 4, ns, ns), "g_frames"), arg(g_slopes, (B, 2 * nv), "g_slopes")
         act = arg(actuators, (B, A), "actuators")
-        mptr, _keep = self._pyramid_mask(mask, "pyramid_gradient")
+        mptr, _keep = self._instrument_mask("pyramid", mask, "pyramid_gradient")
         if self._precision != "fp64":
             self._upload_gradient()   # (fast handles contract with the output gradient's modes operands)
         grad = torch.zeros((B, A), dtype=torch.float64, device=self.device)
@@ -1363,12 +1354,8 @@ class BatchedAOEnv:
         if self._pyramid is None:
             raise ValueError("pyramid_clean: this environment was built without a pyramid sensor (pyramid=dict(...))")
         B, A, ns, nv = self.num_envs, self.num_modes, self._pyramid.pixels, self._pyramid.n_valid
-        act = None
-        if actuators is not None:
-            act = torch.as_tensor(actuators, device=self.device).to(torch.float64).contiguous()
-            if tuple(act.shape) != (B, A):
-                raise ValueError(f"pyramid_clean: actuators must have shape {(B, A)}, got {tuple(act.shape)}")
-        mptr, _keep = self._pyramid_mask(mask, "pyramid_clean")
+        act = self._f64_arg(actuators, (B, A), "pyramid_clean", "actuators")
+        mptr, _keep = self._instrument_mask("pyramid", mask, "pyramid_clean")
         frames = torch.zeros((B, 4, ns, ns), dtype=torch.float64, device=self.device)
         slopes = torch.zeros((B, 2 * nv), dtype=torch.float64, device=self.device)
         p = C.c_void_p
@@ -1383,7 +1370,7 @@ class BatchedAOEnv:
         [A, 2 n_valid], reference slopes [2 n_valid]) as numpy arrays (also ``pyramid_response``); ``PYR_step`` calls it when needed."""
         from .optics_host import inverse_tikhonov
 
-        self._pyramid_mask(None, "pyramid_calibrate")
+        self._instrument_mask("pyramid", None, "pyramid_calibrate")
         A, N, cfg = self.num_modes, self.num_pupil_pixels, self.pyramid
         sensor = {k: cfg[k] for k in ("samples", "q", "pixels", "n_mod", "r_mod")}
         scratch = BatchedAOEnv(2 * A + 1, self.device, act_type=self.act_type, act_dim=A, obs_dim=self.obs_dim, rew_type=self.rew_type,
@@ -1410,7 +1397,7 @@ class BatchedAOEnv:
         Returns (actuators [B, A] float64, slopes [B, 2 n_valid] float64); the mirror itself is not touched — step with the actuators
         (an env built with ``SH_operation=True`` takes them as its action)."""
         torch = self._torch
-        self._pyramid_mask(None, "PYR_step")
+        self._instrument_mask("pyramid", None, "PYR_step")
         if not self._pyramid_calibrated:
             self.pyramid_calibrate()
         act = torch.empty((self.num_envs, self.num_modes), dtype=torch.float64, device=self.device)

@@ -129,6 +129,13 @@ int refuse_pre_evolved(const aog_env* e, const char* who) {
   return AOG_OK;
 }
 
+int instrument_gate(const aog_env* e, const char* who, bool ready, const char* what, const char* upload_name) {
+  if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "%s before aog_upload_tables/aog_set_screens", who);
+  if (!ready) return fail(AOG_ERR_STATE, "%s: %s not uploaded (%s, again after aog_upload_tables)", who, what, upload_name);
+  if (int rc = check_poisoned(e, who)) return rc;
+  return refuse_pre_evolved(e, who);
+}
+
 int check_env_range(const char* who, int first, int count, int B) {
   if (first < 0 || count < 0 || first + count > B) return fail(AOG_ERR_INVALID, "%s: env range [%d,%d) outside [0,%d)", who, first, first + count, B);
   return AOG_OK;

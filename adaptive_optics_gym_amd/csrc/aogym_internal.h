@@ -125,12 +125,16 @@ struct aog_env {
   double* obs_E = nullptr;
   double* obs_T = nullptr;
   double* obs_F = nullptr;
+  // The off-step instruments below (wavefront fit, output gradient, science camera, pyramid sensor and its gradient) read the mirror through one
+  // scratch pair (instrument_operands): the calls on a handle are ordered by their one stream and each rewrites the pair in full before it
+  // reads it, so nothing is carried from one call to the next.  Made on first need, inst_act_ll only once a call asks for the third term.
+  _Float16* inst_act16 = nullptr;  // the call's own copy of the actuators (or of its act_src) in act16's layout
+  _Float16* inst_act_ll = nullptr; // and their third f16 term, in focal_act_ll's layout
   // wavefront fit (aog_upload_wavefront_fit, aog_wavefront_truth; wavefront.hip).  Nothing here is read or written by a reset or step.
   bool wf_ready = false;         // the fit is uploaded (aog_upload_tables clears it)
   double* wf_fit = nullptr;      // [A][A] P = pinv(Mc' Mc)
   double* wf_colsum = nullptr;   // [A] column sums of the mode matrix over the aperture
   _Float16* wf_tab16 = nullptr;  // modes as table operands: [n_ptiles][A_pad rows in blocks of 32][step 2][hi|lo][lane 64][8] (tab16's pixel order)
-  _Float16* wf_act16 = nullptr;  // the call's own copy of the actuators in act16's layout
   double* wf_slabs = nullptr;    // [pixel chunk][A_pad + 2][Bp] partial sums, allocated by the first call
   double* wf_w = nullptr;        // float64 handles: [B][n_ap] path error of the call, allocated by the first call
   // output gradient (aog_upload_gradient, aog_output_gradient; gradient.hip).  Nothing here is read or written by a reset or step.
@@ -140,7 +144,6 @@ struct aog_env {
   _Float16* grad_ttab16 = nullptr; // the same tables transposed (32 pixel rows, K = 32 tables): [n_ptiles][step 2][hi|lo][64][8]
   _Float16* grad_mtab16 = nullptr; // modes as table operands (wf_tab16's recipe)
   double* grad_stab = nullptr;     // [n_ptiles][h 2][16] science table in accumulator order
-  _Float16* grad_act16 = nullptr;  // the call's own copy of the actuators in act16's layout
   _Float16* grad_cop16 = nullptr;  // [n_etiles][step 2][re|im][hi|lo][64][8] C of every env as B operands
   float* grad_csci = nullptr;      // [Bp][2] the science arm's C
   double* grad_fslabs = nullptr;   // forward partial sums [pixel chunk][rows][Bp], allocated by the first call (as the four below)
@@ -155,7 +158,6 @@ struct aog_env {
   double gobs_unscale = 1.0;       // 2^-(e1 + e2) of the two tables below
   _Float16* gobs_m1t = nullptr;    // m1' 2^e1 as A operands: [ceil(Nyp / 32)][2] tiles, lane y, K = v accumulator
   _Float16* gobs_m2t = nullptr;    // m2' 2^e2 as B operands: [Nxp / 32][2] tiles, lane x, K = u natural
-  _Float16* gobs_act_ll = nullptr; // the call's own third f16 term of the actuators (grad_act16 holds the first two)
   _Float16* gobs_wop = nullptr;    // [chunk][step 2][4][64][8] W / wscale of every env as A operands (row v, K = u)
   double* gobs_wscale = nullptr;   // [B] the power of two W was divided by
   double* gobs_slabs = nullptr;    // [pixel chunk][A rows][Bp] partial sums of the modes contraction of the observation's q
@@ -175,8 +177,6 @@ struct aog_env {
   _Float16* sci_m1s = nullptr;   // K4's m1s layout with ceil(w / 32) v blocks
   _Float16* sci_m2s = nullptr;   // K4's m2s layout with ceil(w / 32) u blocks
   MftWork sci_work;              // phases at the science wavelength; Nxp = N rounded up to 128, ceil(w / 32) v blocks
-  _Float16* sci_act16 = nullptr; // the calls' own copy of the actuators in act16's layout, and their third f16 term
-  _Float16* sci_act_ll = nullptr;
   double* sci_m1d = nullptr;     // float64 handles: m1 [w][N], m2 [N][w] complex, E [N][N], T [w][N], F [w][w] complex
   double* sci_m2d = nullptr;
   double* sci_E = nullptr;
@@ -200,8 +200,6 @@ struct aog_env {
   _Float16* pyr_b2s = nullptr;   // [2][ceil(n_s / 32)][2 ceil(w / 32)] tiles: lane x', K = u accumulator
   MftWork pyr_work;              // phases at lambda_wfs; Nxp = N rounded up to 128, ceil(w / 32) v blocks
   _Float16* pyr_fop = nullptr;   // [chunk][nvb][2 nvb] tiles: F_j 2^6, split, k_pyr_back's A operands (lane u, K = v accumulator)
-  _Float16* pyr_act16 = nullptr; // the calls' own copy of the actuators in act16's layout, and their third f16 term
-  _Float16* pyr_act_ll = nullptr;
   float* pyr_tile_keep = nullptr;  // dynamic handles whose psi_tile a sensor call refreshes (obs_tiles): psi_tile as the call found it, put back behind the call
   double* pyr_m1d = nullptr;     // float64 handles: the four tables, E [N][N], T [w][N], F [w][w], X [2][n_s][w], G [4][n_s][n_s] complex
   double* pyr_m2d = nullptr;

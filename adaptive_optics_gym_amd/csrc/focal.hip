@@ -66,7 +66,19 @@ void launch_mft64(aog_env* e, hipStream_t s, const Mft64& t, double* F, float* F
 int alloc_act_operands(aog_env* e, _Float16** act16, _Float16** act_ll) {
   const size_t n = (size_t)e->n_etiles * 32 * e->A_pad;
   if (int rc = act16 ? need(e, act16, 2 * n, true) : AOG_OK) return rc;
-  return need(e, act_ll, n, true);
+  return act_ll ? need(e, act_ll, n, true) : AOG_OK;
+}
+
+int instrument_operands(aog_env* e, hipStream_t s, bool want_ll, const double* act_src) {
+  if (!e->inst_act16 || (want_ll && !e->inst_act_ll)) {
+    if (int rc = alloc_act_operands(e, &e->inst_act16, want_ll ? &e->inst_act_ll : nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());   // (zeroed on the null stream: s may not wait for it)
+  }
+  // psi_tile holding the screens the last step read: always current on quasi_static / semi_dynamic handles; dynamic ones whose step kernel
+  // does not write it refresh it from the master screens (psi_tile alone: nothing a step reads is touched, and the int8 extrusion's work
+  // ahead stays, because only what the last step left is read); the operands are the call's own copy: act_rev / act16 are not touched
+  if (int rc = obs_tiles(e, s)) return rc;
+  return load_actuators(e, s, {nullptr, e->inst_act16, want_ll ? e->inst_act_ll : nullptr}, act_src);
 }
 
 void launch_obs_pass1(aog_env* e, hipStream_t s, int n) {

@@ -56,7 +56,6 @@ int aog_upload_gradient(aog_env* e, const aog_tables* t) {
   if ((rc = upload(e, &e->grad_ttab16, t16, true)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->grad_mtab16, m16, true)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->grad_stab, st, true)) != AOG_OK) return rc;
-  if (!e->grad_act16 && (rc = dev_alloc(e, &e->grad_act16, (size_t)e->n_etiles * e->A_pad * 32 * 2, true)) != AOG_OK) return rc;
   if (!e->grad_cop16 && (rc = dev_alloc(e, &e->grad_cop16, (size_t)e->n_etiles * 8 * 64 * 8, true)) != AOG_OK) return rc;
   if (!e->grad_csci && (rc = dev_alloc(e, &e->grad_csci, (size_t)e->n_etiles * 32 * 2, true)) != AOG_OK) return rc;
   e->grad_ready = true;
@@ -71,11 +70,7 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
   if (grad_action_dev && e->cfg.sh_operation)
     return fail(AOG_ERR_INVALID, "aog_output_gradient: grad_action on an sh_operation handle (its action is the actuators: ask for grad_act)");
   if (grad_action_dev && !action_dev) return fail(AOG_ERR_INVALID, "aog_output_gradient: grad_action needs action_dev");
-  if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "aog_output_gradient before aog_upload_tables/aog_set_screens");
-  if (!e->grad_ready)
-    return fail(AOG_ERR_STATE, "aog_output_gradient: the gradient's tables were not uploaded (aog_upload_gradient, again after aog_upload_tables)");
-  if (int rc = check_poisoned(e, "aog_output_gradient")) return rc;
-  if (int rc = refuse_pre_evolved(e, "aog_output_gradient")) return rc;
+  if (int rc = instrument_gate(e, "aog_output_gradient", e->grad_ready, "the gradient's tables were", "aog_upload_gradient")) return rc;
   if (g_obs_dev && e->obs_sep && !e->gobs_ready)
     return fail(AOG_ERR_UNSUPPORTED, "aog_output_gradient: g_obs on the separable observation route (cfg.obs_separable = 1: the observation is a "
                 "matrix Fourier transform, not a row of wfs_coef); the power and Strehl gradients are available");
@@ -94,14 +89,11 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
   if (!e->grad_cbuf && (rc = dev_alloc(e, &e->grad_cbuf, (size_t)e->B * MR * 2, false)) != AOG_OK) return rc;
   if (!e->grad_cscale && (rc = dev_alloc(e, &e->grad_cscale, (size_t)e->B, false)) != AOG_OK) return rc;
   if (fast) {
-    // psi_tile holding the screens the last step read, refreshed the way aog_wavefront_truth does it (psi_tile alone: nothing a step reads is
-    // touched); the actuator operands are the call's own copy
-    if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
-    if ((rc = load_actuators(e, s, {nullptr, e->grad_act16, obs_part ? e->gobs_act_ll : nullptr})) != AOG_OK) return rc;
+    if ((rc = instrument_operands(e, s, obs_part)) != AOG_OK) return rc;   // (the third term: grad_obs_part's phase grid reads it)
     with_apad(e->A_pad, [&](auto apad) {
       hipLaunchKernelGGL((aog::k_grad_forward<apad()>), dim3(n_chunks, e->n_etiles), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
                          reinterpret_cast<const aog::f16x8*>(e->grad_ftab16), e->grad_stab, reinterpret_cast<const aog::f32x4*>(e->psi_tile),
-                         reinterpret_cast<const aog::f16x8*>(e->grad_act16), e->grad_fslabs, e->n_ptiles, e->n_ap, e->Bp, ratio);
+                         reinterpret_cast<const aog::f16x8*>(e->inst_act16), e->grad_fslabs, e->n_ptiles, e->n_ap, e->Bp, ratio);
     });
   } else {
     if (!e->grad_trig && (rc = dev_alloc(e, &e->grad_trig, (size_t)e->B * e->n_ap * 4, false)) != AOG_OK) return rc;
@@ -140,7 +132,7 @@ int aog_output_gradient(aog_env* e, const double* g_obs_dev, const double* g_pow
     with_apad(e->A_pad, [&](auto apad) {
       hipLaunchKernelGGL((aog::k_grad_backward<apad()>), dim3(n_chunks, e->n_etiles), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
                          reinterpret_cast<const aog::f16x8*>(e->grad_ttab16), e->grad_stab, reinterpret_cast<const aog::f16x8*>(e->grad_mtab16),
-                         reinterpret_cast<const aog::f32x4*>(e->psi_tile), reinterpret_cast<const aog::f16x8*>(e->grad_act16),
+                         reinterpret_cast<const aog::f32x4*>(e->psi_tile), reinterpret_cast<const aog::f16x8*>(e->inst_act16),
                          reinterpret_cast<const aog::f16x8*>(e->grad_cop16), e->grad_csci, e->grad_bslabs, e->n_ptiles, e->n_ap, e->Bp, ratio,
                          e->grad_tscale);
     });

@@ -45,7 +45,7 @@ int grad_obs_part(aog_env* e, hipStream_t s, const double* g_obs, double* values
   }
   for (int env0 = 0; env0 < e->B; env0 += e->gobs_chunk) {
     const int n = std::min(e->gobs_chunk, e->B - env0), n_et = (n + 31) / 32;
-    launch_phase_grid(e, s, e->grad_act16, e->gobs_act_ll, e->obs_work.grid, grid_env, Nxp, env0 / 32, n_et);
+    launch_phase_grid(e, s, e->inst_act16, e->inst_act_ll, e->obs_work.grid, grid_env, Nxp, env0 / 32, n_et);
     launch_obs_pass1(e, s, n);
     hipLaunchKernelGGL(aog::k_grad_obs_field, dim3((n + 3) / 4), dim3(256), 0, s, f16x8p(e->obs_work.T16), f16x8p(e->obs_m2s), nxt, n, o, e->obs_unscale,
                        g_obs ? g_obs + (size_t)env0 * n_obs : nullptr,
@@ -107,7 +107,6 @@ int aog_upload_gradient_obs(aog_env* e, const aog_obs_mft* t) {
   e->gobs_unscale = 1.0 / (s1 * s2);
   if ((rc = upload(e, &e->gobs_m1t, m1t, true)) != AOG_OK) return rc;
   if ((rc = upload(e, &e->gobs_m2t, m2t, true)) != AOG_OK) return rc;
-  if ((rc = alloc_act_operands(e, nullptr, &e->gobs_act_ll)) != AOG_OK) return rc;
   // whole env tiles per round: what obs_work holds, or fewer (AOG_GRAD_OBS_CHUNK; tests: several rounds at small sizes)
   e->gobs_chunk = e->obs_work.chunk;
   if (const char* v = getenv("AOG_GRAD_OBS_CHUNK")) e->gobs_chunk = std::max(32, std::min(e->gobs_chunk, atoi(v) / 32 * 32));

@@ -149,6 +149,9 @@ void poison(aog_env* e, int bits);
 int clear_poison(aog_env* e);   // the host word and the device-side sticky word (the caller has drained the streams that could set them)
 int check_poisoned(const aog_env* e, const char* who);
 int refuse_pre_evolved(const aog_env* e, const char* who);
+// The checks every off-step instrument's call shares, in this order: tables and screens there; the instrument's own tables uploaded
+// (`ready`; `what` = "the science camera was", upload_name = "aog_upload_science"); check_poisoned; refuse_pre_evolved
+int instrument_gate(const aog_env* e, const char* who, bool ready, const char* what, const char* upload_name);
 int clear_poison_if_whole(aog_env* e, int first, int count, hipStream_t s);
 // AOG_ERR_INVALID unless envs [first, first + count) lie inside [0, B)
 int check_env_range(const char* who, int first, int count, int B);
@@ -169,6 +172,9 @@ struct ActTargets {
 };
 // (act_src: nullable [B][A] float64 device actuators to load instead of the mirror's)
 int load_actuators(aog_env* e, hipStream_t s, ActTargets to, const double* act_src = nullptr);
+// focal.hip: the operand prologue of an off-step instrument's call on a fast handle — psi_tile holding the screens the last step read
+// (obs_tiles) and the actuators (the mirror's, or act_src) in e->inst_act16 and, with want_ll, e->inst_act_ll, made on first need
+int instrument_operands(aog_env* e, hipStream_t s, bool want_ll, const double* act_src = nullptr);
 // The kernels instantiated per padded mode count outside the step path: f(std::integral_constant<int, 16 | 32 | 64 | 128>) for A_pad (anything
 // else gets 128), e.g. with_apad(e->A_pad, [&](auto apad) { hipLaunchKernelGGL((k<apad()>), ...); }).  (The step path's own table of
 // launchers is launchers_for in aogym.hip.)
@@ -229,9 +235,9 @@ void launch_obs_pass1(aog_env* e, hipStream_t s, int n);
 aog::DetectorArgs detector_args(const aog_env* e, const uint8_t* mask);
 // gradient_obs.hip (K14 on the separable route, after aog_upload_gradient_obs): the observation's part of one aog_output_gradient call, behind
 // its k_grad_coef — the float64 obs_raw into the observation slots of `values` (nullable) and, with g_obs (nullable), the modes contraction of
-// the observation's q into e->gobs_slabs for k_grad_finish.  The actuator operands (grad_act16, gobs_act_ll) are the caller's.
+// the observation's q into e->gobs_slabs for k_grad_finish.  The actuator operands (inst_act16, inst_act_ll) are the caller's.
 int grad_obs_part(aog_env* e, hipStream_t s, const double* g_obs_dev, double* values_dev);
-// pyramid.hip: the checks every call on an uploaded sensor shares, and the sum over the modulation points of every selected env into pyr_acc
+// pyramid.hip: the checks every call on an uploaded sensor shares (instrument_gate), and the sum over the modulation points of every selected env into pyr_acc
 // (no division yet) at the mirror's actuators or at act_src (nullable [B][A] device) — the forward launches of aog_pyramid_frames, which
 // aog_pyramid_gradient (pyramid_grad.hip) runs for its clean frame
 int pyramid_ready(aog_env* e, const char* who);

@@ -79,7 +79,7 @@ float mft_operand_tables(const double* m1, const double* m2, int N, int nf, cons
 // whole tiles, at least one, and at the value of the environment variable chunk_env (nullable; tests: several chunks at small sizes); the
 // grid starts out as "outside the aperture" everywhere (only aperture pixels are ever written).  Blocking.
 int mft_work_alloc(aog_env* e, MftWork* w, size_t grid_env, size_t t16_env, size_t cap_envs, const char* chunk_env);
-// a feature's own actuator operands (load_actuators' act16, nullable, and act_ll), zeroed; buffers that are there already stay
+// a feature's own actuator operands (load_actuators' act16 and act_ll, either nullable), zeroed; buffers that are there already stay
 int alloc_act_operands(aog_env* e, _Float16** act16, _Float16** act_ll);
 
 // The steps of the float64 validation forms for one env.  launch_focal_field: E = exp(2 pi i ratio u_p) on the aperture pixels of the

@@ -22,8 +22,6 @@ void release_pyramid(aog_env* e) {
   dev_release(e, &e->pyr_work.grid);   // (focal_ap_yx stays: K4, K11 and the science camera use it too)
   dev_release(e, &e->pyr_work.T16);
   dev_release(e, &e->pyr_fop);
-  dev_release(e, &e->pyr_act16);
-  dev_release(e, &e->pyr_act_ll);
   dev_release(e, &e->pyr_tile_keep);
   dev_release(e, &e->pyr_m1d);
   dev_release(e, &e->pyr_m2d);
@@ -48,10 +46,7 @@ namespace aog_host {
 
 // the checks every call on an uploaded sensor shares (aog_science_integrate's preconditions)
 int pyramid_ready(aog_env* e, const char* who) {
-  if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "%s before aog_upload_tables/aog_set_screens", who);
-  if (!e->pyr_ready) return fail(AOG_ERR_STATE, "%s: the pyramid sensor was not uploaded (aog_upload_pyramid, again after aog_upload_tables)", who);
-  if (int rc = check_poisoned(e, who)) return rc;
-  return refuse_pre_evolved(e, who);
+  return instrument_gate(e, who, e->pyr_ready, "the pyramid sensor was", "aog_upload_pyramid");
 }
 
 // The sum over the modulation points of every selected env into pyr_acc (no division yet: k_pyr_finish).
@@ -103,13 +98,10 @@ static bool pyr_keeps_tiles(const aog_env* e) { return e->pyr_tile_keep && e->ke
 static size_t pyr_tile_bytes(const aog_env* e) { return sizeof(float) * (size_t)e->n_etiles * e->n_ptiles * 1024; }
 
 int pyramid_operands_begin(aog_env* e, hipStream_t s, const double* act_src) {
-  int rc;
-  // psi_tile holding the screens the last step read (psi_tile alone: nothing a step reads is touched); the actuator operands are the call's own
   // (a dynamic handle that steps with the VALU kernel keeps a psi_tile nobody reads between its screen installations, but the state blob
   // carries it: the call leaves it as it found it, so that aog_get_state does not depend on whether the sensor was called)
   if (pyr_keeps_tiles(e)) HIP_TRY(hipMemcpyAsync(e->pyr_tile_keep, e->psi_tile, pyr_tile_bytes(e), hipMemcpyDeviceToDevice, s));
-  if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
-  return load_actuators(e, s, {nullptr, e->pyr_act16, e->pyr_act_ll}, act_src);
+  return instrument_operands(e, s, true, act_src);
 }
 
 int pyramid_operands_end(aog_env* e, hipStream_t s) {
@@ -119,7 +111,7 @@ int pyramid_operands_end(aog_env* e, hipStream_t s) {
 
 void pyramid_phase_grid(aog_env* e, hipStream_t s, int env0, int n) {
   const MftGeom g = pyr_geom(e);
-  launch_phase_grid(e, s, e->pyr_act16, e->pyr_act_ll, e->pyr_work.grid, g.grid_env(), g.Nxp, env0 / 32, (n + 31) / 32);
+  launch_phase_grid(e, s, e->inst_act16, e->inst_act_ll, e->pyr_work.grid, g.grid_env(), g.Nxp, env0 / 32, (n + 31) / 32);
 }
 
 // F_j of the chunk's envs into pyr_fop: the two forward passes
@@ -226,7 +218,6 @@ int aog_upload_pyramid(aog_env* e, const aog_pyramid_tables* t) {
                            "AOG_PYRAMID_CHUNK")) != AOG_OK)
     return rc;
   if ((rc = dev_alloc(e, &e->pyr_fop, (size_t)e->pyr_work.chunk * fop_env, true)) != AOG_OK) return rc;   // (the pads stay zero)
-  if ((rc = alloc_act_operands(e, &e->pyr_act16, &e->pyr_act_ll)) != AOG_OK) return rc;
   if (e->cfg.atm_dynamic && !e->ring_direct && (rc = dev_alloc(e, &e->pyr_tile_keep, (size_t)e->n_etiles * e->n_ptiles * 1024, false)) != AOG_OK) return rc;
   e->pyr_ready = true;
   return AOG_OK;

@@ -17,8 +17,6 @@ void release_science(aog_env* e) {
   dev_release(e, &e->sci_m2s);
   dev_release(e, &e->sci_work.grid);   // (focal_ap_yx stays: K4 and K11 use it too)
   dev_release(e, &e->sci_work.T16);
-  dev_release(e, &e->sci_act16);
-  dev_release(e, &e->sci_act_ll);
   dev_release(e, &e->sci_m1d);
   dev_release(e, &e->sci_m2d);
   dev_release(e, &e->sci_E);
@@ -31,10 +29,7 @@ void release_science(aog_env* e) {
 
 // the checks every call on an uploaded camera shares (aog_focal_images' preconditions)
 int science_ready(aog_env* e, const char* who) {
-  if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "%s before aog_upload_tables/aog_set_screens", who);
-  if (!e->sci_ready) return fail(AOG_ERR_STATE, "%s: the science camera was not uploaded (aog_upload_science, again after aog_upload_tables)", who);
-  if (int rc = check_poisoned(e, who)) return rc;
-  return refuse_pre_evolved(e, who);
+  return instrument_gate(e, who, e->sci_ready, "the science camera was", "aog_upload_science");
 }
 
 }  // namespace
@@ -86,7 +81,6 @@ int aog_upload_science(aog_env* e, const double* m1_host, const double* m2_host,
   const size_t grid_env = g.grid_env(), t16_env = g.t16_env();
   if ((rc = mft_work_alloc(e, &e->sci_work, grid_env, t16_env, ((size_t)256 << 20) / std::max(grid_env * 4, t16_env * 2), "AOG_SCIENCE_CHUNK")) != AOG_OK)
     return rc;
-  if ((rc = alloc_act_operands(e, &e->sci_act16, &e->sci_act_ll)) != AOG_OK) return rc;
   e->sci_ready = true;
   return AOG_OK;
 }
@@ -107,10 +101,7 @@ int aog_science_integrate(aog_env* e, const uint8_t* mask_dev, void* stream) {
     return AOG_OK;
   }
   int rc;
-  // psi_tile holding the screens the last step read, refreshed the way aog_wavefront_truth does it (psi_tile alone: nothing a step reads is
-  // touched); the actuator operands are the call's own copy
-  if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
-  if ((rc = load_actuators(e, s, {nullptr, e->sci_act16, e->sci_act_ll})) != AOG_OK) return rc;
+  if ((rc = instrument_operands(e, s, true)) != AOG_OK) return rc;
   const MftGeom g = sci_geom(e);
   const int Nxp = g.Nxp, Nyp = g.Nyp, nvb = g.nvb, nwg = (nvb + 3) / 4;
   // windows of at most two 32-column blocks: the four waves of a workgroup share the two blocks (k_science_pass1); AOG_SCIENCE_SPLIT=0
@@ -125,8 +116,8 @@ int aog_science_integrate(aog_env* e, const uint8_t* mask_dev, void* stream) {
       constexpr int NSTEP = apad() / 16;
       hipLaunchKernelGGL((aog::k_science_phase<apad()>), dim3((e->n_ptiles + 3) / 4, n_et), dim3(256), 0, s, f16x8p(e->modes16),
                          reinterpret_cast<const aog::f32x4*>(e->psi_tile) + (size_t)etile0 * e->n_ptiles * 4 * 64,
-                         f16x8p(e->sci_act16) + (size_t)etile0 * NSTEP * 2 * 64,
-                         f16x8p(e->sci_act_ll) + (size_t)etile0 * NSTEP * 64, e->focal_ap_yx, e->sci_work.grid, grid_env, Nxp,
+                         f16x8p(e->inst_act16) + (size_t)etile0 * NSTEP * 2 * 64,
+                         f16x8p(e->inst_act_ll) + (size_t)etile0 * NSTEP * 64, e->focal_ap_yx, e->sci_work.grid, grid_env, Nxp,
                          e->n_ptiles, n_et, e->n_ap, e->B - etile0 * 32, e->sci_ratio, mask_dev ? mask_dev + (size_t)etile0 * 32 : nullptr);
     });
     hipLaunchKernelGGL(aog::k_science_pass1, dim3(Nxp / 128, nwg, n), dim3(256), 0, s, e->sci_work.grid, f16x8p(e->sci_m1s), f16x8p(e->sci_work.T16), Nxp,

@@ -24,7 +24,6 @@ int aog_upload_wavefront_fit(aog_env* e, const double* modes_host, const double*
     const std::vector<_Float16> t16 = pack_tab16_rows(e->n_ptiles, n_ap, A, aog::pupil_blocks(e->A_pad), aog::kModeScale,
                                                       [&](int p, int k) { return modes_host[(size_t)p * A + k]; });
     if ((rc = upload(e, &e->wf_tab16, t16, true)) != AOG_OK) return rc;
-    if (!e->wf_act16 && (rc = dev_alloc(e, &e->wf_act16, (size_t)e->n_etiles * e->A_pad * 32 * 2, true)) != AOG_OK) return rc;
   }
   e->wf_ready = true;
   return AOG_OK;
@@ -33,10 +32,7 @@ int aog_upload_wavefront_fit(aog_env* e, const double* modes_host, const double*
 int aog_wavefront_truth(aog_env* e, double* rms_dev, double* fit_rms_dev, double* coef_dev, double* act_ideal_dev, void* stream) {
   if (!e) return fail(AOG_ERR_INVALID, "aog_wavefront_truth: null argument");
   if (!rms_dev && !fit_rms_dev && !coef_dev && !act_ideal_dev) return fail(AOG_ERR_INVALID, "aog_wavefront_truth: every output pointer is null");
-  if (!e->tables_ready || !e->screens_ready) return fail(AOG_ERR_STATE, "aog_wavefront_truth before aog_upload_tables/aog_set_screens");
-  if (!e->wf_ready) return fail(AOG_ERR_STATE, "aog_wavefront_truth: the wavefront fit was not uploaded (aog_upload_wavefront_fit, again after aog_upload_tables)");
-  if (int rc = check_poisoned(e, "aog_wavefront_truth")) return rc;
-  if (int rc = refuse_pre_evolved(e, "aog_wavefront_truth")) return rc;
+  if (int rc = instrument_gate(e, "aog_wavefront_truth", e->wf_ready, "the wavefront fit was", "aog_upload_wavefront_fit")) return rc;
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool fast = e->cfg.precision == AOG_PRECISION_FAST;
@@ -45,15 +41,11 @@ int aog_wavefront_truth(aog_env* e, double* rms_dev, double* fit_rms_dev, double
   // work buffers of the call's own, on first use (never initialised: every element that is read is written by the call first)
   if (!e->wf_slabs && (rc = dev_alloc(e, &e->wf_slabs, (size_t)n_chunks * rows * e->Bp, false)) != AOG_OK) return rc;
   if (fast) {
-    // psi_tile holding the screens the last step read: always current on quasi_static / semi_dynamic handles; dynamic ones whose step kernel
-    // does not write it refresh it from the master screens (psi_tile alone: nothing a step reads is touched, and the int8 extrusion's work
-    // ahead stays, because only what the last step left is read)
-    if ((rc = obs_tiles(e, s)) != AOG_OK) return rc;
-    if ((rc = load_actuators(e, s, {nullptr, e->wf_act16, nullptr})) != AOG_OK) return rc;   // (own copy: act_rev / act16 are not touched)
+    if ((rc = instrument_operands(e, s, false)) != AOG_OK) return rc;
     with_apad(e->A_pad, [&](auto apad) {
       hipLaunchKernelGGL((aog::k_wavefront_fit<apad()>), dim3(n_chunks, e->n_etiles), dim3(256), 0, s, reinterpret_cast<const aog::f16x8*>(e->modes16),
                          reinterpret_cast<const aog::f16x8*>(e->wf_tab16), reinterpret_cast<const aog::f32x4*>(e->psi_tile),
-                         reinterpret_cast<const aog::f16x8*>(e->wf_act16), e->wf_slabs, e->n_ptiles, e->n_ap, e->Bp);
+                         reinterpret_cast<const aog::f16x8*>(e->inst_act16), e->wf_slabs, e->n_ptiles, e->n_ap, e->Bp);
     });
   } else {
     if (!e->wf_w && (rc = dev_alloc(e, &e->wf_w, (size_t)e->B * e->n_ap, false)) != AOG_OK) return rc;

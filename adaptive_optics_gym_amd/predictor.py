@@ -80,7 +80,7 @@ def pseudo_open_loop(env, measurement, who):
         if measurement == "truth":
             return env.ideal_action()
         torch = env._torch
-        env._pyramid_mask(None, who)
+        env._instrument_mask("pyramid", None, who)
         if not env._pyramid_calibrated:
             env.pyramid_calibrate()
         y = torch.empty((env.num_envs, env.num_modes), dtype=torch.float64, device=env.device)

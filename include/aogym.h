@@ -443,8 +443,8 @@ int aog_upload_wavefront_fit(aog_env* env, const double* modes_host, const doubl
  * (at least one non-NULL).  Whole batch, stream-ordered, no host synchronisation.
  * Fast handles: the split-f16 phase contraction of the step kernels fused with a second matrix-core contraction of that phase against the
  * modes, float64 sums in a fixed order (a batch split over handles reproduces the whole batch bit for bit); float64 validation handles: a
- * plain float64 kernel.  Reads the state the last reset or step left and changes nothing a step reads or writes (its actuator operands and
- * partial sums live in buffers of its own, allocated by the first call).  AOG_ERR_STATE before tables, screens or the fit are installed,
+ * plain float64 kernel.  Reads the state the last reset or step left and changes nothing a step reads or writes (its partial sums live in
+ * a buffer of its own, its actuator operands in the scratch the off-step instruments of a handle share; the first call allocates both).  AOG_ERR_STATE before tables, screens or the fit are installed,
  * while a pipelined or policy-attached step has an action pending, and between two steps of a lookahead episode. */
 int aog_wavefront_truth(aog_env* env, double* rms_dev, double* fit_rms_dev,
                         double* coef_dev, double* act_ideal_dev, void* stream);
@@ -462,7 +462,8 @@ int aog_wavefront_truth(aog_env* env, double* rms_dev, double* fit_rms_dev,
  * Host tables, float64 / int32 HOST pointers: m1 [w][N][2], m2 [N][w][2] (re, im), ee_bin [w*w] the radial bin 0 .. n_ee - 1 of each
  * window pixel (-1 = outside every radius), peak_fraction = the unaberrated peak's share of the beam's power (unaberrated_PSF.max() of a
  * unit-power beam).  After aog_upload_tables; a later aog_upload_tables clears the camera.  Builds the split-f16 operand tables of the
- * matrix-core path; every buffer of the camera is allocated here, not at aog_create, so handles that never ask keep their device_bytes.
+ * matrix-core path; every buffer of the camera is allocated here, not at aog_create, so handles that never ask keep their device_bytes
+ * (the actuator operands of a call are the scratch the off-step instruments of a handle share, made by the first call that needs it).
  * A second upload replaces the first (and its exposures).  AOG_ERR_INVALID for an odd window, one outside [2, 4096] or n_ee outside
  * [1, 32].  The focal grid's size n_s is not part of aog_config — m1 / m2 define the grid — so w <= n_s is the caller's to hold
  * (BatchedAOEnv raises ValueError above 240); the library's cap bounds the exposure's size only.  phase_ratio is used as given on fast
@@ -591,8 +592,9 @@ typedef struct aog_pyramid_tables {
   double photons;       /* expected photo-electrons per frame of a beam that puts 1 into every pixel (0: no photon noise) */
 } aog_pyramid_tables;
 
-/* Install the sensor.  After aog_upload_tables (a later aog_upload_tables clears it); every buffer of the sensor is allocated here, so
- * handles that never ask keep their device_bytes and their launches.  A second upload replaces the first and restarts the frame count.
+/* Install the sensor.  After aog_upload_tables (a later aog_upload_tables clears it); every buffer of the sensor is allocated here (but
+ * the actuator operands of a call: the off-step instruments' shared scratch, made by the first call that needs it), so handles that never
+ * ask keep their device_bytes and their launches.  A second upload replaces the first and restarts the frame count.
  * Work proceeds in chunks of whole env tiles, capped at ~256 MB per work buffer or at the environment variable AOG_PYRAMID_CHUNK (read
  * here).  AOG_ERR_INVALID for a size outside the ranges above, a bad valid index or a non-finite / negative photons. */
 int aog_upload_pyramid(aog_env* env, const aog_pyramid_tables* tables);
