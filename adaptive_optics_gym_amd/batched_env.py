@@ -1421,7 +1421,7 @@ class BatchedAOEnv:
         host RNG streams.  ``set_state`` on an env built with the same arguments resumes bit-identically."""
         torch = self._torch
         n = int(self.lib.aog_state_bytes(self._handle))
-        blob = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        blob = torch.zeros((n,), dtype=torch.uint8, device=self.device)   # (the library pads every part to 256 bytes and leaves the padding alone)
         ts = C.c_int64()
         _lib.check(self.lib.aog_get_state(self._handle, C.c_void_p(blob.data_ptr()), C.byref(ts), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()

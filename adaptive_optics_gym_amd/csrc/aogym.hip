@@ -64,7 +64,12 @@ int ensure_dynamic_lds(const void* fn, size_t bytes, int device) {
 int dev_alloc_bytes(aog_env* e, void** out, size_t bytes, bool zero) {
   void* p = nullptr;
   HIP_TRY(hipMalloc(&p, bytes));
-  if (zero) HIP_TRY(hipMemset(p, 0, bytes));
+  if (zero) {
+    // the fill runs on the null stream, which a non-blocking caller's stream does not wait for, and hipMemset on device memory may return
+    // before it has run: wait for it here, so that whatever stream reads the buffer first finds the zeros (an allocation path only)
+    HIP_TRY(hipMemset(p, 0, bytes));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+  }
   e->allocs.push_back(p);
   e->alloc_bytes.push_back(bytes);
   e->dev_bytes += (int64_t)bytes;

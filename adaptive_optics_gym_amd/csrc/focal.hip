@@ -72,7 +72,7 @@ int alloc_act_operands(aog_env* e, _Float16** act16, _Float16** act_ll) {
 int instrument_operands(aog_env* e, hipStream_t s, bool want_ll, const double* act_src) {
   if (!e->inst_act16 || (want_ll && !e->inst_act_ll)) {
     if (int rc = alloc_act_operands(e, &e->inst_act16, want_ll ? &e->inst_act_ll : nullptr)) return rc;
-    HIP_TRY(hipDeviceSynchronize());   // (zeroed on the null stream: s may not wait for it)
+    // (zeroed on the null stream, which s may not wait for: dev_alloc_bytes has waited for the fill)
   }
   // psi_tile holding the screens the last step read: always current on quasi_static / semi_dynamic handles; dynamic ones whose step kernel
   // does not write it refresh it from the master screens (psi_tile alone: nothing a step reads is touched, and the int8 extrusion's work
