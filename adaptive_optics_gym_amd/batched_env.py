@@ -1417,8 +1417,23 @@ class BatchedAOEnv:
         return out
 
     def get_state(self):
-        """Snapshot of everything that evolves: library state blob (screens, actuators, counters) + Python-side counters and the
-        host RNG streams.  ``set_state`` on an env built with the same arguments resumes bit-identically."""
+        """Snapshot of the simulation state: ``set_state`` on an env built with the same arguments, or on this one after it has moved on,
+        resumes bit-identically — every later observation, reward, ``done``, Strehl, power, screen and instrument reading is that of the
+        uninterrupted run.
+
+        In it: the library's blob (screens, or the master screens, ring origins and extrusion counters of a dynamic atmosphere; the
+        screen-synthesis counters; mirror and Shack-Hartmann actuators; render times; and in its tail the seed, the Shack-Hartmann call
+        count, the steps since the reset, the detector's frame and the pyramid sensor's frame), ``timestep``, ``episode_no``,
+        ``observation_frames``, ``pyramid_frame_count``, the Fried parameters, the detector's values and the host RNG streams.
+
+        Deliberately not in it: the science camera's exposure and frame counts (measurement data: ``set_state`` leaves them exactly as
+        they were; ``science_clear`` at the snapshot point makes two runs' exposures comparable), the tensor given to
+        ``accumulate_returns`` (the caller's) and profiling records.  What belongs to another object is that object's to save: a
+        ``rollout.DeviceActor`` and a ``rollout.DeviceOUNoise`` have ``get_state`` / ``set_state`` of their own (the call index and the
+        OU state key the exploration streams), like the controllers of ``device_handle``.
+
+        Raises while a pipelined or policy-attached step has an action pending and between two steps of a lookahead episode: take the
+        snapshot where nothing is pending (``next_actions=None``, an episode's last step)."""
         torch = self._torch
         n = int(self.lib.aog_state_bytes(self._handle))
         blob = torch.zeros((n,), dtype=torch.uint8, device=self.device)   # (the library pads every part to 256 bytes and leaves the padding alone)
@@ -1427,35 +1442,48 @@ class BatchedAOEnv:
         torch.cuda.current_stream(self.device).synchronize()
         rng = [self._env_rng(e).get_state() for e in range(self.num_envs)] if self._host_rng else None
         return {"blob": blob, "lib_timestep": int(ts.value), "timestep": self.timestep, "episode_no": self.episode_no, "rng": rng,
-                "fried_parameters": self._fried.copy(),
+                "num_envs": self.num_envs, "fried_parameters": self._fried.copy(),
                 "observation_frames": self.observation_frames,
-                "detector": None if self._detector is None else {k: v.copy() for k, v in self._detector.items()}}
+                "detector": None if self._detector is None else {k: v.copy() for k, v in self._detector.items()},
+                "pyramid": None if self.pyramid is None else {k: self.pyramid[k] for k in ("samples", "q", "pixels", "n_mod", "r_mod", "photons")},
+                "pyramid_frame_count": self.pyramid_frame_count}
 
     def set_state(self, state):
+        """Resume from a ``get_state`` snapshot (see there for what it holds and what it leaves alone).  Whatever the handle had pending
+        — a pipelined or policy-attached action, a lookahead extrusion, the int8 extrusion's work ahead — is forgotten.  ``ValueError`` for
+        a state of another configuration: another ``num_envs``, a detector or a pyramid sensor on one side only."""
         torch = self._torch
+        # every refusal comes before the handle is touched (blobs of different num_envs can have one size: their parts are padded to 256 bytes)
+        fried = state.get("fried_parameters")
+        saved_envs = state.get("num_envs", None if fried is None else np.asarray(fried).shape[0])
+        if saved_envs is not None and int(saved_envs) != self.num_envs:
+            raise ValueError(f"set_state: the state was saved with num_envs = {int(saved_envs)} and this environment has {self.num_envs}")
         det = state.get("detector")
         if (det is None) != (self._detector is None):
             raise ValueError("set_state: the state was saved " + ("without" if det is None else "with") + " a detector and this environment was built "
                              + ("with" if det is None else "without") + " one (obs_photons)")
+        if "pyramid" in state and (state["pyramid"] is None) != (self.pyramid is None):   # (states from before the sensor was saved: no rule)
+            raise ValueError("set_state: the state was saved " + ("without" if state["pyramid"] is None else "with") + " a pyramid sensor and this "
+                             "environment was built " + ("with" if state["pyramid"] is None else "without") + " one (pyramid=dict(...))")
         if det is not None and any(np.asarray(det[k]).shape != (self.num_envs,) for k in ("photons", "read_noise", "background")):
             raise ValueError("state's detector values do not match this environment's num_envs")
         blob = state["blob"].to(self.device).contiguous()
         if blob.numel() != int(self.lib.aog_state_bytes(self._handle)):
             raise ValueError("state blob does not match this environment's configuration")
+        self._upload_pyramid()   # (no-op when the sensor is there: an upload AFTER the restore would restart the frame count the blob brings)
         _lib.check(self.lib.aog_set_state(self._handle, C.c_void_p(blob.data_ptr()), int(state["lib_timestep"]), self._stream()))
         self.state_epoch += 1
         self._last_action = None
         torch.cuda.current_stream(self.device).synchronize()
+        self._next_actions_keepalive = None   # (the library forgot a pending pipelined action: the next step's is not checked against it)
         self.timestep = int(state["timestep"])
         self.episode_no = int(state["episode_no"])
         self.observation_frames = int(state.get("observation_frames", 0))   # (the library's own count came with the blob)
+        self.pyramid_frame_count = int(state.get("pyramid_frame_count", 0))   # (likewise)
         if state.get("rng") is not None:
             for e, st in enumerate(state["rng"]):
                 self._env_rng(e).set_state(st)
-        fried = state.get("fried_parameters")
         if fried is not None and not np.array_equal(np.asarray(fried, dtype=np.float64), self._fried):
-            if np.asarray(fried).shape != (self.num_envs,):
-                raise ValueError("state's fried_parameters do not match this environment's num_envs")
             self._apply_fried(fried)   # (the values only: the screens came with the blob)
         if det is not None:
             self._detector = {k: np.ascontiguousarray(det[k], dtype=np.float64).copy() for k in ("photons", "read_noise", "background")}

@@ -950,6 +950,7 @@ struct StateTail {  // host-side counters that steer the device RNG streams; sto
   uint32_t sh_calls, steps_since_reset;
   uint64_t obs_frame;   // (blobs written before the detector existed left these bytes unwritten: such a blob restores an arbitrary frame count,
                         // which only matters once a detector is switched on — the stream then starts wherever the count stands)
+  uint64_t pyr_frame;   // the pyramid sensor's photon stream (blobs written before it was saved read 0: what they ran with after an upload)
 };
 static_assert(sizeof(StateTail) <= 256, "the state blob reserves 256 bytes for the tail");
 }  // namespace
@@ -975,7 +976,7 @@ int aog_get_state(aog_env* e, void* blob_dev, int64_t* timestep_out, void* strea
     char bytes[256];
   } t{};
   memset(t.bytes, 0, sizeof t.bytes);
-  t.tail = StateTail{e->timestep, e->rng_seed, e->sh_calls, (uint32_t)e->steps_since_reset, e->obs_frame};
+  t.tail = StateTail{e->timestep, e->rng_seed, e->sh_calls, (uint32_t)e->steps_since_reset, e->obs_frame, e->pyr_frame};
   HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
   HIP_TRY(hipMemcpy(static_cast<char*>(blob_dev) + off, t.bytes, sizeof t.bytes, hipMemcpyHostToDevice));
   if (timestep_out) *timestep_out = e->timestep;
@@ -1007,6 +1008,7 @@ int aog_set_state(aog_env* e, const void* blob_dev, int64_t timestep, void* stre
   e->sh_calls = tail.sh_calls;
   e->steps_since_reset = tail.steps_since_reset;
   e->obs_frame = tail.obs_frame;
+  e->pyr_frame = tail.pyr_frame;   // (aog_upload_pyramid restarts the count: a sensor is uploaded before the state is restored, not after)
   e->sh_sums_ready = false;
   if (poisoned(e))   // a restored state replaces every screen: the handle is usable again
     if (int rc = clear_poison(e)) return rc;

@@ -169,7 +169,7 @@ struct aog_env {
   double* gobs_H = nullptr;
   double* gobs_q = nullptr;
   // science camera (aog_upload_science, aog_science_*; science.hip).  Nothing here is read or written by a reset or step, and none of it
-  // is part of the aog_get_state blob.
+  // is part of the aog_get_state blob: the exposure is measurement data, and aog_set_state leaves sci_exposure / sci_frames as they were.
   bool sci_ready = false;        // the camera is uploaded (aog_upload_tables clears it)
   int sci_w = 0, sci_n_ee = 0;   // window side, number of encircled-energy radii
   double sci_ratio = 0, sci_peak = 0;   // lambda_wfs / lambda_sci; the unaberrated peak's share of the beam's power
@@ -185,13 +185,14 @@ struct aog_env {
   int32_t* sci_bin = nullptr;    // [w][w] radial bin of each pixel of the window (-1: outside every radius)
   double* sci_exposure = nullptr;   // [B][w][w] sum of the integrated frames
   int32_t* sci_frames = nullptr;    // [B] frames integrated
-  // pyramid wavefront sensor (aog_upload_pyramid, aog_pyramid_*; pyramid.hip).  Nothing here is read or written by a reset or step, and none
-  // of it is part of the aog_get_state blob.  Every buffer is allocated by aog_upload_pyramid / aog_upload_pyramid_reconstructor.
+  // pyramid wavefront sensor (aog_upload_pyramid, aog_pyramid_*; pyramid.hip).  Nothing here is read or written by a reset or step, and of
+  // all of it only pyr_frame travels with the aog_get_state blob (in its tail).  Every buffer is allocated by aog_upload_pyramid /
+  // aog_upload_pyramid_reconstructor.
   bool pyr_ready = false;        // the sensor is uploaded (aog_upload_tables clears it)
   bool pyr_rec_ready = false;    // and its reconstructor
   int pyr_wq = 0, pyr_ns = 0, pyr_nmod = 0, pyr_nvalid = 0;   // samples per quadrant side, detector pixels per side, modulation points, valid pixels
   double pyr_photons = 0;        // photo-electrons per unit of frame value (0: no photon noise)
-  uint64_t pyr_frame = 0;        // sensor calls since the upload: the frame of the photon stream's counter
+  uint64_t pyr_frame = 0;        // sensor calls since the upload (or what aog_set_state restored): the frame of the photon stream's counter
   float pyr_unscale = 1.f;       // what undoes the powers of two of m1s x m2s
   double pyr_back_unscale = 1.0; // and of the stored field x b1s x b2s
   _Float16* pyr_m1s = nullptr;   // [n_mod] x the science camera's m1s layout with ceil(w / 32) v blocks

@@ -134,6 +134,20 @@ class DeviceOUNoise:
             raise ValueError(f"DeviceOUNoise.reset: mask must be a bool vector of {self.state.shape[0]} entries")
         self.state[m] = self.mu
 
+    def get_state(self):
+        """A copy of the float64 state [num_envs, action_dim]: with ``DeviceActor.get_state`` and the env's, what a checkpoint of an
+        exploring rollout holds."""
+        return self.state.clone()
+
+    def set_state(self, state):
+        """Resume from ``get_state`` (in place: queries already hold the tensor's address).  ValueError for another shape."""
+        import torch
+
+        st = torch.as_tensor(state, device=self.state.device)
+        if tuple(st.shape) != tuple(self.state.shape):
+            raise ValueError(f"DeviceOUNoise.set_state: the state is {tuple(st.shape)}, this process {tuple(self.state.shape)}")
+        self.state.copy_(st.to(torch.float64))
+
     def check(self, batch: int, action_dim: int, device):
         """ValueError unless the state fits a query of ``batch`` rows and ``action_dim`` units on ``device``."""
         import torch
@@ -197,6 +211,18 @@ class DeviceActor:
         if a is None:
             raise RuntimeError("DeviceActor: the actor module it was built for has been garbage-collected")
         return a
+
+    def get_state(self):
+        """What keys the query's random streams besides the env ids: {"seed", "calls", "env_id_base", "dropout_p"}.  The env's ``get_state`` does
+        not hold it (the policy is not the env's); a checkpoint of an exploring rollout saves both (and the weights, which are torch's)."""
+        return {"seed": self.seed, "calls": self.calls, "env_id_base": self.env_id_base, "dropout_p": self.dropout_p}
+
+    def set_state(self, state):
+        """Resume from ``get_state``: the next query draws what the saved instance's next query would have drawn.  ValueError when the
+        state was saved for another ``env_id_base`` (another slice of the batch)."""
+        if int(state["env_id_base"]) != self.env_id_base:
+            raise ValueError(f"DeviceActor.set_state: the state was saved at env_id_base {state['env_id_base']}, this instance serves {self.env_id_base}")
+        self.seed, self.calls, self.dropout_p = int(state["seed"]), int(state["calls"]), float(state["dropout_p"])
 
     def layers(self):
         """The four ``nn.Linear`` of the module, checked: contiguous float32 CUDA weights (ValueError otherwise)."""

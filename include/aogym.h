@@ -362,7 +362,10 @@ int aog_sh_update(aog_env* env, const double* noisy_image_dev, double* action_de
 /* Checkpointing (the reference has none for the env): every piece of per-env state the handle owns — screens
  * (and ring-buffer origins / RNG stream positions for dynamic handles), mirror and Shack-Hartmann actuators, per-episode step
  * counters — as one opaque device blob of aog_state_bytes() bytes, plus the global step counter.  A blob is only valid for a
- * handle created with the same configuration. */
+ * handle created with the same configuration.  Its last 256 bytes carry the host-side positions of the device random streams: the seed,
+ * the Shack-Hartmann call count, the steps since the reset, the detector's frame and the pyramid sensor's frame.  Not in it, and left as
+ * they are by aog_set_state: the science camera's exposure and frame counts (measurement data), the return accumulator's tensor (the
+ * caller's) and the profiling records. */
 int64_t aog_state_bytes(const aog_env* env);
 int aog_get_state(aog_env* env, void* blob_dev, int64_t* timestep_out, void* stream);
 int aog_set_state(aog_env* env, const void* blob_dev, int64_t timestep, void* stream);
@@ -594,7 +597,8 @@ typedef struct aog_pyramid_tables {
 
 /* Install the sensor.  After aog_upload_tables (a later aog_upload_tables clears it); every buffer of the sensor is allocated here (but
  * the actuator operands of a call: the off-step instruments' shared scratch, made by the first call that needs it), so handles that never
- * ask keep their device_bytes and their launches.  A second upload replaces the first and restarts the frame count.
+ * ask keep their device_bytes and their launches.  A second upload replaces the first and restarts the frame count; aog_set_state
+ * restores the count its blob was saved with, so upload the sensor before a state is restored, not after.
  * Work proceeds in chunks of whole env tiles, capped at ~256 MB per work buffer or at the environment variable AOG_PYRAMID_CHUNK (read
  * here).  AOG_ERR_INVALID for a size outside the ranges above, a bad valid index or a non-finite / negative photons. */
 int aog_upload_pyramid(aog_env* env, const aog_pyramid_tables* tables);

@@ -193,6 +193,11 @@ def test_the_step_path_is_untouched(atm, kernel):
             assert torch.equal(env.get_actuators(), twin.get_actuators()), f"step {t}: the mirror moved"
         assert torch.equal(env.get_screens(), twin.get_screens())
         (b1, t1), (b2, t2) = _blob(torch, env), _blob(torch, twin)
+        # the blob's 256-byte tail carries the sensor's own frame count (bytes 32 .. 40: after timestep, rng_seed, sh_calls, steps_since_reset
+        # and obs_frame); every other byte is the twin's
+        frame = lambda b: int(b[-256 + 32:-256 + 40].cpu().numpy().view(np.uint64)[0])
+        assert frame(b1) == env.pyramid_frame_count == T + 1 and frame(b2) == 0
+        b1[-256 + 32:-256 + 40] = 0
         assert t1 == t2 and b1.numel() > 0 and torch.equal(b1, b2), "the state blob moved"
         assert env.device_status() == 0
     finally:
