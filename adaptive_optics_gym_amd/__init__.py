@@ -5,15 +5,17 @@
     from adaptive_optics_gym_amd.envs import AOEnv        # the reference's single-env gym API
     from adaptive_optics_gym_amd import ModalTelemetry, ModalIntegrator   # loop telemetry (PSDs) and the optimised modal integrator
     from adaptive_optics_gym_amd import LinkTelemetry     # the optical link's read-out: fades, power histogram, bit-error rate
+    from adaptive_optics_gym_amd import ModalDisturbance  # vibration and static aberrations for LayeredAOEnv(disturbance=...)
     import gym_AO                                         # registers 'AO-v0' like the reference (needs gymnasium)
 """
 from .batched_env import BatchedAOEnv  # noqa: F401
+from .disturbance import ModalDisturbance  # noqa: F401
 from .layered import LayeredAOEnv  # noqa: F401
 from .link import LinkTelemetry  # noqa: F401
 from .params import OpticalParams  # noqa: F401
 from .telemetry import ModalIntegrator, ModalTelemetry  # noqa: F401
 
-__all__ = ["BatchedAOEnv", "LayeredAOEnv", "LinkTelemetry", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "register"]
+__all__ = ["BatchedAOEnv", "LayeredAOEnv", "LinkTelemetry", "ModalDisturbance", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "register"]
 
 
 def register():

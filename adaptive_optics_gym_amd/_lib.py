@@ -101,6 +101,13 @@ class AogLinkConfig(C.Structure):  # mirrors aog_link_config (additive in ABI 22
 AOG_LINK_REF = {"absolute": 0, "mean": 1}
 
 
+class AogDisturbanceConfig(C.Structure):  # mirrors aog_disturbance_config (include/aogym_disturbance.h; its size query is aog_disturbance_config_size)
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "num_envs", "n_terms", "env_id_base")] + [("seed", C.c_uint64)]
+
+
+DISTURBANCE_MAX_TERMS = 8   # AOG_DISTURBANCE_MAX_TERMS
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -222,6 +229,22 @@ SYMBOLS = {
     "aog_profile_read_kernel": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }
 
+# every symbol include/aogym_disturbance.h declares
+DISTURBANCE_SYMBOLS = {
+    "aog_disturbance_config_size": (C.c_int64, []),
+    "aog_disturbance_create": (C.c_int, [C.POINTER(AogDisturbanceConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "aog_disturbance_destroy": (None, [C.c_void_p]),
+    "aog_disturbance_set_params": (C.c_int, [C.c_void_p] * 7),
+    "aog_disturbance_reset": (C.c_int, [C.c_void_p] * 4),
+    "aog_disturbance_advance": (C.c_int, [C.c_void_p] * 5),
+    "aog_disturbance_coefficients": (C.c_int, [C.c_void_p] * 3),
+    "aog_disturbance_state_bytes": (C.c_int64, [C.c_void_p]),
+    "aog_disturbance_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_disturbance_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_upload_disturbance_basis": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "aog_install_layer_sum_disturbed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -239,7 +262,7 @@ def load():
     except Exception:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -256,6 +279,9 @@ def load():
     for which, cls in enumerate((AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite, AogObsMft, AogActionNoise)):
         if lib.aog_struct_size(which) != C.sizeof(cls):
             raise RuntimeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, the library's struct {lib.aog_struct_size(which)}")
+    if lib.aog_disturbance_config_size() != C.sizeof(AogDisturbanceConfig):
+        raise RuntimeError(f"AogDisturbanceConfig: ctypes layout is {C.sizeof(AogDisturbanceConfig)} bytes, the library's struct "
+                           f"{lib.aog_disturbance_config_size()}")
     _lib = lib
     return lib
 

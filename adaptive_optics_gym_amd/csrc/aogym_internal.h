@@ -244,7 +244,9 @@ struct aog_env {
   float* psi_rev = nullptr;     // [n_quads][Bp][4]  (handles that run the VALU kernel only)
   double* pack_mean = nullptr;   // [B] aperture means of the screens being installed (k_screen_means -> k_pack_tiles)
   double* layer_mean = nullptr;  // [B] aperture means of the layer sum being installed (aog_install_layer_sum: k_layer_mean -> k_layer_sum_*), allocated by the first call
-  float* psi_tile = nullptr;     // [Bp/32][n_ptiles][4][64][4]
+  double* dist_basis = nullptr;  // [dist_terms][n_ap] pupil shapes of the modal disturbance in the masters' unit (aog_upload_disturbance_basis; aog_install_layer_sum_disturbed reads them)
+  int dist_terms = 0;
+  float* psi_tile = nullptr;    // [Bp/32][n_ptiles][4][64][4]
   double* psi64 = nullptr;       // validation: [B][n_ap]
   double* act_dm = nullptr;      // [B][A]
   float* act_rev = nullptr;      // [A_pad][Bp]

@@ -43,6 +43,19 @@ __device__ __forceinline__ void sincos_rev(float u, float& s, float& c) {
   }
 }
 
+// One rounded float64 product / sum that is never fused with its neighbour.  The library is compiled with the HIP default
+// -ffp-contract=fast, under which __dmul_rn / __dadd_rn are the plain operators and a product that feeds a sum becomes one fma wherever
+// both carry the `contract` flag; operations formed under contract(off) carry none, inlined or not.  For arithmetic a host replay must
+// reproduce bit for bit when the product is not exact.
+__device__ __forceinline__ double mul_rn(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ double add_rn(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
 __device__ __forceinline__ double block_reduce_sum(double v, double* sm) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

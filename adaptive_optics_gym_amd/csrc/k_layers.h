@@ -1,5 +1,6 @@
 // Layered atmosphere: the float64 master screens of up to 8 dynamic handles, each read through its own ring origin, summed into the
-// screen layouts of a quasi-static front handle (aog_install_layer_sum).
+// screen layouts of a quasi-static front handle (aog_install_layer_sum), optionally with a modal disturbance added inside that sum
+// (aog_install_layer_sum_disturbed: the *_dist kernels at the end).
 #pragma once
 #include "k_common.h"
 
@@ -71,6 +72,26 @@ __global__ __launch_bounds__(256) void k_layer_mean(LayerSources src, const int3
 // banks apart (one 16-B slot each, 16 distinct slots of the 64-bank row), the row-wise 4-byte writes are consecutive.
 // Pad pixels (p >= n_ap) and pad envs (>= B, whole pad env tiles included) are written as exact zeros.
 constexpr int kLayerIters = 4;
+// The tile staging of one iteration, from a wave's eight sums s[q] of pixel p (names of the enclosing kernel) to this pass's rows of
+// psi_tile: the one definition for k_layer_sum_tiles and k_layer_sum_tiles_dist.  Text, not a function: as an inlined function it changed
+// the register allocation and the schedule of k_layer_sum_tiles, whose machine code stays that of the kernel without the disturbance.
+#define AOG_LAYER_STAGE_ROWS()                                                                                                              \
+  if (it) __syncthreads(); /* the previous iteration's rows have left the staging tile */                                                   \
+  _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                                                           \
+    const int e = wave * 8 + q;                                                                                                             \
+    const bool ok = valid_p && et * 32 + e < B;                                                                                             \
+    stage[e * LD + lane] = ok ? (float)((s[q] - mean[min(et * 32 + e, B - 1)]) * inv_two_pi_lambda) : 0.f;                                  \
+  }                                                                                                                                         \
+  __syncthreads();                                                                                                                          \
+  /* rows of psi_tile: [et][pt][g][lane = 32 h + e][4]; this pass owns pt0, pt0 + 1 (8 rows); wave w writes rows 2w, 2w+1 */                \
+  for (int rr = 0; rr < 2; ++rr) {                                                                                                          \
+    const int row = wave * 2 + rr, tl = row >> 2, g = row & 3;                                                                              \
+    const int pt = pt0 + tl;                                                                                                                \
+    if (pt >= n_ptiles) continue;                                                                                                           \
+    const int h = lane >> 5, e = lane & 31;                                                                                                 \
+    const float* from = stage + e * LD + tl * 32 + 8 * g + 4 * h;                                                                           \
+    reinterpret_cast<float4*>(psi_tile)[(((size_t)et * n_ptiles + pt) * 4 + g) * 64 + lane] = make_float4(from[0], from[1], from[2], from[3]); \
+  }
 template <int L>
 __global__ __launch_bounds__(256) void k_layer_sum_tiles(LayerSources src, const int32_t* __restrict__ ap_index, const double* __restrict__ mean,
                                                           float* __restrict__ psi_tile, int B, int N, int n_ap, int n_ptiles, double inv_two_pi_lambda) {
@@ -97,23 +118,7 @@ __global__ __launch_bounds__(256) void k_layer_sum_tiles(LayerSources src, const
       }
       s[q] = layer_sum_at<L>(src, (size_t)env * N * N, iy, ix, oy, ox, N);
     }
-    if (it) __syncthreads();   // the previous iteration's rows have left the staging tile
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int e = wave * 8 + q;
-      const bool ok = valid_p && et * 32 + e < B;
-      stage[e * LD + lane] = ok ? (float)((s[q] - mean[min(et * 32 + e, B - 1)]) * inv_two_pi_lambda) : 0.f;
-    }
-    __syncthreads();
-    // rows of psi_tile: [et][pt][g][lane = 32 h + e][4]; this pass owns pt0, pt0 + 1 (8 rows); wave w writes rows 2w, 2w+1
-    for (int rr = 0; rr < 2; ++rr) {
-      const int row = wave * 2 + rr, tl = row >> 2, g = row & 3;
-      const int pt = pt0 + tl;
-      if (pt >= n_ptiles) continue;
-      const int h = lane >> 5, e = lane & 31;
-      const float* from = stage + e * LD + tl * 32 + 8 * g + 4 * h;
-      reinterpret_cast<float4*>(psi_tile)[(((size_t)et * n_ptiles + pt) * 4 + g) * 64 + lane] = make_float4(from[0], from[1], from[2], from[3]);
-    }
+    AOG_LAYER_STAGE_ROWS()
   }
 }
 
@@ -133,6 +138,120 @@ __global__ __launch_bounds__(256) void k_layer_sum_f64(LayerSources src, const i
   for (int p = threadIdx.x; p < n_ap; p += blockDim.x) {
     const int flat = ap_index[p], iy = flat / N, ix = flat - iy * N;
     psi64[(size_t)env * n_ap + p] = layer_sum_at<L>(src, env_base, iy, ix, oy, ox, N) - mu;
+  }
+}
+
+// ---- the same three passes with a modal disturbance added inside the sum (aog_install_layer_sum_disturbed, include/aogym_disturbance.h) ----
+// At env b and packed aperture pixel p: s = layer_sum_at, then s = s + coeff[b][k] basis[k][p] for k = 0 .. K - 1, each product rounded,
+// then each sum (mul_rn / add_rn of k_common.h, never one fma: the host restatement is bit-exact).  Kernels of their own beside the three above, which keep their
+// text and their machine code; layer_sum_at and AOG_LAYER_STAGE_ROWS are shared.  The coefficients of an env are uniform over the wave
+// that works on it (scalar loads); a basis row is read coalesced along p, once for all the envs or pixels a lane holds, and the K rows
+// stay in L2 (8 K n_ap bytes, shared by every env).
+constexpr int kMaxTerms = 8;
+struct ModalTerms {
+  const double* __restrict__ basis;   // [K][n_ap]
+  const double* __restrict__ coeff;   // [B][K]
+  int K, n_ap;
+};
+// s[j] += the K terms of env[j] at pixel p[j] (< n_ap), j < J
+template <int J>
+__device__ __forceinline__ void add_terms(const ModalTerms& terms, double (&s)[J], const int (&env)[J], const int (&p)[J]) {
+  for (int k = 0; k < terms.K; ++k) {
+    double b[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) b[j] = terms.basis[(size_t)k * terms.n_ap + p[j]];
+#pragma unroll
+    for (int j = 0; j < J; ++j) s[j] = add_rn(s[j], mul_rn(terms.coeff[(size_t)env[j] * terms.K + k], b[j]));
+  }
+}
+
+template <int L>
+__global__ __launch_bounds__(256) void k_layer_mean_dist(LayerSources src, ModalTerms terms, const int32_t* __restrict__ ap_index, double* __restrict__ mean,
+                                                          int N, int n_ap) {
+  __shared__ double sm[8];
+  const int env = blockIdx.x;
+  const size_t env_base = (size_t)env * N * N;
+  int oy[L], ox[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    ox[l] = src.origin[l][2 * env];
+    oy[l] = src.origin[l][2 * env + 1];
+  }
+  double acc = 0;
+  for (int p0 = threadIdx.x; p0 < n_ap; p0 += 8 * (int)blockDim.x) {
+    double s[8];
+    int envs[8], pc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int p = p0 + u * (int)blockDim.x;
+      envs[u] = env;
+      pc[u] = p < n_ap ? p : n_ap - 1;
+      const int flat = ap_index[pc[u]], iy = flat / N, ix = flat - iy * N;
+      s[u] = layer_sum_at<L>(src, env_base, iy, ix, oy, ox, N);
+    }
+    add_terms(terms, s, envs, pc);
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (p0 + u * (int)blockDim.x < n_ap) acc += s[u];
+  }
+  const double total = block_reduce_sum(acc, sm);
+  if (threadIdx.x == 0) mean[env] = total / (double)n_ap;
+}
+
+template <int L>
+__global__ __launch_bounds__(256) void k_layer_sum_tiles_dist(LayerSources src, ModalTerms terms, const int32_t* __restrict__ ap_index,
+                                                               const double* __restrict__ mean, float* __restrict__ psi_tile, int B, int N, int n_ap,
+                                                               int n_ptiles, double inv_two_pi_lambda) {
+  constexpr int LD = 68;
+  __shared__ float stage[32 * LD];
+  const int et = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int it = 0; it < kLayerIters; ++it) {
+    const int pt0 = (blockIdx.x * kLayerIters + it) * 2;
+    if (pt0 >= n_ptiles) break;   // uniform
+    const int p = pt0 * 32 + lane;
+    const bool valid_p = p < n_ap;
+    const int pc1 = valid_p ? p : n_ap - 1;
+    const int flat = ap_index[pc1];
+    const int iy = flat / N, ix = flat - iy * N;
+    double s[8];
+    int envs[8], pc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {   // (the env, and with it the origins and the coefficients, is wave-uniform: scalar loads)
+      const int env = min(et * 32 + wave * 8 + q, B - 1);
+      int oy[L], ox[L];
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        ox[l] = src.origin[l][2 * env];
+        oy[l] = src.origin[l][2 * env + 1];
+      }
+      envs[q] = env;
+      pc[q] = pc1;
+      s[q] = layer_sum_at<L>(src, (size_t)env * N * N, iy, ix, oy, ox, N);
+    }
+    add_terms(terms, s, envs, pc);
+    AOG_LAYER_STAGE_ROWS()
+  }
+}
+
+template <int L>
+__global__ __launch_bounds__(256) void k_layer_sum_f64_dist(LayerSources src, ModalTerms terms, const int32_t* __restrict__ ap_index,
+                                                             const double* __restrict__ mean, double* __restrict__ psi64, int N, int n_ap) {
+  const int env = blockIdx.x;
+  const size_t env_base = (size_t)env * N * N;
+  int oy[L], ox[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    ox[l] = src.origin[l][2 * env];
+    oy[l] = src.origin[l][2 * env + 1];
+  }
+  const double mu = mean[env];
+  for (int p = threadIdx.x; p < n_ap; p += blockDim.x) {
+    const int flat = ap_index[p], iy = flat / N, ix = flat - iy * N;
+    double s[1] = {layer_sum_at<L>(src, env_base, iy, ix, oy, ox, N)};
+    const int envs[1] = {env}, pc[1] = {p};
+    add_terms(terms, s, envs, pc);
+    psi64[(size_t)env * n_ap + p] = s[0] - mu;
   }
 }
 

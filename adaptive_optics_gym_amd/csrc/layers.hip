@@ -1,9 +1,13 @@
 // Layered atmosphere (several frozen-flow layers per env): the atmosphere-only step of a layer handle and the installation of the layers'
-// sum in a quasi-static front handle.  No existing launch changes: a handle that never comes here runs what it ran before.
+// sum in a quasi-static front handle, plain or with a modal disturbance added inside the sum.  No existing launch changes: a handle that
+// never comes here runs what it ran before, and an installation without a disturbance launches the kernels it launched before.
 #include "host_common.h"
 #include "k_layers.h"
+#include "../../include/aogym_disturbance.h"
 
 using namespace aog_host;
+
+static_assert(aog::kMaxTerms == AOG_DISTURBANCE_MAX_TERMS, "the disturbance's term limit");
 
 namespace {
 
@@ -19,6 +23,69 @@ namespace {
     case 7: hipLaunchKernelGGL((aog::KERNEL<7>), grid, block, 0, s, __VA_ARGS__); break;                 \
     default: hipLaunchKernelGGL((aog::KERNEL<8>), grid, block, 0, s, __VA_ARGS__); break;                \
   }
+
+// The one installation behind aog_install_layer_sum (coeff_dev null: the kernels without terms) and aog_install_layer_sum_disturbed
+// (`who` names the entry point in every message)
+int install_layer_sum(const char* who, aog_env* dst, aog_env* const* layers, int n_layers, const double* coeff_dev, int n_terms, bool disturbed,
+                      void* stream) {
+  if (!dst || !layers || (disturbed && !coeff_dev)) return fail(AOG_ERR_INVALID, "%s: null argument", who);
+  if (n_layers < 1 || n_layers > aog::kMaxLayers) return fail(AOG_ERR_INVALID, "%s: %d layers (1 .. %d)", who, n_layers, aog::kMaxLayers);
+  if (dst->cfg.atm_dynamic) return fail(AOG_ERR_INVALID, "%s: the front handle must not be atm_dynamic (its screens are installed, not evolved)", who);
+  if (!dst->tables_ready) return fail(AOG_ERR_INVALID, "%s before aog_upload_tables", who);
+  if (disturbed && !dst->dist_basis) return fail(AOG_ERR_INVALID, "%s before aog_upload_disturbance_basis", who);
+  if (disturbed && n_terms != dst->dist_terms)
+    return fail(AOG_ERR_INVALID, "%s: %d terms of coefficients, the uploaded basis has %d", who, n_terms, dst->dist_terms);
+  aog::LayerSources src{};
+  for (int l = 0; l < n_layers; ++l) {
+    const aog_env* y = layers[l];
+    if (!y) return fail(AOG_ERR_INVALID, "%s: layer %d is null", who, l);
+    if (!y->cfg.atm_dynamic || !y->screens_ready || !y->psi_master) return fail(AOG_ERR_INVALID, "%s: layer %d is not a dynamic handle with screens", who, l);
+    if (y->device != dst->device || y->cfg.n_pupil != dst->cfg.n_pupil || y->B != dst->B || y->cfg.env_id_base != dst->cfg.env_id_base)
+      return fail(AOG_ERR_INVALID, "%s: layer %d (device %d, N %d, B %d, env_id_base %d) does not match the front handle (device %d, N %d, B %d, "
+                  "env_id_base %d)", who, l, y->device, y->cfg.n_pupil, y->B, y->cfg.env_id_base, dst->device, dst->cfg.n_pupil, dst->B, dst->cfg.env_id_base);
+    if (y->pre_evolved) return fail(AOG_ERR_INVALID, "%s: the atmosphere of layer %d already stands at the next step (aog_set_lookahead)", who, l);
+    char layer_who[96];
+    std::snprintf(layer_who, sizeof layer_who, "%s (layer)", who);
+    if (int rc = check_poisoned(y, layer_who)) return rc;
+    src.master[l] = y->psi_master;
+    src.origin[l] = y->origin;
+  }
+  const bool fast = dst->cfg.precision == AOG_PRECISION_FAST;
+  if (fast && dst->kernel != AOG_KERNEL_MFMA)
+    return fail(AOG_ERR_UNSUPPORTED, "%s: the front handle runs the VALU kernel (its screen layout is not written here; use kernel 'auto' or 'mfma')", who);
+  if (int rc = check_poisoned(dst, who)) return rc;
+  HIP_TRY(hipSetDevice(dst->device));
+  if (!dst->layer_mean)
+    if (int rc = dev_alloc(dst, &dst->layer_mean, (size_t)dst->B, false)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int N = dst->cfg.n_pupil;
+  const dim3 tiles(((dst->n_ptiles + 1) / 2 + aog::kLayerIters - 1) / aog::kLayerIters, dst->n_etiles);
+  // pass 1 reads every master once; pass 2 reads them again (8 n_ap bytes per env and layer, mostly from L2 / Infinity Cache); the
+  // disturbed forms add the K basis rows (8 K n_ap bytes, shared by every env: L2) to each pass
+  if (disturbed) {
+    const aog::ModalTerms terms{dst->dist_basis, coeff_dev, n_terms, dst->n_ap};
+    AOG_LAYER_DISPATCH(n_layers, k_layer_mean_dist, dim3(dst->B), dim3(256), s, src, terms, dst->ap_index, dst->layer_mean, N, dst->n_ap);
+    if (fast) {
+      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_tiles_dist, tiles, dim3(256), s, src, terms, dst->ap_index, dst->layer_mean, dst->psi_tile, dst->B, N, dst->n_ap,
+                         dst->n_ptiles, rev_per_metre(dst));
+    } else {
+      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_f64_dist, dim3(dst->B), dim3(256), s, src, terms, dst->ap_index, dst->layer_mean, dst->psi64, N, dst->n_ap);
+    }
+  } else {
+    AOG_LAYER_DISPATCH(n_layers, k_layer_mean, dim3(dst->B), dim3(256), s, src, dst->ap_index, dst->layer_mean, N, dst->n_ap);
+    if (fast) {
+      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_tiles, tiles, dim3(256), s, src, dst->ap_index, dst->layer_mean, dst->psi_tile, dst->B, N, dst->n_ap, dst->n_ptiles,
+                         rev_per_metre(dst));
+    } else {
+      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_f64, dim3(dst->B), dim3(256), s, src, dst->ap_index, dst->layer_mean, dst->psi64, N, dst->n_ap);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  dst->screens_ready = true;
+  dst->reset_obs_valid = false;   // new screens: the kept reset observation is of the old ones
+  dst->sh_sums_ready = false;
+  return AOG_OK;
+}
 
 }  // namespace
 
@@ -42,47 +109,28 @@ int aog_evolve_atmosphere(aog_env* e, void* stream) {
 }
 
 int aog_install_layer_sum(aog_env* dst, aog_env* const* layers, int n_layers, void* stream) {
-  if (!dst || !layers) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: null argument");
-  if (n_layers < 1 || n_layers > aog::kMaxLayers) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: %d layers (1 .. %d)", n_layers, aog::kMaxLayers);
-  if (dst->cfg.atm_dynamic) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: the front handle must not be atm_dynamic (its screens are installed, not evolved)");
-  if (!dst->tables_ready) return fail(AOG_ERR_INVALID, "aog_install_layer_sum before aog_upload_tables");
-  aog::LayerSources src{};
-  for (int l = 0; l < n_layers; ++l) {
-    const aog_env* y = layers[l];
-    if (!y) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: layer %d is null", l);
-    if (!y->cfg.atm_dynamic || !y->screens_ready || !y->psi_master)
-      return fail(AOG_ERR_INVALID, "aog_install_layer_sum: layer %d is not a dynamic handle with screens", l);
-    if (y->device != dst->device || y->cfg.n_pupil != dst->cfg.n_pupil || y->B != dst->B || y->cfg.env_id_base != dst->cfg.env_id_base)
-      return fail(AOG_ERR_INVALID, "aog_install_layer_sum: layer %d (device %d, N %d, B %d, env_id_base %d) does not match the front handle (device %d, N %d, B %d, "
-                  "env_id_base %d)", l, y->device, y->cfg.n_pupil, y->B, y->cfg.env_id_base, dst->device, dst->cfg.n_pupil, dst->B, dst->cfg.env_id_base);
-    if (y->pre_evolved) return fail(AOG_ERR_INVALID, "aog_install_layer_sum: the atmosphere of layer %d already stands at the next step (aog_set_lookahead)", l);
-    if (int rc = check_poisoned(y, "aog_install_layer_sum (layer)")) return rc;
-    src.master[l] = y->psi_master;
-    src.origin[l] = y->origin;
-  }
-  const bool fast = dst->cfg.precision == AOG_PRECISION_FAST;
-  if (fast && dst->kernel != AOG_KERNEL_MFMA)
-    return fail(AOG_ERR_UNSUPPORTED, "aog_install_layer_sum: the front handle runs the VALU kernel (its screen layout is not written here; use kernel 'auto' or 'mfma')");
-  if (int rc = check_poisoned(dst, "aog_install_layer_sum")) return rc;
+  return install_layer_sum("aog_install_layer_sum", dst, layers, n_layers, nullptr, 0, false, stream);
+}
+
+int aog_upload_disturbance_basis(aog_env* dst, const double* basis_host, int n_terms) {
+  if (!dst || !basis_host) return fail(AOG_ERR_INVALID, "aog_upload_disturbance_basis: null argument");
+  if (n_terms < 1 || n_terms > aog::kMaxTerms) return fail(AOG_ERR_INVALID, "aog_upload_disturbance_basis: %d terms (1 .. %d)", n_terms, aog::kMaxTerms);
+  if (!dst->tables_ready) return fail(AOG_ERR_INVALID, "aog_upload_disturbance_basis before aog_upload_tables");
+  const size_t count = (size_t)n_terms * dst->n_ap;
+  for (size_t i = 0; i < count; ++i)
+    if (!std::isfinite(basis_host[i]))
+      return fail(AOG_ERR_INVALID, "aog_upload_disturbance_basis: term %d is not finite at aperture pixel %d", (int)(i / dst->n_ap), (int)(i % dst->n_ap));
   HIP_TRY(hipSetDevice(dst->device));
-  if (!dst->layer_mean)
-    if (int rc = dev_alloc(dst, &dst->layer_mean, (size_t)dst->B, false)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int N = dst->cfg.n_pupil;
-  // pass 1 reads every master once; pass 2 reads them again (8 n_ap bytes per env and layer, mostly from L2 / Infinity Cache)
-  AOG_LAYER_DISPATCH(n_layers, k_layer_mean, dim3(dst->B), dim3(256), s, src, dst->ap_index, dst->layer_mean, N, dst->n_ap);
-  if (fast) {
-    const dim3 grid(((dst->n_ptiles + 1) / 2 + aog::kLayerIters - 1) / aog::kLayerIters, dst->n_etiles);
-    AOG_LAYER_DISPATCH(n_layers, k_layer_sum_tiles, grid, dim3(256), s, src, dst->ap_index, dst->layer_mean, dst->psi_tile, dst->B, N, dst->n_ap, dst->n_ptiles,
-                       rev_per_metre(dst));
-  } else {
-    AOG_LAYER_DISPATCH(n_layers, k_layer_sum_f64, dim3(dst->B), dim3(256), s, src, dst->ap_index, dst->layer_mean, dst->psi64, N, dst->n_ap);
-  }
-  HIP_TRY(hipGetLastError());
-  dst->screens_ready = true;
-  dst->reset_obs_valid = false;   // new screens: the kept reset observation is of the old ones
-  dst->sh_sums_ready = false;
+  HIP_TRY(hipDeviceSynchronize());   // (an installation that reads the basis being replaced may still be queued)
+  if (dst->dist_basis && dst->dist_terms != n_terms) dev_release(dst, &dst->dist_basis);
+  dst->dist_terms = 0;
+  if (int rc = upload(dst, &dst->dist_basis, basis_host, count, true)) return rc;
+  dst->dist_terms = n_terms;
   return AOG_OK;
+}
+
+int aog_install_layer_sum_disturbed(aog_env* dst, aog_env* const* layers, int n_layers, const double* coeff_dev, int n_terms, void* stream) {
+  return install_layer_sum("aog_install_layer_sum_disturbed", dst, layers, n_layers, coeff_dev, n_terms, true, stream);
 }
 
 }  // extern "C"

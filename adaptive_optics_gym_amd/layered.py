@@ -10,8 +10,11 @@ unchanged.
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
+from . import _lib
 from .batched_env import BatchedAOEnv, _mask_array
 from .params import resolve_per_env, resolve_turbulence
 
@@ -64,6 +67,10 @@ class LayeredAOEnv(BatchedAOEnv):
     ``screens`` do not apply) plus
 
     atm_layers   [{"fraction": f_l, "speed": v_l}, ...], 1 .. 8 layers (``resolve_layers``); ``atm_fried`` is the r0 of their sum.
+    disturbance  None, or dict(shapes=, vibrations=, static=) for a ``disturbance.ModalDisturbance``: vibration lines and static
+                 aberrations on K <= 8 pupil shapes, advanced once per step and added inside the layer sum (so everything that reads the
+                 front sees them).  ``env.disturbance`` is the object; ``get_state`` / ``set_state`` carry its state; ``set_turbulence`` and
+                 ``reset`` leave it alone.  Without it the env runs exactly the launches it ran before.
 
     Layer l is a private dynamic env with a seed of its own (``layer_seed``) and therefore wind directions and stencil draws of its own,
     as the reference draws them per layer; it shares this env's tables, ``extrusion``, ``screen_source`` and global env ids.  ``reset`` is
@@ -76,9 +83,10 @@ class LayeredAOEnv(BatchedAOEnv):
     def __init__(self, num_envs=1, device=None, atm_layers=None, atm_fried=0.15, act_type="num_actuators", act_dim=64, obs_dim=2,
                  rew_type="strehl_ratio", rew_threshold=None, timesteps_per_episode=20, flat_mirror_start_per_episode=True, SH_operation=False, *,
                  atm_type="dynamic", seed=None, screen_source="device", rng=None, global_env_offset=0, total_envs=None, extrusion="auto",
-                 verbose=True, **kw):
+                 verbose=True, disturbance=None, **kw):
         self._layers = []
         self._handle = None
+        self.disturbance = None
         if atm_type != "dynamic":
             raise ValueError("LayeredAOEnv: atm_type is 'dynamic' (a layered atmosphere evolves every step)")
         for bad in ("atm_vel", "screens"):
@@ -103,6 +111,8 @@ class LayeredAOEnv(BatchedAOEnv):
                                                  tables=self.tables, extrusion=extrusion, verbose=False, **layer_kw))
             self.velocity_vectors = np.stack([lay.velocity_vectors for lay in self._layers])   # [L, B, 2] m/s
             self.velocity = [lay.velocity for lay in self._layers]
+            if disturbance is not None:
+                self._attach_disturbance(disturbance)
             self._install()   # the first reset sees t = 0
         except Exception:
             self.close()
@@ -124,12 +134,50 @@ class LayeredAOEnv(BatchedAOEnv):
     def _host_extrusion_noise(self):
         """The layers draw their own normals (``evolve_atmosphere``)."""
 
+    def _attach_disturbance(self, disturbance):
+        """``disturbance``: dict(shapes=, vibrations=, static=[, seed=]) for a ``ModalDisturbance`` of this env, or such an object made for
+        this env's batch, global env ids and device.  Its basis goes to the front; from here on every installation is the disturbed form."""
+        from .disturbance import ModalDisturbance
+
+        if isinstance(disturbance, dict):
+            if not set(disturbance) <= {"shapes", "vibrations", "static", "seed"} or "shapes" not in disturbance:
+                raise ValueError("disturbance: a dict with 'shapes' and, optionally, 'vibrations', 'static' and 'seed'")
+            disturbance = ModalDisturbance(self, **disturbance)
+        elif not isinstance(disturbance, ModalDisturbance):
+            raise ValueError("disturbance: a dict(shapes=, vibrations=, static=) or a ModalDisturbance")
+        d = disturbance
+        index = self.device.index if self.device.index is not None else self._torch.cuda.current_device()
+        if d.device.index != index or d.num_envs != self.num_envs or d.global_env_offset != self.global_env_offset:
+            raise ValueError(f"disturbance: made for {d.num_envs} envs from global id {d.global_env_offset} on {d.device}, this env has "
+                             f"{self.num_envs} from {self.global_env_offset} on {self.device}")
+        if d.basis.shape[1] != int(self.tables.n_ap):
+            raise ValueError(f"disturbance: its shapes cover {d.basis.shape[1]} aperture pixels, this env's pupil has {int(self.tables.n_ap)}")
+        d.upload_basis(self)
+        self.disturbance = d
+        self._coeff = d.coefficients()
+
     def _install(self):
-        self.install_layer_sum(self._layers)
+        if self.disturbance is None:
+            self.install_layer_sum(self._layers)
+        else:
+            self.install_layer_sum_disturbed(self._layers, self._coeff)
+
+    def install_layer_sum_disturbed(self, layers, coeff):
+        """``install_layer_sum`` with ``sum_k coeff[b][k] shape_k`` added inside the float64 sum (``aog_install_layer_sum_disturbed``; the
+        shapes are those last uploaded with ``ModalDisturbance.upload_basis``).  ``coeff``: [B, K] float64 device tensor, metres of optical path."""
+        torch = self._torch
+        if not isinstance(coeff, torch.Tensor) or coeff.dtype != torch.float64 or coeff.dim() != 2 or coeff.shape[0] != self.num_envs or not coeff.is_contiguous():
+            raise ValueError(f"install_layer_sum_disturbed: coeff must be a contiguous float64 [{self.num_envs}, K] device tensor")
+        handles = (C.c_void_p * len(layers))(*[lay._handle.value for lay in layers])
+        _lib.check(self.lib.aog_install_layer_sum_disturbed(self._handle, handles, len(layers), C.c_void_p(coeff.data_ptr()), int(coeff.shape[1]),
+                                                            self._stream()))
+        self.state_epoch += 1
 
     def _advance(self):
         for lay in self._layers:
             lay.evolve_atmosphere()
+        if self.disturbance is not None:
+            self._coeff = self.disturbance.advance()
         self._install()
 
     def step(self, actions, out=None, next_actions=BatchedAOEnv._PIPELINE_END):
@@ -188,13 +236,21 @@ class LayeredAOEnv(BatchedAOEnv):
     def get_state(self):
         state = super().get_state()
         state["layers"] = [lay.get_state() for lay in self._layers]
+        if self.disturbance is not None:
+            state["disturbance"] = self.disturbance.state_dict()
         return state
 
     def set_state(self, state):
         if len(state.get("layers", ())) != len(self._layers):
             raise ValueError("set_state: the state was saved with another number of layers")
+        if ("disturbance" in state) != (self.disturbance is not None):
+            raise ValueError("set_state: the state was saved " + ("with" if "disturbance" in state else "without") + " a disturbance, this env was built "
+                             + ("without" if self.disturbance is None else "with") + " one")
         for lay, st in zip(self._layers, state["layers"]):
             lay.set_state(st)
+        if self.disturbance is not None:
+            self.disturbance.load_state_dict(state["disturbance"])
+            self._coeff = self.disturbance.coefficients()
         super().set_state(state)
         self._install()   # (the front's blob holds the same tiles; installing again keeps one path)
 
@@ -202,4 +258,7 @@ class LayeredAOEnv(BatchedAOEnv):
         for lay in self.__dict__.get("_layers", ()):
             lay.close()
         self._layers = []
+        if self.__dict__.get("disturbance") is not None:
+            self.disturbance.close()
+            self.disturbance = None
         super().close()

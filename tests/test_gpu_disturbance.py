@@ -1,0 +1,390 @@
+"""The modal disturbance on the device: the generator (aog_disturbance_*, k_disturbance) against a host replay of its recorded normals, the
+disturbed installation (aog_install_layer_sum_disturbed: k_layer_mean_dist, k_layer_sum_tiles_dist, k_layer_sum_f64_dist) against the host
+restatement, and ``LayeredAOEnv(disturbance=...)`` on top of them.
+
+Shapes follow test_gpu_layered.py: N = 32 and 48 (n_ap no multiple of 64: the last pair of pixel tiles is half empty), B in {1, 5, 33} (an
+env tile with pad envs, a second tile almost empty), A = 6 Zernike modes."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import disturbance_reference as ref
+import layered_reference as lref
+from test_gpu_layered import _actions, _kw, _layers, _step_tensors
+from test_gpu_parity import _torch
+
+pytestmark = pytest.mark.gpu
+
+DT = 1e-3
+
+
+def _static_env(B, N=32, **more):
+    from adaptive_optics_gym_amd import BatchedAOEnv
+
+    return BatchedAOEnv(B, "cuda:0", atm_type="quasi_static", atm_fried=0.15, seed=11, screens=np.zeros((B, N, N)), **_kw(N=N, **more))
+
+
+def _layered(B, L=2, seed=11, r0=0.15, disturbance=None, **kw):
+    from adaptive_optics_gym_amd import LayeredAOEnv
+
+    return LayeredAOEnv(B, "cuda:0", atm_layers=_layers(L), atm_fried=r0, seed=seed, disturbance=disturbance, **_kw(**kw))
+
+
+def _generator(B, K, seed=5, offset=0, total=None, host=None):
+    """A ModalDisturbance of K explicit random shapes with a vibration on every term (per-env frequencies and rms keyed by global env id)."""
+    from adaptive_optics_gym_amd import ModalDisturbance
+
+    total = B if total is None else total
+    host = _static_env(B, global_env_offset=offset, total_envs=total) if host is None else host
+    N = host.num_pupil_pixels
+    shapes = np.random.RandomState(1).randn(K, N, N)
+    g = np.arange(total)
+    vib = [dict(term=k, frequency=20.0 + 7.0 * k + g, damping=0.02 + 0.01 * k, rms=1e-8 * (1 + k) * (1.0 + 0.1 * g)) for k in range(K)]
+    static = np.random.RandomState(2).randn(total, K)[offset:offset + B] * 1e-8
+    return host, ModalDisturbance(host, shapes, vibrations=vib, static=static, seed=seed)
+
+
+def _split_blob(blob, B, K):
+    raw = blob.cpu().numpy()
+    n = 8 * B * K
+    return raw[:n].view(np.float64).reshape(B, K), raw[n:2 * n].view(np.float64).reshape(B, K), int(raw[2 * n:].view(np.uint64)[0])
+
+
+# ---- 1. generator against the host replay ----------------------------------------------------------------------------------------------------
+def test_generator_equals_the_host_replay_of_its_normals():
+    torch = _torch()
+    B, K, T = 5, 3, 64
+    host, gen = _generator(B, K)
+    model = ref.Generator(gen.params)
+    start = torch.zeros((B, K, 2), dtype=torch.float64, device="cuda")
+    gen.reset(noise_out=start)
+    model.counter = 1          # (the constructor's own reset came first; this one redraws every env at counter 1)
+    model.reset(start.cpu().numpy())
+    x, x_prev, counter = _split_blob(gen.get_state(), B, K)
+    np.testing.assert_array_equal(x, model.x)
+    np.testing.assert_array_equal(x_prev, model.x_prev)
+    assert counter == model.counter == 2
+    masks = [np.array([True, False, True, True, False]), np.array([False, True, True, False, True])]
+    noise = torch.zeros((B, K), dtype=torch.float64, device="cuda")
+    for t in range(T):
+        mask = masks[t >= T // 2] if t % 3 else None
+        noise.fill_(float("nan"))
+        got = gen.advance(None if mask is None else torch.from_numpy(mask).cuda(), noise_out=noise).cpu().numpy()
+        n = noise.cpu().numpy()
+        sel = np.ones(B, dtype=bool) if mask is None else mask
+        assert np.all(np.isfinite(n[sel])) and np.all(np.isnan(n[~sel])), "normals are written for the selected envs only"
+        want = model.advance(np.nan_to_num(n), mask)
+        np.testing.assert_array_equal(got, want, err_msg=f"advance {t}")
+        np.testing.assert_array_equal(gen.coefficients().cpu().numpy(), model.coefficients())
+    assert np.array_equal(gen.get_state().cpu().numpy(), model.blob())
+    assert float(np.abs(model.x).min()) > 0
+    gen.close(), host.close()
+
+
+# ---- 2. statistics of the normals ----------------------------------------------------------------------------------------------------------
+def test_normals_are_standard():
+    """65 536 seeded normals: |mean| < 0.02, |variance - 1| < 0.03 (about 5 standard errors: 0.0039 and 0.0055)."""
+    torch = _torch()
+    B, K, T = 64, 4, 256
+    host, gen = _generator(B, K, seed=2024)
+    noise = torch.zeros((B, K), dtype=torch.float64, device="cuda")
+    rows = []
+    for _ in range(T):
+        gen.advance(noise_out=noise)
+        rows.append(noise.clone())
+    n = torch.stack(rows).cpu().numpy()
+    assert n.size == 65536
+    mean, var = float(n.mean()), float(n.var())
+    print(f"normals: mean {mean:+.5f}, variance {var:.5f}")
+    assert abs(mean) < 0.02 and abs(var - 1.0) < 0.03
+    assert np.unique(n).size > 0.99 * n.size   # (no stream repeats another)
+    gen.close(), host.close()
+
+
+# ---- 3. batch independence and resume ------------------------------------------------------------------------------------------------------
+def test_split_handles_reproduce_the_whole_and_a_checkpoint_resumes():
+    torch = _torch()
+    B, K = 33, 3
+    host, whole = _generator(B, K, total=B)
+    parts = [_generator(16, K, offset=0, total=B), _generator(17, K, offset=16, total=B)]
+    cat = lambda f: torch.cat([f(g) for _, g in parts], dim=0)
+    assert torch.equal(whole.coefficients(), cat(lambda g: g.coefficients()))
+    mask = torch.from_numpy(np.arange(B) % 3 != 1).cuda()
+    for t in range(6):
+        m = mask if t == 3 else None
+        got = whole.advance(m).clone()
+        halves = torch.cat([parts[0][1].advance(None if m is None else m[:16].contiguous()),
+                            parts[1][1].advance(None if m is None else m[16:].contiguous())], dim=0)
+        assert torch.equal(got, halves), f"advance {t}"
+    whole.reset(mask)
+    parts[0][1].reset(mask[:16].contiguous()), parts[1][1].reset(mask[16:].contiguous())
+    assert torch.equal(whole.advance(), cat(lambda g: g.advance()))
+    # resume
+    for _ in range(10):
+        whole.advance()
+    state = whole.state_dict()
+    first = [whole.advance().clone() for _ in range(10)]
+    whole.load_state_dict(state)
+    again = [whole.advance().clone() for _ in range(10)]
+    assert all(torch.equal(a, b) for a, b in zip(first, again)) and not torch.equal(first[0], first[1])
+    with pytest.raises(ValueError, match="another disturbance"):
+        parts[0][1].load_state_dict(state)
+    for h, g in [(host, whole)] + parts:
+        g.close(), h.close()
+
+
+# ---- 4. install against the restatement ----------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def layer_sets():
+    """Per (N, B): three evolved dynamic layers whose rings have turned (shared by every case; nothing below changes them)."""
+    torch = _torch()
+    from adaptive_optics_gym_amd import BatchedAOEnv
+
+    sets = {}
+    for N in (32, 48):
+        for B in (1, 33):
+            lays = [BatchedAOEnv(B, "cuda:0", atm_type="dynamic", atm_vel=30.0 + 20.0 * i, atm_fried=0.15, seed=3 + i, **_kw(N=N, T=0)) for i in range(3)]
+            for lay in lays:
+                for _ in range(3):
+                    lay.evolve_atmosphere()
+            sets[N, B] = lays
+    torch.cuda.synchronize()
+    yield sets
+    for lays in sets.values():
+        for lay in lays:
+            lay.close()
+
+
+def _install(front, layers, coeff):
+    handles = (C.c_void_p * len(layers))(*[lay._handle.value for lay in layers])
+    rc = front.lib.aog_install_layer_sum_disturbed(front._handle, handles, len(layers), C.c_void_p(coeff.data_ptr()), int(coeff.shape[1]), front._stream())
+    return rc, front.lib.aog_last_error().decode()
+
+
+def _upload(front, basis_master):
+    b = np.ascontiguousarray(basis_master, dtype=np.float64)
+    return front.lib.aog_upload_disturbance_basis(front._handle, b.ctypes.data_as(C.c_void_p), int(b.shape[0])), front.lib.aog_last_error().decode()
+
+
+@pytest.mark.parametrize("precision", ["fast", "fp64"])
+@pytest.mark.parametrize("K", [1, 8])
+@pytest.mark.parametrize("L", [1, 3])
+@pytest.mark.parametrize("N,B", [(32, 1), (32, 33), (48, 1), (48, 33)])
+def test_install_matches_the_host_restatement(layer_sets, N, B, L, K, precision):
+    """float64 front: psi64 bit for bit (the restatement sums the mean in the fixed order the header states).  Fast front: the standard of
+    test_gpu_layered.test_install_matches_the_host_restatement — one fp32 ulp of the value, pad pixels and pad envs exact zeros.  All-zero
+    coefficients give the bits of aog_install_layer_sum."""
+    torch = _torch()
+    layers = layer_sets[N, B][:L]
+    front = _static_env(B, N=N, precision=precision)
+    ap = np.asarray(front.tables.ap_index)
+    n_ap = ap.size
+    assert n_ap % 64 != 0
+    rng = np.random.RandomState(100 * K + L)
+    basis = rng.randn(K, n_ap) * 2 * np.pi
+    coeff = rng.randn(B, K) * 1e-7
+    assert _upload(front, basis)[0] == 0
+    cdev = torch.from_numpy(coeff).cuda()
+    rc, msg = _install(front, layers, cdev)
+    assert rc == 0, msg
+    fp64 = precision == "fp64"
+    got = lref.front_store(front, fp64=fp64)
+    screens = [lay.get_screens().cpu().numpy() for lay in layers]
+    want = ref.install(screens, [np.zeros((B, 2), dtype=int)] * L, ap, N, front.wavelength_wfs, coeff, basis)
+    if fp64:
+        np.testing.assert_array_equal(got, want["psi64"])
+    else:
+        assert got.shape == want["tiles"].shape
+        rev, pad_nonzero = lref.unpack_tiles(got, B, n_ap)
+        assert pad_nonzero == 0
+        err = np.abs(rev.astype(np.float64) - want["rev"].astype(np.float64))
+        ulp = np.spacing(np.abs(want["rev"])).astype(np.float64)
+        print(f"N={N} B={B} L={L} K={K}: {np.count_nonzero(err)} of {err.size} values differ, worst {np.max(err / ulp):.2f} ulp")
+        assert np.all(err <= ulp)
+    assert np.abs(want["s"] - lref.layer_sum(screens, [np.zeros((B, 2), dtype=int)] * L, ap, N)).max() > 1e-8   # (the terms are there)
+    # zero coefficients: the plain installation's bits
+    rc, msg = _install(front, layers, torch.zeros_like(cdev))
+    assert rc == 0, msg
+    zero = lref.front_store(front, fp64=fp64).copy()
+    front.install_layer_sum(layers)
+    np.testing.assert_array_equal(zero, lref.front_store(front, fp64=fp64))
+    front.close()
+
+
+# ---- 5. linearity seen through an instrument -------------------------------------------------------------------------------------------------
+def test_a_static_shape_moves_the_ideal_actuators_by_its_own_fit():
+    """wavefront_truth is linear in the screen: ideal_actuators with a static disturbance c x shape minus those without equal -coef / 2 of the
+    least-squares fit of c x shape alone on the env's own modes (tests/wavefront_reference.py's definition), to 1e-9 of its largest entry.
+    float64 fronts: the two screens differ by the shape and by float64 rounding only."""
+    from wavefront_reference import truth_of
+
+    B, N, c = 5, 32, 4e-8
+    plain = _layered(B, N=N, precision="fp64")
+    dist = _layered(B, N=N, precision="fp64", disturbance=dict(shapes=["focus"], static=[c]))
+    plain.reset(), dist.reset()
+    diff = (dist.wavefront_truth()["ideal_actuators"] - plain.wavefront_truth()["ideal_actuators"]).cpu().numpy()
+    w = c * dist.disturbance.basis        # [1, n_ap] metres of optical path
+    want = truth_of(w, plain.tables.modes, np.zeros((1, plain.num_modes)))["ideal_actuators"][0]
+    scale = np.abs(want).max()
+    assert scale > 1e-9
+    print(f"linearity: worst {np.abs(diff - want[None]).max() / scale:.2e} of the largest entry")
+    np.testing.assert_allclose(diff, np.broadcast_to(want, diff.shape), rtol=0, atol=1e-9 * scale)
+    plain.close(), dist.close()
+
+
+# ---- 6. the loop sees the vibration ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("f0", [62.5])
+def test_the_vibration_line_shows_in_the_modal_psd(f0):
+    torch = _torch()
+    from adaptive_optics_gym_amd import ModalTelemetry
+
+    B, N, T = 4, 32, 512
+    # rms: at r0 = 1 m and D = 0.5 m the turbulence leaves ~0.45 (D / r0)^(5/3) rad^2 = (0.38 rad)^2 of tip and tilt, ~6e-8 m of path per
+    # axis, below 0.3 v / D ~ 20 .. 40 Hz; a 2e-7 m line (0.13 waves at 1.5 um) carries ten times that variance within one or two bins
+    vib = dict(shapes=["tip"], vibrations=[dict(term=0, frequency=f0, damping=0.02, rms=2e-7)])
+    peaks = {}
+    for name, disturbance in (("with", vib), ("without", None)):
+        env = _layered(B, N=N, T=T, r0=1.0, disturbance=disturbance)
+        tel = ModalTelemetry(B, env.num_modes, length=T, device="cuda:0")
+        act = _actions(torch, 1, B, env.num_modes)[0]
+        env.reset()
+        for _ in range(T):
+            env.step(act)
+            tel.push(env.wavefront_truth()["ideal_actuators"])   # (the pseudo-open-loop measurement: independent of the mirror)
+        psd = tel.psd()[1].cpu().numpy()     # [B, A, S / 2 + 1]
+        S = 2 * (psd.shape[-1] - 1)
+        if name == "with":
+            tip = np.asarray(env.disturbance.basis[0])
+            mode = int(np.argmax(np.abs(tip @ np.asarray(env.tables.modes)) / np.linalg.norm(env.tables.modes, axis=0)))
+            want_bin = int(np.argmin(np.abs(np.arange(S // 2 + 1) / (S * DT) - f0)))
+        peaks[name] = np.argmax(psd[:, mode, :], axis=-1)
+        env.close(), tel.close()
+    print(f"tip mode {mode}, bin of {f0} Hz: {want_bin}; peaks with {peaks['with']}, without {peaks['without']}")
+    assert np.all(peaks["with"] == want_bin) and np.all(peaks["without"] != want_bin)
+
+
+# ---- 7. whole-env properties ---------------------------------------------------------------------------------------------------------------------
+DIST = dict(shapes=["tip", "tilt", "focus"], vibrations=[dict(term=0, frequency=30.0, damping=0.02, rms=4e-8),
+                                                          dict(term=1, frequency=45.0, damping=0.05, rms=np.linspace(1e-8, 5e-8, 33))],
+            static=[0.0, 1e-8, -3e-8])
+
+
+def test_split_batch_reproduces_the_whole_batch():
+    torch = _torch()
+    B, N, A, T = 33, 32, 6, 4
+    whole = _layered(B, N=N, A=A, T=T, total_envs=B, disturbance=DIST)
+    halves = [_layered(n, N=N, A=A, T=T, global_env_offset=off, total_envs=B, disturbance=DIST) for off, n in ((0, 16), (16, 17))]
+    acts = _actions(torch, T, B, A)
+    cat = lambda xs: torch.cat(list(xs), dim=0)
+    assert torch.equal(whole.reset()[0], cat(h.reset()[0] for h in halves))
+    for t in range(T):
+        rw = _step_tensors(whole.step(acts[t]))
+        rh = [_step_tensors(h.step(acts[t, off:off + n].contiguous())) for h, (off, n) in zip(halves, ((0, 16), (16, 17)))]
+        for k, x in enumerate(rw):
+            assert torch.equal(x, cat(r[k] for r in rh)), f"step {t}, output {k}"
+        assert torch.equal(whole.disturbance.coeff, cat(h.disturbance.coeff for h in halves))
+    assert float(whole.disturbance.coeff.abs().min()) > 0
+    for e in [whole] + halves:
+        e.close()
+
+
+def test_state_restore_resumes_bit_identically():
+    torch = _torch()
+    B, N, A, T = 5, 32, 6, 6
+    env = _layered(B, N=N, A=A, T=T, disturbance=DIST | {"vibrations": DIST["vibrations"][:1]})
+    acts = _actions(torch, T, B, A)
+    env.reset()
+    for t in range(2):
+        env.step(acts[t])
+    state = env.get_state()
+    run = lambda e: [_step_tensors(e.step(acts[t])) + [e.disturbance.coeff.clone(), e.wavefront_truth()["coef"].clone()] for t in range(2, 5)]
+    first = run(env)
+    env.set_turbulence(0.2)     # (leaves the generator alone: the next coefficients are those of a run without it)
+    nxt = env.disturbance.advance().clone()
+    env.set_state(state)
+    again = run(env)
+    other = _layered(B, N=N, A=A, T=T, disturbance=DIST | {"vibrations": DIST["vibrations"][:1]})
+    other.set_state(state)
+    third = run(other)
+    for a, b, c in zip(first, again, third):
+        for x, y, z in zip(a, b, c):
+            assert torch.equal(x, y) and torch.equal(x, z)
+    assert torch.equal(other.disturbance.advance(), nxt)
+    bare = _layered(B, N=N, A=A, T=T)
+    with pytest.raises(ValueError, match="disturbance"):
+        bare.set_state(state)
+    with pytest.raises(ValueError, match="disturbance"):
+        env.set_state(bare.get_state())
+    for e in (env, other, bare):
+        e.close()
+
+
+def test_fused_policy_stepping_equals_the_unfused_loop():
+    torch = _torch()
+    from adaptive_optics_gym_amd.rollout import DeviceActor, make_actor, rollout
+
+    B, N, A, T = 5, 32, 8, 4
+    torch.manual_seed(3)
+    actor = make_actor(4, A, 32, device="cuda:0")
+    outs = []
+    for fused in (False, True):
+        env = _layered(B, N=N, A=A, T=T, disturbance=DIST | {"vibrations": DIST["vibrations"][:1]})
+        outs.append(rollout(env, actor, episodes=2, actor_impl="hip", dev_actor=DeviceActor(actor, seed=10), fused_policy=fused))
+        outs[-1]["_coeff"] = env.disturbance.coeff.clone()
+        env.close()
+    compared = 0
+    for k, v in outs[0].items():
+        if isinstance(v, torch.Tensor):
+            assert torch.equal(v, outs[1][k]), k
+            compared += 1
+    assert compared >= 5
+
+
+def test_refusals_name_their_reason_and_leave_the_front_usable(layer_sets):
+    torch = _torch()
+    from adaptive_optics_gym_amd import LayeredAOEnv, ModalDisturbance
+
+    B, N, A = 33, 32, 6
+    layers = layer_sets[N, B][:2]
+    env = _layered(B, N=N, A=A, disturbance=DIST)
+    before = lref.front_store(env).copy()
+    coeff = torch.zeros((B, 3), dtype=torch.float64, device="cuda")
+    bare = _static_env(B, N=N)
+    valu = _static_env(B, N=N, kernel="valu")
+    assert _upload(valu, env.disturbance.basis_master)[0] == 0
+    n_ap = int(env.tables.n_ap)
+    for rc_msg, code, word in ((_install(bare, layers, coeff), -1, "aog_upload_disturbance_basis"),
+                               (_install(env, list(env.layers), coeff[:, :2].contiguous()), -1, "2 terms"),
+                               (_install(valu, layers, coeff), -4, "VALU"),
+                               (_install(env, [layer_sets[N, 1][0]], coeff), -1, "does not match"),
+                               (_upload(bare, np.zeros((9, n_ap))), -1, "9 terms"),
+                               (_upload(bare, np.full((1, n_ap), np.nan)), -1, "not finite")):
+        rc, msg = rc_msg
+        assert rc == code and word in msg and "disturb" in msg, (rc, msg)
+    # a generator made for another batch (or another device) is refused before anything is created for it
+    small = _static_env(B - 5, N=N)
+    wrong = ModalDisturbance(small, ["tip"])
+    with pytest.raises(ValueError, match="disturbance: made for 28 envs"):
+        LayeredAOEnv(B, "cuda:0", atm_layers=_layers(2), atm_fried=0.15, seed=11, disturbance=wrong, **_kw(N=N, A=A))
+    if torch.cuda.device_count() > 1:
+        from adaptive_optics_gym_amd import BatchedAOEnv
+
+        far_host = BatchedAOEnv(B, "cuda:1", atm_type="quasi_static", atm_fried=0.15, seed=11, screens=np.zeros((B, N, N)), **_kw(N=N))
+        far = ModalDisturbance(far_host, ["tip"])
+        with pytest.raises(ValueError, match="disturbance: made for"):
+            LayeredAOEnv(B, "cuda:0", atm_layers=_layers(2), atm_fried=0.15, seed=11, disturbance=far, **_kw(N=N, A=A))
+        far.close(), far_host.close()
+    with pytest.raises(ValueError, match="shapes"):
+        _layered(B, N=N, A=A, disturbance=dict(vibrations=[]))
+    with pytest.raises(ValueError, match="coeff"):
+        env.install_layer_sum_disturbed(env.layers, coeff.float())
+    # nothing was written, and the front still steps
+    np.testing.assert_array_equal(lref.front_store(env), before)
+    env.reset()
+    obs, rew, done, _, info = env.step(_actions(torch, 1, B, A)[0])
+    assert bool(torch.isfinite(info["obs_raw"]).all()) and 0 <= float(info["strehl"].min()) <= float(info["strehl"].max()) <= 1
+    assert env.device_status() == 0
+    wrong.close()
+    for e in (env, bare, valu, small):
+        e.close()
