@@ -10,12 +10,12 @@
 """
 from .batched_env import BatchedAOEnv  # noqa: F401
 from .disturbance import ModalDisturbance  # noqa: F401
-from .layered import LayeredAOEnv  # noqa: F401
+from .layered import LayeredAOEnv, Sightline  # noqa: F401
 from .link import LinkTelemetry  # noqa: F401
 from .params import OpticalParams  # noqa: F401
 from .telemetry import ModalIntegrator, ModalTelemetry  # noqa: F401
 
-__all__ = ["BatchedAOEnv", "LayeredAOEnv", "LinkTelemetry", "ModalDisturbance", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "register"]
+__all__ = ["BatchedAOEnv", "LayeredAOEnv", "LinkTelemetry", "ModalDisturbance", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "Sightline", "register"]
 
 
 def register():

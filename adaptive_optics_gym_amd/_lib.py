@@ -245,6 +245,11 @@ DISTURBANCE_SYMBOLS = {
     "aog_install_layer_sum_disturbed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
+# every symbol include/aogym_sightline.h declares
+SIGHTLINE_SYMBOLS = {
+    "aog_install_layer_sum_sightline": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -262,7 +267,7 @@ def load():
     except Exception:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

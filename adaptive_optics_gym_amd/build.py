@@ -4,7 +4,7 @@ One translation unit per kernel family, compiled in parallel: ``aogym.hip`` (C-A
 (dynamic atmosphere), ``screens.hip`` (screen synthesis), ``shack.hip`` (Shack-Hartmann chain), ``focal.hip`` (K4 and the separable observation K11), ``actor.hip`` (policy query),
 ``wavefront.hip`` (wavefront fit K12), ``science.hip`` (science camera K13), ``gradient.hip`` (output gradient K14), ``gradient_obs.hip`` (its observation part on the separable route), ``layers.hip`` (layered atmosphere: sum of several dynamic handles), ``pyramid.hip`` (pyramid wavefront sensor), ``pyramid_grad.hip`` (its gradient), ``predictor.hip`` (predictive controller K17), ``telemetry.hip`` (modal telemetry K18), ``spgd.hip`` (SPGD controller K19), ``link.hip`` (link telemetry K20), ``disturbance.hip`` (modal disturbance generator K21) and ``fused_inst.hip`` once per padded mode count (the fused-kernel template instantiations).
 
-The library is tied to its sources: ``source_id()`` is a SHA-256 over ``csrc/*.{h,hip}`` + ``include/aogym.h`` + ``include/aogym_disturbance.h``; it is compiled into the core
+The library is tied to its sources: ``source_id()`` is a SHA-256 over ``csrc/*.{h,hip}`` + ``include/aogym.h`` + ``include/aogym_disturbance.h`` + ``include/aogym_sightline.h``; it is compiled into the core
 unit (``aog_build_id()``), ``needs_build()`` compares it with the id the existing library reports (not file times), every object carries the
 hash of what it was compiled from (``build/<name>.o.id``) so an edit recompiles only the units it touches, and ``_lib.load()`` refuses a
 library whose id differs from the sources beside it."""
@@ -23,6 +23,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 ABI_HEADER = os.path.join(HERE, "..", "include", "aogym.h")
 DISTURBANCE_HEADER = os.path.join(HERE, "..", "include", "aogym_disturbance.h")   # (declares what layers.hip and disturbance.hip add)
+SIGHTLINE_HEADER = os.path.join(HERE, "..", "include", "aogym_sightline.h")   # (declares what layers.hip adds for sightlines)
 OUT = os.path.join(HERE, "libaogym.so")
 APADS = (16, 32, 64, 128)
 UNITS = ("aogym", "atmosphere", "screens", "shack", "focal", "actor", "wavefront", "science", "gradient", "gradient_obs", "layers", "pyramid", "pyramid_grad", "predictor", "telemetry", "spgd", "link", "disturbance")
@@ -52,7 +53,7 @@ def _sha(paths, extra="") -> str:
 
 
 def source_files():
-    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip"))) + [ABI_HEADER, DISTURBANCE_HEADER]
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip"))) + [ABI_HEADER, DISTURBANCE_HEADER, SIGHTLINE_HEADER]
 
 
 def source_id() -> str:
@@ -80,7 +81,8 @@ def needs_build() -> bool:
 
 def _unit_deps(unit: str):
     fam = [os.path.join(CSRC, h) for h in SHARED + FAMILY[unit] if os.path.exists(os.path.join(CSRC, h))]
-    return [os.path.join(CSRC, unit + ".hip")] + fam + [ABI_HEADER] + ([DISTURBANCE_HEADER] if unit in ("layers", "disturbance") else [])
+    return [os.path.join(CSRC, unit + ".hip")] + fam + [ABI_HEADER] + ([DISTURBANCE_HEADER] if unit in ("layers", "disturbance") else []) + (
+        [SIGHTLINE_HEADER] if unit == "layers" else [])
 
 
 def build(force: bool = False, verbose: bool = True, fast: bool = False, dev: bool = False) -> str:

@@ -643,6 +643,9 @@ void aog_destroy(aog_env* e) {
   if (e->det_ev) (void)hipEventSynchronize(e->det_ev);
   if (e->det_stage) (void)hipHostFree(e->det_stage);
   if (e->det_ev) (void)hipEventDestroy(e->det_ev);
+  if (e->sight_ev) (void)hipEventSynchronize(e->sight_ev);
+  if (e->sight_stage) (void)hipHostFree(e->sight_stage);
+  if (e->sight_ev) (void)hipEventDestroy(e->sight_ev);
   if (e->x8_plan_stream) {
     (void)hipStreamSynchronize(e->x8_plan_stream);
     (void)hipStreamDestroy(e->x8_plan_stream);

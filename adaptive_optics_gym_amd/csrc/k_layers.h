@@ -255,4 +255,139 @@ __global__ __launch_bounds__(256) void k_layer_sum_f64_dist(LayerSources src, Mo
   }
 }
 
+// ---- the same three passes along a sightline (aog_install_layer_sum_sightline, include/aogym_sightline.h) ----
+// Layer l has N_l >= N pixels (margin c_l = (N_l - N) / 2) and is read at the logical position (iy + c_l + sy, ix + c_l + sx), bilinearly;
+// (sx, sy) belongs to (layer, env).  Kernels of their own beside the six above, which keep their text; add_terms (terms.K may be 0),
+// AOG_LAYER_STAGE_ROWS and block_reduce_sum are shared.  Per env and layer — wave-uniform, scalar loads — a LayerTap holds the integer
+// part of the shift folded with the margin and the ring origin into one offset per axis, reduced modulo N_l, and the four weights; a
+// pixel then costs four loads (two neighbouring pairs: the second of each pair hits the line of the first), four products and three sums.
+struct LayerSight {
+  const double* shift[kMaxLayers];   // [B][2] (sx, sy) of this layer, pixels
+  int n[kMaxLayers];                 // N_l
+  int c[kMaxLayers];                 // c_l
+};
+struct LayerTap {
+  int by0, by1, bx0, bx1;   // ring origins of the rows y0, y0 + 1 and the columns x0, x0 + 1 of front pixel (0, 0): each in [0, N_l)
+  double gy, fy, gx, fx;    // 1 - fy, fy, 1 - fx, fx
+};
+// (v mod n) in [0, n) for any int v
+__device__ __forceinline__ int ring_mod(int v, int n) {
+  const int r = v % n;
+  return r < 0 ? r + n : r;
+}
+template <int L>
+__device__ __forceinline__ void load_taps(const LayerSources& src, const LayerSight& sight, int env, LayerTap (&tap)[L]) {
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    const int n = sight.n[l];
+    const double sx = sight.shift[l][2 * env], sy = sight.shift[l][2 * env + 1];
+    const double x0 = floor(sx), y0 = floor(sy);
+    tap[l].fx = sx - x0;
+    tap[l].fy = sy - y0;
+    tap[l].gx = 1.0 - tap[l].fx;
+    tap[l].gy = 1.0 - tap[l].fy;
+    tap[l].bx0 = ring_mod(src.origin[l][2 * env] + sight.c[l] + (int)x0, n);
+    tap[l].by0 = ring_mod(src.origin[l][2 * env + 1] + sight.c[l] + (int)y0, n);
+    tap[l].bx1 = tap[l].bx0 + 1 == n ? 0 : tap[l].bx0 + 1;
+    tap[l].by1 = tap[l].by0 + 1 == n ? 0 : tap[l].by0 + 1;
+  }
+}
+// s = v_0 + v_1 + ... in layer order at front pixel (iy, ix) < N <= N_l of one env; every sample goes through layer_phys with a folded
+// origin < N_l, so one conditional subtraction per axis suffices and every address lies inside the env's screen
+template <int L>
+__device__ __forceinline__ double sight_sum_at(const LayerSources& src, const LayerSight& sight, int env, int iy, int ix, const LayerTap (&tap)[L]) {
+  double v[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    const int n = sight.n[l];
+    const double* m = src.master[l] + (size_t)env * n * n;
+    const double v00 = m[layer_phys(iy, ix, tap[l].by0, tap[l].bx0, n)], v01 = m[layer_phys(iy, ix, tap[l].by0, tap[l].bx1, n)];
+    const double v10 = m[layer_phys(iy, ix, tap[l].by1, tap[l].bx0, n)], v11 = m[layer_phys(iy, ix, tap[l].by1, tap[l].bx1, n)];
+    const double top = add_rn(mul_rn(tap[l].gx, v00), mul_rn(tap[l].fx, v01));
+    const double bottom = add_rn(mul_rn(tap[l].gx, v10), mul_rn(tap[l].fx, v11));
+    v[l] = add_rn(mul_rn(tap[l].gy, top), mul_rn(tap[l].fy, bottom));
+  }
+  double s = v[0];
+#pragma unroll
+  for (int l = 1; l < L; ++l) s = add_rn(s, v[l]);
+  return s;
+}
+
+// (four pixels per thread in flight, not eight: every pixel requests 4 L samples; the order of a thread's additions is the same)
+template <int L>
+__global__ __launch_bounds__(256) void k_layer_mean_sight(LayerSources src, LayerSight sight, ModalTerms terms, const int32_t* __restrict__ ap_index,
+                                                           double* __restrict__ mean, int N, int n_ap) {
+  __shared__ double sm[8];
+  const int env = blockIdx.x;
+  LayerTap tap[L];
+  load_taps<L>(src, sight, env, tap);
+  double acc = 0;
+  for (int p0 = threadIdx.x; p0 < n_ap; p0 += 4 * (int)blockDim.x) {
+    double s[4];
+    int envs[4], pc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int p = p0 + u * (int)blockDim.x;
+      envs[u] = env;
+      pc[u] = p < n_ap ? p : n_ap - 1;
+      const int flat = ap_index[pc[u]], iy = flat / N, ix = flat - iy * N;
+      s[u] = sight_sum_at<L>(src, sight, env, iy, ix, tap);
+    }
+    add_terms(terms, s, envs, pc);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (p0 + u * (int)blockDim.x < n_ap) acc += s[u];
+  }
+  const double total = block_reduce_sum(acc, sm);
+  if (threadIdx.x == 0) mean[env] = total / (double)n_ap;
+}
+
+template <int L>
+__global__ __launch_bounds__(256) void k_layer_sum_tiles_sight(LayerSources src, LayerSight sight, ModalTerms terms, const int32_t* __restrict__ ap_index,
+                                                                const double* __restrict__ mean, float* __restrict__ psi_tile, int B, int N, int n_ap,
+                                                                int n_ptiles, double inv_two_pi_lambda) {
+  constexpr int LD = 68;
+  __shared__ float stage[32 * LD];
+  const int et = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int it = 0; it < kLayerIters; ++it) {
+    const int pt0 = (blockIdx.x * kLayerIters + it) * 2;
+    if (pt0 >= n_ptiles) break;   // uniform
+    const int p = pt0 * 32 + lane;
+    const bool valid_p = p < n_ap;
+    const int pc1 = valid_p ? p : n_ap - 1;
+    const int flat = ap_index[pc1];
+    const int iy = flat / N, ix = flat - iy * N;
+    double s[8];
+    int envs[8], pc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {   // (the env, and with it the taps and the coefficients, is wave-uniform: scalar loads, one tap per env and layer)
+      const int env = min(et * 32 + wave * 8 + q, B - 1);
+      LayerTap tap[L];
+      load_taps<L>(src, sight, env, tap);
+      envs[q] = env;
+      pc[q] = pc1;
+      s[q] = sight_sum_at<L>(src, sight, env, iy, ix, tap);
+    }
+    add_terms(terms, s, envs, pc);
+    AOG_LAYER_STAGE_ROWS()
+  }
+}
+
+template <int L>
+__global__ __launch_bounds__(256) void k_layer_sum_f64_sight(LayerSources src, LayerSight sight, ModalTerms terms, const int32_t* __restrict__ ap_index,
+                                                              const double* __restrict__ mean, double* __restrict__ psi64, int N, int n_ap) {
+  const int env = blockIdx.x;
+  LayerTap tap[L];
+  load_taps<L>(src, sight, env, tap);
+  const double mu = mean[env];
+  for (int p = threadIdx.x; p < n_ap; p += blockDim.x) {
+    const int flat = ap_index[p], iy = flat / N, ix = flat - iy * N;
+    double s[1] = {sight_sum_at<L>(src, sight, env, iy, ix, tap)};
+    const int envs[1] = {env}, pc[1] = {p};
+    add_terms(terms, s, envs, pc);
+    psi64[(size_t)env * n_ap + p] = s[0] - mu;
+  }
+}
+
 }  // namespace aog

@@ -1,9 +1,11 @@
 // Layered atmosphere (several frozen-flow layers per env): the atmosphere-only step of a layer handle and the installation of the layers'
-// sum in a quasi-static front handle, plain or with a modal disturbance added inside the sum.  No existing launch changes: a handle that
-// never comes here runs what it ran before, and an installation without a disturbance launches the kernels it launched before.
+// sum in a quasi-static front handle, plain, with a modal disturbance added inside the sum, or read along a sightline (layers larger than
+// the front, displaced by a fraction of a pixel).  No existing launch changes: a handle that never comes here runs what it ran before, and
+// an installation without a disturbance or a sightline launches the kernels it launched before.
 #include "host_common.h"
 #include "k_layers.h"
 #include "../../include/aogym_disturbance.h"
+#include "../../include/aogym_sightline.h"
 
 using namespace aog_host;
 
@@ -24,10 +26,44 @@ namespace {
     default: hipLaunchKernelGGL((aog::KERNEL<8>), grid, block, 0, s, __VA_ARGS__); break;                \
   }
 
-// The one installation behind aog_install_layer_sum (coeff_dev null: the kernels without terms) and aog_install_layer_sum_disturbed
-// (`who` names the entry point in every message)
+// The shifts of a sightline installation, checked against every layer's margin and brought to the front's own buffer on `s`: through
+// pinned staging, which keeps the values of the last installation, so that the same values arriving again cost a comparison and no copy.
+// Nothing of the handle changes before every value has passed.
+int stage_shifts(const char* who, aog_env* dst, aog_env* const* layers, int n_layers, const double* shift_host, hipStream_t s) {
+  const size_t B = (size_t)dst->B, count = (size_t)n_layers * B * 2;
+  for (int l = 0; l < n_layers; ++l) {
+    const int c = (layers[l]->cfg.n_pupil - dst->cfg.n_pupil) / 2;
+    const double limit = c > 0 ? (double)(c - 1) : 0.0;
+    for (size_t i = 0; i < 2 * B; ++i) {
+      const double v = shift_host[(size_t)l * 2 * B + i];
+      if (!std::isfinite(v) || std::fabs(v) > limit)
+        return fail(AOG_ERR_INVALID, "%s: shift %c = %.17g pixels of layer %d, env %d is outside the margin (|shift| <= %g: the layer has %d pixels, "
+                    "the front %d, c = %d)", who, (i & 1) ? 'y' : 'x', v, l, (int)(i / 2), limit, layers[l]->cfg.n_pupil, dst->cfg.n_pupil, c);
+    }
+  }
+  const size_t capacity = (size_t)aog::kMaxLayers * B * 2;
+  if (!dst->sight_shift)
+    if (int rc = dev_alloc(dst, &dst->sight_shift, capacity, false)) return rc;
+  if (!dst->sight_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&dst->sight_stage), sizeof(double) * capacity, hipHostMallocDefault));
+  if (!dst->sight_ev) HIP_TRY(hipEventCreateWithFlags(&dst->sight_ev, hipEventDisableTiming));
+  if (dst->sight_layers == n_layers && std::memcmp(dst->sight_stage, shift_host, sizeof(double) * count) == 0) return AOG_OK;
+  HIP_TRY(hipEventSynchronize(dst->sight_ev));   // (the previous copy out of the staging buffer; long done in practice)
+  dst->sight_layers = 0;
+  std::memcpy(dst->sight_stage, shift_host, sizeof(double) * count);
+  HIP_TRY(hipMemcpyAsync(dst->sight_shift, dst->sight_stage, sizeof(double) * count, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(dst->sight_ev, s));
+  dst->sight_layers = n_layers;
+  return AOG_OK;
+}
+
+// The one installation behind aog_install_layer_sum (coeff_dev null: the kernels without terms), aog_install_layer_sum_disturbed and
+// aog_install_layer_sum_sightline (shift_host non-null: layers of N_l >= N, the *_sight kernels, terms when n_terms > 0); `who` names the
+// entry point in every message
 int install_layer_sum(const char* who, aog_env* dst, aog_env* const* layers, int n_layers, const double* coeff_dev, int n_terms, bool disturbed,
-                      void* stream) {
+                      void* stream, const double* shift_host = nullptr) {
+  const bool sight = shift_host != nullptr;
+  if (sight && n_terms < 0) return fail(AOG_ERR_INVALID, "%s: %d terms", who, n_terms);
+  if (sight) disturbed = n_terms > 0;
   if (!dst || !layers || (disturbed && !coeff_dev)) return fail(AOG_ERR_INVALID, "%s: null argument", who);
   if (n_layers < 1 || n_layers > aog::kMaxLayers) return fail(AOG_ERR_INVALID, "%s: %d layers (1 .. %d)", who, n_layers, aog::kMaxLayers);
   if (dst->cfg.atm_dynamic) return fail(AOG_ERR_INVALID, "%s: the front handle must not be atm_dynamic (its screens are installed, not evolved)", who);
@@ -40,9 +76,13 @@ int install_layer_sum(const char* who, aog_env* dst, aog_env* const* layers, int
     const aog_env* y = layers[l];
     if (!y) return fail(AOG_ERR_INVALID, "%s: layer %d is null", who, l);
     if (!y->cfg.atm_dynamic || !y->screens_ready || !y->psi_master) return fail(AOG_ERR_INVALID, "%s: layer %d is not a dynamic handle with screens", who, l);
-    if (y->device != dst->device || y->cfg.n_pupil != dst->cfg.n_pupil || y->B != dst->B || y->cfg.env_id_base != dst->cfg.env_id_base)
+    const bool n_ok = sight ? y->cfg.n_pupil >= dst->cfg.n_pupil : y->cfg.n_pupil == dst->cfg.n_pupil;
+    if (y->device != dst->device || !n_ok || y->B != dst->B || y->cfg.env_id_base != dst->cfg.env_id_base)
       return fail(AOG_ERR_INVALID, "%s: layer %d (device %d, N %d, B %d, env_id_base %d) does not match the front handle (device %d, N %d, B %d, "
                   "env_id_base %d)", who, l, y->device, y->cfg.n_pupil, y->B, y->cfg.env_id_base, dst->device, dst->cfg.n_pupil, dst->B, dst->cfg.env_id_base);
+    if (sight && (y->cfg.n_pupil - dst->cfg.n_pupil) % 2)
+      return fail(AOG_ERR_INVALID, "%s: layer %d has %d pixels, the front %d: the difference must be even (the meta-pupil is centred on the pupil)", who, l,
+                  y->cfg.n_pupil, dst->cfg.n_pupil);
     if (y->pre_evolved) return fail(AOG_ERR_INVALID, "%s: the atmosphere of layer %d already stands at the next step (aog_set_lookahead)", who, l);
     char layer_who[96];
     std::snprintf(layer_who, sizeof layer_who, "%s (layer)", who);
@@ -55,14 +95,32 @@ int install_layer_sum(const char* who, aog_env* dst, aog_env* const* layers, int
     return fail(AOG_ERR_UNSUPPORTED, "%s: the front handle runs the VALU kernel (its screen layout is not written here; use kernel 'auto' or 'mfma')", who);
   if (int rc = check_poisoned(dst, who)) return rc;
   HIP_TRY(hipSetDevice(dst->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (sight)
+    if (int rc = stage_shifts(who, dst, layers, n_layers, shift_host, s)) return rc;
   if (!dst->layer_mean)
     if (int rc = dev_alloc(dst, &dst->layer_mean, (size_t)dst->B, false)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const int N = dst->cfg.n_pupil;
   const dim3 tiles(((dst->n_ptiles + 1) / 2 + aog::kLayerIters - 1) / aog::kLayerIters, dst->n_etiles);
   // pass 1 reads every master once; pass 2 reads them again (8 n_ap bytes per env and layer, mostly from L2 / Infinity Cache); the
   // disturbed forms add the K basis rows (8 K n_ap bytes, shared by every env: L2) to each pass
-  if (disturbed) {
+  if (sight) {
+    // four samples per pixel and layer instead of one, mostly from L2 / Infinity Cache (neighbours of a line already requested)
+    aog::LayerSight geo{};
+    for (int l = 0; l < n_layers; ++l) {
+      geo.shift[l] = dst->sight_shift + (size_t)l * dst->B * 2;
+      geo.n[l] = layers[l]->cfg.n_pupil;
+      geo.c[l] = (layers[l]->cfg.n_pupil - N) / 2;
+    }
+    const aog::ModalTerms terms{disturbed ? dst->dist_basis : nullptr, disturbed ? coeff_dev : nullptr, disturbed ? n_terms : 0, dst->n_ap};
+    AOG_LAYER_DISPATCH(n_layers, k_layer_mean_sight, dim3(dst->B), dim3(256), s, src, geo, terms, dst->ap_index, dst->layer_mean, N, dst->n_ap);
+    if (fast) {
+      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_tiles_sight, tiles, dim3(256), s, src, geo, terms, dst->ap_index, dst->layer_mean, dst->psi_tile, dst->B, N,
+                         dst->n_ap, dst->n_ptiles, rev_per_metre(dst));
+    } else {
+      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_f64_sight, dim3(dst->B), dim3(256), s, src, geo, terms, dst->ap_index, dst->layer_mean, dst->psi64, N, dst->n_ap);
+    }
+  } else if (disturbed) {
     const aog::ModalTerms terms{dst->dist_basis, coeff_dev, n_terms, dst->n_ap};
     AOG_LAYER_DISPATCH(n_layers, k_layer_mean_dist, dim3(dst->B), dim3(256), s, src, terms, dst->ap_index, dst->layer_mean, N, dst->n_ap);
     if (fast) {
@@ -131,6 +189,12 @@ int aog_upload_disturbance_basis(aog_env* dst, const double* basis_host, int n_t
 
 int aog_install_layer_sum_disturbed(aog_env* dst, aog_env* const* layers, int n_layers, const double* coeff_dev, int n_terms, void* stream) {
   return install_layer_sum("aog_install_layer_sum_disturbed", dst, layers, n_layers, coeff_dev, n_terms, true, stream);
+}
+
+int aog_install_layer_sum_sightline(aog_env* dst, aog_env* const* layers, int n_layers, const double* shift_host, const double* coeff_dev, int n_terms,
+                                    void* stream) {
+  if (!shift_host) return fail(AOG_ERR_INVALID, "aog_install_layer_sum_sightline: null argument");
+  return install_layer_sum("aog_install_layer_sum_sightline", dst, layers, n_layers, coeff_dev, n_terms, false, stream, shift_host);
 }
 
 }  // extern "C"

@@ -7,10 +7,17 @@ sums the layers' float64 master screens into the screen tiles of a quasi-static 
 steps with the static fused kernel it already has.  Everything that reads the front's screens — reset, step, the separable observation
 route, Shack-Hartmann, ``wavefront_truth``, the science camera, ``output_gradient``, ``step_with_policy``, ``step_with_spgd``, pipelined steps — works on it
 unchanged.
+
+With ``layer_altitudes`` the layers leave the pupil plane: a layer at altitude h is seen displaced by h x angle along a line of sight at
+that angle, so it is drawn on a meta-pupil larger than the pupil and every front — the env's own (``field_angle``) and any number of
+further ``Sightline`` fronts over the same layers (``add_sightline``) — reads it at its own sub-pixel shift
+(``aog_install_layer_sum_sightline``).  The part of the wavefront that differs between two sightlines is angular anisoplanatism: no
+controller that senses on one of them removes it on the other.
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -62,6 +69,123 @@ def resolve_layers(atm_layers, atm_fried, num_envs, total_envs=None, global_env_
     return out
 
 
+def resolve_altitudes(layer_altitudes, num_layers):
+    """``layer_altitudes`` checked: [L] float64 metres, one per layer, finite and >= 0 (None stays None: every layer in the pupil plane).
+    ``ValueError`` otherwise."""
+    if layer_altitudes is None:
+        return None
+    h = np.asarray(layer_altitudes, dtype=np.float64)
+    if h.ndim != 1 or h.size != num_layers:
+        raise ValueError(f"layer_altitudes: expected one altitude in metres per layer ({num_layers}), got shape {h.shape}")
+    if not np.all(np.isfinite(h)) or np.any(h < 0):
+        raise ValueError("layer_altitudes: altitudes must be finite and >= 0")
+    return h.copy()
+
+
+def resolve_field_angle(angle, num_envs, total_envs=None, global_env_offset=0, name="field_angle"):
+    """A line of sight as [num_envs, 2] float64 radians (theta_x, theta_y): one pair for every env, or per-env pairs [num_envs, 2] /
+    [total_envs, 2] under ``resolve_per_env``'s rules (the latter indexed by global env id).  None is on axis.  ``ValueError`` otherwise."""
+    total_envs = global_env_offset + num_envs if total_envs is None else int(total_envs)
+    if angle is None:
+        return np.zeros((num_envs, 2))
+    a = np.asarray(angle, dtype=np.float64)
+    if a.shape == (2,):
+        cols = (a[0], a[1])
+    elif a.ndim == 2 and a.shape[1] == 2:
+        cols = (a[:, 0], a[:, 1])
+    else:
+        raise ValueError(f"{name}: expected (theta_x, theta_y) in radians or an array [num_envs, 2] / [total_envs, 2], got shape {a.shape}")
+    return np.stack([resolve_per_env(name, c, num_envs, total_envs, global_env_offset)[0] for c in cols], axis=1)
+
+
+def sightline_shifts(altitudes, angle, pupil_pixel):
+    """[L, B, 2] float64 (sx, sy) in pixels: layer l at altitude h_l is read h_l theta / pupil_pixel further along +x / +y by a front that
+    looks along theta = (theta_x, theta_y) — front pixel (iy, ix) reads the layer's meta-pupil at (iy + c + sy, ix + c + sx).  One rounded
+    product and one rounded quotient per value, in that order."""
+    h = np.asarray(altitudes, dtype=np.float64)
+    a = np.asarray(angle, dtype=np.float64)
+    return np.ascontiguousarray((h[:, None, None] * a[None, :, :]) / float(pupil_pixel))
+
+
+def required_margin(altitudes, angles, pupil_pixel):
+    """The margin c (pixels on every side) a meta-pupil needs for the sightlines ``angles`` (a list of [B, 2] arrays):
+    ceil(max |h_l theta| / pupil_pixel) + 1 — the integer part of the shift and the bilinear read's second sample."""
+    worst = 0.0
+    for a in angles:
+        s = sightline_shifts(altitudes, a, pupil_pixel)
+        worst = max(worst, float(np.abs(s).max()) if s.size else 0.0)
+    return int(np.ceil(worst)) + 1
+
+
+def default_meta_pupil_pixels(num_pupil_pixels, margin):
+    """The smallest meta-pupil N_L >= N + 2 margin the dynamic handle accepts as a layer of a front with N pixels: N_L - N even (the
+    meta-pupil is centred on the pupil) and, for N a multiple of 4, N_L a multiple of 4 as well (the two-band screen synthesis and the
+    ring's vector rows are built for such sizes)."""
+    n = int(num_pupil_pixels) + 2 * int(margin)
+    if num_pupil_pixels % 4 == 0:
+        n = (n + 3) // 4 * 4
+    return n
+
+
+def check_margin(shifts, margins, what):
+    """``ValueError`` unless every shift of layer l lies inside its margin: |s| <= c_l - 1, exactly 0 for c_l = 0 (what the library checks
+    again).  ``shifts`` [L, B, 2], ``margins`` [L]."""
+    for l, c in enumerate(margins):
+        limit = max(int(c) - 1, 0)
+        worst = float(np.abs(shifts[l]).max())
+        if not np.isfinite(worst) or worst > limit:
+            raise ValueError(f"{what}: layer {l} would be read {worst:.3f} pixels off the pupil, its meta-pupil leaves {limit} "
+                             f"(margin c = {int(c)}; build the env with a larger meta_pupil_pixels)")
+
+
+def install_layer_sum_sightline(front, layers, shifts, coeff=None):
+    """``BatchedAOEnv.install_layer_sum`` along a line of sight (``aog_install_layer_sum_sightline``, include/aogym_sightline.h): ``front`` a
+    quasi-static env with N pixels, ``layers`` 1 .. 8 dynamic envs of N_l >= N pixels (N_l - N even) of its batch and device, ``shifts``
+    [L, B, 2] float64 host array of (sx, sy) in pixels, |s| <= (N_l - N) / 2 - 1.  ``coeff``: None, or the [B, K] float64 device tensor of
+    ``install_layer_sum_disturbed`` (the front holds a basis of K terms).  Stream-ordered, no host synchronisation."""
+    shifts = np.ascontiguousarray(shifts, dtype=np.float64)
+    if shifts.shape != (len(layers), front.num_envs, 2):
+        raise ValueError(f"install_layer_sum_sightline: shifts must be [{len(layers)}, {front.num_envs}, 2], got {shifts.shape}")
+    if coeff is not None:
+        torch = front._torch
+        if not isinstance(coeff, torch.Tensor) or coeff.dtype != torch.float64 or coeff.dim() != 2 or coeff.shape[0] != front.num_envs or not coeff.is_contiguous():
+            raise ValueError(f"install_layer_sum_sightline: coeff must be a contiguous float64 [{front.num_envs}, K] device tensor")
+    handles = (C.c_void_p * len(layers))(*[lay._handle.value for lay in layers])
+    _lib.check(front.lib.aog_install_layer_sum_sightline(front._handle, handles, len(layers), shifts.ctypes.data_as(C.c_void_p),
+                                                         None if coeff is None else C.c_void_p(coeff.data_ptr()), 0 if coeff is None else int(coeff.shape[1]),
+                                                         front._stream()))
+    front.state_epoch += 1
+
+
+class Sightline:
+    """A second line of sight through a ``LayeredAOEnv``'s layers (``LayeredAOEnv.add_sightline``): a quasi-static front of its own that
+    gets the same layers' sum installed at its own shifts every step and steps with the env's action.  ``env`` is that front, an ordinary
+    ``BatchedAOEnv``, for instruments (``wavefront_truth``, the science camera, ...); ``angle`` [B, 2] radians; ``last`` the dict of its
+    last step (what ``info["sightlines"][name]`` carries)."""
+
+    def __init__(self, owner, name, env, angle):
+        self._owner, self.name, self.env, self.angle = owner, name, env, angle
+        self.last = None
+
+    def set_angle(self, angle):
+        """Point this sightline elsewhere (inside the meta-pupil's margin: ``ValueError`` otherwise, before anything changes).  The next
+        installation — the next step, or ``reset`` — reads the layers there."""
+        self._owner._set_angle(self, angle, f"sightline {self.name!r}")
+
+
+class _SightlineFront(BatchedAOEnv):
+    """The front of a ``Sightline``: like the ``LayeredAOEnv``'s own front it draws no screens, its layers do."""
+
+    def _generate_screens(self, mask=None):
+        pass
+
+    def _push_turbulence(self):
+        pass
+
+    def _host_extrusion_noise(self):
+        pass
+
+
 class LayeredAOEnv(BatchedAOEnv):
     """``BatchedAOEnv`` over a layered dynamic atmosphere.  Keywords as ``BatchedAOEnv`` (``atm_type`` is 'dynamic'; ``atm_vel`` and
     ``screens`` do not apply) plus
@@ -71,6 +195,30 @@ class LayeredAOEnv(BatchedAOEnv):
                  aberrations on K <= 8 pupil shapes, advanced once per step and added inside the layer sum (so everything that reads the
                  front sees them).  ``env.disturbance`` is the object; ``get_state`` / ``set_state`` carry its state; ``set_turbulence`` and
                  ``reset`` leave it alone.  Without it the env runs exactly the launches it ran before.
+    layer_altitudes   None (every layer in the pupil plane: the env constructs and launches exactly what it did before), or [h_l] in
+                 metres, one per layer, each >= 0.
+    field_angle  the env's own line of sight, (theta_x, theta_y) in radians — one pair, or per-env pairs [B, 2] (or [total_envs, 2]
+                 indexed by global env id).  Default on axis.  Needs ``layer_altitudes``.
+    meta_pupil_pixels   N_L, the side of the meta-pupil the layers above the ground are drawn on (``N_L - N`` even, >= 0).  Default
+                 (``default_meta_pupil_pixels``): the smallest accepted size that leaves the margin c >= ceil(max |h_l theta| /
+                 pupil_pixel) + 1 over every sightline declared at construction (``field_angle`` and ``sightlines``).
+    sightlines   None, or {name: angle} — ``add_sightline(angle, name)`` for each at the end of construction, counted in the default margin.
+
+    Layered geometry.  A layer at altitude 0 keeps N pixels and this env's tables; a layer above is built with
+    ``dataclasses.replace(params, num_pupil_pixels=N_L, telescope_diameter=D N_L / N)`` — the same pixel pitch and Cn^2 on a wider
+    screen, with tables of its own (shared among the layers of one size).  Layer l is read ``h_l theta / pupil_pixel`` pixels along the
+    angle (``sightline_shifts``), bilinearly: whole-pixel shifts are exact translations, fractional ones attenuate the highest spatial
+    frequencies (per axis by ``|1 - f + f exp(-i w)|`` at w radians per pixel: nothing at the scales r0 and the actuators resolve, up to
+    all of it at the grid's Nyquist frequency).  ``add_sightline(angle, name)`` returns a ``Sightline``: a second quasi-static front built
+    like the env's own (tables, ``act_type``, ``obs_dim``, reward, detector settings, global env ids, seed).  In every ``step`` the layers
+    evolve once, every front gets the sum installed at its own shifts — the disturbance's coefficients are common-path, the same for all —
+    the env's front steps, then every sightline's front steps with the same action; ``info["sightlines"][name]`` carries that front's
+    ``obs``, ``reward``, ``power`` and ``strehl``.  ``reset`` resets them together, ``get_state`` / ``set_state`` carry them (angles
+    included), ``close`` closes them; ``set_field_angle`` / ``Sightline.set_angle`` move a line of sight inside the margin.  A point-ahead
+    study observes and controls on the beacon (the env) and reads power and fades on ``add_sightline((theta_pa, 0), "uplink")``, e.g.
+    ``LinkTelemetry.push(info["sightlines"]["uplink"]["power"])``.  With sightlines attached ``step_with_policy`` / ``step_with_spgd`` raise
+    ``RuntimeError``: fused policy stepping hands no action back before the step has run, so there is nothing to step the other fronts
+    with; ``rollout()`` needs no new option — its unfused loop (``fused_policy=False``) goes through ``step``.
 
     Layer l is a private dynamic env with a seed of its own (``layer_seed``) and therefore wind directions and stencil draws of its own,
     as the reference draws them per layer; it shares this env's tables, ``extrusion``, ``screen_source`` and global env ids.  ``reset`` is
@@ -83,16 +231,46 @@ class LayeredAOEnv(BatchedAOEnv):
     def __init__(self, num_envs=1, device=None, atm_layers=None, atm_fried=0.15, act_type="num_actuators", act_dim=64, obs_dim=2,
                  rew_type="strehl_ratio", rew_threshold=None, timesteps_per_episode=20, flat_mirror_start_per_episode=True, SH_operation=False, *,
                  atm_type="dynamic", seed=None, screen_source="device", rng=None, global_env_offset=0, total_envs=None, extrusion="auto",
-                 verbose=True, disturbance=None, **kw):
+                 verbose=True, disturbance=None, layer_altitudes=None, field_angle=None, meta_pupil_pixels=None, sightlines=None, **kw):
         self._layers = []
         self._handle = None
         self.disturbance = None
+        self._sightlines = {}
+        self._altitudes = None
         if atm_type != "dynamic":
             raise ValueError("LayeredAOEnv: atm_type is 'dynamic' (a layered atmosphere evolves every step)")
         for bad in ("atm_vel", "screens"):
             if bad in kw:
                 raise ValueError(f"LayeredAOEnv: {bad} does not apply (every layer has its own speed and draws its own screens)")
         plan = resolve_layers(atm_layers, atm_fried, int(num_envs), total_envs, int(global_env_offset))
+        # the geometry, checked before anything is created
+        altitudes = resolve_altitudes(layer_altitudes, len(plan))
+        if altitudes is None and (field_angle is not None or meta_pupil_pixels is not None or sightlines):
+            raise ValueError("LayeredAOEnv: field_angle, meta_pupil_pixels and sightlines need layer_altitudes (without altitudes every layer sits "
+                             "in the pupil plane and every direction sees the same wavefront)")
+        geometry = None
+        if altitudes is not None:
+            from .params import OpticalParams
+
+            params = kw.get("params") or OpticalParams(num_pupil_pixels=int(kw.get("num_pupil_pixels", 240)))
+            n_env, n_off = int(num_envs), int(global_env_offset)
+            angle = resolve_field_angle(field_angle, n_env, total_envs, n_off)
+            if sightlines is not None and not isinstance(sightlines, dict):
+                raise ValueError("sightlines: a dict {name: angle}")
+            declared = {str(k): resolve_field_angle(v, n_env, total_envs, n_off, f"sightline {k!r}") for k, v in (sightlines or {}).items()}
+            N = params.num_pupil_pixels
+            if meta_pupil_pixels is None:
+                n_meta = default_meta_pupil_pixels(N, required_margin(altitudes, [angle] + list(declared.values()), params.pupil_pixel))
+            else:
+                n_meta = int(meta_pupil_pixels)
+                if n_meta != meta_pupil_pixels or n_meta < N or (n_meta - N) % 2:
+                    raise ValueError(f"meta_pupil_pixels: expected an integer >= num_pupil_pixels ({N}) with an even difference, got {meta_pupil_pixels!r}")
+            margins = np.where(altitudes > 0, (n_meta - N) // 2, 0)
+            for what, a in [("field_angle", angle)] + [(f"sightline {k!r}", v) for k, v in declared.items()]:
+                check_margin(sightline_shifts(altitudes, a, params.pupil_pixel), margins, what)
+            geometry = dict(angle=angle, declared=declared, n_meta=n_meta, margins=margins)
+        self._front_args = dict(args=(act_type, act_dim, obs_dim, rew_type, rew_threshold, timesteps_per_episode, flat_mirror_start_per_episode,
+                                      SH_operation), seed=seed, extrusion=extrusion, kw=dict(kw))
         # The front: a quasi-static handle whose screens are installed, never drawn (_generate_screens below is a no-op); it consumes no
         # host random draws, so layer 0 sees the streams a plain dynamic env with the same seed sees.
         super().__init__(num_envs, device, "quasi_static", 0, atm_fried, act_type, act_dim, obs_dim, rew_type, rew_threshold, timesteps_per_episode,
@@ -103,17 +281,36 @@ class LayeredAOEnv(BatchedAOEnv):
         self.layer_fractions = np.array([p["fraction"] for p in plan])
         layer_kw = {k: kw[k] for k in ("screen_oversampling", "precision", "kernel", "pixel_chunks", "screen_method") if k in kw}
         try:
+            meta_params = meta_tables = None
             for i, p in enumerate(plan):
+                lay_params, lay_tables = self.params, self.tables
+                if geometry is not None and geometry["margins"][i] > 0:
+                    # a layer above the ground on the meta-pupil: the same pitch (and with it the same Cn^2 per r0) on a wider screen
+                    if meta_params is None:
+                        N, n_meta = self.num_pupil_pixels, geometry["n_meta"]
+                        meta_params = dataclasses.replace(self.params, num_pupil_pixels=n_meta, telescope_diameter=self.params.telescope_diameter * n_meta / N)
+                    lay_params, lay_tables = meta_params, meta_tables
                 # (timesteps_per_episode = 0: a layer is never reset, and the int8 extrusion only works ahead inside an episode)
                 self._layers.append(BatchedAOEnv(self.num_envs, self.device, "dynamic", p["speed"], p["fried"], act_type, act_dim, obs_dim, rew_type,
-                                                 None, 0, True, False, params=self.params, seed=layer_seed(seed, i), screen_source=screen_source,
+                                                 None, 0, True, False, params=lay_params, seed=layer_seed(seed, i), screen_source=screen_source,
                                                  rng=rng, global_env_offset=self.global_env_offset, total_envs=self.total_envs,
-                                                 tables=self.tables, extrusion=extrusion, verbose=False, **layer_kw))
+                                                 tables=lay_tables, extrusion=extrusion, verbose=False, **layer_kw))
+                if lay_params is meta_params:
+                    meta_tables = self._layers[-1].tables
             self.velocity_vectors = np.stack([lay.velocity_vectors for lay in self._layers])   # [L, B, 2] m/s
             self.velocity = [lay.velocity for lay in self._layers]
             if disturbance is not None:
                 self._attach_disturbance(disturbance)
+            if geometry is not None:
+                self._altitudes = altitudes
+                self.meta_pupil_pixels = geometry["n_meta"]
+                self.layer_margins = geometry["margins"]          # [L] c_l: the meta-pupil's margin on every side, 0 for a ground layer
+                self.field_angle = geometry["angle"]              # [B, 2] radians
+                self._shifts = sightline_shifts(altitudes, self.field_angle, self.params.pupil_pixel)
             self._install()   # the first reset sees t = 0
+            if geometry is not None:
+                for name, angle in geometry["declared"].items():
+                    self.add_sightline(angle, name)
         except Exception:
             self.close()
             raise
@@ -157,10 +354,69 @@ class LayeredAOEnv(BatchedAOEnv):
         self._coeff = d.coefficients()
 
     def _install(self):
-        if self.disturbance is None:
+        coeff = None if self.disturbance is None else self._coeff
+        if self._altitudes is not None:
+            # every front reads the same layers at its own shifts; the coefficients are common-path
+            install_layer_sum_sightline(self, self._layers, self._shifts, coeff)
+            for sl in self._sightlines.values():
+                install_layer_sum_sightline(sl.env, self._layers, sl._shifts, coeff)
+        elif coeff is None:
             self.install_layer_sum(self._layers)
         else:
-            self.install_layer_sum_disturbed(self._layers, self._coeff)
+            self.install_layer_sum_disturbed(self._layers, coeff)
+
+    layer_altitudes = property(lambda self: None if self._altitudes is None else self._altitudes.copy(), doc="[L] metres, or None")
+    sightlines = property(lambda self: dict(self._sightlines), doc="{name: Sightline}")
+
+    def _shifts_for(self, angle, what):
+        """``angle`` resolved to [B, 2] and its shifts [L, B, 2], checked against the margins (``ValueError`` before anything changes)."""
+        if self._altitudes is None:
+            raise ValueError(f"{what}: this env was built without layer_altitudes (every layer sits in the pupil plane and every direction sees "
+                             "the same wavefront)")
+        angle = resolve_field_angle(angle, self.num_envs, self.total_envs, self.global_env_offset, what)
+        shifts = sightline_shifts(self._altitudes, angle, self.params.pupil_pixel)
+        check_margin(shifts, self.layer_margins, what)
+        return angle, shifts
+
+    def add_sightline(self, angle, name=None):
+        """A second front over the same layers that looks along ``angle`` ((theta_x, theta_y) radians, or per-env pairs): returns its
+        ``Sightline``.  ``ValueError`` when the angle leaves the meta-pupil's margin or the name is taken, before anything is created."""
+        name = f"sightline{len(self._sightlines)}" if name is None else str(name)
+        if name in self._sightlines:
+            raise ValueError(f"add_sightline: there is a sightline {name!r} already")
+        angle, shifts = self._shifts_for(angle, f"sightline {name!r}")
+        fa = self._front_args
+        front = _SightlineFront(self.num_envs, self.device, "quasi_static", 0, self.fried_parameter, *fa["args"], seed=fa["seed"], screen_source="device",
+                                rng=None, global_env_offset=self.global_env_offset, total_envs=self.total_envs, extrusion=fa["extrusion"],
+                                verbose=False, **{**fa["kw"], "tables": self.tables, "params": self.params})
+        try:
+            if self.disturbance is not None:
+                self.disturbance.upload_basis(front)
+            sl = Sightline(self, name, front, angle)
+            sl._shifts = shifts
+            install_layer_sum_sightline(front, self._layers, shifts, None if self.disturbance is None else self._coeff)
+        except Exception:
+            front.close()
+            raise
+        self._sightlines[name] = sl
+        return sl
+
+    def _set_angle(self, target, angle, what):
+        angle, shifts = self._shifts_for(angle, what)
+        if target is self:
+            self.field_angle, self._shifts = angle, shifts
+        else:
+            target.angle, target._shifts = angle, shifts
+
+    def set_field_angle(self, angle):
+        """Point the env's own line of sight elsewhere (inside the meta-pupil's margin: ``ValueError`` otherwise, before anything changes).
+        The next installation — the next step — reads the layers there."""
+        self._set_angle(self, angle, "field_angle")
+
+    def _refuse_with_sightlines(self, who):
+        if self._sightlines:
+            raise RuntimeError(f"{who}: this env has sightlines attached ({', '.join(self._sightlines)}); fused stepping hands no action back before "
+                               "the step has run, so their fronts cannot be stepped with it — use step(), or rollout(fused_policy=False)")
 
     def install_layer_sum_disturbed(self, layers, coeff):
         """``install_layer_sum`` with ``sum_k coeff[b][k] shape_k`` added inside the float64 sum (``aog_install_layer_sum_disturbed``; the
@@ -182,13 +438,43 @@ class LayeredAOEnv(BatchedAOEnv):
 
     def step(self, actions, out=None, next_actions=BatchedAOEnv._PIPELINE_END):
         self._advance()
-        return super().step(actions, out=out, next_actions=next_actions)
+        ret = super().step(actions, out=out, next_actions=next_actions)
+        if self._sightlines:
+            # (after the env's own front: every sightline's front takes the same action, on the sum _advance installed at its shifts)
+            seen = {}
+            for name, sl in self._sightlines.items():
+                obs, reward, _, _, info = sl.env.step(actions)
+                sl.last = seen[name] = {"obs": obs, "reward": reward, "power": info["power"], "strehl": info["strehl"]}
+            ret[4]["sightlines"] = seen
+        return ret
+
+    def reset(self, mask=None, seed=None, options=None):
+        ret = super().reset(mask, seed, options)
+        self._reset_sightlines(mask)
+        return ret
+
+    def _reset_sightlines(self, mask):
+        for sl in self._sightlines.values():
+            sl.env.reset(mask)
+            sl.last = None
+
+    def reset_with_policy(self, policy, cov_var=0.5, policy_out=None, mask=None, ou_noise=None, action_mode="sample"):
+        ret = super().reset_with_policy(policy, cov_var, policy_out=policy_out, mask=mask, ou_noise=ou_noise, action_mode=action_mode)
+        self._reset_sightlines(mask)
+        return ret
+
+    def reset_with_spgd(self, ctrl, mask=None, action_out=None):
+        ret = super().reset_with_spgd(ctrl, mask=mask, action_out=action_out)
+        self._reset_sightlines(mask)
+        return ret
 
     def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None, ou_noise=None, action_mode="sample"):
+        self._refuse_with_sightlines("step_with_policy")
         self._advance()
         return super().step_with_policy(policy, cov_var, out=out, policy_out=policy_out, action=action, ou_noise=ou_noise, action_mode=action_mode)
 
     def step_with_spgd(self, ctrl, out=None, action=None, action_out=None):
+        self._refuse_with_sightlines("step_with_spgd")
         self._advance()
         return super().step_with_spgd(ctrl, out=out, action=action, action_out=action_out)
 
@@ -214,10 +500,15 @@ class LayeredAOEnv(BatchedAOEnv):
         return self._layers[layer].get_screens(first, count)
 
     def get_screens(self, first=0, count=None):
-        """The float64 sum of the layers' screens in layer order (what ``install_layer_sum`` forms before it removes the aperture mean)."""
-        total = self._layers[0].get_screens(first, count)
-        for lay in self._layers[1:]:
-            total = total + lay.get_screens(first, count)
+        """The float64 sum of the layers' screens in layer order (what ``install_layer_sum`` forms before it removes the aperture mean).
+        With ``layer_altitudes``: of the pupil-sized centres of the layers' meta-pupils — the sum an on-axis sightline reads."""
+        N = self.num_pupil_pixels
+        total = None
+        for lay in self._layers:
+            c = (lay.num_pupil_pixels - N) // 2
+            part = lay.get_screens(first, count)
+            part = part if c == 0 else part[:, c:c + N, c:c + N].contiguous()
+            total = part if total is None else total + part
         return total
 
     def set_turbulence(self, fried, mask=None):
@@ -238,6 +529,9 @@ class LayeredAOEnv(BatchedAOEnv):
         state["layers"] = [lay.get_state() for lay in self._layers]
         if self.disturbance is not None:
             state["disturbance"] = self.disturbance.state_dict()
+        if self._altitudes is not None:
+            state["field_angle"] = self.field_angle.copy()
+            state["sightlines"] = {name: dict(angle=sl.angle.copy(), env=sl.env.get_state()) for name, sl in self._sightlines.items()}
         return state
 
     def set_state(self, state):
@@ -246,8 +540,24 @@ class LayeredAOEnv(BatchedAOEnv):
         if ("disturbance" in state) != (self.disturbance is not None):
             raise ValueError("set_state: the state was saved " + ("with" if "disturbance" in state else "without") + " a disturbance, this env was built "
                              + ("without" if self.disturbance is None else "with") + " one")
+        if ("field_angle" in state) != (self._altitudes is not None) or set(state.get("sightlines", ())) != set(self._sightlines):
+            raise ValueError(f"set_state: the state was saved with layer altitudes {'on' if 'field_angle' in state else 'off'} and the sightlines "
+                             f"{sorted(state.get('sightlines', ()))}, this env has them {'on' if self._altitudes is not None else 'off'} and "
+                             f"{sorted(self._sightlines)}")
+        if self._altitudes is not None:
+            # (every angle is checked against this env's margins before anything changes)
+            moved = [(self, self._shifts_for(state["field_angle"], "set_state: field_angle"))]
+            moved += [(sl, self._shifts_for(state["sightlines"][name]["angle"], f"set_state: sightline {name!r}")) for name, sl in self._sightlines.items()]
+            for target, (angle, shifts) in moved:
+                if target is self:
+                    self.field_angle, self._shifts = angle, shifts
+                else:
+                    target.angle, target._shifts = angle, shifts
         for lay, st in zip(self._layers, state["layers"]):
             lay.set_state(st)
+        for name, sl in self._sightlines.items():
+            sl.env.set_state(state["sightlines"][name]["env"])
+            sl.last = None
         if self.disturbance is not None:
             self.disturbance.load_state_dict(state["disturbance"])
             self._coeff = self.disturbance.coefficients()
@@ -258,6 +568,9 @@ class LayeredAOEnv(BatchedAOEnv):
         for lay in self.__dict__.get("_layers", ()):
             lay.close()
         self._layers = []
+        for sl in self.__dict__.get("_sightlines", {}).values():
+            sl.env.close()
+        self._sightlines = {}
         if self.__dict__.get("disturbance") is not None:
             self.disturbance.close()
             self.disturbance = None
