@@ -724,8 +724,22 @@ class BatchedAOEnv:
         """Install the float64 sum of the current screens of ``layers`` (1 .. 8 dynamic ``BatchedAOEnv`` of this env's batch, pupil and
         device) as this quasi-static env's screens (``aog_install_layer_sum``): aperture mean removed, stream-ordered, no host
         synchronisation.  Actuators and counters stay; the next ``reset`` / ``step`` observes the new screens."""
+        self._install_layers(self.lib.aog_install_layer_sum, layers)
+
+    def _install_layers(self, entry, layers, *lead, terms=False, coeff=None, coeff_optional=False):
+        """The one call behind ``install_layer_sum``, ``LayeredAOEnv.install_layer_sum_disturbed`` and ``layered.install_layer_sum_sightline``:
+        ``entry(handle, layer handles, L, *lead[, coeff, K], stream)`` on this env's stream.  ``terms``: the entry point takes coefficients,
+        a [B, K] float64 device tensor (None only where ``coeff_optional``: no terms)."""
+        who, tail = entry.__name__[len("aog_"):], []
+        if terms and coeff is None and coeff_optional:
+            tail = [None, 0]
+        elif terms:
+            torch = self._torch
+            if not isinstance(coeff, torch.Tensor) or coeff.dtype != torch.float64 or coeff.dim() != 2 or coeff.shape[0] != self.num_envs or not coeff.is_contiguous():
+                raise ValueError(f"{who}: coeff must be a contiguous float64 [{self.num_envs}, K] device tensor")
+            tail = [C.c_void_p(coeff.data_ptr()), int(coeff.shape[1])]
         handles = (C.c_void_p * len(layers))(*[lay._handle.value for lay in layers])
-        _lib.check(self.lib.aog_install_layer_sum(self._handle, handles, len(layers), self._stream()))
+        _lib.check(entry(self._handle, handles, len(layers), *lead, *tail, self._stream()))
         self.state_epoch += 1
 
     def lookahead(self, enable=True):

@@ -247,7 +247,7 @@ struct aog_env {
   double* dist_basis = nullptr;  // [dist_terms][n_ap] pupil shapes of the modal disturbance in the masters' unit (aog_upload_disturbance_basis; aog_install_layer_sum_disturbed reads them)
   int dist_terms = 0;
   // sightline installation (aog_install_layer_sum_sightline): the shifts of the last one, [sight_layers][B][2] (sx, sy) in pixels
-  double* sight_shift = nullptr;   // device, room for 8 layers; the *_sight kernels read it
+  double* sight_shift = nullptr;   // device, room for 8 layers; the kernels read it through SightLayers
   double* sight_stage = nullptr;   // pinned, the same values: what a new installation's shifts are compared with and copied from
   hipEvent_t sight_ev = nullptr;   // recorded after the last copy out of the staging buffer
   int sight_layers = 0;            // layers the two buffers hold values for (0: none yet)

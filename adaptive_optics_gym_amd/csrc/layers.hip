@@ -1,7 +1,6 @@
 // Layered atmosphere (several frozen-flow layers per env): the atmosphere-only step of a layer handle and the installation of the layers'
 // sum in a quasi-static front handle, plain, with a modal disturbance added inside the sum, or read along a sightline (layers larger than
-// the front, displaced by a fraction of a pixel).  No existing launch changes: a handle that never comes here runs what it ran before, and
-// an installation without a disturbance or a sightline launches the kernels it launched before.
+// the front, displaced by a fraction of a pixel).  A handle that never comes here launches nothing of this file.
 #include "host_common.h"
 #include "k_layers.h"
 #include "../../include/aogym_disturbance.h"
@@ -13,18 +12,43 @@ static_assert(aog::kMaxTerms == AOG_DISTURBANCE_MAX_TERMS, "the disturbance's te
 
 namespace {
 
-// launches `KERNEL<L>` for the run-time layer count (1 .. kMaxLayers)
-#define AOG_LAYER_DISPATCH(L, KERNEL, grid, block, s, ...)                                               \
-  switch (L) {                                                                                           \
-    case 1: hipLaunchKernelGGL((aog::KERNEL<1>), grid, block, 0, s, __VA_ARGS__); break;                 \
-    case 2: hipLaunchKernelGGL((aog::KERNEL<2>), grid, block, 0, s, __VA_ARGS__); break;                 \
-    case 3: hipLaunchKernelGGL((aog::KERNEL<3>), grid, block, 0, s, __VA_ARGS__); break;                 \
-    case 4: hipLaunchKernelGGL((aog::KERNEL<4>), grid, block, 0, s, __VA_ARGS__); break;                 \
-    case 5: hipLaunchKernelGGL((aog::KERNEL<5>), grid, block, 0, s, __VA_ARGS__); break;                 \
-    case 6: hipLaunchKernelGGL((aog::KERNEL<6>), grid, block, 0, s, __VA_ARGS__); break;                 \
-    case 7: hipLaunchKernelGGL((aog::KERNEL<7>), grid, block, 0, s, __VA_ARGS__); break;                 \
-    default: hipLaunchKernelGGL((aog::KERNEL<8>), grid, block, 0, s, __VA_ARGS__); break;                \
+// which of the three installations: what reads the layers and what is added inside the sum
+enum class LayerForm {
+  plain,       // aog_install_layer_sum: layers in the pupil plane, no terms
+  disturbed,   // aog_install_layer_sum_disturbed: layers in the pupil plane, the uploaded basis's terms
+  sightline,   // aog_install_layer_sum_sightline: layers of N_l >= N read at `shift_host`, terms when n_terms > 0
+};
+
+// The two launches of one installation.  Pass 1 reads every master once; pass 2 reads them again (8 n_ap bytes per env and layer, mostly
+// from L2 / Infinity Cache; along a sightline four samples per pixel and layer, neighbours of a line already requested); ModalTerms add
+// the K basis rows (8 K n_ap bytes, shared by every env: L2) to each pass.
+template <int L, class Layers, class Terms>
+void launch_passes(const Layers& layers, const Terms& terms, const aog_env* dst, hipStream_t s) {
+  const aog::LayerSum<Layers, Terms> sum{layers, terms};
+  const int N = dst->cfg.n_pupil;
+  hipLaunchKernelGGL((aog::k_layer_mean<L, Layers, Terms>), dim3(dst->B), dim3(256), 0, s, sum, dst->ap_index, dst->layer_mean, N, dst->n_ap);
+  if (dst->cfg.precision == AOG_PRECISION_FAST) {
+    const dim3 tiles(((dst->n_ptiles + 1) / 2 + aog::kLayerIters - 1) / aog::kLayerIters, dst->n_etiles);
+    hipLaunchKernelGGL((aog::k_layer_sum_tiles<L, Layers, Terms>), tiles, dim3(256), 0, s, sum, dst->ap_index, dst->layer_mean, dst->psi_tile, dst->B, N, dst->n_ap,
+                       dst->n_ptiles, rev_per_metre(dst));
+  } else {
+    hipLaunchKernelGGL((aog::k_layer_sum_f64<L, Layers, Terms>), dim3(dst->B), dim3(256), 0, s, sum, dst->ap_index, dst->layer_mean, dst->psi64, N, dst->n_ap);
   }
+}
+// ... for the run-time layer count (1 .. kMaxLayers)
+template <class Layers, class Terms>
+void launch_passes(int n_layers, const Layers& layers, const Terms& terms, const aog_env* dst, hipStream_t s) {
+  switch (n_layers) {
+    case 1: return launch_passes<1>(layers, terms, dst, s);
+    case 2: return launch_passes<2>(layers, terms, dst, s);
+    case 3: return launch_passes<3>(layers, terms, dst, s);
+    case 4: return launch_passes<4>(layers, terms, dst, s);
+    case 5: return launch_passes<5>(layers, terms, dst, s);
+    case 6: return launch_passes<6>(layers, terms, dst, s);
+    case 7: return launch_passes<7>(layers, terms, dst, s);
+    default: return launch_passes<8>(layers, terms, dst, s);
+  }
+}
 
 // The shifts of a sightline installation, checked against every layer's margin and brought to the front's own buffer on `s`: through
 // pinned staging, which keeps the values of the last installation, so that the same values arriving again cost a comparison and no copy.
@@ -56,14 +80,13 @@ int stage_shifts(const char* who, aog_env* dst, aog_env* const* layers, int n_la
   return AOG_OK;
 }
 
-// The one installation behind aog_install_layer_sum (coeff_dev null: the kernels without terms), aog_install_layer_sum_disturbed and
-// aog_install_layer_sum_sightline (shift_host non-null: layers of N_l >= N, the *_sight kernels, terms when n_terms > 0); `who` names the
-// entry point in every message
-int install_layer_sum(const char* who, aog_env* dst, aog_env* const* layers, int n_layers, const double* coeff_dev, int n_terms, bool disturbed,
-                      void* stream, const double* shift_host = nullptr) {
-  const bool sight = shift_host != nullptr;
+// The one installation behind the three entry points; `who` names the entry point in every message.  `shift_host` belongs to the sightline
+// form, `coeff_dev` and `n_terms` to the two forms with terms.
+int install_layer_sum(const char* who, LayerForm form, aog_env* dst, aog_env* const* layers, int n_layers, const double* shift_host, const double* coeff_dev,
+                      int n_terms, void* stream) {
+  const bool sight = form == LayerForm::sightline;
   if (sight && n_terms < 0) return fail(AOG_ERR_INVALID, "%s: %d terms", who, n_terms);
-  if (sight) disturbed = n_terms > 0;
+  const bool disturbed = sight ? n_terms > 0 : form == LayerForm::disturbed;   // (terms are added)
   if (!dst || !layers || (disturbed && !coeff_dev)) return fail(AOG_ERR_INVALID, "%s: null argument", who);
   if (n_layers < 1 || n_layers > aog::kMaxLayers) return fail(AOG_ERR_INVALID, "%s: %d layers (1 .. %d)", who, n_layers, aog::kMaxLayers);
   if (dst->cfg.atm_dynamic) return fail(AOG_ERR_INVALID, "%s: the front handle must not be atm_dynamic (its screens are installed, not evolved)", who);
@@ -100,43 +123,19 @@ int install_layer_sum(const char* who, aog_env* dst, aog_env* const* layers, int
     if (int rc = stage_shifts(who, dst, layers, n_layers, shift_host, s)) return rc;
   if (!dst->layer_mean)
     if (int rc = dev_alloc(dst, &dst->layer_mean, (size_t)dst->B, false)) return rc;
-  const int N = dst->cfg.n_pupil;
-  const dim3 tiles(((dst->n_ptiles + 1) / 2 + aog::kLayerIters - 1) / aog::kLayerIters, dst->n_etiles);
-  // pass 1 reads every master once; pass 2 reads them again (8 n_ap bytes per env and layer, mostly from L2 / Infinity Cache); the
-  // disturbed forms add the K basis rows (8 K n_ap bytes, shared by every env: L2) to each pass
+  const aog::ModalTerms terms{disturbed ? dst->dist_basis : nullptr, disturbed ? coeff_dev : nullptr, disturbed ? n_terms : 0, dst->n_ap};
   if (sight) {
-    // four samples per pixel and layer instead of one, mostly from L2 / Infinity Cache (neighbours of a line already requested)
-    aog::LayerSight geo{};
+    aog::SightLayers seen{src, {}};
     for (int l = 0; l < n_layers; ++l) {
-      geo.shift[l] = dst->sight_shift + (size_t)l * dst->B * 2;
-      geo.n[l] = layers[l]->cfg.n_pupil;
-      geo.c[l] = (layers[l]->cfg.n_pupil - N) / 2;
+      seen.sight.shift[l] = dst->sight_shift + (size_t)l * dst->B * 2;
+      seen.sight.n[l] = layers[l]->cfg.n_pupil;
+      seen.sight.c[l] = (layers[l]->cfg.n_pupil - dst->cfg.n_pupil) / 2;
     }
-    const aog::ModalTerms terms{disturbed ? dst->dist_basis : nullptr, disturbed ? coeff_dev : nullptr, disturbed ? n_terms : 0, dst->n_ap};
-    AOG_LAYER_DISPATCH(n_layers, k_layer_mean_sight, dim3(dst->B), dim3(256), s, src, geo, terms, dst->ap_index, dst->layer_mean, N, dst->n_ap);
-    if (fast) {
-      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_tiles_sight, tiles, dim3(256), s, src, geo, terms, dst->ap_index, dst->layer_mean, dst->psi_tile, dst->B, N,
-                         dst->n_ap, dst->n_ptiles, rev_per_metre(dst));
-    } else {
-      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_f64_sight, dim3(dst->B), dim3(256), s, src, geo, terms, dst->ap_index, dst->layer_mean, dst->psi64, N, dst->n_ap);
-    }
+    launch_passes(n_layers, seen, terms, dst, s);
   } else if (disturbed) {
-    const aog::ModalTerms terms{dst->dist_basis, coeff_dev, n_terms, dst->n_ap};
-    AOG_LAYER_DISPATCH(n_layers, k_layer_mean_dist, dim3(dst->B), dim3(256), s, src, terms, dst->ap_index, dst->layer_mean, N, dst->n_ap);
-    if (fast) {
-      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_tiles_dist, tiles, dim3(256), s, src, terms, dst->ap_index, dst->layer_mean, dst->psi_tile, dst->B, N, dst->n_ap,
-                         dst->n_ptiles, rev_per_metre(dst));
-    } else {
-      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_f64_dist, dim3(dst->B), dim3(256), s, src, terms, dst->ap_index, dst->layer_mean, dst->psi64, N, dst->n_ap);
-    }
+    launch_passes(n_layers, src, terms, dst, s);
   } else {
-    AOG_LAYER_DISPATCH(n_layers, k_layer_mean, dim3(dst->B), dim3(256), s, src, dst->ap_index, dst->layer_mean, N, dst->n_ap);
-    if (fast) {
-      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_tiles, tiles, dim3(256), s, src, dst->ap_index, dst->layer_mean, dst->psi_tile, dst->B, N, dst->n_ap, dst->n_ptiles,
-                         rev_per_metre(dst));
-    } else {
-      AOG_LAYER_DISPATCH(n_layers, k_layer_sum_f64, dim3(dst->B), dim3(256), s, src, dst->ap_index, dst->layer_mean, dst->psi64, N, dst->n_ap);
-    }
+    launch_passes(n_layers, src, aog::NoTerms{}, dst, s);
   }
   HIP_TRY(hipGetLastError());
   dst->screens_ready = true;
@@ -167,7 +166,7 @@ int aog_evolve_atmosphere(aog_env* e, void* stream) {
 }
 
 int aog_install_layer_sum(aog_env* dst, aog_env* const* layers, int n_layers, void* stream) {
-  return install_layer_sum("aog_install_layer_sum", dst, layers, n_layers, nullptr, 0, false, stream);
+  return install_layer_sum("aog_install_layer_sum", LayerForm::plain, dst, layers, n_layers, nullptr, nullptr, 0, stream);
 }
 
 int aog_upload_disturbance_basis(aog_env* dst, const double* basis_host, int n_terms) {
@@ -188,13 +187,13 @@ int aog_upload_disturbance_basis(aog_env* dst, const double* basis_host, int n_t
 }
 
 int aog_install_layer_sum_disturbed(aog_env* dst, aog_env* const* layers, int n_layers, const double* coeff_dev, int n_terms, void* stream) {
-  return install_layer_sum("aog_install_layer_sum_disturbed", dst, layers, n_layers, coeff_dev, n_terms, true, stream);
+  return install_layer_sum("aog_install_layer_sum_disturbed", LayerForm::disturbed, dst, layers, n_layers, nullptr, coeff_dev, n_terms, stream);
 }
 
 int aog_install_layer_sum_sightline(aog_env* dst, aog_env* const* layers, int n_layers, const double* shift_host, const double* coeff_dev, int n_terms,
                                     void* stream) {
   if (!shift_host) return fail(AOG_ERR_INVALID, "aog_install_layer_sum_sightline: null argument");
-  return install_layer_sum("aog_install_layer_sum_sightline", dst, layers, n_layers, coeff_dev, n_terms, false, stream, shift_host);
+  return install_layer_sum("aog_install_layer_sum_sightline", LayerForm::sightline, dst, layers, n_layers, shift_host, coeff_dev, n_terms, stream);
 }
 
 }  // extern "C"

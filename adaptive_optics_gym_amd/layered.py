@@ -21,7 +21,6 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib
 from .batched_env import BatchedAOEnv, _mask_array
 from .params import resolve_per_env, resolve_turbulence
 
@@ -146,15 +145,7 @@ def install_layer_sum_sightline(front, layers, shifts, coeff=None):
     shifts = np.ascontiguousarray(shifts, dtype=np.float64)
     if shifts.shape != (len(layers), front.num_envs, 2):
         raise ValueError(f"install_layer_sum_sightline: shifts must be [{len(layers)}, {front.num_envs}, 2], got {shifts.shape}")
-    if coeff is not None:
-        torch = front._torch
-        if not isinstance(coeff, torch.Tensor) or coeff.dtype != torch.float64 or coeff.dim() != 2 or coeff.shape[0] != front.num_envs or not coeff.is_contiguous():
-            raise ValueError(f"install_layer_sum_sightline: coeff must be a contiguous float64 [{front.num_envs}, K] device tensor")
-    handles = (C.c_void_p * len(layers))(*[lay._handle.value for lay in layers])
-    _lib.check(front.lib.aog_install_layer_sum_sightline(front._handle, handles, len(layers), shifts.ctypes.data_as(C.c_void_p),
-                                                         None if coeff is None else C.c_void_p(coeff.data_ptr()), 0 if coeff is None else int(coeff.shape[1]),
-                                                         front._stream()))
-    front.state_epoch += 1
+    front._install_layers(front.lib.aog_install_layer_sum_sightline, layers, C.c_void_p(shifts.ctypes.data), terms=True, coeff=coeff, coeff_optional=True)
 
 
 class Sightline:
@@ -170,23 +161,27 @@ class Sightline:
     def set_angle(self, angle):
         """Point this sightline elsewhere (inside the meta-pupil's margin: ``ValueError`` otherwise, before anything changes).  The next
         installation — the next step, or ``reset`` — reads the layers there."""
-        self._owner._set_angle(self, angle, f"sightline {self.name!r}")
+        self._look(*self._owner._shifts_for(angle, f"sightline {self.name!r}"))
+
+    def _look(self, angle, shifts):
+        """Store a checked line of sight (``LayeredAOEnv._shifts_for``): the next installation reads the layers at ``shifts``."""
+        self.angle, self._shifts = angle, shifts
 
 
-class _SightlineFront(BatchedAOEnv):
-    """The front of a ``Sightline``: like the ``LayeredAOEnv``'s own front it draws no screens, its layers do."""
+class _InstalledFront(BatchedAOEnv):
+    """A front whose screens are installed, never drawn: the ``LayeredAOEnv``'s own and the front of every ``Sightline``."""
 
     def _generate_screens(self, mask=None):
-        pass
+        """The front draws no screens: its layers do (at construction and in ``set_turbulence``)."""
 
     def _push_turbulence(self):
-        pass
+        """Nor does its handle need the per-env Cn^2 (only screen synthesis and the extrusion read them)."""
 
     def _host_extrusion_noise(self):
-        pass
+        """The layers draw their own normals (``evolve_atmosphere``)."""
 
 
-class LayeredAOEnv(BatchedAOEnv):
+class LayeredAOEnv(_InstalledFront):
     """``BatchedAOEnv`` over a layered dynamic atmosphere.  Keywords as ``BatchedAOEnv`` (``atm_type`` is 'dynamic'; ``atm_vel`` and
     ``screens`` do not apply) plus
 
@@ -271,7 +266,7 @@ class LayeredAOEnv(BatchedAOEnv):
             geometry = dict(angle=angle, declared=declared, n_meta=n_meta, margins=margins)
         self._front_args = dict(args=(act_type, act_dim, obs_dim, rew_type, rew_threshold, timesteps_per_episode, flat_mirror_start_per_episode,
                                       SH_operation), seed=seed, extrusion=extrusion, kw=dict(kw))
-        # The front: a quasi-static handle whose screens are installed, never drawn (_generate_screens below is a no-op); it consumes no
+        # The front: a quasi-static handle whose screens are installed, never drawn (_InstalledFront); it consumes no
         # host random draws, so layer 0 sees the streams a plain dynamic env with the same seed sees.
         super().__init__(num_envs, device, "quasi_static", 0, atm_fried, act_type, act_dim, obs_dim, rew_type, rew_threshold, timesteps_per_episode,
                          flat_mirror_start_per_episode, SH_operation, seed=seed, screen_source="device", rng=None,
@@ -321,15 +316,6 @@ class LayeredAOEnv(BatchedAOEnv):
     def wind_speeds(self):
         """[L, B] float64 wind speed of every layer and env."""
         return np.stack([lay.wind_speeds for lay in self._layers])
-
-    def _generate_screens(self, mask=None):
-        """The front draws no screens: its layers do (at construction and in ``set_turbulence``)."""
-
-    def _push_turbulence(self):
-        """Nor does its handle need the per-env Cn^2 (only screen synthesis and the extrusion read them)."""
-
-    def _host_extrusion_noise(self):
-        """The layers draw their own normals (``evolve_atmosphere``)."""
 
     def _attach_disturbance(self, disturbance):
         """``disturbance``: dict(shapes=, vibrations=, static=[, seed=]) for a ``ModalDisturbance`` of this env, or such an object made for
@@ -386,14 +372,14 @@ class LayeredAOEnv(BatchedAOEnv):
             raise ValueError(f"add_sightline: there is a sightline {name!r} already")
         angle, shifts = self._shifts_for(angle, f"sightline {name!r}")
         fa = self._front_args
-        front = _SightlineFront(self.num_envs, self.device, "quasi_static", 0, self.fried_parameter, *fa["args"], seed=fa["seed"], screen_source="device",
+        front = _InstalledFront(self.num_envs, self.device, "quasi_static", 0, self.fried_parameter, *fa["args"], seed=fa["seed"], screen_source="device",
                                 rng=None, global_env_offset=self.global_env_offset, total_envs=self.total_envs, extrusion=fa["extrusion"],
                                 verbose=False, **{**fa["kw"], "tables": self.tables, "params": self.params})
         try:
             if self.disturbance is not None:
                 self.disturbance.upload_basis(front)
             sl = Sightline(self, name, front, angle)
-            sl._shifts = shifts
+            sl._look(angle, shifts)
             install_layer_sum_sightline(front, self._layers, shifts, None if self.disturbance is None else self._coeff)
         except Exception:
             front.close()
@@ -401,17 +387,14 @@ class LayeredAOEnv(BatchedAOEnv):
         self._sightlines[name] = sl
         return sl
 
-    def _set_angle(self, target, angle, what):
-        angle, shifts = self._shifts_for(angle, what)
-        if target is self:
-            self.field_angle, self._shifts = angle, shifts
-        else:
-            target.angle, target._shifts = angle, shifts
-
     def set_field_angle(self, angle):
         """Point the env's own line of sight elsewhere (inside the meta-pupil's margin: ``ValueError`` otherwise, before anything changes).
         The next installation — the next step — reads the layers there."""
-        self._set_angle(self, angle, "field_angle")
+        self._look(*self._shifts_for(angle, "field_angle"))
+
+    def _look(self, angle, shifts):
+        """``Sightline._look`` for the env's own line of sight."""
+        self.field_angle, self._shifts = angle, shifts
 
     def _refuse_with_sightlines(self, who):
         if self._sightlines:
@@ -421,13 +404,7 @@ class LayeredAOEnv(BatchedAOEnv):
     def install_layer_sum_disturbed(self, layers, coeff):
         """``install_layer_sum`` with ``sum_k coeff[b][k] shape_k`` added inside the float64 sum (``aog_install_layer_sum_disturbed``; the
         shapes are those last uploaded with ``ModalDisturbance.upload_basis``).  ``coeff``: [B, K] float64 device tensor, metres of optical path."""
-        torch = self._torch
-        if not isinstance(coeff, torch.Tensor) or coeff.dtype != torch.float64 or coeff.dim() != 2 or coeff.shape[0] != self.num_envs or not coeff.is_contiguous():
-            raise ValueError(f"install_layer_sum_disturbed: coeff must be a contiguous float64 [{self.num_envs}, K] device tensor")
-        handles = (C.c_void_p * len(layers))(*[lay._handle.value for lay in layers])
-        _lib.check(self.lib.aog_install_layer_sum_disturbed(self._handle, handles, len(layers), C.c_void_p(coeff.data_ptr()), int(coeff.shape[1]),
-                                                            self._stream()))
-        self.state_epoch += 1
+        self._install_layers(self.lib.aog_install_layer_sum_disturbed, layers, terms=True, coeff=coeff)
 
     def _advance(self):
         for lay in self._layers:
@@ -548,11 +525,8 @@ class LayeredAOEnv(BatchedAOEnv):
             # (every angle is checked against this env's margins before anything changes)
             moved = [(self, self._shifts_for(state["field_angle"], "set_state: field_angle"))]
             moved += [(sl, self._shifts_for(state["sightlines"][name]["angle"], f"set_state: sightline {name!r}")) for name, sl in self._sightlines.items()]
-            for target, (angle, shifts) in moved:
-                if target is self:
-                    self.field_angle, self._shifts = angle, shifts
-                else:
-                    target.angle, target._shifts = angle, shifts
+            for target, look in moved:
+                target._look(*look)
         for lay, st in zip(self._layers, state["layers"]):
             lay.set_state(st)
         for name, sl in self._sightlines.items():

@@ -1,5 +1,5 @@
 """The modal disturbance on the device: the generator (aog_disturbance_*, k_disturbance) against a host replay of its recorded normals, the
-disturbed installation (aog_install_layer_sum_disturbed: k_layer_mean_dist, k_layer_sum_tiles_dist, k_layer_sum_f64_dist) against the host
+disturbed installation (aog_install_layer_sum_disturbed: the ModalTerms form of k_layer_mean, k_layer_sum_tiles and k_layer_sum_f64) against the host
 restatement, and ``LayeredAOEnv(disturbance=...)`` on top of them.
 
 Shapes follow test_gpu_layered.py: N = 32 and 48 (n_ap no multiple of 64: the last pair of pixel tiles is half empty), B in {1, 5, 33} (an

@@ -1,5 +1,5 @@
-"""Layer altitudes and sightlines on the device: aog_install_layer_sum_sightline (k_layer_mean_sight, k_layer_sum_tiles_sight,
-k_layer_sum_f64_sight) against the host restatement (tests/sightline_reference.py), anchored to the two existing installations, and
+"""Layer altitudes and sightlines on the device: aog_install_layer_sum_sightline (the SightLayers form of k_layer_mean,
+k_layer_sum_tiles and k_layer_sum_f64) against the host restatement (tests/sightline_reference.py), anchored to the two existing installations, and
 ``LayeredAOEnv(layer_altitudes=...)`` / ``add_sightline`` on top of it.
 
 Shapes follow test_gpu_layered.py, for its reasons: N = 32 under a meta-pupil of N_L = 48 (margin c = 8; n_ap no multiple of 64: the last
