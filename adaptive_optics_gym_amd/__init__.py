@@ -6,6 +6,7 @@
     from adaptive_optics_gym_amd import ModalTelemetry, ModalIntegrator   # loop telemetry (PSDs) and the optimised modal integrator
     from adaptive_optics_gym_amd import LinkTelemetry     # the optical link's read-out: fades, power histogram, bit-error rate
     from adaptive_optics_gym_amd import ModalDisturbance  # vibration and static aberrations for LayeredAOEnv(disturbance=...)
+    from adaptive_optics_gym_amd import MirrorServo       # loop latency and mirror dynamics for BatchedAOEnv(servo=...)
     import gym_AO                                         # registers 'AO-v0' like the reference (needs gymnasium)
 """
 from .batched_env import BatchedAOEnv  # noqa: F401
@@ -13,9 +14,10 @@ from .disturbance import ModalDisturbance  # noqa: F401
 from .layered import LayeredAOEnv, Sightline  # noqa: F401
 from .link import LinkTelemetry  # noqa: F401
 from .params import OpticalParams  # noqa: F401
+from .servo import MirrorServo  # noqa: F401
 from .telemetry import ModalIntegrator, ModalTelemetry  # noqa: F401
 
-__all__ = ["BatchedAOEnv", "LayeredAOEnv", "LinkTelemetry", "ModalDisturbance", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "Sightline", "register"]
+__all__ = ["BatchedAOEnv", "LayeredAOEnv", "LinkTelemetry", "MirrorServo", "ModalDisturbance", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "Sightline", "register"]
 
 
 def register():

@@ -108,6 +108,13 @@ class AogDisturbanceConfig(C.Structure):  # mirrors aog_disturbance_config (incl
 DISTURBANCE_MAX_TERMS = 8   # AOG_DISTURBANCE_MAX_TERMS
 
 
+class AogServoConfig(C.Structure):  # mirrors aog_servo_config (include/aogym_servo.h; its size query is aog_servo_config_size)
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "num_envs", "act_dim", "max_latency")]
+
+
+SERVO_MAX_LATENCY, SERVO_MAX_ACT = 4, 128   # AOG_SERVO_MAX_LATENCY, AOG_SERVO_MAX_ACT
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -250,6 +257,19 @@ SIGHTLINE_SYMBOLS = {
     "aog_install_layer_sum_sightline": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
+# every symbol include/aogym_servo.h declares
+SERVO_SYMBOLS = {
+    "aog_servo_config_size": (C.c_int64, []),
+    "aog_servo_create": (C.c_int, [C.POINTER(AogServoConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "aog_servo_destroy": (None, [C.c_void_p]),
+    "aog_servo_set_params": (C.c_int, [C.c_void_p] * 6),
+    "aog_servo_reset": (C.c_int, [C.c_void_p] * 3),
+    "aog_servo_apply": (C.c_int, [C.c_void_p] * 5),
+    "aog_servo_state_bytes": (C.c_int64, [C.c_void_p]),
+    "aog_servo_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_servo_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -267,7 +287,7 @@ def load():
     except Exception:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS, **SERVO_SYMBOLS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -287,6 +307,8 @@ def load():
     if lib.aog_disturbance_config_size() != C.sizeof(AogDisturbanceConfig):
         raise RuntimeError(f"AogDisturbanceConfig: ctypes layout is {C.sizeof(AogDisturbanceConfig)} bytes, the library's struct "
                            f"{lib.aog_disturbance_config_size()}")
+    if lib.aog_servo_config_size() != C.sizeof(AogServoConfig):
+        raise RuntimeError(f"AogServoConfig: ctypes layout is {C.sizeof(AogServoConfig)} bytes, the library's struct {lib.aog_servo_config_size()}")
     _lib = lib
     return lib
 

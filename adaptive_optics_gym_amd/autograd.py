@@ -44,7 +44,16 @@ def step_outputs(env, action):
     gradient of an episode's return.  The Strehl reward (AO_env.py:476) is ``strehl`` itself; the SSIM reward (AO_env.py:487) is a function
     of ``obs_raw`` and ``power`` that callers write in torch and chain through these outputs.  On the separable observation route the
     observation has its gradient on envs made with ``obs_gradient=True``; without it ``obs_raw`` comes back as NaN and its cotangent is
-    ignored, while power and Strehl keep theirs."""
+    ignored, while power and Strehl keep theirs.
+
+    Not on an env built with ``servo=`` (``RuntimeError``, before anything is stepped): there the mirror receives ``servo.apply(action)``,
+    which depends on the earlier commands and on the mirror's state, so one step is no longer the whole chain and the derivative with
+    respect to the command is not this call's to give (it is ``response (1 - f)`` of the applied action's at a latency below one frame,
+    zero from one frame on, and earlier steps' gradients flow into later outputs).  ``env.step(action)`` followed by
+    ``env.output_gradient(wrt="action")`` gives the gradient with respect to ``info["applied_action"]``, what the mirror received."""
+    env._refuse_with_servo("step_outputs", 'env.step(action) and env.output_gradient(wrt="action"), the gradient with respect to info["applied_action"]',
+                           why="the mirror receives servo.apply(action), which depends on earlier commands, so the one-step gradient with respect to "
+                               "the command is not the derivative of what the step returns")
     obs_raw, power, strehl = _StepOutputs.apply(action, env)
     return obs_raw, power, strehl
 

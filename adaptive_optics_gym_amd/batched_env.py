@@ -100,6 +100,17 @@ class BatchedAOEnv:
     envs from 8): ``output_gradient`` then takes ``g_obs`` and returns the float64 ``obs_raw`` in its values, and ``autograd.step_outputs``
     differentiates through the observation.  ``ValueError`` on a table-route env, which has that gradient already; ``env.obs_gradient``
     reads the flag.  Off the step path as well; its work buffers are allocated by the first ``output_gradient`` call.
+
+    ``servo`` (default None: ``step(a)`` sets the mirror to ``a`` at once and exactly, and the env launches what it always launched) puts a
+    mirror servo between the action and the mirror: ``dict(latency=0.0, response=1.0, stroke=None, stuck=None, max_latency=None)`` — frames of
+    loop latency (fractional allowed), the mirror's first-order response, its drive range and its dead actuators, each as
+    ``servo.MirrorServo`` takes them — or a ``MirrorServo`` made for this env (the env closes it).  ``env.servo`` is the object.  ``step``
+    steps with ``servo.apply(actions)`` and returns it as ``info["applied_action"]``; ``reset(mask)`` puts the selected envs' servo to rest
+    when ``flat_mirror_start_per_episode`` is true (the mirror is flat then, and so is its history) and leaves it alone otherwise;
+    ``get_state`` / ``set_state`` carry its state under ``"servo"``; ``set_actuators`` bypasses it and leaves it untouched.  The forms that
+    make or load the action inside a launch — ``step(next_actions=...)``, ``step_with_policy`` / ``reset_with_policy``, ``step_with_spgd`` /
+    ``reset_with_spgd`` — raise ``RuntimeError`` on such an env; ``rollout`` runs its unfused loop.  A controller's loop delay is then
+    ``1 + latency`` frames (``telemetry.gain_limit``, ``ModalIntegrator(delay=...)``).
     """
 
     def __init__(self, num_envs=1, device=None, atm_type="quasi_static", atm_vel=0, atm_fried=0.15,
@@ -108,10 +119,12 @@ class BatchedAOEnv:
                  num_pupil_pixels=240, seed=None, screen_source="device", screen_oversampling=16, screens=None,
                  precision="fast", kernel="auto", pixel_chunks=0, rng=None, verbose=True, params=None,
                  global_env_offset=0, total_envs=None, sh_fft_precision="single", screen_method="twoband", tables=None, extrusion="auto",
-                 obs_photons=None, obs_read_noise=0.0, obs_background=0.0, science_window=None, science_radii=None, obs_gradient=False, pyramid=None):
+                 obs_photons=None, obs_read_noise=0.0, obs_background=0.0, science_window=None, science_radii=None, obs_gradient=False, pyramid=None,
+                 servo=None):
         import torch
 
         self._handle = None   # (first: close() and accumulate_returns() read it on an env whose construction failed below)
+        self.servo = None
         self._returns_ref = None
         self._torch = torch
         self.lib = _lib.load()  # raises if the HIP extension is missing — no CPU fallback
@@ -233,6 +246,7 @@ class BatchedAOEnv:
             self._pyramid = pyramid_tables(self.num_pupil_pixels, self.tables.n_ap, cfg["samples"], cfg["q"], cfg["pixels"], cfg["n_mod"],
                                            cfg["r_mod"])   # (ValueError before anything is created)
             self.pyramid = cfg
+        servo_plan = self._servo_plan(servo)   # (ValueError before anything is created)
         self._create_handle(precision, kernel, pixel_chunks)
         self._upload_tables()
         layer = self._draw_wind_and_stencils()
@@ -249,6 +263,34 @@ class BatchedAOEnv:
         if self.SH_operation:
             self._upload_shack_hartmann()
         self._push_detector()   # (last: in host-RNG mode without a seed it draws the handle's seed after the reference's own draws)
+        if servo_plan is not None:
+            from .servo import MirrorServo
+
+            self.servo = servo if isinstance(servo, MirrorServo) else MirrorServo(self, **servo_plan)
+
+    def _servo_plan(self, servo):
+        """``servo=``: None, a dict of ``MirrorServo``'s keywords (checked here; returned for the constructor) or a ``MirrorServo`` made for
+        this env's batch, action width, global env ids and device."""
+        if servo is None:
+            return None
+        from .servo import MirrorServo, resolve_servo
+
+        if isinstance(servo, MirrorServo):
+            index = self.device.index if self.device.index is not None else self._torch.cuda.current_device()
+            mine = (self.num_envs, self.num_modes, self.global_env_offset, index)
+            if (servo.num_envs, servo.act_dim, servo.global_env_offset, servo.device.index) != mine:
+                raise ValueError(f"servo: made for {servo.num_envs} envs x {servo.act_dim} actuators from global id {servo.global_env_offset} on "
+                                 f"{servo.device}, this env has {self.num_envs} x {self.num_modes} from {self.global_env_offset} on {self.device}")
+            return {}
+        if not isinstance(servo, dict) or not set(servo) <= {"latency", "response", "stroke", "stuck", "max_latency"}:
+            raise ValueError("servo: a dict with any of 'latency', 'response', 'stroke', 'stuck' and 'max_latency', or a MirrorServo")
+        resolve_servo(self.num_envs, self.total_envs, self.global_env_offset, self.num_modes, **servo)
+        return dict(servo)
+
+    def _refuse_with_servo(self, who, instead, why=None):
+        if self.servo is not None:
+            why = why or f"{who} forms or loads the action inside a launch, where the servo has no place"
+            raise RuntimeError(f"{who}: this env has a mirror servo attached; {why} — use {instead}")
 
     def _create_handle(self, precision, kernel, pixel_chunks):
         """Fill the library's aog_config from this instance, create the handle on the env's device and give it its seed."""
@@ -805,6 +847,8 @@ class BatchedAOEnv:
         _lib.check(self.lib.aog_reset(self._handle, C.c_void_p(m.data_ptr()) if m is not None else None,
                                       C.c_void_p(obs_raw.data_ptr()), C.c_void_p(obs.data_ptr()), self._stream()))
         self._observed(obs, obs_raw)
+        if self.servo is not None and self.flat_mirror_start_per_episode:
+            self.servo.reset(m)   # (the mirror starts flat, and so does the history of its commands)
         return obs, {}
 
     _PIPELINE_END = object()
@@ -824,9 +868,14 @@ class BatchedAOEnv:
         ``next_actions=None``.
         Returns (obs float16 [B, o^2], reward float32 [B], done bool [B], trunc bool [B] (all False),
         {"power": [B] float32, "obs_raw": [B, o^2] float32, "strehl": [B] float32}).
+        An env built with ``servo=`` steps with ``applied = servo.apply(actions)`` — what the mirror receives this frame after the loop's
+        latency, the mirror's response, its stroke and its stuck actuators (``servo.MirrorServo``) — and returns it as
+        ``info["applied_action"]`` [B, A] float32; ``next_actions`` is refused there (``RuntimeError``).
         ``out`` (optional): (obs float16 [B, o^2], reward float32 [B], done bool/uint8 [B]) contiguous device tensors to write
         into — a rollout hands in slices of its transition buffers, so nothing is copied afterwards."""
         a = self._as_actions(actions)
+        if next_actions is not BatchedAOEnv._PIPELINE_END:
+            self._refuse_with_servo("step(next_actions=...)", "step(actions), one call per step")
         if self.atm_type == "dynamic" and self._host_rng:
             self._host_extrusion_noise()
         cached = self._persistent_out and out is None
@@ -838,6 +887,10 @@ class BatchedAOEnv:
             ret, ptrs = self._step_outputs(out)
             if cached:
                 self._step_cache = (ret, ptrs)
+        if self.servo is not None:
+            # (last before the launch: a call refused above — a bad ``out``, say — has pushed no frame into the servo's history.  A new
+            # tensor per step: _last_action and info["applied_action"] keep it)
+            a = ret[4]["applied_action"] = self.servo.apply(a)
         self._launch_step(a, next_actions, ptrs)
         self._last_action = a   # (output_gradient(wrt="action") differentiates through it)
         self._last_step = ret   # (SPGDController.action reads its metric)
@@ -967,6 +1020,7 @@ class BatchedAOEnv:
         into.  Masked resets are not fused (the query covers the whole batch): use ``reset(mask)`` and pass the first action.
         ``ou_noise`` (a ``rollout.DeviceOUNoise`` of [B, A]) / ``action_mode="mean"``: the query's action form, as in ``DeviceActor.__call__``
         (``aog_reset_act_noise``)."""
+        self._refuse_with_servo("reset_with_policy", "reset() and step(policy(obs)), or rollout(fused_policy=False)")
         if mask is not None:
             raise ValueError("reset_with_policy resets the whole batch; reset some envs with reset(mask) and step with an explicit action")
         net, pol, noise = self._policy_net(policy, cov_var, policy_out, ou_noise, action_mode)
@@ -984,6 +1038,7 @@ class BatchedAOEnv:
         episode's last step (no query, no call index consumed, ``policy_out`` untouched).  ``out`` as in ``step``; ``policy_out`` as in
         ``reset_with_policy``; ``ou_noise`` / ``action_mode`` as there (``aog_step_act_noise``: the OU state advances only when the policy is
         queried)."""
+        self._refuse_with_servo("step_with_policy", "step(policy(obs)), or rollout(fused_policy=False)")
         a = self._as_actions(action) if action is not None else None
         net, pol, noise = self._policy_net(policy, cov_var, policy_out, ou_noise, action_mode)
         ptrs, noise = self._policy_ptrs(pol, noise)
@@ -1010,6 +1065,7 @@ class BatchedAOEnv:
         reset's last launch also resets the controller (``ctrl.reset()``: flat start or the env's actuators, iteration counters kept) and
         loads its first command into the mirror, so the next ``step_with_spgd`` steps it (pass no ``action`` there).  Returns
         ``((obs, info), action)``.  Masked resets are not fused: use ``reset(mask)`` + ``ctrl.reset(mask)`` and pass the action."""
+        self._refuse_with_servo("reset_with_spgd", "reset(), ctrl.reset() and step(action), or rollout(fused_policy=False)")
         if mask is not None:
             raise ValueError("reset_with_spgd resets the whole batch; reset some envs with reset(mask) + ctrl.reset(mask) and step with an explicit action")
         action = self._spgd_checked(ctrl, action_out, "reset_with_spgd")
@@ -1022,6 +1078,7 @@ class BatchedAOEnv:
         ``ctrl.action()`` + the next ``step``'s prologue take three, bit-identical to that unfused loop.  Returns ``(step tuple, action)``, or
         ``(step tuple, None)`` on the episode's last step (no query, controller and ``action_out`` untouched).  ``out`` as in ``step``, or a
         dict ``{"obs", "reward", "done"}`` of those tensors that may also carry ``"action"`` (= ``action_out``)."""
+        self._refuse_with_servo("step_with_spgd", "step(ctrl.action()), or rollout(fused_policy=False)")
         if isinstance(out, dict):
             action_out = out.get("action", action_out)
             out = (out["obs"], out["reward"], out["done"])
@@ -1210,7 +1267,8 @@ class BatchedAOEnv:
         ``L = sum(g_obs * obs_raw) + sum(g_power * power) + sum(g_strehl * strehl)`` (cotangents: [B, o^2], [B], [B]; ``None`` = zero, at
         least one given) as a float64 device tensor [B, A].  ``wrt="actuators"``: with respect to ``get_actuators()`` (per metre of surface);
         ``wrt="action"``: with respect to the float32 action through the normalisation of AO_env.py:119-120 (``action`` defaults to the last
-        action passed to ``step()``; not on ``SH_operation`` environments, whose action is the actuators).  The atmosphere never depends on
+        action the mirror received: the one passed to ``step()``, or on an env with a servo ``info["applied_action"]`` — the gradient is with
+        respect to what the mirror received, not to the command; not on ``SH_operation`` environments, whose action is the actuators).  The atmosphere never depends on
         the action and a step sets the mirror absolutely, so this one-step gradient is the complete derivative of everything step t returns
         with respect to the policy.  The observation noise of ``set_detector`` does not enter: the gradient is of the clean outputs.
         ``with_values=True`` returns ``(grad, values)`` with ``values`` [B, o^2 + 2] the float64 obs_raw, power and Strehl the gradient was
@@ -1460,7 +1518,15 @@ class BatchedAOEnv:
                 "observation_frames": self.observation_frames,
                 "detector": None if self._detector is None else {k: v.copy() for k, v in self._detector.items()},
                 "pyramid": None if self.pyramid is None else {k: self.pyramid[k] for k in ("samples", "q", "pixels", "n_mod", "r_mod", "photons")},
-                "pyramid_frame_count": self.pyramid_frame_count}
+                "pyramid_frame_count": self.pyramid_frame_count, **({} if self.servo is None else {"servo": self.servo.state_dict()})}
+
+    def _check_servo_state(self, state):
+        """``ValueError`` unless ``state`` and this env both have a mirror servo, of one configuration, or neither has; nothing is touched."""
+        if ("servo" in state) != (self.servo is not None):
+            raise ValueError("set_state: the state was saved " + ("with" if "servo" in state else "without") + " a mirror servo, this environment was "
+                             "built " + ("without" if self.servo is None else "with") + " one (servo=dict(...))")
+        if self.servo is not None:
+            self.servo.check_state_dict(state["servo"])
 
     def set_state(self, state):
         """Resume from a ``get_state`` snapshot (see there for what it holds and what it leaves alone).  Whatever the handle had pending
@@ -1479,11 +1545,14 @@ class BatchedAOEnv:
         if "pyramid" in state and (state["pyramid"] is None) != (self.pyramid is None):   # (states from before the sensor was saved: no rule)
             raise ValueError("set_state: the state was saved " + ("without" if state["pyramid"] is None else "with") + " a pyramid sensor and this "
                              "environment was built " + ("with" if state["pyramid"] is None else "without") + " one (pyramid=dict(...))")
+        self._check_servo_state(state)
         if det is not None and any(np.asarray(det[k]).shape != (self.num_envs,) for k in ("photons", "read_noise", "background")):
             raise ValueError("state's detector values do not match this environment's num_envs")
         blob = state["blob"].to(self.device).contiguous()
         if blob.numel() != int(self.lib.aog_state_bytes(self._handle)):
             raise ValueError("state blob does not match this environment's configuration")
+        if self.servo is not None:
+            self.servo.load_state_dict(state["servo"])   # (ValueError for a servo of another configuration, before the handle is touched)
         self._upload_pyramid()   # (no-op when the sensor is there: an upload AFTER the restore would restart the frame count the blob brings)
         _lib.check(self.lib.aog_set_state(self._handle, C.c_void_p(blob.data_ptr()), int(state["lib_timestep"]), self._stream()))
         self.state_epoch += 1
@@ -1550,6 +1619,9 @@ class BatchedAOEnv:
         h, self._handle = self._handle, None
         if h:
             self.lib.aog_destroy(h)
+        servo, self.servo = self.__dict__.get("servo"), None
+        if servo is not None:
+            servo.close()
 
     def __del__(self):
         try:

@@ -198,6 +198,8 @@ class LayeredAOEnv(_InstalledFront):
                  (``default_meta_pupil_pixels``): the smallest accepted size that leaves the margin c >= ceil(max |h_l theta| /
                  pupil_pixel) + 1 over every sightline declared at construction (``field_angle`` and ``sightlines``).
     sightlines   None, or {name: angle} — ``add_sightline(angle, name)`` for each at the end of construction, counted in the default margin.
+    servo        as ``BatchedAOEnv``'s (through ``**kw``): one mirror, one servo — the env's own front steps with ``servo.apply(actions)`` and
+                 every sightline's front with the same applied action; the sightline fronts get no servo of their own.
 
     Layered geometry.  A layer at altitude 0 keeps N pixels and this env's tables; a layer above is built with
     ``dataclasses.replace(params, num_pupil_pixels=N_L, telescope_diameter=D N_L / N)`` — the same pixel pitch and Cn^2 on a wider
@@ -265,7 +267,7 @@ class LayeredAOEnv(_InstalledFront):
                 check_margin(sightline_shifts(altitudes, a, params.pupil_pixel), margins, what)
             geometry = dict(angle=angle, declared=declared, n_meta=n_meta, margins=margins)
         self._front_args = dict(args=(act_type, act_dim, obs_dim, rew_type, rew_threshold, timesteps_per_episode, flat_mirror_start_per_episode,
-                                      SH_operation), seed=seed, extrusion=extrusion, kw=dict(kw))
+                                      SH_operation), seed=seed, extrusion=extrusion, kw={k: v for k, v in kw.items() if k != "servo"})   # (one mirror, one servo: the env's)
         # The front: a quasi-static handle whose screens are installed, never drawn (_InstalledFront); it consumes no
         # host random draws, so layer 0 sees the streams a plain dynamic env with the same seed sees.
         super().__init__(num_envs, device, "quasi_static", 0, atm_fried, act_type, act_dim, obs_dim, rew_type, rew_threshold, timesteps_per_episode,
@@ -414,13 +416,17 @@ class LayeredAOEnv(_InstalledFront):
         self._install()
 
     def step(self, actions, out=None, next_actions=BatchedAOEnv._PIPELINE_END):
+        if next_actions is not BatchedAOEnv._PIPELINE_END:
+            self._refuse_with_servo("step(next_actions=...)", "step(actions), one call per step")   # (before the layers move)
         self._advance()
         ret = super().step(actions, out=out, next_actions=next_actions)
         if self._sightlines:
-            # (after the env's own front: every sightline's front takes the same action, on the sum _advance installed at its shifts)
+            # (after the env's own front: every sightline's front takes the same action — with a servo the one the mirror received — on the
+            # sum _advance installed at its shifts)
             seen = {}
+            applied = ret[4].get("applied_action", actions)
             for name, sl in self._sightlines.items():
-                obs, reward, _, _, info = sl.env.step(actions)
+                obs, reward, _, _, info = sl.env.step(applied)
                 sl.last = seen[name] = {"obs": obs, "reward": reward, "power": info["power"], "strehl": info["strehl"]}
             ret[4]["sightlines"] = seen
         return ret
@@ -447,11 +453,13 @@ class LayeredAOEnv(_InstalledFront):
 
     def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None, ou_noise=None, action_mode="sample"):
         self._refuse_with_sightlines("step_with_policy")
+        self._refuse_with_servo("step_with_policy", "step(policy(obs)), or rollout(fused_policy=False)")
         self._advance()
         return super().step_with_policy(policy, cov_var, out=out, policy_out=policy_out, action=action, ou_noise=ou_noise, action_mode=action_mode)
 
     def step_with_spgd(self, ctrl, out=None, action=None, action_out=None):
         self._refuse_with_sightlines("step_with_spgd")
+        self._refuse_with_servo("step_with_spgd", "step(ctrl.action()), or rollout(fused_policy=False)")
         self._advance()
         return super().step_with_spgd(ctrl, out=out, action=action, action_out=action_out)
 
@@ -517,6 +525,7 @@ class LayeredAOEnv(_InstalledFront):
         if ("disturbance" in state) != (self.disturbance is not None):
             raise ValueError("set_state: the state was saved " + ("with" if "disturbance" in state else "without") + " a disturbance, this env was built "
                              + ("without" if self.disturbance is None else "with") + " one")
+        self._check_servo_state(state)   # (here too, before a layer is touched: super().set_state checks it again)
         if ("field_angle" in state) != (self._altitudes is not None) or set(state.get("sightlines", ())) != set(self._sightlines):
             raise ValueError(f"set_state: the state was saved with layer altitudes {'on' if 'field_angle' in state else 'off'} and the sightlines "
                              f"{sorted(state.get('sightlines', ()))}, this env has them {'on' if self._altitudes is not None else 'off'} and "

@@ -408,6 +408,8 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     ``actor_impl="hip"`` (or ``policy="spgd"``, above), and takes a ``DeviceOUNoise`` and ``action_mode`` but not the torch
     ``OrnsteinUhlenbeckNoise`` (that noise would have to be added between the query and the prologue).  Returns the same dict, bit for
     bit, as the unfused loop with the same ``DeviceActor`` (seed and call counter) and, if any, an OU state equal to the unfused loop's.
+    Not for an env built with ``servo=``: its steps go through ``env.step``, the unfused loop, where the servo sits between the stored action
+    (the command, ``out["act"]``) and the mirror.
 
     ``lookahead=True`` (dynamic atmosphere on the device stream): the next step's wind extrusion is launched on the library's own stream
     beside this step's epilogue and the policy query — bit-identical results; the screens are off limits between two steps of an
@@ -432,6 +434,9 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     B = env.num_envs
     if gatherer is None:
         gatherer = EpisodeReturnGatherer(B, env.device, False)
+    if fused_policy and getattr(env, "servo", None) is not None:
+        raise ValueError("fused_policy=True: this env has a mirror servo attached, and the fused forms load the action inside the step's launch, "
+                         "where the servo has no place — the unfused loop (fused_policy=False) steps through it")
     if policy not in _POLICIES:
         raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive', 'modal' or 'spgd'")
     if action_mode not in ("sample", "mean"):

@@ -163,7 +163,8 @@ class ModalIntegrator:
     non-finite value leaves its env's command as it was.  ``retune(grid=None, segment=None)`` sets ``gains`` to
     ``telemetry.optimise_gains(delay, grid, segment)`` (envs that hold fewer samples than a segment keep theirs) and returns the
     predicted costs.  ``delay`` is the lag, in frames, between a measurement and the command it yields reaching the mirror: 1 in
-    ``rollout``'s loop."""
+    ``rollout``'s loop, and ``1 + latency`` for an env built with ``servo=dict(latency=...)`` (``servo.MirrorServo``: whole frames here; round
+    a fractional latency up, the conservative side of ``gain_limit``)."""
 
     def __init__(self, env, measurement="truth", delay=1, gain=0.4, leak=1.0, telemetry=None):
         check_measurement(env, measurement)
