@@ -121,7 +121,7 @@ class AogInfo(C.Structure):
         "kernel", "n_sums", "reserved")] + [("device_bytes", C.c_int64)]
 
 
-# every symbol include/aogym.h declares: name -> (restype, argtypes)
+# every symbol include/aogym.h declares: name -> (restype, argtypes); the stand-alone handles' lifecycle calls come from STANDALONE below
 SYMBOLS = {
     "aog_abi_version": (C.c_int, []),
     "aog_last_error": (C.c_char_p, []),
@@ -192,39 +192,19 @@ SYMBOLS = {
     "aog_upload_pyramid_reconstructor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_pyramid_update": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_pyramid_gradient": (C.c_int, [C.c_void_p] * 9),
-    "aog_predictor_create": (C.c_int, [C.POINTER(AogPredictorConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "aog_predictor_destroy": (None, [C.c_void_p]),
     "aog_predictor_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_predictor_update": (C.c_int, [C.c_void_p] * 6),
-    "aog_predictor_state_bytes": (C.c_int64, [C.c_void_p]),
-    "aog_predictor_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_predictor_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_telemetry_create": (C.c_int, [C.POINTER(AogTelemetryConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "aog_telemetry_destroy": (None, [C.c_void_p]),
     "aog_telemetry_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_telemetry_push": (C.c_int, [C.c_void_p] * 4),
     "aog_telemetry_psd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_telemetry_gains": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int] + [C.c_void_p] * 5),
-    "aog_telemetry_state_bytes": (C.c_int64, [C.c_void_p]),
-    "aog_telemetry_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_telemetry_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_spgd_create": (C.c_int, [C.POINTER(AogSpgdConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "aog_spgd_destroy": (None, [C.c_void_p]),
     "aog_spgd_set_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_spgd_reset": (C.c_int, [C.c_void_p] * 5),
     "aog_spgd_update": (C.c_int, [C.c_void_p] * 5),
-    "aog_spgd_state_bytes": (C.c_int64, [C.c_void_p]),
-    "aog_spgd_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_spgd_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_link_create": (C.c_int, [C.POINTER(AogLinkConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "aog_link_destroy": (None, [C.c_void_p]),
     "aog_link_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_link_push": (C.c_int, [C.c_void_p] * 4),
     "aog_link_statistics": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int,
                                       C.POINTER(C.c_double), C.c_int] + [C.c_void_p] * 13),
-    "aog_link_state_bytes": (C.c_int64, [C.c_void_p]),
-    "aog_link_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_link_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_reset_spgd": (C.c_int, [C.c_void_p] * 6),
     "aog_step_spgd": (C.c_int, [C.c_void_p] * 10 + [C.POINTER(C.c_int), C.c_void_p]),
     "aog_selftest_poisson":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
@@ -239,15 +219,10 @@ SYMBOLS = {
 # every symbol include/aogym_disturbance.h declares
 DISTURBANCE_SYMBOLS = {
     "aog_disturbance_config_size": (C.c_int64, []),
-    "aog_disturbance_create": (C.c_int, [C.POINTER(AogDisturbanceConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "aog_disturbance_destroy": (None, [C.c_void_p]),
     "aog_disturbance_set_params": (C.c_int, [C.c_void_p] * 7),
     "aog_disturbance_reset": (C.c_int, [C.c_void_p] * 4),
     "aog_disturbance_advance": (C.c_int, [C.c_void_p] * 5),
     "aog_disturbance_coefficients": (C.c_int, [C.c_void_p] * 3),
-    "aog_disturbance_state_bytes": (C.c_int64, [C.c_void_p]),
-    "aog_disturbance_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_disturbance_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aog_upload_disturbance_basis": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "aog_install_layer_sum_disturbed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
@@ -260,15 +235,26 @@ SIGHTLINE_SYMBOLS = {
 # every symbol include/aogym_servo.h declares
 SERVO_SYMBOLS = {
     "aog_servo_config_size": (C.c_int64, []),
-    "aog_servo_create": (C.c_int, [C.POINTER(AogServoConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "aog_servo_destroy": (None, [C.c_void_p]),
     "aog_servo_set_params": (C.c_int, [C.c_void_p] * 6),
     "aog_servo_reset": (C.c_int, [C.c_void_p] * 3),
     "aog_servo_apply": (C.c_int, [C.c_void_p] * 5),
-    "aog_servo_state_bytes": (C.c_int64, [C.c_void_p]),
-    "aog_servo_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "aog_servo_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+
+
+def _lifecycle(prefix, config):
+    """The five calls every stand-alone handle has (csrc/standalone_handle.h)."""
+    return {prefix + "_create": (C.c_int, [C.POINTER(config), C.c_int, C.POINTER(C.c_void_p)]), prefix + "_destroy": (None, [C.c_void_p]),
+            prefix + "_state_bytes": (C.c_int64, [C.c_void_p]), prefix + "_get_state": (C.c_int, [C.c_void_p] * 3),
+            prefix + "_set_state": (C.c_int, [C.c_void_p] * 3)}
+
+
+# the stand-alone handles: prefix -> (config class, the symbols of the header that declares it); their own calls are listed above
+STANDALONE = {"aog_predictor": (AogPredictorConfig, SYMBOLS), "aog_telemetry": (AogTelemetryConfig, SYMBOLS), "aog_spgd": (AogSpgdConfig, SYMBOLS),
+              "aog_link": (AogLinkConfig, SYMBOLS), "aog_disturbance": (AogDisturbanceConfig, DISTURBANCE_SYMBOLS),
+              "aog_servo": (AogServoConfig, SERVO_SYMBOLS)}
+for _prefix, (_config, _symbols) in STANDALONE.items():
+    _symbols.update(_lifecycle(_prefix, _config))
+del _prefix, _config, _symbols
 
 _lib = None
 
@@ -301,14 +287,12 @@ def load():
         if have.split("+")[0] != want:
             raise RuntimeError(f"libaogym.so was built from other sources (build id {have}, sources {want}): run "
                                "`python -m adaptive_optics_gym_amd.build` (or __graft_entry__.build())")
-    for which, cls in enumerate((AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite, AogObsMft, AogActionNoise)):
-        if lib.aog_struct_size(which) != C.sizeof(cls):
-            raise RuntimeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, the library's struct {lib.aog_struct_size(which)}")
-    if lib.aog_disturbance_config_size() != C.sizeof(AogDisturbanceConfig):
-        raise RuntimeError(f"AogDisturbanceConfig: ctypes layout is {C.sizeof(AogDisturbanceConfig)} bytes, the library's struct "
-                           f"{lib.aog_disturbance_config_size()}")
-    if lib.aog_servo_config_size() != C.sizeof(AogServoConfig):
-        raise RuntimeError(f"AogServoConfig: ctypes layout is {C.sizeof(AogServoConfig)} bytes, the library's struct {lib.aog_servo_config_size()}")
+    sized = [(cls, lib.aog_struct_size(which)) for which, cls in enumerate(
+        (AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite, AogObsMft, AogActionNoise))]
+    sized += [(AogDisturbanceConfig, lib.aog_disturbance_config_size()), (AogServoConfig, lib.aog_servo_config_size())]
+    for cls, size in sized:
+        if size != C.sizeof(cls):
+            raise RuntimeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, the library's struct {size}")
     _lib = lib
     return lib
 

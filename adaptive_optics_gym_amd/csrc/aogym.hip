@@ -1297,9 +1297,9 @@ static int step_spgd_tail(const aog_env* e, const aog_spgd* g, const char* who, 
                 "amplitude means nothing there", who);
   if (g->cfg.act_dim != e->A) return fail(AOG_ERR_INVALID, "%s: the controller's act_dim %d is not the handle's n_modes %d", who, g->cfg.act_dim, e->A);
   if (g->cfg.num_envs != e->B) return fail(AOG_ERR_INVALID, "%s: the controller's num_envs %d is not the handle's %d", who, g->cfg.num_envs, e->B);
-  if (g->cfg.env_id_base != e->cfg.env_id_base || g->device != e->device)
+  if (g->cfg.env_id_base != e->cfg.env_id_base || g->state.device != e->device)
     return fail(AOG_ERR_INVALID, "%s: the controller (env_id_base %d, device %d) does not belong to the handle (env_id_base %d, device %d)", who,
-                g->cfg.env_id_base, g->device, e->cfg.env_id_base, e->device);
+                g->cfg.env_id_base, g->state.device, e->cfg.env_id_base, e->device);
   const size_t lds = aog::step_spgd_lds_bytes(epilogue_lds(e));
   if (lds > kLdsBytes) return fail(AOG_ERR_UNSUPPORTED, "%s: the fused tail needs %zu bytes of LDS > %zu", who, lds, kLdsBytes);
   return AOG_OK;

@@ -86,8 +86,8 @@ int launch_with_lds(int device, hipStream_t s, void (*kernel)(Params...), dim3 g
     HIP_TRY(hipGetLastError());                                                                    \
   } while (0)
 
-// The per-env records of a handle that is no aog_env (aog_predictor, aog_telemetry, aog_spgd): one device buffer, and the stream-ordered
-// copies of its checkpoint (*_get_state / *_set_state: `blob` is a device buffer of `bytes` bytes)
+// The records of a handle that is no aog_env (the six of standalone_handle.h, which holds one each): one device buffer, and the
+// stream-ordered copies of its checkpoint (*_get_state / *_set_state: `blob` is a device buffer of `bytes` bytes)
 struct RecordStore {
   int device = 0;
   size_t bytes = 0;

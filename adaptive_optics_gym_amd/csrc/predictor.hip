@@ -1,14 +1,12 @@
 // K17: the predictive linear controller's per-env recursive-least-squares state (aog_predictor_*).  Independent of any aog_env.
-#include "host_common.h"
+#include "standalone_handle.h"
 #include "k_predictor.h"
 
 using namespace aog_host;
 
-struct aog_predictor {
-  aog_predictor_config cfg{};
+struct aog_predictor : StandaloneHandle<aog_predictor_config> {   // state: [batch] records (k_predictor.h)
   int n = 0;
   size_t rec_bytes = 0;
-  RecordStore state;   // [batch] records (k_predictor.h)
 };
 
 namespace {
@@ -48,52 +46,30 @@ int launch_update(const aog_predictor* p, const aog::PredictorArgs& a, hipStream
   return launch_with_lds(p->state.device, s, aog::k_predictor_update<NW, RPW, CB, CBW, KEEP>, dim3(p->cfg.batch), dim3(NW * 64), lds, a);
 }
 
-void release(aog_predictor* p) {
-  p->state.release();
-  delete p;
-}
-
 }  // namespace
 
 extern "C" {
 
 int aog_predictor_create(const aog_predictor_config* cfg, int device, aog_predictor** out) {
-  if (!cfg || !out) return fail(AOG_ERR_INVALID, "aog_predictor_create: null argument");
-  *out = nullptr;
-  if (int rc = predictor_check(cfg)) return rc;
-  HIP_TRY(hipSetDevice(device));
-  aog_predictor* p = new aog_predictor;
-  p->cfg = *cfg;
-  p->n = cfg->act_dim * cfg->order;
-  p->rec_bytes = aog::predictor_record_words(cfg->act_dim, p->n) * sizeof(double);
-  hipError_t err = p->state.alloc(device, p->rec_bytes * (size_t)cfg->batch);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(aog::k_predictor_reset, dim3(cfg->batch), dim3(256), 0, nullptr, predictor_args(p, nullptr));
-    err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
-  }
-  if (err != hipSuccess) {
-    release(p);
-    return fail(AOG_ERR_HIP, "aog_predictor_create: %s", hipGetErrorString(err));
-  }
-  *out = p;
-  return AOG_OK;
+  return handle_create("aog_predictor_create", cfg, device, out, predictor_check, [](aog_predictor* p) {
+    p->n = p->cfg.act_dim * p->cfg.order;
+    p->rec_bytes = aog::predictor_record_words(p->cfg.act_dim, p->n) * sizeof(double);
+    if (hipError_t err = p->alloc_state(p->rec_bytes * (size_t)p->cfg.batch, false)) return err;
+    hipLaunchKernelGGL(aog::k_predictor_reset, dim3(p->cfg.batch), dim3(256), 0, nullptr, predictor_args(p, nullptr));
+    return hipGetLastError();
+  });
 }
 
-void aog_predictor_destroy(aog_predictor* p) {
-  if (!p) return;
-  (void)hipSetDevice(p->state.device);
-  release(p);
-}
+void aog_predictor_destroy(aog_predictor* p) { handle_destroy(p); }
 
 int aog_predictor_reset(aog_predictor* p, const uint8_t* mask_dev, void* stream) {
-  if (!p) return fail(AOG_ERR_INVALID, "aog_predictor_reset: null argument");
+  REFUSE_NULL("aog_predictor_reset", {"p", p});
   LAUNCH_PLAIN(p->state.device, stream, aog::k_predictor_reset, dim3(p->cfg.batch), dim3(256), predictor_args(p, mask_dev));
   return AOG_OK;
 }
 
 int aog_predictor_update(aog_predictor* p, const double* y_dev, const uint8_t* mask_dev, double* pred_dev, double* innov_dev, void* stream) {
-  if (!p || !y_dev || !pred_dev) return fail(AOG_ERR_INVALID, "aog_predictor_update: null argument");
+  REFUSE_NULL("aog_predictor_update", {"p", p}, {"y_dev", y_dev}, {"pred_dev", pred_dev});
   HIP_TRY(hipSetDevice(p->state.device));
   aog::PredictorArgs a = predictor_args(p, mask_dev);
   a.y = y_dev;
@@ -107,16 +83,14 @@ int aog_predictor_update(aog_predictor* p, const double* y_dev, const uint8_t* m
   return launch_update<8, 0, 4, 4, false>(p, a, s);
 }
 
-int64_t aog_predictor_state_bytes(const aog_predictor* p) { return p ? (int64_t)p->state.bytes : 0; }
+int64_t aog_predictor_state_bytes(const aog_predictor* p) { return handle_state_bytes(p); }
 
 int aog_predictor_get_state(aog_predictor* p, void* blob_dev, void* stream) {
-  if (!p || !blob_dev) return fail(AOG_ERR_INVALID, "aog_predictor_get_state: null argument");
-  return p->state.copy_out(blob_dev, stream);
+  return handle_get_state("aog_predictor_get_state", "p", p, blob_dev, stream);
 }
 
 int aog_predictor_set_state(aog_predictor* p, const void* blob_dev, void* stream) {
-  if (!p || !blob_dev) return fail(AOG_ERR_INVALID, "aog_predictor_set_state: null argument");
-  return p->state.copy_in(blob_dev, stream);
+  return handle_set_state("aog_predictor_set_state", "p", p, blob_dev, stream);
 }
 
 }  // extern "C"

@@ -1,17 +1,13 @@
 // K22: the mirror servo (aog_servo_*): loop latency, first-order mirror response, finite stroke and stuck actuators between the commanded
 // action and the action the mirror receives.  Independent of any aog_env; whoever owns the handle steps the env with what it writes.
-#include "host_common.h"
-#include <initializer_list>
-#include <utility>
+#include "standalone_handle.h"
 #include "k_servo.h"
 #include "../../include/aogym_servo.h"
 
 using namespace aog_host;
 
-struct aog_servo {
-  aog_servo_config cfg{};
-  RecordStore state;            // y [B][A] float64, counter (uint64), ring [B][R][A] float32 (k_servo.h)
-  char* params = nullptr;       // frac, response, stroke [B] float64 each | stuck_value [B][A] float32 | delay [B] int32 | stuck [B][A] uint8
+struct aog_servo : StandaloneHandle<aog_servo_config> {   // state: y [B][A] float64, counter (uint64), ring [B][R][A] float32 (k_servo.h)
+  char* params = nullptr;       // the block ServoParams carves
   unsigned long long calls = 0; // the counter, kept here: every aog_servo_apply hands n mod R and n + 1 to its launch
 };
 
@@ -21,38 +17,44 @@ size_t envs(const aog_servo* g) { return (size_t)g->cfg.num_envs; }
 size_t cells(const aog_servo* g) { return envs(g) * g->cfg.act_dim; }
 int depth(const aog_servo* g) { return g->cfg.max_latency + 2; }
 size_t counter_offset(const aog_servo* g) { return sizeof(double) * cells(g); }
-size_t param_bytes(const aog_servo* g) { return (3 * sizeof(double) + sizeof(int32_t)) * envs(g) + (sizeof(float) + 1) * cells(g); }
 
-// the parameter block as it goes to the device: the identity until aog_servo_set_params
-struct HostParams {
-  std::vector<char> bytes;
+// The parameter block, on the host and on the device: frac | response | stroke ([B] float64 each) | stuck_value ([B][A] float32) |
+// delay ([B] int32) | stuck ([B][A] uint8), carved from `base` for B envs and n = B A cells (base null: only `bytes` means anything)
+struct ServoParams {
   double *frac, *response, *stroke;
   float* stuck_value;
   int32_t* delay;
   uint8_t* stuck;
-  explicit HostParams(const aog_servo* g) : bytes(param_bytes(g), 0) {
-    const size_t B = envs(g), n = cells(g);
-    frac = reinterpret_cast<double*>(bytes.data());
-    response = frac + B;
-    stroke = response + B;
-    stuck_value = reinterpret_cast<float*>(stroke + B);
-    delay = reinterpret_cast<int32_t*>(stuck_value + n);
-    stuck = reinterpret_cast<uint8_t*>(delay + B);
+  size_t bytes = 0;
+  ServoParams(char* base, size_t B, size_t n) {
+    auto take = [&](auto*& p, size_t count) {
+      p = base ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + bytes) : nullptr;
+      bytes += count * sizeof(*p);
+    };
+    take(frac, B), take(response, B), take(stroke, B), take(stuck_value, n), take(delay, B), take(stuck, n);
   }
+};
+size_t param_bytes(const aog_servo* g) { return ServoParams(nullptr, envs(g), cells(g)).bytes; }
+
+// the block as it goes to the device, staged on the host
+struct HostParams {
+  std::vector<char> bytes;
+  ServoParams at;
+  explicit HostParams(const aog_servo* g) : bytes(param_bytes(g), 0), at(bytes.data(), envs(g), cells(g)) {}
 };
 
 aog::ServoArgs servo_args(const aog_servo* g, const float* in, const uint8_t* mask, float* out) {
-  const size_t B = envs(g), n = cells(g);
+  const ServoParams p(g->params, envs(g), cells(g));
   aog::ServoArgs a{};
   a.y = reinterpret_cast<double*>(g->state.ptr);
   a.counter = reinterpret_cast<unsigned long long*>(g->state.ptr + counter_offset(g));
   a.ring = reinterpret_cast<float*>(g->state.ptr + counter_offset(g) + sizeof(unsigned long long));
-  a.frac = reinterpret_cast<const double*>(g->params);
-  a.response = a.frac + B;
-  a.stroke = a.response + B;
-  a.stuck_value = reinterpret_cast<const float*>(a.stroke + B);
-  a.delay = reinterpret_cast<const int*>(a.stuck_value + n);
-  a.stuck = reinterpret_cast<const uint8_t*>(a.delay + B);
+  a.frac = p.frac;
+  a.response = p.response;
+  a.stroke = p.stroke;
+  a.stuck_value = p.stuck_value;
+  a.delay = p.delay;
+  a.stuck = p.stuck;
   a.in = in;
   a.mask = mask;
   a.out = out;
@@ -66,32 +68,7 @@ aog::ServoArgs servo_args(const aog_servo* g, const float* in, const uint8_t* ma
 
 dim3 grid_of(const aog_servo* g) { return dim3((unsigned)((cells(g) + 255) / 256)); }
 
-// the first null pointer among an entry point's arguments, by name (nullptr: none is null)
-const char* first_null(std::initializer_list<std::pair<const char*, const void*>> args) {
-  for (const auto& a : args)
-    if (!a.second) return a.first;
-  return nullptr;
-}
-#define REFUSE_NULL(who, ...)                                                                      \
-  do {                                                                                             \
-    if (const char* name__ = first_null({__VA_ARGS__})) return fail(AOG_ERR_INVALID, who ": null argument %s", name__); \
-  } while (0)
-
-void release(aog_servo* g) {
-  g->state.release();
-  if (g->params) (void)hipFree(g->params);
-  delete g;
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t aog_servo_config_size(void) { return (int64_t)sizeof(aog_servo_config); }
-
-int aog_servo_create(const aog_servo_config* cfg, int device, aog_servo** out) {
-  REFUSE_NULL("aog_servo_create", {"cfg", cfg}, {"out", out});
-  *out = nullptr;
+int servo_check(const aog_servo_config* cfg) {
   if (cfg->abi_version != AOG_ABI_VERSION) return fail(AOG_ERR_INVALID, "aog_servo_create: abi_version %d, the library is %d", cfg->abi_version, AOG_ABI_VERSION);
   if (cfg->num_envs < 1) return fail(AOG_ERR_INVALID, "aog_servo_create: num_envs %d must be >= 1", cfg->num_envs);
   if (cfg->act_dim < 1 || cfg->act_dim > AOG_SERVO_MAX_ACT)
@@ -101,34 +78,31 @@ int aog_servo_create(const aog_servo_config* cfg, int device, aog_servo** out) {
   // (the kernels index the ring with 32-bit env and actuator numbers)
   if ((long long)cfg->num_envs * cfg->act_dim * (cfg->max_latency + 2) > 0x7FFFFFFFll)
     return fail(AOG_ERR_INVALID, "aog_servo_create: num_envs %d x act_dim %d x (max_latency + 2) exceeds 2^31 - 1 ring entries", cfg->num_envs, cfg->act_dim);
-  HIP_TRY(hipSetDevice(device));
-  aog_servo* g = new aog_servo;
-  g->cfg = *cfg;
-  const size_t n = cells(g);
-  HostParams host(g);
-  for (size_t b = 0; b < envs(g); ++b) {
-    host.response[b] = 1.0;
-    host.stroke[b] = HUGE_VAL;
-  }
-  hipError_t err = g->state.alloc(device, sizeof(double) * n + sizeof(unsigned long long) + sizeof(float) * n * depth(g));
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&g->params), host.bytes.size());
-  // the state starts as zeros; the fill runs on the null stream, which a caller's non-blocking stream does not wait for
-  if (err == hipSuccess) err = hipMemset(g->state.ptr, 0, g->state.bytes);
-  if (err == hipSuccess) err = hipMemcpy(g->params, host.bytes.data(), host.bytes.size(), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
-  if (err != hipSuccess) {
-    release(g);
-    return fail(AOG_ERR_HIP, "aog_servo_create: %s", hipGetErrorString(err));
-  }
-  *out = g;
   return AOG_OK;
 }
 
-void aog_servo_destroy(aog_servo* g) {
-  if (!g) return;
-  (void)hipSetDevice(g->state.device);
-  release(g);
+}  // namespace
+
+extern "C" {
+
+int64_t aog_servo_config_size(void) { return (int64_t)sizeof(aog_servo_config); }
+
+int aog_servo_create(const aog_servo_config* cfg, int device, aog_servo** out) {
+  // the state starts as zeros, the parameters as the identity until aog_servo_set_params
+  return handle_create("aog_servo_create", cfg, device, out, servo_check, [](aog_servo* g) {
+    const size_t n = cells(g);
+    HostParams host(g);
+    for (size_t b = 0; b < envs(g); ++b) {
+      host.at.response[b] = 1.0;
+      host.at.stroke[b] = HUGE_VAL;
+    }
+    if (hipError_t err = g->alloc_state(sizeof(double) * n + sizeof(unsigned long long) + sizeof(float) * n * depth(g), true)) return err;
+    if (hipError_t err = g->own(&g->params, host.bytes.size(), false)) return err;
+    return hipMemcpy(g->params, host.bytes.data(), host.bytes.size(), hipMemcpyHostToDevice);
+  });
 }
+
+void aog_servo_destroy(aog_servo* g) { handle_destroy(g); }
 
 int aog_servo_set_params(aog_servo* g, const double* latency, const double* response, const double* stroke, const uint8_t* stuck,
                          const float* stuck_value) {
@@ -143,15 +117,15 @@ int aog_servo_set_params(aog_servo* g, const double* latency, const double* resp
     if (!(response[b] > 0.0 && response[b] <= 1.0)) return fail(AOG_ERR_INVALID, "aog_servo_set_params: response[%d] = %g outside (0, 1]", env, response[b]);
     if (!(stroke[b] > 0.0)) return fail(AOG_ERR_INVALID, "aog_servo_set_params: stroke[%d] = %g must be > 0 (+inf: no limit)", env, stroke[b]);
     const double d = std::floor(latency[b]);
-    host.delay[b] = (int32_t)d;
-    host.frac[b] = latency[b] - d;
-    host.response[b] = response[b];
-    host.stroke[b] = stroke[b];
+    host.at.delay[b] = (int32_t)d;
+    host.at.frac[b] = latency[b] - d;
+    host.at.response[b] = response[b];
+    host.at.stroke[b] = stroke[b];
     for (int j = 0; j < A; ++j) {
       const float v = stuck_value[b * A + j];
       if (!std::isfinite(v)) return fail(AOG_ERR_INVALID, "aog_servo_set_params: stuck_value[%d][%d] = %g is not finite", env, j, (double)v);
-      host.stuck_value[b * A + j] = v;
-      host.stuck[b * A + j] = stuck[b * A + j] ? 1 : 0;
+      host.at.stuck_value[b * A + j] = v;
+      host.at.stuck[b * A + j] = stuck[b * A + j] ? 1 : 0;
     }
   }
   HIP_TRY(hipSetDevice(g->state.device));
@@ -173,16 +147,12 @@ int aog_servo_apply(aog_servo* g, const float* action_in_dev, const uint8_t* mas
   return AOG_OK;
 }
 
-int64_t aog_servo_state_bytes(const aog_servo* g) { return g ? (int64_t)g->state.bytes : 0; }
+int64_t aog_servo_state_bytes(const aog_servo* g) { return handle_state_bytes(g); }
 
-int aog_servo_get_state(aog_servo* g, void* blob_dev, void* stream) {
-  REFUSE_NULL("aog_servo_get_state", {"servo", g}, {"blob_dev", blob_dev});
-  return g->state.copy_out(blob_dev, stream);
-}
+int aog_servo_get_state(aog_servo* g, void* blob_dev, void* stream) { return handle_get_state("aog_servo_get_state", "servo", g, blob_dev, stream); }
 
 int aog_servo_set_state(aog_servo* g, const void* blob_dev, void* stream) {
-  REFUSE_NULL("aog_servo_set_state", {"servo", g}, {"blob_dev", blob_dev});
-  if (int rc = g->state.copy_in(blob_dev, stream)) return rc;
+  if (int rc = handle_set_state("aog_servo_set_state", "servo", g, blob_dev, stream)) return rc;
   // the host's counter comes back from the blob: the one wait of this handle's calls
   unsigned long long calls = 0;
   HIP_TRY(hipMemcpyAsync(&calls, g->state.ptr + counter_offset(g), sizeof calls, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));

@@ -1,12 +1,9 @@
 // The SPGD controller's handle (aog_spgd), shared by spgd.hip (its own entry points) and aogym.hip (aog_reset_spgd / aog_step_spgd).
 #pragma once
-#include "host_common.h"
+#include "standalone_handle.h"
 #include "k_spgd.h"
 
-struct aog_spgd {
-  aog_spgd_config cfg{};
-  int device = 0;
-  aog_host::RecordStore state;   // [B] records (k_spgd.h)
+struct aog_spgd : aog_host::StandaloneHandle<aog_spgd_config> {   // state: [B] records (k_spgd.h)
   double* gain = nullptr;        // [B]
   double* amplitude = nullptr;   // [B]
   float* metric = nullptr;       // [B] where a fused step stores the metric when the caller passes no output for it

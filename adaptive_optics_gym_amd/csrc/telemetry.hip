@@ -1,14 +1,12 @@
 // K18: closed-loop modal telemetry (aog_telemetry_*): per-env rings of measurements, their Welch PSDs and the optimised integrator gains.
 // Independent of any aog_env.
-#include "host_common.h"
+#include "standalone_handle.h"
 #include "k_telemetry.h"
 
 using namespace aog_host;
 
-struct aog_telemetry {
-  aog_telemetry_config cfg{};
+struct aog_telemetry : StandaloneHandle<aog_telemetry_config> {   // state: [batch] records (k_telemetry.h)
   size_t rec_bytes = 0;
-  RecordStore state;       // [batch] records (k_telemetry.h)
   double* r2 = nullptr;    // |R_k(g)|^2 of the last aog_telemetry_gains and its grid: kTelMaxG (kTelMaxT / 2 + 1) float64
 };
 
@@ -58,12 +56,6 @@ int launch_psd_for(const aog_telemetry* t, int S, const aog::TelemetryArgs& a, h
   }
 }
 
-void release(aog_telemetry* t) {
-  t->state.release();
-  if (t->r2) (void)hipFree(t->r2);
-  delete t;
-}
-
 // the stability limit of z^d - z^(d-1) + g = 0: 2 at d = 1, 1 at d = 2
 double gain_limit(int delay) { return 2.0 * std::sin(M_PI / (2.0 * (2.0 * delay - 1.0))); }
 
@@ -72,42 +64,25 @@ double gain_limit(int delay) { return 2.0 * std::sin(M_PI / (2.0 * (2.0 * delay 
 extern "C" {
 
 int aog_telemetry_create(const aog_telemetry_config* cfg, int device, aog_telemetry** out) {
-  if (!cfg || !out) return fail(AOG_ERR_INVALID, "aog_telemetry_create: null argument");
-  *out = nullptr;
-  if (int rc = telemetry_check(cfg)) return rc;
-  HIP_TRY(hipSetDevice(device));
-  aog_telemetry* t = new aog_telemetry;
-  t->cfg = *cfg;
-  t->rec_bytes = aog::telemetry_record_words(cfg->act_dim, cfg->length) * sizeof(double);
-  hipError_t err = t->state.alloc(device, t->rec_bytes * (size_t)cfg->batch);
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&t->r2), sizeof(double) * aog::kTelMaxG * (aog::kTelMaxT / 2 + 1));
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(aog::k_telemetry_reset, dim3(cfg->batch), dim3(256), 0, nullptr, telemetry_args(t, nullptr));
-    err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
-  }
-  if (err != hipSuccess) {
-    release(t);
-    return fail(AOG_ERR_HIP, "aog_telemetry_create: %s", hipGetErrorString(err));
-  }
-  *out = t;
-  return AOG_OK;
+  return handle_create("aog_telemetry_create", cfg, device, out, telemetry_check, [](aog_telemetry* t) {
+    t->rec_bytes = aog::telemetry_record_words(t->cfg.act_dim, t->cfg.length) * sizeof(double);
+    if (hipError_t err = t->alloc_state(t->rec_bytes * (size_t)t->cfg.batch, false)) return err;
+    if (hipError_t err = t->own(&t->r2, sizeof(double) * aog::kTelMaxG * (aog::kTelMaxT / 2 + 1), false)) return err;
+    hipLaunchKernelGGL(aog::k_telemetry_reset, dim3(t->cfg.batch), dim3(256), 0, nullptr, telemetry_args(t, nullptr));
+    return hipGetLastError();
+  });
 }
 
-void aog_telemetry_destroy(aog_telemetry* t) {
-  if (!t) return;
-  (void)hipSetDevice(t->state.device);
-  release(t);
-}
+void aog_telemetry_destroy(aog_telemetry* t) { handle_destroy(t); }
 
 int aog_telemetry_reset(aog_telemetry* t, const uint8_t* mask_dev, void* stream) {
-  if (!t) return fail(AOG_ERR_INVALID, "aog_telemetry_reset: null argument");
+  REFUSE_NULL("aog_telemetry_reset", {"t", t});
   LAUNCH_PLAIN(t->state.device, stream, aog::k_telemetry_reset, dim3(t->cfg.batch), dim3(256), telemetry_args(t, mask_dev));
   return AOG_OK;
 }
 
 int aog_telemetry_push(aog_telemetry* t, const double* y_dev, const uint8_t* mask_dev, void* stream) {
-  if (!t || !y_dev) return fail(AOG_ERR_INVALID, "aog_telemetry_push: null argument");
+  REFUSE_NULL("aog_telemetry_push", {"t", t}, {"y_dev", y_dev});
   aog::TelemetryArgs a = telemetry_args(t, mask_dev);
   a.y = y_dev;
   LAUNCH_PLAIN(t->state.device, stream, aog::k_telemetry_push, dim3(t->cfg.batch), dim3(aog::kTelMaxA), a);
@@ -115,7 +90,7 @@ int aog_telemetry_push(aog_telemetry* t, const double* y_dev, const uint8_t* mas
 }
 
 int aog_telemetry_psd(aog_telemetry* t, int segment, double* psd_dev, int32_t* segments_dev, const uint8_t* mask_dev, void* stream) {
-  if (!t || !psd_dev) return fail(AOG_ERR_INVALID, "aog_telemetry_psd: null argument");
+  REFUSE_NULL("aog_telemetry_psd", {"t", t}, {"psd_dev", psd_dev});
   if (int rc = segment_check(t, "aog_telemetry_psd", segment)) return rc;
   HIP_TRY(hipSetDevice(t->state.device));
   aog::TelemetryArgs a = telemetry_args(t, mask_dev);
@@ -126,7 +101,7 @@ int aog_telemetry_psd(aog_telemetry* t, int segment, double* psd_dev, int32_t* s
 
 int aog_telemetry_gains(aog_telemetry* t, int segment, int delay, const double* grid_host, int n_grid, double* gain_dev, double* cost_dev,
                         double* cost_all_dev, const uint8_t* mask_dev, void* stream) {
-  if (!t || !grid_host || !gain_dev || !cost_dev) return fail(AOG_ERR_INVALID, "aog_telemetry_gains: null argument");
+  REFUSE_NULL("aog_telemetry_gains", {"t", t}, {"grid_host", grid_host}, {"gain_dev", gain_dev}, {"cost_dev", cost_dev});
   if (int rc = segment_check(t, "aog_telemetry_gains", segment)) return rc;
   if (delay < 1 || delay > aog::kTelMaxDelay) return fail(AOG_ERR_INVALID, "aog_telemetry_gains: delay %d outside [1, %d]", delay, aog::kTelMaxDelay);
   if (n_grid < 1 || n_grid > aog::kTelMaxG) return fail(AOG_ERR_INVALID, "aog_telemetry_gains: %d candidates outside [1, %d]", n_grid, aog::kTelMaxG);
@@ -153,16 +128,14 @@ int aog_telemetry_gains(aog_telemetry* t, int segment, int delay, const double* 
   return launch_psd_for(t, segment, a, static_cast<hipStream_t>(stream));
 }
 
-int64_t aog_telemetry_state_bytes(const aog_telemetry* t) { return t ? (int64_t)t->state.bytes : 0; }
+int64_t aog_telemetry_state_bytes(const aog_telemetry* t) { return handle_state_bytes(t); }
 
 int aog_telemetry_get_state(aog_telemetry* t, void* blob_dev, void* stream) {
-  if (!t || !blob_dev) return fail(AOG_ERR_INVALID, "aog_telemetry_get_state: null argument");
-  return t->state.copy_out(blob_dev, stream);
+  return handle_get_state("aog_telemetry_get_state", "t", t, blob_dev, stream);
 }
 
 int aog_telemetry_set_state(aog_telemetry* t, const void* blob_dev, void* stream) {
-  if (!t || !blob_dev) return fail(AOG_ERR_INVALID, "aog_telemetry_set_state: null argument");
-  return t->state.copy_in(blob_dev, stream);
+  return handle_set_state("aog_telemetry_set_state", "t", t, blob_dev, stream);
 }
 
 }  // extern "C"

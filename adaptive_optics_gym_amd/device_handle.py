@@ -1,5 +1,6 @@
-"""What the wrappers of the library's stand-alone handles share (``aog_predictor``, ``aog_telemetry``, ``aog_spgd``, ``aog_link``: per-env records on one
-device, independent of any ``aog_env``): the handle's life, the stream, the argument checks and the checkpoint calls."""
+"""What the wrappers of the library's stand-alone handles share (the six of ``_lib.STANDALONE``, ``aog_predictor`` to ``aog_servo``: per-env records on
+one device, independent of any ``aog_env``): the handle's life, the stream, the argument checks and the checkpoint calls.  The host's side of
+the same life is ``csrc/standalone_handle.h``."""
 from __future__ import annotations
 
 import ctypes as C
