@@ -1,7 +1,9 @@
 // Layered atmosphere (several frozen-flow layers per env): the atmosphere-only step of a layer handle and the installation of the layers'
 // sum in a quasi-static front handle, plain, with a modal disturbance added inside the sum, or read along a sightline (layers larger than
-// the front, displaced by a fraction of a pixel).  A handle that never comes here launches nothing of this file.
+// the front, displaced by a fraction of a pixel; altitude mirrors' surfaces as further sources).  A handle that never comes here launches
+// nothing of this file.
 #include "host_common.h"
+#include "conjugate_host.h"
 #include "k_layers.h"
 #include "../../include/aogym_disturbance.h"
 #include "../../include/aogym_sightline.h"
@@ -16,7 +18,13 @@ namespace {
 enum class LayerForm {
   plain,       // aog_install_layer_sum: layers in the pupil plane, no terms
   disturbed,   // aog_install_layer_sum_disturbed: layers in the pupil plane, the uploaded basis's terms
-  sightline,   // aog_install_layer_sum_sightline: layers of N_l >= N read at `shift_host`, terms when n_terms > 0
+  sightline,   // aog_install_layer_sum_sightline, aog_install_layer_sum_conjugate: sources of N_l >= N read at `shift_host`, terms when n_terms > 0
+};
+
+// one source of a sightline installation as the margin check names it: layer l, or mirror j behind the layers
+struct SightSource {
+  const char* kind;
+  int index, n;   // N_l
 };
 
 // The two launches of one installation.  Pass 1 reads every master once; pass 2 reads them again (8 n_ap bytes per env and layer, mostly
@@ -50,19 +58,20 @@ void launch_passes(int n_layers, const Layers& layers, const Terms& terms, const
   }
 }
 
-// The shifts of a sightline installation, checked against every layer's margin and brought to the front's own buffer on `s`: through
+// The shifts of a sightline installation, checked against every source's margin and brought to the front's own buffer on `s`: through
 // pinned staging, which keeps the values of the last installation, so that the same values arriving again cost a comparison and no copy.
 // Nothing of the handle changes before every value has passed.
-int stage_shifts(const char* who, aog_env* dst, aog_env* const* layers, int n_layers, const double* shift_host, hipStream_t s) {
-  const size_t B = (size_t)dst->B, count = (size_t)n_layers * B * 2;
-  for (int l = 0; l < n_layers; ++l) {
-    const int c = (layers[l]->cfg.n_pupil - dst->cfg.n_pupil) / 2;
+int stage_shifts(const char* who, aog_env* dst, const SightSource* sources, int n_sources, const double* shift_host, hipStream_t s) {
+  const size_t B = (size_t)dst->B, count = (size_t)n_sources * B * 2;
+  for (int l = 0; l < n_sources; ++l) {
+    const SightSource& y = sources[l];
+    const int c = (y.n - dst->cfg.n_pupil) / 2;
     const double limit = c > 0 ? (double)(c - 1) : 0.0;
     for (size_t i = 0; i < 2 * B; ++i) {
       const double v = shift_host[(size_t)l * 2 * B + i];
       if (!std::isfinite(v) || std::fabs(v) > limit)
-        return fail(AOG_ERR_INVALID, "%s: shift %c = %.17g pixels of layer %d, env %d is outside the margin (|shift| <= %g: the layer has %d pixels, "
-                    "the front %d, c = %d)", who, (i & 1) ? 'y' : 'x', v, l, (int)(i / 2), limit, layers[l]->cfg.n_pupil, dst->cfg.n_pupil, c);
+        return fail(AOG_ERR_INVALID, "%s: shift %c = %.17g pixels of %s %d, env %d is outside the margin (|shift| <= %g: the %s has %d pixels, "
+                    "the front %d, c = %d)", who, (i & 1) ? 'y' : 'x', v, y.kind, y.index, (int)(i / 2), limit, y.kind, y.n, dst->cfg.n_pupil, c);
     }
   }
   const size_t capacity = (size_t)aog::kMaxLayers * B * 2;
@@ -70,25 +79,31 @@ int stage_shifts(const char* who, aog_env* dst, aog_env* const* layers, int n_la
     if (int rc = dev_alloc(dst, &dst->sight_shift, capacity, false)) return rc;
   if (!dst->sight_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&dst->sight_stage), sizeof(double) * capacity, hipHostMallocDefault));
   if (!dst->sight_ev) HIP_TRY(hipEventCreateWithFlags(&dst->sight_ev, hipEventDisableTiming));
-  if (dst->sight_layers == n_layers && std::memcmp(dst->sight_stage, shift_host, sizeof(double) * count) == 0) return AOG_OK;
+  if (dst->sight_layers == n_sources && std::memcmp(dst->sight_stage, shift_host, sizeof(double) * count) == 0) return AOG_OK;
   HIP_TRY(hipEventSynchronize(dst->sight_ev));   // (the previous copy out of the staging buffer; long done in practice)
   dst->sight_layers = 0;
   std::memcpy(dst->sight_stage, shift_host, sizeof(double) * count);
   HIP_TRY(hipMemcpyAsync(dst->sight_shift, dst->sight_stage, sizeof(double) * count, hipMemcpyHostToDevice, s));
   HIP_TRY(hipEventRecord(dst->sight_ev, s));
-  dst->sight_layers = n_layers;
+  dst->sight_layers = n_sources;
   return AOG_OK;
 }
 
-// The one installation behind the three entry points; `who` names the entry point in every message.  `shift_host` belongs to the sightline
-// form, `coeff_dev` and `n_terms` to the two forms with terms.
+// The one installation behind the four entry points; `who` names the entry point in every message.  `shift_host` and the mirrors (sources
+// n_layers .. n_layers + n_mirrors - 1, each read as a layer of M pixels whose ring has not turned) belong to the sightline form,
+// `coeff_dev` and `n_terms` to the forms with terms.
 int install_layer_sum(const char* who, LayerForm form, aog_env* dst, aog_env* const* layers, int n_layers, const double* shift_host, const double* coeff_dev,
-                      int n_terms, void* stream) {
+                      int n_terms, void* stream, aog_altmirror* const* mirrors = nullptr, int n_mirrors = 0) {
   const bool sight = form == LayerForm::sightline;
   if (sight && n_terms < 0) return fail(AOG_ERR_INVALID, "%s: %d terms", who, n_terms);
   const bool disturbed = sight ? n_terms > 0 : form == LayerForm::disturbed;   // (terms are added)
   if (!dst || !layers || (disturbed && !coeff_dev)) return fail(AOG_ERR_INVALID, "%s: null argument", who);
   if (n_layers < 1 || n_layers > aog::kMaxLayers) return fail(AOG_ERR_INVALID, "%s: %d layers (1 .. %d)", who, n_layers, aog::kMaxLayers);
+  if (n_mirrors < 0 || n_layers + n_mirrors > aog::kMaxLayers || (n_mirrors > 0 && !mirrors))
+    return fail(AOG_ERR_INVALID, "%s: %d layers and %d mirrors (n_mirrors >= 0 with its array, together at most %d sources)", who, n_layers, n_mirrors,
+                aog::kMaxLayers);
+  const int n_sources = n_layers + n_mirrors;
+  SightSource sources[aog::kMaxLayers];
   if (dst->cfg.atm_dynamic) return fail(AOG_ERR_INVALID, "%s: the front handle must not be atm_dynamic (its screens are installed, not evolved)", who);
   if (!dst->tables_ready) return fail(AOG_ERR_INVALID, "%s before aog_upload_tables", who);
   if (disturbed && !dst->dist_basis) return fail(AOG_ERR_INVALID, "%s before aog_upload_disturbance_basis", who);
@@ -112,6 +127,21 @@ int install_layer_sum(const char* who, LayerForm form, aog_env* dst, aog_env* co
     if (int rc = check_poisoned(y, layer_who)) return rc;
     src.master[l] = y->psi_master;
     src.origin[l] = y->origin;
+    sources[l] = {"layer", l, y->cfg.n_pupil};
+  }
+  for (int j = 0; j < n_mirrors; ++j) {
+    const aog_altmirror* m = mirrors[j];
+    if (!m) return fail(AOG_ERR_INVALID, "%s: mirror %d is null", who, j);
+    const int M = m->cfg.n_pixels;
+    if (m->state.device != dst->device || m->cfg.num_envs != dst->B || M < dst->cfg.n_pupil)
+      return fail(AOG_ERR_INVALID, "%s: mirror %d (device %d, n_pixels %d, num_envs %d) does not match the front handle (device %d, N %d, B %d)", who, j,
+                  m->state.device, M, m->cfg.num_envs, dst->device, dst->cfg.n_pupil, dst->B);
+    if ((M - dst->cfg.n_pupil) % 2)
+      return fail(AOG_ERR_INVALID, "%s: mirror %d has %d pixels, the front %d: the difference must be even (the meta-pupil is centred on the pupil)", who,
+                  j, M, dst->cfg.n_pupil);
+    src.master[n_layers + j] = m->surface;
+    src.origin[n_layers + j] = m->origin;
+    sources[n_layers + j] = {"mirror", j, M};
   }
   const bool fast = dst->cfg.precision == AOG_PRECISION_FAST;
   if (fast && dst->kernel != AOG_KERNEL_MFMA)
@@ -120,18 +150,18 @@ int install_layer_sum(const char* who, LayerForm form, aog_env* dst, aog_env* co
   HIP_TRY(hipSetDevice(dst->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (sight)
-    if (int rc = stage_shifts(who, dst, layers, n_layers, shift_host, s)) return rc;
+    if (int rc = stage_shifts(who, dst, sources, n_sources, shift_host, s)) return rc;
   if (!dst->layer_mean)
     if (int rc = dev_alloc(dst, &dst->layer_mean, (size_t)dst->B, false)) return rc;
   const aog::ModalTerms terms{disturbed ? dst->dist_basis : nullptr, disturbed ? coeff_dev : nullptr, disturbed ? n_terms : 0, dst->n_ap};
   if (sight) {
     aog::SightLayers seen{src, {}};
-    for (int l = 0; l < n_layers; ++l) {
+    for (int l = 0; l < n_sources; ++l) {
       seen.sight.shift[l] = dst->sight_shift + (size_t)l * dst->B * 2;
-      seen.sight.n[l] = layers[l]->cfg.n_pupil;
-      seen.sight.c[l] = (layers[l]->cfg.n_pupil - dst->cfg.n_pupil) / 2;
+      seen.sight.n[l] = sources[l].n;
+      seen.sight.c[l] = (sources[l].n - dst->cfg.n_pupil) / 2;
     }
-    launch_passes(n_layers, seen, terms, dst, s);
+    launch_passes(n_sources, seen, terms, dst, s);
   } else if (disturbed) {
     launch_passes(n_layers, src, terms, dst, s);
   } else {
@@ -194,6 +224,13 @@ int aog_install_layer_sum_sightline(aog_env* dst, aog_env* const* layers, int n_
                                     void* stream) {
   if (!shift_host) return fail(AOG_ERR_INVALID, "aog_install_layer_sum_sightline: null argument");
   return install_layer_sum("aog_install_layer_sum_sightline", LayerForm::sightline, dst, layers, n_layers, shift_host, coeff_dev, n_terms, stream);
+}
+
+int aog_install_layer_sum_conjugate(aog_env* dst, aog_env* const* layers, int n_layers, aog_altmirror* const* mirrors, int n_mirrors,
+                                    const double* shift_host, const double* coeff_dev, int n_terms, void* stream) {
+  if (!shift_host) return fail(AOG_ERR_INVALID, "aog_install_layer_sum_conjugate: null argument");
+  return install_layer_sum("aog_install_layer_sum_conjugate", LayerForm::sightline, dst, layers, n_layers, shift_host, coeff_dev, n_terms, stream, mirrors,
+                           n_mirrors);
 }
 
 }  // extern "C"

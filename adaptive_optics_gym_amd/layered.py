@@ -12,7 +12,8 @@ With ``layer_altitudes`` the layers leave the pupil plane: a layer at altitude h
 that angle, so it is drawn on a meta-pupil larger than the pupil and every front — the env's own (``field_angle``) and any number of
 further ``Sightline`` fronts over the same layers (``add_sightline``) — reads it at its own sub-pixel shift
 (``aog_install_layer_sum_sightline``).  The part of the wavefront that differs between two sightlines is angular anisoplanatism: no
-controller that senses on one of them removes it on the other.
+controller that senses on one of them removes it on the other.  ``altitude_mirrors`` adds the corrector that acts on it: deformable
+mirrors conjugated to altitudes (``conjugate.AltitudeMirror``), whose surfaces every front reads displaced like a layer at that altitude.
 """
 from __future__ import annotations
 
@@ -126,14 +127,15 @@ def default_meta_pupil_pixels(num_pupil_pixels, margin):
     return n
 
 
-def check_margin(shifts, margins, what):
+def check_margin(shifts, margins, what, first_mirror=None):
     """``ValueError`` unless every shift of layer l lies inside its margin: |s| <= c_l - 1, exactly 0 for c_l = 0 (what the library checks
-    again).  ``shifts`` [L, B, 2], ``margins`` [L]."""
+    again).  ``shifts`` [L, B, 2], ``margins`` [L].  ``first_mirror``: sources from that index on are altitude mirrors, named "mirror j"."""
     for l, c in enumerate(margins):
         limit = max(int(c) - 1, 0)
         worst = float(np.abs(shifts[l]).max())
         if not np.isfinite(worst) or worst > limit:
-            raise ValueError(f"{what}: layer {l} would be read {worst:.3f} pixels off the pupil, its meta-pupil leaves {limit} "
+            source = f"layer {l}" if first_mirror is None or l < first_mirror else f"mirror {l - first_mirror}"
+            raise ValueError(f"{what}: {source} would be read {worst:.3f} pixels off the pupil, its meta-pupil leaves {limit} "
                              f"(margin c = {int(c)}; build the env with a larger meta_pupil_pixels)")
 
 
@@ -198,6 +200,21 @@ class LayeredAOEnv(_InstalledFront):
                  (``default_meta_pupil_pixels``): the smallest accepted size that leaves the margin c >= ceil(max |h_l theta| /
                  pupil_pixel) + 1 over every sightline declared at construction (``field_angle`` and ``sightlines``).
     sightlines   None, or {name: angle} — ``add_sightline(angle, name)`` for each at the end of construction, counted in the default margin.
+    altitude_mirrors   None (the env constructs and launches exactly what it did before), or [dict(altitude=h, actuators=9), ...] —
+                 ``conjugate.resolve_mirror``'s forms — for one ``conjugate.AltitudeMirror`` each: ``env.altitude_mirrors`` is the list.  Needs
+                 ``layer_altitudes``; layers plus mirrors are at most 8; the mirrors' altitudes count in the default margin and in every
+                 margin check (construction, ``add_sightline``, ``set_angle``, ``set_field_angle``).  Every front — the env's own and each
+                 sightline's — gets the mirrors' surfaces installed beside the layers at its own ``h_m theta / pupil_pixel``
+                 (``aog_install_layer_sum_conjugate``).  A mirror is absolute, like the pupil mirror: a command
+                 (``env.altitude_mirrors[j].set_command``) stands until it is set again and shows in the next installation (the next
+                 ``step``).  ``reset(mask)`` with ``flat_mirror_start_per_episode`` zeroes the masked envs' commands and installs again;
+                 ``get_state`` / ``set_state`` carry the commands; ``close`` closes the mirrors.  There is no servo on the altitude mirrors:
+                 a command acts in full on the step it precedes.
+    altitude_action    None, or a scale: ``action_space`` (and ``single_action_space``) widen by the mirrors' mode counts, ``step`` takes
+                 [B, A + sum K_m] actions, sets ``scale x`` the tail as the mirrors' commands (in mirror order, float64) before the layers
+                 advance and steps with the head; ``info["altitude_commands"]`` is the list of what was set.  With it ``step_with_policy``,
+                 ``step_with_spgd`` and ``step(next_actions=...)`` raise ``RuntimeError`` (the fused forms form or hold the action inside
+                 a launch, where there is nothing to split); ``rollout()`` runs its unfused loop.
     servo        as ``BatchedAOEnv``'s (through ``**kw``): one mirror, one servo — the env's own front steps with ``servo.apply(actions)`` and
                  every sightline's front with the same applied action; the sightline fronts get no servo of their own.
 
@@ -228,8 +245,11 @@ class LayeredAOEnv(_InstalledFront):
     def __init__(self, num_envs=1, device=None, atm_layers=None, atm_fried=0.15, act_type="num_actuators", act_dim=64, obs_dim=2,
                  rew_type="strehl_ratio", rew_threshold=None, timesteps_per_episode=20, flat_mirror_start_per_episode=True, SH_operation=False, *,
                  atm_type="dynamic", seed=None, screen_source="device", rng=None, global_env_offset=0, total_envs=None, extrusion="auto",
-                 verbose=True, disturbance=None, layer_altitudes=None, field_angle=None, meta_pupil_pixels=None, sightlines=None, **kw):
+                 verbose=True, disturbance=None, layer_altitudes=None, field_angle=None, meta_pupil_pixels=None, sightlines=None, altitude_mirrors=None,
+                 altitude_action=None, **kw):
         self._layers = []
+        self._mirrors = []
+        self._altitude_scale = None
         self._handle = None
         self.disturbance = None
         self._sightlines = {}
@@ -245,9 +265,23 @@ class LayeredAOEnv(_InstalledFront):
         if altitudes is None and (field_angle is not None or meta_pupil_pixels is not None or sightlines):
             raise ValueError("LayeredAOEnv: field_angle, meta_pupil_pixels and sightlines need layer_altitudes (without altitudes every layer sits "
                              "in the pupil plane and every direction sees the same wavefront)")
+        if altitudes is None and altitude_mirrors:
+            raise ValueError("LayeredAOEnv: altitude_mirrors need layer_altitudes (a mirror conjugated to an altitude is drawn on the layers' meta-pupil)")
+        if altitude_action is not None and not altitude_mirrors:
+            raise ValueError("LayeredAOEnv: altitude_action needs altitude_mirrors")
+        if altitude_action is not None and not np.isfinite(float(altitude_action)):
+            raise ValueError(f"altitude_action: a finite scale, got {altitude_action!r}")
         geometry = None
         if altitudes is not None:
+            from .conjugate import MAX_SOURCES, mirror_altitude, resolve_mirror
             from .params import OpticalParams
+
+            mirror_specs = list(altitude_mirrors or ())
+            if len(plan) + len(mirror_specs) > MAX_SOURCES:
+                raise ValueError(f"LayeredAOEnv: {len(plan)} layers and {len(mirror_specs)} altitude mirrors: an installation reads at most "
+                                 f"{MAX_SOURCES} sources")
+            # (the altitudes of every source an installation reads: the layers', then the mirrors')
+            seen_at = np.concatenate([altitudes, [mirror_altitude(m) for m in mirror_specs]]) if mirror_specs else altitudes
 
             params = kw.get("params") or OpticalParams(num_pupil_pixels=int(kw.get("num_pupil_pixels", 240)))
             n_env, n_off = int(num_envs), int(global_env_offset)
@@ -257,15 +291,18 @@ class LayeredAOEnv(_InstalledFront):
             declared = {str(k): resolve_field_angle(v, n_env, total_envs, n_off, f"sightline {k!r}") for k, v in (sightlines or {}).items()}
             N = params.num_pupil_pixels
             if meta_pupil_pixels is None:
-                n_meta = default_meta_pupil_pixels(N, required_margin(altitudes, [angle] + list(declared.values()), params.pupil_pixel))
+                n_meta = default_meta_pupil_pixels(N, required_margin(seen_at, [angle] + list(declared.values()), params.pupil_pixel))
             else:
                 n_meta = int(meta_pupil_pixels)
                 if n_meta != meta_pupil_pixels or n_meta < N or (n_meta - N) % 2:
                     raise ValueError(f"meta_pupil_pixels: expected an integer >= num_pupil_pixels ({N}) with an even difference, got {meta_pupil_pixels!r}")
-            margins = np.where(altitudes > 0, (n_meta - N) // 2, 0)
+            margins = np.where(seen_at > 0, (n_meta - N) // 2, 0)
             for what, a in [("field_angle", angle)] + [(f"sightline {k!r}", v) for k, v in declared.items()]:
-                check_margin(sightline_shifts(altitudes, a, params.pupil_pixel), margins, what)
-            geometry = dict(angle=angle, declared=declared, n_meta=n_meta, margins=margins)
+                check_margin(sightline_shifts(seen_at, a, params.pupil_pixel), margins, what, first_mirror=len(plan))
+            for m in mirror_specs:
+                resolve_mirror(m, N, n_meta)   # (actuators, coupling and a given basis's shape)
+            geometry = dict(angle=angle, declared=declared, n_meta=n_meta, margins=margins[:len(plan)], seen_at=seen_at, seen_margins=margins,
+                            mirrors=mirror_specs)
         self._front_args = dict(args=(act_type, act_dim, obs_dim, rew_type, rew_threshold, timesteps_per_episode, flat_mirror_start_per_episode,
                                       SH_operation), seed=seed, extrusion=extrusion, kw={k: v for k, v in kw.items() if k != "servo"})   # (one mirror, one servo: the env's)
         # The front: a quasi-static handle whose screens are installed, never drawn (_InstalledFront); it consumes no
@@ -303,7 +340,19 @@ class LayeredAOEnv(_InstalledFront):
                 self.meta_pupil_pixels = geometry["n_meta"]
                 self.layer_margins = geometry["margins"]          # [L] c_l: the meta-pupil's margin on every side, 0 for a ground layer
                 self.field_angle = geometry["angle"]              # [B, 2] radians
-                self._shifts = sightline_shifts(altitudes, self.field_angle, self.params.pupil_pixel)
+                self._seen_at, self._seen_margins = geometry["seen_at"], geometry["seen_margins"]   # the layers', then the mirrors'
+                self._shifts = sightline_shifts(self._seen_at, self.field_angle, self.params.pupil_pixel)
+                if geometry["mirrors"]:
+                    from .conjugate import AltitudeMirror
+
+                    for m in geometry["mirrors"]:
+                        self._mirrors.append(AltitudeMirror(self, **m))
+                    if altitude_action is not None:
+                        from .spaces import make_box
+
+                        self._altitude_scale = float(altitude_action)
+                        width = self.num_modes + sum(m.n_modes for m in self._mirrors)
+                        self.action_space = self.single_action_space = make_box(-1, 1, (width,), np.float16)
             self._install()   # the first reset sees t = 0
             if geometry is not None:
                 for name, angle in geometry["declared"].items():
@@ -341,13 +390,22 @@ class LayeredAOEnv(_InstalledFront):
         self.disturbance = d
         self._coeff = d.coefficients()
 
+    def _install_front(self, front, shifts, coeff):
+        """One front's installation along its line of sight: the layers, and the altitude mirrors' surfaces when the env has any."""
+        if self._mirrors:
+            from .conjugate import install_layer_sum_conjugate
+
+            install_layer_sum_conjugate(front, self._layers, self._mirrors, shifts, coeff)
+        else:
+            install_layer_sum_sightline(front, self._layers, shifts, coeff)
+
     def _install(self):
         coeff = None if self.disturbance is None else self._coeff
         if self._altitudes is not None:
-            # every front reads the same layers at its own shifts; the coefficients are common-path
-            install_layer_sum_sightline(self, self._layers, self._shifts, coeff)
+            # every front reads the same layers (and mirrors) at its own shifts; the coefficients are common-path
+            self._install_front(self, self._shifts, coeff)
             for sl in self._sightlines.values():
-                install_layer_sum_sightline(sl.env, self._layers, sl._shifts, coeff)
+                self._install_front(sl.env, sl._shifts, coeff)
         elif coeff is None:
             self.install_layer_sum(self._layers)
         else:
@@ -355,6 +413,7 @@ class LayeredAOEnv(_InstalledFront):
 
     layer_altitudes = property(lambda self: None if self._altitudes is None else self._altitudes.copy(), doc="[L] metres, or None")
     sightlines = property(lambda self: dict(self._sightlines), doc="{name: Sightline}")
+    altitude_mirrors = property(lambda self: list(self._mirrors), doc="[conjugate.AltitudeMirror], in the order of ``altitude_mirrors=``")
 
     def _shifts_for(self, angle, what):
         """``angle`` resolved to [B, 2] and its shifts [L, B, 2], checked against the margins (``ValueError`` before anything changes)."""
@@ -362,8 +421,8 @@ class LayeredAOEnv(_InstalledFront):
             raise ValueError(f"{what}: this env was built without layer_altitudes (every layer sits in the pupil plane and every direction sees "
                              "the same wavefront)")
         angle = resolve_field_angle(angle, self.num_envs, self.total_envs, self.global_env_offset, what)
-        shifts = sightline_shifts(self._altitudes, angle, self.params.pupil_pixel)
-        check_margin(shifts, self.layer_margins, what)
+        shifts = sightline_shifts(self._seen_at, angle, self.params.pupil_pixel)
+        check_margin(shifts, self._seen_margins, what, first_mirror=len(self._layers))
         return angle, shifts
 
     def add_sightline(self, angle, name=None):
@@ -382,7 +441,7 @@ class LayeredAOEnv(_InstalledFront):
                 self.disturbance.upload_basis(front)
             sl = Sightline(self, name, front, angle)
             sl._look(angle, shifts)
-            install_layer_sum_sightline(front, self._layers, shifts, None if self.disturbance is None else self._coeff)
+            self._install_front(front, shifts, None if self.disturbance is None else self._coeff)
         except Exception:
             front.close()
             raise
@@ -403,6 +462,18 @@ class LayeredAOEnv(_InstalledFront):
             raise RuntimeError(f"{who}: this env has sightlines attached ({', '.join(self._sightlines)}); fused stepping hands no action back before "
                                "the step has run, so their fronts cannot be stepped with it — use step(), or rollout(fused_policy=False)")
 
+    def _refuse_with_altitude_action(self, who):
+        if self._altitude_scale is not None:
+            raise RuntimeError(f"{who}: this env splits its action between the pupil mirror and the altitude mirrors (altitude_action); {who} forms or "
+                               "holds the action inside a launch, where there is nothing to split — use step(), or rollout(fused_policy=False)")
+
+    def _flatten_altitude_mirrors(self, mask):
+        """The masked envs' altitude mirrors start the episode flat (``flat_mirror_start_per_episode``), installed before the reset observes."""
+        if self._mirrors and self.flat_mirror_start_per_episode:
+            for m in self._mirrors:
+                m.set_command(self._torch.zeros((self.num_envs, m.n_modes), dtype=self._torch.float64, device=self.device), mask)
+            self._install()
+
     def install_layer_sum_disturbed(self, layers, coeff):
         """``install_layer_sum`` with ``sum_k coeff[b][k] shape_k`` added inside the float64 sum (``aog_install_layer_sum_disturbed``; the
         shapes are those last uploaded with ``ModalDisturbance.upload_basis``).  ``coeff``: [B, K] float64 device tensor, metres of optical path."""
@@ -417,9 +488,24 @@ class LayeredAOEnv(_InstalledFront):
 
     def step(self, actions, out=None, next_actions=BatchedAOEnv._PIPELINE_END):
         if next_actions is not BatchedAOEnv._PIPELINE_END:
+            self._refuse_with_altitude_action("step(next_actions=...)")
             self._refuse_with_servo("step(next_actions=...)", "step(actions), one call per step")   # (before the layers move)
+        commands = None
+        if self._altitude_scale is not None:
+            # the tail of the action is the altitude mirrors', in mirror order: set before the layers advance, installed with them
+            torch = self._torch
+            widths = [self.num_modes] + [m.n_modes for m in self._mirrors]
+            a = torch.as_tensor(actions, device=self.device)
+            if a.dim() != 2 or tuple(a.shape) != (self.num_envs, sum(widths)):
+                raise ValueError(f"step: actions must be [{self.num_envs}, {sum(widths)}] ({self.num_modes} for the pupil mirror, then "
+                                 f"{widths[1:]} for the altitude mirrors), got {list(a.shape)}")
+            actions, *tails = torch.split(a.to(torch.float32), widths, dim=1)
+            actions = actions.contiguous()
+            commands = [m.set_command(t.to(torch.float64) * self._altitude_scale) for m, t in zip(self._mirrors, tails)]
         self._advance()
         ret = super().step(actions, out=out, next_actions=next_actions)
+        if commands is not None:
+            ret[4]["altitude_commands"] = commands
         if self._sightlines:
             # (after the env's own front: every sightline's front takes the same action — with a servo the one the mirror received — on the
             # sum _advance installed at its shifts)
@@ -432,6 +518,7 @@ class LayeredAOEnv(_InstalledFront):
         return ret
 
     def reset(self, mask=None, seed=None, options=None):
+        self._flatten_altitude_mirrors(mask)
         ret = super().reset(mask, seed, options)
         self._reset_sightlines(mask)
         return ret
@@ -442,22 +529,26 @@ class LayeredAOEnv(_InstalledFront):
             sl.last = None
 
     def reset_with_policy(self, policy, cov_var=0.5, policy_out=None, mask=None, ou_noise=None, action_mode="sample"):
+        self._flatten_altitude_mirrors(mask)
         ret = super().reset_with_policy(policy, cov_var, policy_out=policy_out, mask=mask, ou_noise=ou_noise, action_mode=action_mode)
         self._reset_sightlines(mask)
         return ret
 
     def reset_with_spgd(self, ctrl, mask=None, action_out=None):
+        self._flatten_altitude_mirrors(mask)
         ret = super().reset_with_spgd(ctrl, mask=mask, action_out=action_out)
         self._reset_sightlines(mask)
         return ret
 
     def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None, ou_noise=None, action_mode="sample"):
+        self._refuse_with_altitude_action("step_with_policy")
         self._refuse_with_sightlines("step_with_policy")
         self._refuse_with_servo("step_with_policy", "step(policy(obs)), or rollout(fused_policy=False)")
         self._advance()
         return super().step_with_policy(policy, cov_var, out=out, policy_out=policy_out, action=action, ou_noise=ou_noise, action_mode=action_mode)
 
     def step_with_spgd(self, ctrl, out=None, action=None, action_out=None):
+        self._refuse_with_altitude_action("step_with_spgd")
         self._refuse_with_sightlines("step_with_spgd")
         self._refuse_with_servo("step_with_spgd", "step(ctrl.action()), or rollout(fused_policy=False)")
         self._advance()
@@ -517,6 +608,8 @@ class LayeredAOEnv(_InstalledFront):
         if self._altitudes is not None:
             state["field_angle"] = self.field_angle.copy()
             state["sightlines"] = {name: dict(angle=sl.angle.copy(), env=sl.env.get_state()) for name, sl in self._sightlines.items()}
+        if self._mirrors:
+            state["altitude_mirrors"] = [m.get_state() for m in self._mirrors]
         return state
 
     def set_state(self, state):
@@ -530,6 +623,8 @@ class LayeredAOEnv(_InstalledFront):
             raise ValueError(f"set_state: the state was saved with layer altitudes {'on' if 'field_angle' in state else 'off'} and the sightlines "
                              f"{sorted(state.get('sightlines', ()))}, this env has them {'on' if self._altitudes is not None else 'off'} and "
                              f"{sorted(self._sightlines)}")
+        if len(state.get("altitude_mirrors", ())) != len(self._mirrors):
+            raise ValueError(f"set_state: the state was saved with {len(state.get('altitude_mirrors', ()))} altitude mirrors, this env has {len(self._mirrors)}")
         if self._altitudes is not None:
             # (every angle is checked against this env's margins before anything changes)
             moved = [(self, self._shifts_for(state["field_angle"], "set_state: field_angle"))]
@@ -544,6 +639,8 @@ class LayeredAOEnv(_InstalledFront):
         if self.disturbance is not None:
             self.disturbance.load_state_dict(state["disturbance"])
             self._coeff = self.disturbance.coefficients()
+        for m, blob in zip(self._mirrors, state.get("altitude_mirrors", ())):
+            m.set_state(blob)
         super().set_state(state)
         self._install()   # (the front's blob holds the same tiles; installing again keeps one path)
 
@@ -554,6 +651,9 @@ class LayeredAOEnv(_InstalledFront):
         for sl in self.__dict__.get("_sightlines", {}).values():
             sl.env.close()
         self._sightlines = {}
+        for m in self.__dict__.get("_mirrors", ()):
+            m.close()
+        self._mirrors = []
         if self.__dict__.get("disturbance") is not None:
             self.disturbance.close()
             self.disturbance = None
