@@ -122,6 +122,14 @@ class AogAltMirrorConfig(C.Structure):  # mirrors aog_altmirror_config (include/
 ALTMIRROR_MAX_MODES = 256   # AOG_ALTMIRROR_MAX_MODES
 
 
+class AogTomoConfig(C.Structure):  # mirrors aog_tomo_config (include/aogym_tomography.h; its size query is aog_tomo_config_size)
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "num_envs", "n_out", "n_inputs")] + [("width", C.c_int32 * 4), ("env_id_base", C.c_int32),
+                                                                                           ("reserved", C.c_int32)]
+
+
+WAVEFRONT_MAX_SHAPES, TOMO_MAX_OUT, TOMO_MAX_INPUTS, TOMO_MAX_WIDTH = 512, 576, 4, 576   # AOG_WAVEFRONT_MAX_SHAPES, AOG_TOMO_MAX_*
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -263,6 +271,21 @@ CONJUGATE_SYMBOLS = {
                                                   C.c_void_p]),
 }
 
+# every symbol include/aogym_tomography.h declares, the handle's lifecycle calls written out (aog_tomo is no entry of STANDALONE below)
+TOMOGRAPHY_SYMBOLS = {
+    "aog_upload_wavefront_shapes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "aog_wavefront_project": (C.c_int, [C.c_void_p] * 4),
+    "aog_tomo_config_size": (C.c_int64, []),
+    "aog_tomo_create": (C.c_int, [C.POINTER(AogTomoConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "aog_tomo_destroy": (None, [C.c_void_p]),
+    "aog_tomo_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "aog_tomo_update": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_tomo_reset": (C.c_int, [C.c_void_p] * 3),
+    "aog_tomo_state_bytes": (C.c_int64, [C.c_void_p]),
+    "aog_tomo_get_state": (C.c_int, [C.c_void_p] * 3),
+    "aog_tomo_set_state": (C.c_int, [C.c_void_p] * 3),
+}
+
 
 def _lifecycle(prefix, config):
     """The five calls every stand-alone handle has (csrc/standalone_handle.h)."""
@@ -296,7 +319,7 @@ def load():
     except Exception:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS, **SERVO_SYMBOLS, **CONJUGATE_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS, **SERVO_SYMBOLS, **CONJUGATE_SYMBOLS, **TOMOGRAPHY_SYMBOLS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -313,7 +336,7 @@ def load():
     sized = [(cls, lib.aog_struct_size(which)) for which, cls in enumerate(
         (AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite, AogObsMft, AogActionNoise))]
     sized += [(AogDisturbanceConfig, lib.aog_disturbance_config_size()), (AogServoConfig, lib.aog_servo_config_size()),
-              (AogAltMirrorConfig, lib.aog_altmirror_config_size())]
+              (AogAltMirrorConfig, lib.aog_altmirror_config_size()), (AogTomoConfig, lib.aog_tomo_config_size())]
     for cls, size in sized:
         if size != C.sizeof(cls):
             raise RuntimeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, the library's struct {size}")

@@ -691,6 +691,7 @@ int aog_upload_tables(aog_env* e, const aog_tables* t) {
   HIP_TRY(hipSetDevice(e->device));
   e->reset_obs_valid = false;   // new tables: the cached reset observation was made with the old ones
   e->wf_ready = false;          // and the wavefront fit belongs to the old mode matrix (aog_upload_wavefront_fit)
+  e->tomo_ready = false;        // the projection's shapes to the old aperture (aog_upload_wavefront_shapes)
   e->sci_ready = false;         // the science camera's aperture table to the old aperture (aog_upload_science)
   e->grad_ready = false;        // the gradient's operand tables to the old tables (aog_upload_gradient)
   e->pyr_ready = e->pyr_rec_ready = false;   // the pyramid sensor's matrices and mask to the old aperture (aog_upload_pyramid)

@@ -137,6 +137,15 @@ struct aog_env {
   _Float16* wf_tab16 = nullptr;  // modes as table operands: [n_ptiles][A_pad rows in blocks of 32][step 2][hi|lo][lane 64][8] (tab16's pixel order)
   double* wf_slabs = nullptr;    // [pixel chunk][A_pad + 2][Bp] partial sums, allocated by the first call
   double* wf_w = nullptr;        // float64 handles: [B][n_ap] path error of the call, allocated by the first call
+  // wavefront projection onto a caller's shapes (aog_upload_wavefront_shapes, aog_wavefront_project; tomography.hip).  Off the step path like
+  // the block above; float64 handles share wf_w with it (each call rewrites it in full before it reads it).
+  bool tomo_ready = false;       // shapes are uploaded (aog_upload_tables clears it)
+  int tomo_K = 0, tomo_gblk = 0, tomo_groups = 0;   // shapes; 32-row blocks per row group; row groups (fast handles)
+  double tomo_unscale = 1.0;     // 1 / (the upload's operand scale x kActScale)
+  _Float16* tomo_tab16 = nullptr;   // [group][n_ptiles][tomo_gblk blocks of 32 rows][step 2][hi|lo][lane 64][8]: pack_tab16_rows per group
+  double* tomo_shapes64 = nullptr;  // float64 handles: [n_ap][K]
+  double* tomo_rowsum = nullptr;    // [K] sum_p S[k][p]
+  double* tomo_slabs = nullptr;     // [group][pixel chunk][32 tomo_gblk + 1][Bp] (float64 handles: [K + 1][Bp]); the last row is sum u
   // output gradient (aog_upload_gradient, aog_output_gradient; gradient.hip).  Nothing here is read or written by a reset or step.
   bool grad_ready = false;         // the gradient's tables are uploaded (aog_upload_tables clears it)
   float grad_tscale = 1.f;         // power of two the table operands are scaled by

@@ -306,11 +306,16 @@ _POLICIES = {
     # (the controller is reset with the env; every later step queries it on the last step's metric)
     "spgd": _Policy("SPGD controller", lambda env, ctrl, row, first: ctrl.reset(out=row) if first else ctrl.action(out=row), keyword="controller",
                     refuses={"experiment": ("lookahead", "science", "ou_noise", "mean")}, fused="spgd"),
+    # (the integrator assumes the mirrors hold its command: where episodes start with flat mirrors it starts at zero with them)
+    "tomographic": _Policy("tomographic controller", lambda env, ctrl, row, first: (
+        ctrl.reset() if first and getattr(env, "flat_mirror_start_per_episode", False) else None, ctrl.action(out=row))[1], keyword="controller",
+                           refuses=_MEASURES),
 }
 _CONTROLLER_KEYWORDS = {
     "predictor": "policy='predictive' takes its controller as predictor=PredictiveController(env, ...), and no other policy takes one",
     "controller": "policy='modal' takes its controller as controller=ModalIntegrator(env, ...), policy='spgd' as "
-                  "controller=SPGDController(env, ...), and no other policy takes one",
+                  "controller=SPGDController(env, ...), policy='tomographic' as controller=TomographicController(env, ...), and no other "
+                  "policy takes one",
 }
 
 
@@ -395,6 +400,11 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     ``env.reset_with_spgd`` / ``env.step_with_spgd`` (the query rides in the step's last launch) and returns the same dict, bit for bit, as
     the unfused loop from the same controller state.
 
+    ``policy="tomographic"``: ``controller.action()`` of the ``tomography.TomographicController`` passed as ``controller`` (built for this
+    env, a ``LayeredAOEnv`` with ``altitude_mirrors``): the multi-conjugate baseline — it measures on its guide directions, sets the altitude
+    mirrors' commands itself and returns the pupil mirror's actuators, which are the stored action.  Reset with the env at every episode
+    start when episodes start with flat mirrors.  Same conditions as ``"predictive"``; with sightlines attached the loop is the unfused one.
+
     ``ou_noise`` (``algorithm.py:258-259``, DDPG): an ``OrnsteinUhlenbeckNoise`` whose sample is added to every action before the env sees
     it (and before it is stored, like the reference's in-place ``action +=``), or a ``DeviceOUNoise`` (``main.py:218-220``: mu 0, theta
     0.3, sigma 0.05), which the HIP policy query advances and adds itself: float64 state, Philox normals keyed by the global env id (a
@@ -438,7 +448,7 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         raise ValueError("fused_policy=True: this env has a mirror servo attached, and the fused forms load the action inside the step's launch, "
                          "where the servo has no place — the unfused loop (fused_policy=False) steps through it")
     if policy not in _POLICIES:
-        raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive', 'modal' or 'spgd'")
+        raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive', 'modal', 'spgd' or 'tomographic'")
     if action_mode not in ("sample", "mean"):
         raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
     pol, ctrl = _POLICIES[policy], None
