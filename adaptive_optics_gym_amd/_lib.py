@@ -286,6 +286,11 @@ TOMOGRAPHY_SYMBOLS = {
     "aog_tomo_set_state": (C.c_int, [C.c_void_p] * 3),
 }
 
+# every symbol include/aogym_shack_gradient.h declares
+SHACK_GRADIENT_SYMBOLS = {
+    "aog_sh_gradient": (C.c_int, [C.c_void_p] * 9),
+}
+
 
 def _lifecycle(prefix, config):
     """The five calls every stand-alone handle has (csrc/standalone_handle.h)."""
@@ -319,7 +324,8 @@ def load():
     except Exception:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS, **SERVO_SYMBOLS, **CONJUGATE_SYMBOLS, **TOMOGRAPHY_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS, **SERVO_SYMBOLS, **CONJUGATE_SYMBOLS, **TOMOGRAPHY_SYMBOLS,
+                              **SHACK_GRADIENT_SYMBOLS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,4 +1,4 @@
-"""``env.step`` as a differentiable function of the action, and the pyramid sensor as one of the mirror command (``torch.autograd``)."""
+"""``env.step`` as a differentiable function of the action, and the pyramid and Shack-Hartmann sensors as ones of the mirror command (``torch.autograd``)."""
 from __future__ import annotations
 
 import torch
@@ -87,3 +87,34 @@ def pyramid_slopes(env, actuators):
 def pyramid_frames(env, actuators):
     """As ``pyramid_slopes``, for the clean frames [B, 4, n_s, n_s]."""
     return _PyramidOutput.apply(actuators, env, "frames")
+
+
+class _ShackOutput(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, actuators, env, which):
+        a = actuators.detach().to(torch.float64).contiguous()
+        image, slopes = env.sh_clean(actuators=a)   # the gradient call's forward half alone
+        ctx.env, ctx.epoch, ctx.act, ctx.which, ctx.in_dtype = env, env.state_epoch, a, which, actuators.dtype
+        return slopes if which == "slopes" else image
+
+    @staticmethod
+    def backward(ctx, g):
+        env = ctx.env
+        if env.state_epoch != ctx.epoch:
+            raise RuntimeError("sh_" + ctx.which + ": the environment has been stepped, reset or restored since the forward pass; the "
+                               "gradient is that of the state it saw and can only be taken before the state moves on")
+        kw = {"g_slopes": g} if ctx.which == "slopes" else {"g_image": g}
+        return env.sh_gradient(actuators=ctx.act, **kw).to(ctx.in_dtype), None, None
+
+
+def sh_slopes(env, actuators):
+    """The clean slopes [B, 2 n_sub] (float64) of ``env``'s Shack-Hartmann sensor with its mirror at ``actuators`` [B, A] (metres of surface),
+    differentiable with respect to ``actuators``.  The atmosphere is the state the last reset or step left; no mirror is moved.  Forward is
+    ``env.sh_clean``, backward one ``env.sh_gradient`` call; backward raises ``RuntimeError`` once the env has been stepped, reset or
+    restored since.  Photon noise is not part of it."""
+    return _ShackOutput.apply(actuators, env, "slopes")
+
+
+def sh_image(env, actuators):
+    """As ``sh_slopes``, for the clean detector image [B, N*N]."""
+    return _ShackOutput.apply(actuators, env, "image")

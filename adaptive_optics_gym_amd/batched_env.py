@@ -721,6 +721,49 @@ class BatchedAOEnv:
         torch.cuda.current_stream(self.device).synchronize()
         return action
 
+    def _sh_call(self, who, g_image, g_slopes, actuators, mask, want_grad, want_values):
+        """The checks, buffers and the one ``aog_sh_gradient`` call behind ``sh_clean`` and ``sh_gradient``: (grad, image, slopes)."""
+        torch = self._torch
+        if not self.SH_operation:
+            raise ValueError(f"{who}: this environment was built without the Shack-Hartmann sensor (SH_operation=True)")
+        B, A, N2, ns = self.num_envs, self.num_modes, self.num_pupil_pixels ** 2, int(self.sh.n_sub)
+        arg = lambda x, shape, name: self._f64_arg(x, shape, who, name)
+        gi, gs, act = arg(g_image, (B, N2), "g_image"), arg(g_slopes, (B, 2 * ns), "g_slopes"), arg(actuators, (B, A), "actuators")
+        mptr, _keep = (None, None)
+        if mask is not None:
+            _keep = torch.from_numpy(_mask_array(mask, B, who).astype(np.uint8)).to(self.device)
+            mptr = C.c_void_p(_keep.data_ptr())
+        if want_grad:
+            self._upload_gradient()   # (handles on the separable propagation contract with the output gradient's modes operands)
+        grad = torch.zeros((B, A), dtype=torch.float64, device=self.device) if want_grad else None
+        image = torch.zeros((B, N2), dtype=torch.float64, device=self.device) if want_values else None
+        slopes = torch.zeros((B, 2 * ns), dtype=torch.float64, device=self.device) if want_values else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self.lib.aog_sh_gradient(self._handle, mptr, ptr(gi), ptr(gs), ptr(act), ptr(grad), ptr(image), ptr(slopes), self._stream()))
+        return grad, image, slopes
+
+    def sh_clean(self, actuators=None, mask=None):
+        """The CLEAN Shack-Hartmann image [B, N*N] and slopes [B, 2 n_sub] (all s_x, then all s_y: the centroids of the noise-free image
+        minus lenslet centres and reference slopes, what the integrator of ``sh_update`` would see without photon noise) with the sensor's
+        mirror at its own actuators or at ``actuators`` [B, A]: the forward half of ``sh_gradient`` alone.  Draws no noise and changes
+        nothing ``SH_step`` / ``sh_image`` / ``sh_update`` read.  ``mask``: the rows of the envs it leaves out read zero."""
+        _, image, slopes = self._sh_call("sh_clean", None, None, actuators, mask, False, True)
+        return image, slopes
+
+    def sh_gradient(self, g_image=None, g_slopes=None, actuators=None, mask=None, with_values=False):
+        """Vector-Jacobian product of the Shack-Hartmann sensor's clean image and slopes (``aog_sh_gradient``): the gradient of
+        ``L = sum(g_image * image) + sum(g_slopes * slopes)`` (cotangents [B, N*N] and [B, 2 n_sub]; ``None`` = zero, at least one given)
+        with respect to the sensor mirror's actuators (per metre of surface), a float64 device tensor [B, A].  ``actuators`` [B, A]:
+        evaluate there instead of at ``deformable_mirror_shack.actuators`` (never written).  ``mask``: the rows of the envs it leaves out
+        read zero.  ``with_values=True`` returns ``(grad, image, slopes)``.  Photon noise is not differentiated: the call draws nothing
+        and leaves the noise stream, the integrator and everything a step reads alone.  Pupils of 128, 256, 512, 240 and 480 pixels in
+        complex64 run two register-resident backward passes; other envs hipFFT on the padded grid.  Stream-ordered; raises like
+        ``pyramid_gradient`` while an action is pending and between two steps of a lookahead episode."""
+        if g_image is None and g_slopes is None:
+            raise ValueError("sh_gradient: at least one of g_image and g_slopes must be given")
+        grad, image, slopes = self._sh_call("sh_gradient", g_image, g_slopes, actuators, mask, True, with_values)
+        return (grad, image, slopes) if with_values else grad
+
     def _host_extrusion_noise(self):
         """Host-RNG (parity) mode: draw the normals of the coming step's extrusions from each env's numpy stream in hcipy's
         order (all x shifts, then all y shifts; ``normal(0, 1, N)`` per extrusion) and hand them to the library."""

@@ -660,6 +660,7 @@ void aog_destroy(aog_env* e) {
   }
   if (e->fft_plan) hipfftDestroy((hipfftHandle)(uintptr_t)e->fft_plan);
   if (e->sh_plan) hipfftDestroy((hipfftHandle)(uintptr_t)e->sh_plan);
+  if (e->shg_plan) hipfftDestroy((hipfftHandle)(uintptr_t)e->shg_plan);
   for (auto& ev : e->events) {
     (void)hipEventDestroy(ev.first);
     (void)hipEventDestroy(ev.second);

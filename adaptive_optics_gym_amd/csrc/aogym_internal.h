@@ -85,6 +85,22 @@ struct aog_env {
   float* sh_hyq = nullptr;        // [RL][64] complex64 hy[lane + LW r]         (pass 2, layout A)
   double sh_amp = 0, sh_scale = 0, sh_gain = 0, sh_leak = 0;
   uint32_t sh_calls = 0;
+  // aog_sh_gradient (shack_gradient.hip): the call's own scratch, made on its first use
+  _Float16* shg_act16 = nullptr;     // the point of evaluation, B-operand layout
+  float* shg_phase = nullptr;        // psi_tile layout (generic route)
+  double* shg_image = nullptr;       // [B][N*N] the clean image
+  double* shg_coef = nullptr;        // [B][n_sub][4]: g_sx / F, g_sy / F, c_x, c_y
+  double* shg_gscale = nullptr;      // [B] the divisor taken off the cotangent (a power of two)
+  double* shg_qscale = nullptr;      // [B] and the one taken off the q grid
+  float* shg_qgrid = nullptr;        // [B][N][N] q on the pupil grid (separable route)
+  double* shg_q64 = nullptr;         // [B][n_ap] q per packed aperture pixel (generic route)
+  double* shg_slabs = nullptr;       // [pixel chunk][A_pad][Bp] (separable) or [A][Bp] (generic)
+  int32_t* shg_slot_start = nullptr; // [n_sub + 1] the pixels of the selected lenslets, lenslet by lenslet in raster order
+  int32_t* shg_slot_pix = nullptr;
+  void* shg_in = nullptr;            // generic route on a pruned handle: its own padded input, work array, float transfer function and plan
+  void* shg_pad = nullptr;
+  float* shg_tf32 = nullptr;
+  void* shg_plan = nullptr;
   // device screen synthesis (K8)
   void* fft_plan = nullptr;      // hipfftHandle
   int fft_m = 0, fft_batch = 0;

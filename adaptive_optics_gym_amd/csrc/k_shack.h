@@ -31,6 +31,9 @@ __global__ void k_sh_field(const float* __restrict__ phase_tile, const int32_t* 
   pad[(size_t)env * env_stride + (size_t)iy * row_stride + ix] = v;   // zero-padded 2N x 2N (2-D transforms) or compact N x N (pruned passes)
 }
 
+// (AOG_SH_SHARED_ONLY: a second translation unit, shack_gradient.hip, takes the transform blocks and the templated passes from this header
+// and leaves the three plain kernels to shack.hip, which defines them once for the library)
+#ifndef AOG_SH_SHARED_ONLY
 // deformable_mirror_shack.actuators (metres, float64) -> the f16 hi/lo B-operand layout
 __global__ void k_sh_act16(const double* __restrict__ sh_act, _Float16* __restrict__ act16, int B, int A, int A_pad, double two_over_lambda) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -38,6 +41,7 @@ __global__ void k_sh_act16(const double* __restrict__ sh_act, _Float16* __restri
   const int env = idx / A_pad, i = idx % A_pad;
   store_act16(act16, env, i, A_pad, (i < A) ? (float)(sh_act[(size_t)env * A + i] * two_over_lambda) : 0.f);
 }
+#endif
 
 template <typename CT>
 __global__ void k_sh_transfer(CT* __restrict__ f, const CT* __restrict__ tf, size_t per_env) {
@@ -401,6 +405,7 @@ __global__ __launch_bounds__(64 * kShFftWaves, 2) void k_sh_rows_inv(const float
   }
 }
 
+#ifndef AOG_SH_SHARED_ONLY
 __global__ void k_sh_noise(const double* __restrict__ image, double* __restrict__ noisy, int N, size_t env_base, unsigned long long seed, uint32_t call,
                            int sep_rl) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -409,6 +414,7 @@ __global__ void k_sh_noise(const double* __restrict__ image, double* __restrict_
   const int y = idx / N;
   noisy[il] = sh_noisy_value(image[il], env_base + blockIdx.y, y, idx - y * N, N, seed, call, sep_rl);
 }
+#endif
 
 // ---- separable form of the same propagation (the default whenever the transfer function factorises, which the paraxial Fresnel one does:
 // exp(-i z (kx^2 + ky^2) / 2k) = hx(kx) hy(ky)) ------------------------------------------------------------------------------------------
@@ -606,6 +612,7 @@ __global__ __launch_bounds__(64 * kShFftWaves, 2) void k_sh_cols_sep(const float
   }
 }
 
+#ifndef AOG_SH_SHARED_ONLY
 struct ShEstimateArgs {
   const double* image;          // [B][N*N] (already noisy)
   const double* sums_in;        // [B][n_sub][3] from the fused row pass (then `image` is not read), or null
@@ -657,5 +664,6 @@ __global__ __launch_bounds__(256) void k_sh_estimate(ShEstimateArgs p) {
     p.action_out[(size_t)env * p.A + k] = a;
   }
 }
+#endif
 
 }  // namespace aog

@@ -114,5 +114,16 @@ class AOEnv(env_base()):
         action, log_action = self._env.SH_step()
         return action[0].cpu().numpy(), log_action
 
+    def sh_clean(self, actuators=None):
+        """``BatchedAOEnv.sh_clean`` of the one env: (image [N*N], slopes [2 n_sub]) as numpy float64."""
+        a = None if actuators is None else np.asarray(actuators, dtype=np.float64).reshape(1, self.num_modes)
+        image, slopes = self._env.sh_clean(actuators=a)
+        return image[0].cpu().numpy(), slopes[0].cpu().numpy()
+
+    def sh_gradient(self, g_image=None, g_slopes=None, actuators=None):
+        """``BatchedAOEnv.sh_gradient`` of the one env: cotangents [N*N] / [2 n_sub] -> gradient [A] per metre of surface (numpy float64)."""
+        row = lambda x: None if x is None else np.asarray(x, dtype=np.float64).reshape(1, -1)
+        return self._env.sh_gradient(g_image=row(g_image), g_slopes=row(g_slopes), actuators=row(actuators))[0].cpu().numpy()
+
     def close(self):
         self._env.close()
