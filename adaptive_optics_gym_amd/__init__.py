@@ -4,6 +4,7 @@
     from adaptive_optics_gym_amd import LayeredAOEnv      # the same over several frozen-flow wind layers per env
     from adaptive_optics_gym_amd.envs import AOEnv        # the reference's single-env gym API
     from adaptive_optics_gym_amd import ModalTelemetry, ModalIntegrator   # loop telemetry (PSDs) and the optimised modal integrator
+    from adaptive_optics_gym_amd import LQGController     # the LQG baseline: per-mode Kalman prediction of turbulence and vibration lines
     from adaptive_optics_gym_amd import LinkTelemetry     # the optical link's read-out: fades, power histogram, bit-error rate
     from adaptive_optics_gym_amd import ModalDisturbance  # vibration and static aberrations for LayeredAOEnv(disturbance=...)
     from adaptive_optics_gym_amd import MirrorServo       # loop latency and mirror dynamics for BatchedAOEnv(servo=...)
@@ -14,11 +15,12 @@ from .batched_env import BatchedAOEnv  # noqa: F401
 from .disturbance import ModalDisturbance  # noqa: F401
 from .layered import LayeredAOEnv, Sightline  # noqa: F401
 from .link import LinkTelemetry  # noqa: F401
+from .lqg import LQGController  # noqa: F401
 from .params import OpticalParams  # noqa: F401
 from .servo import MirrorServo  # noqa: F401
 from .telemetry import ModalIntegrator, ModalTelemetry  # noqa: F401
 
-__all__ = ["BatchedAOEnv", "LayeredAOEnv", "LinkTelemetry", "MirrorServo", "ModalDisturbance", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "Sightline", "register"]
+__all__ = ["BatchedAOEnv", "LQGController", "LayeredAOEnv", "LinkTelemetry", "MirrorServo", "ModalDisturbance", "ModalIntegrator", "ModalTelemetry", "OpticalParams", "Sightline", "register"]
 
 
 def register():

@@ -130,6 +130,13 @@ class AogTomoConfig(C.Structure):  # mirrors aog_tomo_config (include/aogym_tomo
 WAVEFRONT_MAX_SHAPES, TOMO_MAX_OUT, TOMO_MAX_INPUTS, TOMO_MAX_WIDTH = 512, 576, 4, 576   # AOG_WAVEFRONT_MAX_SHAPES, AOG_TOMO_MAX_*
 
 
+class AogLqgConfig(C.Structure):  # mirrors aog_lqg_config (include/aogym_lqg.h; its size query is aog_lqg_config_size)
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "num_envs", "act_dim", "n_models", "reserved")]
+
+
+LQG_MAX_ACT, LQG_MAX_MODELS, LQG_MAX_DELAY, LQG_MAX_ITERATIONS = 128, 4, 4, 4096   # AOG_LQG_MAX_*
+
+
 class AogInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "abi_version", "num_envs", "num_envs_padded", "n_ap", "n_ap_padded", "n_modes_padded", "pixel_chunks",
@@ -291,6 +298,20 @@ SHACK_GRADIENT_SYMBOLS = {
     "aog_sh_gradient": (C.c_int, [C.c_void_p] * 9),
 }
 
+# every symbol include/aogym_lqg.h declares, the handle's lifecycle calls written out (aog_lqg is no entry of STANDALONE below)
+LQG_SYMBOLS = {
+    "aog_lqg_config_size": (C.c_int64, []),
+    "aog_lqg_create": (C.c_int, [C.POINTER(AogLqgConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "aog_lqg_destroy": (None, [C.c_void_p]),
+    "aog_lqg_set_model": (C.c_int, [C.c_void_p] * 6),
+    "aog_lqg_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_lqg_update": (C.c_int, [C.c_void_p] * 5),
+    "aog_lqg_reset": (C.c_int, [C.c_void_p] * 3),
+    "aog_lqg_state_bytes": (C.c_int64, [C.c_void_p]),
+    "aog_lqg_get_state": (C.c_int, [C.c_void_p] * 3),
+    "aog_lqg_set_state": (C.c_int, [C.c_void_p] * 3),
+}
+
 
 def _lifecycle(prefix, config):
     """The five calls every stand-alone handle has (csrc/standalone_handle.h)."""
@@ -325,7 +346,7 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS, **SERVO_SYMBOLS, **CONJUGATE_SYMBOLS, **TOMOGRAPHY_SYMBOLS,
-                              **SHACK_GRADIENT_SYMBOLS}.items():
+                              **SHACK_GRADIENT_SYMBOLS, **LQG_SYMBOLS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -342,7 +363,8 @@ def load():
     sized = [(cls, lib.aog_struct_size(which)) for which, cls in enumerate(
         (AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite, AogObsMft, AogActionNoise))]
     sized += [(AogDisturbanceConfig, lib.aog_disturbance_config_size()), (AogServoConfig, lib.aog_servo_config_size()),
-              (AogAltMirrorConfig, lib.aog_altmirror_config_size()), (AogTomoConfig, lib.aog_tomo_config_size())]
+              (AogAltMirrorConfig, lib.aog_altmirror_config_size()), (AogTomoConfig, lib.aog_tomo_config_size()),
+              (AogLqgConfig, lib.aog_lqg_config_size())]
     for cls, size in sized:
         if size != C.sizeof(cls):
             raise RuntimeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, the library's struct {size}")

@@ -303,6 +303,7 @@ _POLICIES = {
     "pyramid": _Policy("pyramid integrator", lambda env, ctrl, row, first: row.copy_(env.PYR_step()[0]), pyramid=True),
     "predictive": _Policy("predictive controller", lambda env, ctrl, row, first: row.copy_(ctrl.action()), keyword="predictor", refuses=_MEASURES),
     "modal": _Policy("modal integrator", lambda env, ctrl, row, first: row.copy_(ctrl.action()), keyword="controller", refuses=_MEASURES),
+    "lqg": _Policy("LQG controller", lambda env, ctrl, row, first: row.copy_(ctrl.action()), keyword="controller", refuses=_MEASURES),
     # (the controller is reset with the env; every later step queries it on the last step's metric)
     "spgd": _Policy("SPGD controller", lambda env, ctrl, row, first: ctrl.reset(out=row) if first else ctrl.action(out=row), keyword="controller",
                     refuses={"experiment": ("lookahead", "science", "ou_noise", "mean")}, fused="spgd"),
@@ -313,9 +314,9 @@ _POLICIES = {
 }
 _CONTROLLER_KEYWORDS = {
     "predictor": "policy='predictive' takes its controller as predictor=PredictiveController(env, ...), and no other policy takes one",
-    "controller": "policy='modal' takes its controller as controller=ModalIntegrator(env, ...), policy='spgd' as "
-                  "controller=SPGDController(env, ...), policy='tomographic' as controller=TomographicController(env, ...), and no other "
-                  "policy takes one",
+    "controller": "policy='modal' takes its controller as controller=ModalIntegrator(env, ...), policy='lqg' as "
+                  "controller=LQGController(env, ...), policy='spgd' as controller=SPGDController(env, ...), policy='tomographic' as "
+                  "controller=TomographicController(env, ...), and no other policy takes one",
 }
 
 
@@ -394,6 +395,11 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     integrator with one gain per (env, mode), which also records the measurements it takes (``controller.retune()`` then sets the
     optimised modal gains).  Same conditions as ``"predictive"``; neither its command nor its telemetry is reset at episode ends.
 
+    ``policy="lqg"``: ``controller.action()`` of the ``lqg.LQGController`` passed as ``controller`` (built for this env): per mode a Kalman
+    filter on a turbulence-plus-vibration model that predicts the measurement ``delay`` frames ahead, which also records the measurements it
+    takes (``controller.identify()`` then refits the turbulence).  Same conditions as ``"predictive"``; neither its filter nor its
+    telemetry is reset at episode ends.
+
     ``policy="spgd"``: the sensorless baseline — the ``sensorless.SPGDController`` passed as ``controller`` (built for this env), which
     sees only the scalar metric of the last step; it is reset with the env at every episode start (all envs; its iteration counters go
     on).  Not with ``lookahead``, ``science``, ``ou_noise`` or ``action_mode="mean"``.  With ``fused_policy=True`` it goes through
@@ -448,7 +454,7 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
         raise ValueError("fused_policy=True: this env has a mirror servo attached, and the fused forms load the action inside the step's launch, "
                          "where the servo has no place — the unfused loop (fused_policy=False) steps through it")
     if policy not in _POLICIES:
-        raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive', 'modal', 'spgd' or 'tomographic'")
+        raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive', 'modal', 'lqg', 'spgd' or 'tomographic'")
     if action_mode not in ("sample", "mean"):
         raise ValueError(f"action_mode must be 'sample' or 'mean' (got {action_mode!r})")
     pol, ctrl = _POLICIES[policy], None
