@@ -312,6 +312,13 @@ LQG_SYMBOLS = {
     "aog_lqg_set_state": (C.c_int, [C.c_void_p] * 3),
 }
 
+# every symbol include/aogym_cone.h declares
+CONE_SYMBOLS = {
+    "aog_install_layer_sum_cone": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p]),
+    "aog_cone_check_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+}
+
 
 def _lifecycle(prefix, config):
     """The five calls every stand-alone handle has (csrc/standalone_handle.h)."""
@@ -346,7 +353,7 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS, **SERVO_SYMBOLS, **CONJUGATE_SYMBOLS, **TOMOGRAPHY_SYMBOLS,
-                              **SHACK_GRADIENT_SYMBOLS, **LQG_SYMBOLS}.items():
+                              **SHACK_GRADIENT_SYMBOLS, **LQG_SYMBOLS, **CONE_SYMBOLS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

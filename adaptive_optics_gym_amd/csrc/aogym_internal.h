@@ -271,11 +271,13 @@ struct aog_env {
   double* layer_mean = nullptr;  // [B] aperture means of the layer sum being installed (aog_install_layer_sum: k_layer_mean -> k_layer_sum_*), allocated by the first call
   double* dist_basis = nullptr;  // [dist_terms][n_ap] pupil shapes of the modal disturbance in the masters' unit (aog_upload_disturbance_basis; aog_install_layer_sum_disturbed reads them)
   int dist_terms = 0;
-  // sightline installation (aog_install_layer_sum_sightline): the shifts of the last one, [sight_layers][B][2] (sx, sy) in pixels
-  double* sight_shift = nullptr;   // device, room for 8 layers; the kernels read it through SightLayers
+  // sightline installation (aog_install_layer_sum_sightline): the shifts of the last one, [sight_layers][B][2] (sx, sy) in pixels; a
+  // finite-range installation (aog_install_layer_sum_cone) keeps [sight_layers][B][3] (sx, sy, m) in the same buffers
+  double* sight_shift = nullptr;   // device, room for 8 layers x 3; the kernels read it through SightLayers / ConeLayers
   double* sight_stage = nullptr;   // pinned, the same values: what a new installation's shifts are compared with and copied from
   hipEvent_t sight_ev = nullptr;   // recorded after the last copy out of the staging buffer
   int sight_layers = 0;            // layers the two buffers hold values for (0: none yet)
+  int sight_width = 2;             // values per layer and env they hold: 2 (shifts) or 3 (shifts and magnification)
   float* psi_tile = nullptr;   // [Bp/32][n_ptiles][4][64][4]
   double* psi64 = nullptr;       // validation: [B][n_ap]
   double* act_dm = nullptr;      // [B][A]

@@ -7,7 +7,9 @@
 //           SightLayers derives from LayerSources, so a pass reads `origin` and `master` of either by the same text.
 //   Terms   what is added inside the sum: NoTerms (nothing, and no code for it: aog_install_layer_sum) or ModalTerms (K >= 0 pupil shapes
 //           with per-env coefficients, K at run time: the other two entry points).
-// layers.hip instantiates <LayerSources, NoTerms>, <LayerSources, ModalTerms> and <SightLayers, ModalTerms> for L = 1 .. 8.
+//           A third reader, ConeLayers (k_cone.h: sources at finite range, aog_install_layer_sum_cone), is defined beside this file.
+// layers.hip instantiates <LayerSources, NoTerms>, <LayerSources, ModalTerms>, <SightLayers, ModalTerms> and <ConeLayers, ModalTerms> for
+// L = 1 .. 8.
 #pragma once
 #include "k_common.h"
 

@@ -1,12 +1,14 @@
 // Layered atmosphere (several frozen-flow layers per env): the atmosphere-only step of a layer handle and the installation of the layers'
 // sum in a quasi-static front handle, plain, with a modal disturbance added inside the sum, or read along a sightline (layers larger than
-// the front, displaced by a fraction of a pixel; altitude mirrors' surfaces as further sources).  A handle that never comes here launches
-// nothing of this file.
+// the front, displaced by a fraction of a pixel; altitude mirrors' surfaces as further sources), or from a source at finite range (the
+// footprint on every source shrunk by a magnification).  A handle that never comes here launches nothing of this file.
 #include "host_common.h"
 #include "conjugate_host.h"
 #include "k_layers.h"
+#include "k_cone.h"
 #include "../../include/aogym_disturbance.h"
 #include "../../include/aogym_sightline.h"
+#include "../../include/aogym_cone.h"
 
 using namespace aog_host;
 
@@ -14,11 +16,12 @@ static_assert(aog::kMaxTerms == AOG_DISTURBANCE_MAX_TERMS, "the disturbance's te
 
 namespace {
 
-// which of the three installations: what reads the layers and what is added inside the sum
+// which of the four installations: what reads the layers and what is added inside the sum
 enum class LayerForm {
   plain,       // aog_install_layer_sum: layers in the pupil plane, no terms
   disturbed,   // aog_install_layer_sum_disturbed: layers in the pupil plane, the uploaded basis's terms
   sightline,   // aog_install_layer_sum_sightline, aog_install_layer_sum_conjugate: sources of N_l >= N read at `shift_host`, terms when n_terms > 0
+  cone,        // aog_install_layer_sum_cone: the sightline form with (sx, sy, m) per source and env in `shift_host`
 };
 
 // one source of a sightline installation as the margin check names it: layer l, or mirror j behind the layers
@@ -58,43 +61,78 @@ void launch_passes(int n_layers, const Layers& layers, const Terms& terms, const
   }
 }
 
-// The shifts of a sightline installation, checked against every source's margin and brought to the front's own buffer on `s`: through
-// pinned staging, which keeps the values of the last installation, so that the same values arriving again cost a comparison and no copy.
-// Nothing of the handle changes before every value has passed.
-int stage_shifts(const char* who, aog_env* dst, const SightSource* sources, int n_sources, const double* shift_host, hipStream_t s) {
-  const size_t B = (size_t)dst->B, count = (size_t)n_sources * B * 2;
+// The margin check of a sightline installation: every shift finite and |shift| <= c_l - 1 (0 when c_l = 0).  shift_host [n_sources][B][2].
+int check_shifts(const char* who, int B, int N, const SightSource* sources, int n_sources, const double* shift_host) {
   for (int l = 0; l < n_sources; ++l) {
     const SightSource& y = sources[l];
-    const int c = (y.n - dst->cfg.n_pupil) / 2;
+    const int c = (y.n - N) / 2;
     const double limit = c > 0 ? (double)(c - 1) : 0.0;
-    for (size_t i = 0; i < 2 * B; ++i) {
+    for (size_t i = 0; i < 2 * (size_t)B; ++i) {
       const double v = shift_host[(size_t)l * 2 * B + i];
       if (!std::isfinite(v) || std::fabs(v) > limit)
         return fail(AOG_ERR_INVALID, "%s: shift %c = %.17g pixels of %s %d, env %d is outside the margin (|shift| <= %g: the %s has %d pixels, "
-                    "the front %d, c = %d)", who, (i & 1) ? 'y' : 'x', v, y.kind, y.index, (int)(i / 2), limit, y.kind, y.n, dst->cfg.n_pupil, c);
+                    "the front %d, c = %d)", who, (i & 1) ? 'y' : 'x', v, y.kind, y.index, (int)(i / 2), limit, y.kind, y.n, N, c);
     }
   }
-  const size_t capacity = (size_t)aog::kMaxLayers * B * 2;
+  return AOG_OK;
+}
+
+// The check of a finite-range installation (include/aogym_cone.h): geom_host [n_sources][B][3] = (sx, sy, m); finite, 0 < m <= 1 and on
+// each axis |s| + (1 - m) (N - 1) / 2 <= c_l - 1 (one rounded difference, product and sum), which with c_l = 0 leaves s = 0 and m = 1.
+int check_cone(const char* who, int B, int N, const SightSource* sources, int n_sources, const double* geom_host) {
+  const double ctr = 0.5 * (double)(N - 1);
+  for (int l = 0; l < n_sources; ++l) {
+    const SightSource& y = sources[l];
+    const int c = (y.n - N) / 2;
+    const double limit = c > 0 ? (double)(c - 1) : 0.0;
+    for (int b = 0; b < B; ++b) {
+      const double* g = geom_host + ((size_t)l * B + b) * 3;
+      const double m = g[2];
+      if (!std::isfinite(m) || !(m > 0.0 && m <= 1.0))
+        return fail(AOG_ERR_INVALID, "%s: magnification m = %.17g of %s %d, env %d (0 < m <= 1: m = 1 - altitude / range; margin c = %d)", who, m, y.kind,
+                    y.index, b, c);
+      const double shrink = (1.0 - m) * ctr;
+      for (int a = 0; a < 2; ++a)
+        if (!std::isfinite(g[a]) || std::fabs(g[a]) + shrink > limit)
+          return fail(AOG_ERR_INVALID, "%s: shift %c = %.17g pixels at m = %.17g of %s %d, env %d is outside the margin (|shift| + (1 - m) (N - 1) / 2 "
+                      "<= %g: the %s has %d pixels, the front %d, c = %d)", who, a ? 'y' : 'x', g[a], m, y.kind, y.index, b, limit, y.kind, y.n, N, c);
+    }
+  }
+  return AOG_OK;
+}
+
+// The per-(source, env) values of a sightline (`width` 2: shifts) or finite-range (`width` 3: shifts and magnification) installation,
+// checked against every source's margin and brought to the front's own buffer on `s`: through pinned staging, which keeps the values of
+// the last installation, so that the same values arriving again cost a comparison and no copy.  Nothing of the handle changes before
+// every value has passed.
+int stage_shifts(const char* who, aog_env* dst, const SightSource* sources, int n_sources, const double* shift_host, int width, hipStream_t s) {
+  const size_t B = (size_t)dst->B, count = (size_t)n_sources * B * width;
+  if (int rc = width == 3 ? check_cone(who, dst->B, dst->cfg.n_pupil, sources, n_sources, shift_host)
+                          : check_shifts(who, dst->B, dst->cfg.n_pupil, sources, n_sources, shift_host))
+    return rc;
+  const size_t capacity = (size_t)aog::kMaxLayers * B * 3;
   if (!dst->sight_shift)
     if (int rc = dev_alloc(dst, &dst->sight_shift, capacity, false)) return rc;
   if (!dst->sight_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&dst->sight_stage), sizeof(double) * capacity, hipHostMallocDefault));
   if (!dst->sight_ev) HIP_TRY(hipEventCreateWithFlags(&dst->sight_ev, hipEventDisableTiming));
-  if (dst->sight_layers == n_sources && std::memcmp(dst->sight_stage, shift_host, sizeof(double) * count) == 0) return AOG_OK;
+  if (dst->sight_layers == n_sources && dst->sight_width == width && std::memcmp(dst->sight_stage, shift_host, sizeof(double) * count) == 0) return AOG_OK;
   HIP_TRY(hipEventSynchronize(dst->sight_ev));   // (the previous copy out of the staging buffer; long done in practice)
   dst->sight_layers = 0;
   std::memcpy(dst->sight_stage, shift_host, sizeof(double) * count);
   HIP_TRY(hipMemcpyAsync(dst->sight_shift, dst->sight_stage, sizeof(double) * count, hipMemcpyHostToDevice, s));
   HIP_TRY(hipEventRecord(dst->sight_ev, s));
   dst->sight_layers = n_sources;
+  dst->sight_width = width;
   return AOG_OK;
 }
 
-// The one installation behind the four entry points; `who` names the entry point in every message.  `shift_host` and the mirrors (sources
-// n_layers .. n_layers + n_mirrors - 1, each read as a layer of M pixels whose ring has not turned) belong to the sightline form,
-// `coeff_dev` and `n_terms` to the forms with terms.
+// The one installation behind the five entry points; `who` names the entry point in every message.  `shift_host` and the mirrors (sources
+// n_layers .. n_layers + n_mirrors - 1, each read as a layer of M pixels whose ring has not turned) belong to the sightline and cone
+// forms, `coeff_dev` and `n_terms` to the forms with terms.
 int install_layer_sum(const char* who, LayerForm form, aog_env* dst, aog_env* const* layers, int n_layers, const double* shift_host, const double* coeff_dev,
                       int n_terms, void* stream, aog_altmirror* const* mirrors = nullptr, int n_mirrors = 0) {
-  const bool sight = form == LayerForm::sightline;
+  const bool cone = form == LayerForm::cone;
+  const bool sight = form == LayerForm::sightline || cone;   // (sources larger than the front, terms when n_terms > 0)
   if (sight && n_terms < 0) return fail(AOG_ERR_INVALID, "%s: %d terms", who, n_terms);
   const bool disturbed = sight ? n_terms > 0 : form == LayerForm::disturbed;   // (terms are added)
   if (!dst || !layers || (disturbed && !coeff_dev)) return fail(AOG_ERR_INVALID, "%s: null argument", who);
@@ -150,11 +188,19 @@ int install_layer_sum(const char* who, LayerForm form, aog_env* dst, aog_env* co
   HIP_TRY(hipSetDevice(dst->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (sight)
-    if (int rc = stage_shifts(who, dst, sources, n_sources, shift_host, s)) return rc;
+    if (int rc = stage_shifts(who, dst, sources, n_sources, shift_host, cone ? 3 : 2, s)) return rc;
   if (!dst->layer_mean)
     if (int rc = dev_alloc(dst, &dst->layer_mean, (size_t)dst->B, false)) return rc;
   const aog::ModalTerms terms{disturbed ? dst->dist_basis : nullptr, disturbed ? coeff_dev : nullptr, disturbed ? n_terms : 0, dst->n_ap};
-  if (sight) {
+  if (cone) {
+    aog::ConeLayers seen{src, {}};
+    for (int l = 0; l < n_sources; ++l) {
+      seen.cone.geom[l] = dst->sight_shift + (size_t)l * dst->B * 3;
+      seen.cone.n[l] = sources[l].n;
+      seen.cone.c[l] = (sources[l].n - dst->cfg.n_pupil) / 2;
+    }
+    launch_passes(n_sources, seen, terms, dst, s);
+  } else if (sight) {
     aog::SightLayers seen{src, {}};
     for (int l = 0; l < n_sources; ++l) {
       seen.sight.shift[l] = dst->sight_shift + (size_t)l * dst->B * 2;
@@ -231,6 +277,29 @@ int aog_install_layer_sum_conjugate(aog_env* dst, aog_env* const* layers, int n_
   if (!shift_host) return fail(AOG_ERR_INVALID, "aog_install_layer_sum_conjugate: null argument");
   return install_layer_sum("aog_install_layer_sum_conjugate", LayerForm::sightline, dst, layers, n_layers, shift_host, coeff_dev, n_terms, stream, mirrors,
                            n_mirrors);
+}
+
+int aog_install_layer_sum_cone(aog_env* dst, aog_env* const* layers, int n_layers, aog_altmirror* const* mirrors, int n_mirrors, const double* geom_host,
+                               const double* coeff_dev, int n_terms, void* stream) {
+  if (!geom_host) return fail(AOG_ERR_INVALID, "aog_install_layer_sum_cone: null argument");
+  return install_layer_sum("aog_install_layer_sum_cone", LayerForm::cone, dst, layers, n_layers, geom_host, coeff_dev, n_terms, stream, mirrors, n_mirrors);
+}
+
+int aog_cone_check_geometry(const double* geom_host, int n_layers, int n_mirrors, int num_envs, int n_pupil, const int32_t* source_pixels) {
+  const char* who = "aog_cone_check_geometry";
+  if (!geom_host || !source_pixels) return fail(AOG_ERR_INVALID, "%s: null argument", who);
+  if (n_layers < 1 || n_mirrors < 0 || n_layers + n_mirrors > aog::kMaxLayers)
+    return fail(AOG_ERR_INVALID, "%s: %d layers and %d mirrors (n_layers >= 1, n_mirrors >= 0, together at most %d sources)", who, n_layers, n_mirrors,
+                aog::kMaxLayers);
+  if (num_envs < 1 || n_pupil < 1) return fail(AOG_ERR_INVALID, "%s: num_envs %d, n_pupil %d (each >= 1)", who, num_envs, n_pupil);
+  SightSource sources[aog::kMaxLayers];
+  for (int l = 0; l < n_layers + n_mirrors; ++l) {
+    sources[l] = l < n_layers ? SightSource{"layer", l, source_pixels[l]} : SightSource{"mirror", l - n_layers, source_pixels[l]};
+    if (source_pixels[l] < n_pupil || (source_pixels[l] - n_pupil) % 2)
+      return fail(AOG_ERR_INVALID, "%s: %s %d has %d pixels, the front %d: at least as many, the difference even (the meta-pupil is centred on the "
+                  "pupil)", who, sources[l].kind, sources[l].index, source_pixels[l], n_pupil);
+  }
+  return check_cone(who, num_envs, n_pupil, sources, n_layers + n_mirrors, geom_host);
 }
 
 }  // extern "C"

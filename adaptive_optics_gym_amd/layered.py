@@ -139,6 +139,117 @@ def check_margin(shifts, margins, what, first_mirror=None):
                              f"(margin c = {int(c)}; build the env with a larger meta_pupil_pixels)")
 
 
+def resolve_range(value, num_envs, total_envs=None, global_env_offset=0, name="source_range"):
+    """A source's range as [num_envs] float64 metres: None or inf is a plane wave (inf for every env), otherwise a scalar or per-env values
+    under ``resolve_per_env``'s rules, each > 0 and not NaN (inf is allowed per env).  ``ValueError`` otherwise."""
+    total_envs = global_env_offset + num_envs if total_envs is None else int(total_envs)
+    if value is None:
+        return np.full(num_envs, np.inf)
+    arr = np.asarray(value, dtype=np.float64)
+    if np.any(np.isnan(arr)) or np.any(arr <= 0):
+        raise ValueError(f"{name}: a range is in metres, > 0 (inf or None: a plane wave), got {value!r}")
+    # (resolve_per_env refuses inf: it is this argument's 'none', so it goes through as a finite stand-in)
+    far = np.isinf(arr)
+    out = resolve_per_env(name, np.where(far, 1.0, arr), num_envs, total_envs, global_env_offset)[0]
+    mask = resolve_per_env(name, far.astype(np.float64), num_envs, total_envs, global_env_offset)[0]
+    return np.where(mask != 0, np.inf, out)
+
+
+def _source_name(l, first_mirror):
+    return f"layer {l}" if first_mirror is None or l < first_mirror else f"mirror {l - first_mirror}"
+
+
+def cone_geometry(altitudes, angle, range, pupil_pixel, first_mirror=None, what="source_range"):
+    """[S, B, 3] float64 (sx, sy, m): ``sightline_shifts`` and, beside them, the magnification of source l's footprint seen from a source at
+    ``range`` ([B] metres, or a scalar; inf: a plane wave), m = 1 - h_l / H — one rounded quotient and one rounded difference, so m is
+    exactly 1.0 for H = inf and for h_l = 0.  Front pixel (iy, ix) reads the source at (c + ctr + m (iy - ctr) + sy, c + ctr + m (ix - ctr)
+    + sx), ctr = (N - 1) / 2 (include/aogym_cone.h).  ``ValueError`` naming the layer (or mirror, from index ``first_mirror`` on) that lies at
+    or above the source (h_l >= H)."""
+    h = np.asarray(altitudes, dtype=np.float64)
+    shifts = sightline_shifts(h, angle, pupil_pixel)
+    H = np.broadcast_to(np.asarray(range, dtype=np.float64), (shifts.shape[1],))
+    if np.any(np.isnan(H)) or np.any(H <= 0):
+        raise ValueError(f"{what}: a range is in metres, > 0 (inf: a plane wave)")
+    for l, b in np.argwhere(h[:, None] >= H[None, :]):
+        raise ValueError(f"{what}: {_source_name(int(l), first_mirror)} at {h[l]:g} m lies at or above the source at {H[b]:g} m (env {int(b)}): a "
+                         "layer or mirror must be below every source that is seen through it")
+    m = 1.0 - (h[:, None] / H[None, :])
+    return np.ascontiguousarray(np.concatenate([shifts, m[:, :, None]], axis=2))
+
+
+def cone_reach(geometry, num_pupil_pixels):
+    """[S] float64: how far off the pupil source l is read, max over envs and axes of |s| + (1 - m) (N - 1) / 2 — the shift plus what the
+    shrinking footprint's far edge adds on the side the shift points away from (one rounded difference, product and sum, as the library)."""
+    g = np.asarray(geometry, dtype=np.float64)
+    ctr = 0.5 * (int(num_pupil_pixels) - 1)
+    return (np.abs(g[:, :, :2]) + ((1.0 - g[:, :, 2:3]) * ctr)).reshape(len(g), -1).max(axis=1)
+
+
+def declared_range(value):
+    """A range argument as the 1-D array of every value it declares, whichever envs this instance holds (None: [inf]): what the default
+    meta-pupil is sized for, so that the parts of a split batch and the whole batch get one size."""
+    return np.array([np.inf]) if value is None else np.atleast_1d(np.asarray(value, dtype=np.float64)).ravel()
+
+
+def required_margin_cone(altitudes, looks, pupil_pixel, num_pupil_pixels):
+    """``required_margin`` for sources at finite range: ``looks`` a list of (angle [B, 2], ranges), ranges a 1-D array of any length (the
+    local envs', or every declared value: ``declared_range``).  Per source l the largest |h_l theta| / pupil_pixel over the angles plus the
+    largest (1 - m) (N - 1) / 2 over the ranges — a shrinking footprint moves its far edge that many pixels off the plane wave's — then
+    ceil(max_l) + 1.  The two maxima are taken apart, so the result does not depend on which env has which range; with every range
+    infinite it is ``required_margin``.  ``ValueError`` when a source lies at or above one of the ranges."""
+    h = np.asarray(altitudes, dtype=np.float64)
+    ctr = 0.5 * (int(num_pupil_pixels) - 1)
+    worst = 0.0
+    for a, H in looks:
+        H = np.atleast_1d(np.asarray(H, dtype=np.float64))
+        m = cone_geometry(h, np.zeros((H.size, 2)), H, pupil_pixel)[:, :, 2]
+        s = np.abs(sightline_shifts(h, a, pupil_pixel)).reshape(len(h), -1)
+        if s.size:
+            worst = max(worst, float((s.max(axis=1) + ((1.0 - m) * ctr).max(axis=1)).max()))
+    return int(np.ceil(worst)) + 1
+
+
+def check_margin_cone(geometry, margins, num_pupil_pixels, what, first_mirror=None):
+    """``check_margin`` for sources at finite range: ``ValueError`` unless |s| + (1 - m) (N - 1) / 2 <= c_l - 1 for every source (0 for
+    c_l = 0: no shift and m = 1), and 0 < m <= 1 — what the library checks again.  ``geometry`` [S, B, 3], ``margins`` [S]."""
+    g = np.asarray(geometry, dtype=np.float64)
+    m = g[:, :, 2]
+    if not np.all(np.isfinite(g)) or np.any(m <= 0) or np.any(m > 1):
+        raise ValueError(f"{what}: shifts must be finite and magnifications lie in (0, 1]")
+    reach = cone_reach(g, num_pupil_pixels)
+    for l, c in enumerate(margins):
+        limit = max(int(c) - 1, 0)
+        if reach[l] > limit:
+            raise ValueError(f"{what}: {_source_name(l, first_mirror)} would be read {reach[l]:.3f} pixels off the pupil (shift plus the cone's "
+                             f"(1 - m) (N - 1) / 2), its meta-pupil leaves {limit} (margin c = {int(c)}; build the env with a larger "
+                             "meta_pupil_pixels)")
+
+
+def install_layer_sum_cone(front, layers, mirrors, geometry, coeff=None):
+    """``conjugate.install_layer_sum_conjugate`` for a source at finite range (``aog_install_layer_sum_cone``, include/aogym_cone.h):
+    ``geometry`` [L + n_mirrors, B, 3] float64 host array of (sx, sy, m), the layers' first (``cone_geometry``); ``mirrors`` may be empty.
+    Stream-ordered, no host synchronisation."""
+    n = len(layers) + len(mirrors)
+    geometry = np.ascontiguousarray(geometry, dtype=np.float64)
+    if geometry.shape != (n, front.num_envs, 3):
+        raise ValueError(f"install_layer_sum_cone: geometry must be [{n}, {front.num_envs}, 3], got {geometry.shape}")
+    handles = (C.c_void_p * max(1, len(mirrors)))(*[m._handle.value for m in mirrors])
+    front._install_layers(front.lib.aog_install_layer_sum_cone, layers, handles, len(mirrors), C.c_void_p(geometry.ctypes.data), terms=True, coeff=coeff,
+                          coeff_optional=True)
+
+
+def resolve_sightline(spec, num_envs, total_envs=None, global_env_offset=0, name="sightline"):
+    """One entry of ``sightlines``: an angle ((theta_x, theta_y) or per-env pairs), or dict(angle=, range=) for a source at finite range.
+    Returns (angle [B, 2], range [B])."""
+    rng = None
+    if isinstance(spec, dict):
+        if not set(spec) <= {"angle", "range"} or "angle" not in spec:
+            raise ValueError(f"{name}: a dict with 'angle' and, optionally, 'range'")
+        spec, rng = spec["angle"], spec.get("range")
+    return (resolve_field_angle(spec, num_envs, total_envs, global_env_offset, name),
+            resolve_range(rng, num_envs, total_envs, global_env_offset, f"{name}: range"))
+
+
 def install_layer_sum_sightline(front, layers, shifts, coeff=None):
     """``BatchedAOEnv.install_layer_sum`` along a line of sight (``aog_install_layer_sum_sightline``, include/aogym_sightline.h): ``front`` a
     quasi-static env with N pixels, ``layers`` 1 .. 8 dynamic envs of N_l >= N pixels (N_l - N even) of its batch and device, ``shifts``
@@ -154,20 +265,23 @@ class Sightline:
     """A second line of sight through a ``LayeredAOEnv``'s layers (``LayeredAOEnv.add_sightline``): a quasi-static front of its own that
     gets the same layers' sum installed at its own shifts every step and steps with the env's action.  ``env`` is that front, an ordinary
     ``BatchedAOEnv``, for instruments (``wavefront_truth``, the science camera, ...); ``angle`` [B, 2] radians; ``last`` the dict of its
-    last step (what ``info["sightlines"][name]`` carries)."""
+    last step (what ``info["sightlines"][name]`` carries); ``range`` [B] metres, the distance of what it looks at (inf: a plane wave), fixed
+    when it is added."""
 
-    def __init__(self, owner, name, env, angle):
+    def __init__(self, owner, name, env, angle, range=None):
         self._owner, self.name, self.env, self.angle = owner, name, env, angle
+        self.range = np.full(len(angle), np.inf) if range is None else range
         self.last = None
 
     def set_angle(self, angle):
         """Point this sightline elsewhere (inside the meta-pupil's margin: ``ValueError`` otherwise, before anything changes).  The next
         installation — the next step, or ``reset`` — reads the layers there."""
-        self._look(*self._owner._shifts_for(angle, f"sightline {self.name!r}"))
+        self._look(*self._owner._shifts_for(angle, f"sightline {self.name!r}", self.range))
 
-    def _look(self, angle, shifts):
-        """Store a checked line of sight (``LayeredAOEnv._shifts_for``): the next installation reads the layers at ``shifts``."""
-        self.angle, self._shifts = angle, shifts
+    def _look(self, angle, shifts, geometry=None):
+        """Store a checked line of sight (``LayeredAOEnv._shifts_for``): the next installation reads the layers at ``shifts`` — from a finite
+        range through ``geometry`` [S, B, 3], which is None when every magnification is 1 (the plane-wave installation)."""
+        self.angle, self._shifts, self._geometry = angle, shifts, geometry
 
 
 class _InstalledFront(BatchedAOEnv):
@@ -200,6 +314,17 @@ class LayeredAOEnv(_InstalledFront):
                  (``default_meta_pupil_pixels``): the smallest accepted size that leaves the margin c >= ceil(max |h_l theta| /
                  pupil_pixel) + 1 over every sightline declared at construction (``field_angle`` and ``sightlines``).
     sightlines   None, or {name: angle} — ``add_sightline(angle, name)`` for each at the end of construction, counted in the default margin.
+                 An entry may be ``dict(angle=(tx, ty), range=9e4)`` instead: that sightline looks at a source at finite range.
+    source_range None or inf (a plane wave: the env constructs and launches exactly what it did before), or the distance in metres of
+                 what the env's own front looks at — a laser guide star, an aircraft or satellite terminal — a scalar or per-env values
+                 ([B] / [total_envs], ``resolve_per_env``).  Needs ``layer_altitudes``.  Light from range H crosses a source at altitude h
+                 inside a cone: the front reads the layer's (and altitude mirror's) footprint shrunk by m = 1 - h / H about the point its
+                 angle selects (``cone_geometry``, ``aog_install_layer_sum_cone``).  Every layer and mirror must lie below the source
+                 (``ValueError`` naming it); the default margin counts the (1 - m) (N - 1) / 2 pixels the footprint's far edge moves.
+                 Ranges are fixed at construction (the env's, and each sightline's at ``add_sightline(angle, name, range=)``);
+                 ``get_state`` records them and ``set_state`` refuses a state taken with others.  A front all of whose magnifications are 1
+                 takes the plane-wave installation, bit for bit what it took before.  Not modelled: the spherical wave's amplitude, a laser
+                 spot's elongation, focus indetermination, a range that changes during an episode.
     altitude_mirrors   None (the env constructs and launches exactly what it did before), or [dict(altitude=h, actuators=9), ...] —
                  ``conjugate.resolve_mirror``'s forms — for one ``conjugate.AltitudeMirror`` each: ``env.altitude_mirrors`` is the list.  Needs
                  ``layer_altitudes``; layers plus mirrors are at most 8; the mirrors' altitudes count in the default margin and in every
@@ -246,7 +371,7 @@ class LayeredAOEnv(_InstalledFront):
                  rew_type="strehl_ratio", rew_threshold=None, timesteps_per_episode=20, flat_mirror_start_per_episode=True, SH_operation=False, *,
                  atm_type="dynamic", seed=None, screen_source="device", rng=None, global_env_offset=0, total_envs=None, extrusion="auto",
                  verbose=True, disturbance=None, layer_altitudes=None, field_angle=None, meta_pupil_pixels=None, sightlines=None, altitude_mirrors=None,
-                 altitude_action=None, **kw):
+                 altitude_action=None, source_range=None, **kw):
         self._layers = []
         self._mirrors = []
         self._altitude_scale = None
@@ -254,6 +379,7 @@ class LayeredAOEnv(_InstalledFront):
         self.disturbance = None
         self._sightlines = {}
         self._altitudes = None
+        self.source_range = None
         if atm_type != "dynamic":
             raise ValueError("LayeredAOEnv: atm_type is 'dynamic' (a layered atmosphere evolves every step)")
         for bad in ("atm_vel", "screens"):
@@ -265,6 +391,8 @@ class LayeredAOEnv(_InstalledFront):
         if altitudes is None and (field_angle is not None or meta_pupil_pixels is not None or sightlines):
             raise ValueError("LayeredAOEnv: field_angle, meta_pupil_pixels and sightlines need layer_altitudes (without altitudes every layer sits "
                              "in the pupil plane and every direction sees the same wavefront)")
+        if altitudes is None and source_range is not None:
+            raise ValueError("LayeredAOEnv: source_range needs layer_altitudes (a source's range only shows through layers above the ground)")
         if altitudes is None and altitude_mirrors:
             raise ValueError("LayeredAOEnv: altitude_mirrors need layer_altitudes (a mirror conjugated to an altitude is drawn on the layers' meta-pupil)")
         if altitude_action is not None and not altitude_mirrors:
@@ -288,21 +416,36 @@ class LayeredAOEnv(_InstalledFront):
             angle = resolve_field_angle(field_angle, n_env, total_envs, n_off)
             if sightlines is not None and not isinstance(sightlines, dict):
                 raise ValueError("sightlines: a dict {name: angle}")
-            declared = {str(k): resolve_field_angle(v, n_env, total_envs, n_off, f"sightline {k!r}") for k, v in (sightlines or {}).items()}
+            own_range = resolve_range(source_range, n_env, total_envs, n_off)
+            looks = {str(k): resolve_sightline(v, n_env, total_envs, n_off, f"sightline {k!r}") for k, v in (sightlines or {}).items()}
+            declared = {k: a for k, (a, _) in looks.items()}
             N = params.num_pupil_pixels
+            every = [("field_angle", angle, own_range)] + [(f"sightline {k!r}", a, H) for k, (a, H) in looks.items()]
+            # The ranges as declared, for every env of the whole batch: what is refused and how large the default meta-pupil is must not
+            # depend on which envs this instance holds.  (With every source at infinity the margin is the plane wave's own, as it was.)
+            stated = [declared_range(source_range)] + [declared_range(v.get("range") if isinstance(v, dict) else None) for v in (sightlines or {}).values()]
+            finite = any(np.any(np.isfinite(H)) for H in stated)
+            if finite:
+                for (what, _, _), H in zip(every, stated):   # (a layer or mirror at or above a source, before anything else)
+                    cone_geometry(seen_at, np.zeros((H.size, 2)), H, params.pupil_pixel, first_mirror=len(plan), what=what)
             if meta_pupil_pixels is None:
-                n_meta = default_meta_pupil_pixels(N, required_margin(seen_at, [angle] + list(declared.values()), params.pupil_pixel))
+                n_meta = default_meta_pupil_pixels(N, required_margin_cone(seen_at, [(a, H) for (_, a, _), H in zip(every, stated)], params.pupil_pixel, N)
+                                                   if finite else required_margin(seen_at, [angle] + list(declared.values()), params.pupil_pixel))
             else:
                 n_meta = int(meta_pupil_pixels)
                 if n_meta != meta_pupil_pixels or n_meta < N or (n_meta - N) % 2:
                     raise ValueError(f"meta_pupil_pixels: expected an integer >= num_pupil_pixels ({N}) with an even difference, got {meta_pupil_pixels!r}")
             margins = np.where(seen_at > 0, (n_meta - N) // 2, 0)
-            for what, a in [("field_angle", angle)] + [(f"sightline {k!r}", v) for k, v in declared.items()]:
-                check_margin(sightline_shifts(seen_at, a, params.pupil_pixel), margins, what, first_mirror=len(plan))
+            for what, a, H in every:
+                if np.any(np.isfinite(H)):
+                    check_margin_cone(cone_geometry(seen_at, a, H, params.pupil_pixel, first_mirror=len(plan), what=what), margins, N, what,
+                                      first_mirror=len(plan))
+                else:
+                    check_margin(sightline_shifts(seen_at, a, params.pupil_pixel), margins, what, first_mirror=len(plan))
             for m in mirror_specs:
                 resolve_mirror(m, N, n_meta)   # (actuators, coupling and a given basis's shape)
-            geometry = dict(angle=angle, declared=declared, n_meta=n_meta, margins=margins[:len(plan)], seen_at=seen_at, seen_margins=margins,
-                            mirrors=mirror_specs)
+            geometry = dict(angle=angle, declared=looks, n_meta=n_meta, margins=margins[:len(plan)], seen_at=seen_at, seen_margins=margins,
+                            mirrors=mirror_specs, range=own_range)
         self._front_args = dict(args=(act_type, act_dim, obs_dim, rew_type, rew_threshold, timesteps_per_episode, flat_mirror_start_per_episode,
                                       SH_operation), seed=seed, extrusion=extrusion, kw={k: v for k, v in kw.items() if k != "servo"})   # (one mirror, one servo: the env's)
         # The front: a quasi-static handle whose screens are installed, never drawn (_InstalledFront); it consumes no
@@ -341,7 +484,8 @@ class LayeredAOEnv(_InstalledFront):
                 self.layer_margins = geometry["margins"]          # [L] c_l: the meta-pupil's margin on every side, 0 for a ground layer
                 self.field_angle = geometry["angle"]              # [B, 2] radians
                 self._seen_at, self._seen_margins = geometry["seen_at"], geometry["seen_margins"]   # the layers', then the mirrors'
-                self._shifts = sightline_shifts(self._seen_at, self.field_angle, self.params.pupil_pixel)
+                self.source_range = geometry["range"]             # [B] metres, inf: a plane wave; fixed at construction
+                self._look(*self._shifts_for(self.field_angle, "field_angle", self.source_range))
                 if geometry["mirrors"]:
                     from .conjugate import AltitudeMirror
 
@@ -355,8 +499,8 @@ class LayeredAOEnv(_InstalledFront):
                         self.action_space = self.single_action_space = make_box(-1, 1, (width,), np.float16)
             self._install()   # the first reset sees t = 0
             if geometry is not None:
-                for name, angle in geometry["declared"].items():
-                    self.add_sightline(angle, name)
+                for name, (angle, rng) in geometry["declared"].items():
+                    self.add_sightline(angle, name, rng)
         except Exception:
             self.close()
             raise
@@ -390,9 +534,13 @@ class LayeredAOEnv(_InstalledFront):
         self.disturbance = d
         self._coeff = d.coefficients()
 
-    def _install_front(self, front, shifts, coeff):
-        """One front's installation along its line of sight: the layers, and the altitude mirrors' surfaces when the env has any."""
-        if self._mirrors:
+    def _install_front(self, front, shifts, coeff, geometry=None):
+        """One front's installation along its line of sight: the layers, and the altitude mirrors' surfaces when the env has any.  Only a
+        front that looks at a source at finite range (``geometry``: some m < 1) takes the cone form; every other front calls what it called
+        before there were ranges."""
+        if geometry is not None:
+            install_layer_sum_cone(front, self._layers, self._mirrors, geometry, coeff)
+        elif self._mirrors:
             from .conjugate import install_layer_sum_conjugate
 
             install_layer_sum_conjugate(front, self._layers, self._mirrors, shifts, coeff)
@@ -403,9 +551,9 @@ class LayeredAOEnv(_InstalledFront):
         coeff = None if self.disturbance is None else self._coeff
         if self._altitudes is not None:
             # every front reads the same layers (and mirrors) at its own shifts; the coefficients are common-path
-            self._install_front(self, self._shifts, coeff)
+            self._install_front(self, self._shifts, coeff, self._geometry)
             for sl in self._sightlines.values():
-                self._install_front(sl.env, sl._shifts, coeff)
+                self._install_front(sl.env, sl._shifts, coeff, sl._geometry)
         elif coeff is None:
             self.install_layer_sum(self._layers)
         else:
@@ -415,23 +563,32 @@ class LayeredAOEnv(_InstalledFront):
     sightlines = property(lambda self: dict(self._sightlines), doc="{name: Sightline}")
     altitude_mirrors = property(lambda self: list(self._mirrors), doc="[conjugate.AltitudeMirror], in the order of ``altitude_mirrors=``")
 
-    def _shifts_for(self, angle, what):
-        """``angle`` resolved to [B, 2] and its shifts [L, B, 2], checked against the margins (``ValueError`` before anything changes)."""
+    def _shifts_for(self, angle, what, rng=None):
+        """``angle`` resolved to [B, 2], its shifts [L, B, 2] and, for a source at ``rng`` [B] metres with some magnification below 1, the
+        geometry [L, B, 3] (None otherwise), checked against the margins (``ValueError`` before anything changes)."""
         if self._altitudes is None:
             raise ValueError(f"{what}: this env was built without layer_altitudes (every layer sits in the pupil plane and every direction sees "
                              "the same wavefront)")
         angle = resolve_field_angle(angle, self.num_envs, self.total_envs, self.global_env_offset, what)
+        if rng is not None and np.any(np.isfinite(rng)):
+            geometry = cone_geometry(self._seen_at, angle, rng, self.params.pupil_pixel, first_mirror=len(self._layers), what=what)
+            check_margin_cone(geometry, self._seen_margins, self.num_pupil_pixels, what, first_mirror=len(self._layers))
+            shifts = np.ascontiguousarray(geometry[:, :, :2])
+            return angle, shifts, (geometry if np.any(geometry[:, :, 2] != 1.0) else None)
         shifts = sightline_shifts(self._seen_at, angle, self.params.pupil_pixel)
         check_margin(shifts, self._seen_margins, what, first_mirror=len(self._layers))
-        return angle, shifts
+        return angle, shifts, None
 
-    def add_sightline(self, angle, name=None):
-        """A second front over the same layers that looks along ``angle`` ((theta_x, theta_y) radians, or per-env pairs): returns its
-        ``Sightline``.  ``ValueError`` when the angle leaves the meta-pupil's margin or the name is taken, before anything is created."""
+    def add_sightline(self, angle, name=None, range=None):
+        """A second front over the same layers that looks along ``angle`` ((theta_x, theta_y) radians, or per-env pairs) at a source
+        ``range`` metres away (a scalar or per-env values; None or inf: a plane wave, whatever the env's own ``source_range``): returns its
+        ``Sightline``.  ``ValueError`` when the angle leaves the meta-pupil's margin, a layer or mirror lies at or above the source or the
+        name is taken, before anything is created."""
         name = f"sightline{len(self._sightlines)}" if name is None else str(name)
         if name in self._sightlines:
             raise ValueError(f"add_sightline: there is a sightline {name!r} already")
-        angle, shifts = self._shifts_for(angle, f"sightline {name!r}")
+        rng = resolve_range(range, self.num_envs, self.total_envs, self.global_env_offset, f"sightline {name!r}: range")
+        angle, shifts, geometry = self._shifts_for(angle, f"sightline {name!r}", rng)
         fa = self._front_args
         front = _InstalledFront(self.num_envs, self.device, "quasi_static", 0, self.fried_parameter, *fa["args"], seed=fa["seed"], screen_source="device",
                                 rng=None, global_env_offset=self.global_env_offset, total_envs=self.total_envs, extrusion=fa["extrusion"],
@@ -439,9 +596,9 @@ class LayeredAOEnv(_InstalledFront):
         try:
             if self.disturbance is not None:
                 self.disturbance.upload_basis(front)
-            sl = Sightline(self, name, front, angle)
-            sl._look(angle, shifts)
-            self._install_front(front, shifts, None if self.disturbance is None else self._coeff)
+            sl = Sightline(self, name, front, angle, rng)
+            sl._look(angle, shifts, geometry)
+            self._install_front(front, shifts, None if self.disturbance is None else self._coeff, geometry)
         except Exception:
             front.close()
             raise
@@ -451,11 +608,11 @@ class LayeredAOEnv(_InstalledFront):
     def set_field_angle(self, angle):
         """Point the env's own line of sight elsewhere (inside the meta-pupil's margin: ``ValueError`` otherwise, before anything changes).
         The next installation — the next step — reads the layers there."""
-        self._look(*self._shifts_for(angle, "field_angle"))
+        self._look(*self._shifts_for(angle, "field_angle", self.source_range))
 
-    def _look(self, angle, shifts):
+    def _look(self, angle, shifts, geometry=None):
         """``Sightline._look`` for the env's own line of sight."""
-        self.field_angle, self._shifts = angle, shifts
+        self.field_angle, self._shifts, self._geometry = angle, shifts, geometry
 
     def _refuse_with_sightlines(self, who):
         if self._sightlines:
@@ -608,9 +765,19 @@ class LayeredAOEnv(_InstalledFront):
         if self._altitudes is not None:
             state["field_angle"] = self.field_angle.copy()
             state["sightlines"] = {name: dict(angle=sl.angle.copy(), env=sl.env.get_state()) for name, sl in self._sightlines.items()}
+            self._record_ranges(state)
         if self._mirrors:
             state["altitude_mirrors"] = [m.get_state() for m in self._mirrors]
         return state
+
+    def _record_ranges(self, state):
+        """The ranges' part of ``get_state``: recorded where there is one — a state without them is one of plane waves, as every state was
+        before there were ranges."""
+        if np.any(np.isfinite(self.source_range)):
+            state["source_range"] = self.source_range.copy()
+        for name, sl in self._sightlines.items():
+            if np.any(np.isfinite(sl.range)):
+                state["sightlines"][name]["range"] = sl.range.copy()
 
     def set_state(self, state):
         if len(state.get("layers", ())) != len(self._layers):
@@ -626,9 +793,16 @@ class LayeredAOEnv(_InstalledFront):
         if len(state.get("altitude_mirrors", ())) != len(self._mirrors):
             raise ValueError(f"set_state: the state was saved with {len(state.get('altitude_mirrors', ()))} altitude mirrors, this env has {len(self._mirrors)}")
         if self._altitudes is not None:
+            # (ranges are fixed at construction: a state taken with others belongs to another geometry)
+            far = np.full(self.num_envs, np.inf)
+            for what, have, saved in [("source_range", self.source_range, state.get("source_range", far))] + [
+                    (f"sightline {name!r}: range", sl.range, state["sightlines"][name].get("range", far)) for name, sl in self._sightlines.items()]:
+                if not np.array_equal(np.asarray(saved, dtype=np.float64), have):
+                    raise ValueError(f"set_state: the state was saved with {what} = {np.asarray(saved).tolist()}, this env was built with {have.tolist()}")
             # (every angle is checked against this env's margins before anything changes)
-            moved = [(self, self._shifts_for(state["field_angle"], "set_state: field_angle"))]
-            moved += [(sl, self._shifts_for(state["sightlines"][name]["angle"], f"set_state: sightline {name!r}")) for name, sl in self._sightlines.items()]
+            moved = [(self, self._shifts_for(state["field_angle"], "set_state: field_angle", self.source_range))]
+            moved += [(sl, self._shifts_for(state["sightlines"][name]["angle"], f"set_state: sightline {name!r}", sl.range))
+                      for name, sl in self._sightlines.items()]
             for target, look in moved:
                 target._look(*look)
         for lay, st in zip(self._layers, state["layers"]):

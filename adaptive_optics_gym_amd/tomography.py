@@ -37,10 +37,26 @@ def _one_shift(shift, j):
     return float(s[0]), float(s[1])
 
 
-def displaced_basis(basis, shift, ap_index, N):
+def _one_magnification(m, j):
+    """m of mirror j from a scalar or per-env [B] values, which must agree across the batch; None stays None (a plane wave)."""
+    if m is None:
+        return None
+    m = np.asarray(m, dtype=np.float64).reshape(-1)
+    if not np.all(m == m[0]):
+        raise ValueError(f"sightline_shapes: the magnification of mirror {j} differs across the batch (per-env ranges): this version takes one "
+                         "geometry for the whole batch")
+    if not 0.0 < m[0] <= 1.0:
+        raise ValueError(f"sightline_shapes: the magnification of mirror {j} must lie in (0, 1], got {m[0]!r}")
+    return float(m[0])
+
+
+def displaced_basis(basis, shift, ap_index, N, magnification=None):
     """[K, n_ap]: the [K, M, M] ``basis`` read bilinearly at (iy + c + sy, ix + c + sx), c = (M - N) / 2, on the aperture pixels
     (iy, ix) = divmod(ap_index, N) — the read of the installation (include/aogym_sightline.h), value for value:
-    ``(gy ((gx v00) + (fx v01))) + (fy ((gx v10) + (fx v11)))``, indices modulo M."""
+    ``(gy ((gx v00) + (fx v01))) + (fy ((gx v10) + (fx v11)))``, indices modulo M.  With a ``magnification`` m (a source at finite range:
+    include/aogym_cone.h) the read is that header's instead, at (c + ctr + m (iy - ctr) + sy, c + ctr + m (ix - ctr) + sx), ctr = (N - 1) / 2,
+    per axis ``s0 = floor(s); q = ((m - 1) (i - ctr)) + (s - s0); q0 = floor(q); f = q - q0; g = 1 - f``, first index ``i + s0 + q0`` — at
+    m = 1 the sightline read to the bit."""
     b = np.asarray(basis, dtype=np.float64)
     M = b.shape[-1]
     if b.ndim != 3 or b.shape[1] != M or M < N or (M - N) % 2:
@@ -48,17 +64,26 @@ def displaced_basis(basis, shift, ap_index, N):
     c = (M - N) // 2
     sx, sy = shift
     iy, ix = np.divmod(np.asarray(ap_index, dtype=np.int64), N)
-    x0, y0 = np.floor(sx), np.floor(sy)
-    fx, fy = sx - x0, sy - y0
-    gx, gy = 1.0 - fx, 1.0 - fy
-    py, px = (iy + c + int(y0)) % M, (ix + c + int(x0)) % M
+    if magnification is None:
+        x0, y0 = np.floor(sx), np.floor(sy)
+        fx, fy = sx - x0, sy - y0
+        gx, gy = 1.0 - fx, 1.0 - fy
+        py, px = (iy + c + int(y0)) % M, (ix + c + int(x0)) % M
+    else:
+        k, ctr = float(magnification) - 1.0, 0.5 * (N - 1)
+        sx0, sy0 = np.floor(sx), np.floor(sy)
+        qy, qx = (k * (iy - ctr)) + (sy - sy0), (k * (ix - ctr)) + (sx - sx0)
+        y0, x0 = np.floor(qy), np.floor(qx)
+        fx, fy = qx - x0, qy - y0
+        gx, gy = 1.0 - fx, 1.0 - fy
+        py, px = (iy + c + int(sy0) + y0.astype(np.int64)) % M, (ix + c + int(sx0) + x0.astype(np.int64)) % M
     py1, px1 = (py + 1) % M, (px + 1) % M
     top = (gx * b[:, py, px]) + (fx * b[:, py, px1])
     bottom = (gx * b[:, py1, px]) + (fx * b[:, py1, px1])
     return (gy * top) + (fy * bottom)
 
 
-def sightline_shapes(env_or_tables, mirrors, shifts_g, pupil_mirror=True, num_pupil_pixels=None):
+def sightline_shapes(env_or_tables, mirrors, shifts_g, pupil_mirror=True, num_pupil_pixels=None, magnifications=None):
     """T_g [K_tot, n_ap] float64: the path error in metres on the aperture pixels of one front per unit of each unknown — the pupil
     mirror's A actuators first (``2 x modes``: path = 2 x surface, ``ideal_actuators = actuators - coef / 2``; left out with
     ``pupil_mirror=False``), then every altitude mirror's K_m commands, its basis read at that front's shift and cropped to the pupil as
@@ -66,15 +91,20 @@ def sightline_shapes(env_or_tables, mirrors, shifts_g, pupil_mirror=True, num_pu
 
     env_or_tables  an env (``tables``, ``num_pupil_pixels``) or its host tables (then ``num_pupil_pixels`` is given)
     mirrors        objects with ``basis`` [K_m, M, M] (``conjugate.AltitudeMirror``), or such arrays
-    shifts_g       [n_mirrors, 2] (sx, sy) in pixels of this front, or [n_mirrors, B, 2] whose envs agree (``ValueError`` otherwise)"""
+    shifts_g       [n_mirrors, 2] (sx, sy) in pixels of this front, or [n_mirrors, B, 2] whose envs agree (``ValueError`` otherwise)
+    magnifications None (a plane-wave front), or per mirror the magnification of its footprint on this front ([n_mirrors] or
+                   [n_mirrors, B] whose envs agree): the mirror is then read as ``aog_install_layer_sum_cone`` reads it"""
     tables = getattr(env_or_tables, "tables", env_or_tables)
     N = int(num_pupil_pixels if num_pupil_pixels is not None else env_or_tables.num_pupil_pixels)
     shifts_g = np.asarray(shifts_g, dtype=np.float64)
     if len(shifts_g) != len(mirrors):
         raise ValueError(f"sightline_shapes: {len(mirrors)} mirrors, {len(shifts_g)} shifts")
     rows = [2.0 * np.asarray(tables.modes, dtype=np.float64).T] if pupil_mirror else []
+    if magnifications is not None and len(magnifications) != len(mirrors):
+        raise ValueError(f"sightline_shapes: {len(mirrors)} mirrors, {len(magnifications)} magnifications")
     for j, m in enumerate(mirrors):
-        rows.append(displaced_basis(getattr(m, "basis", m), _one_shift(shifts_g[j], j), tables.ap_index, N) / (2.0 * np.pi))
+        mag = None if magnifications is None else _one_magnification(magnifications[j], j)
+        rows.append(displaced_basis(getattr(m, "basis", m), _one_shift(shifts_g[j], j), tables.ap_index, N, mag) / (2.0 * np.pi))
     if not rows:
         raise ValueError("sightline_shapes: no unknowns (no altitude mirror and pupil_mirror=False)")
     return np.ascontiguousarray(np.concatenate(rows, axis=0))
@@ -84,6 +114,17 @@ def centred(T):
     """The rows of T with their aperture means removed."""
     T = np.asarray(T, dtype=np.float64)
     return T - T.mean(axis=1, keepdims=True)
+
+
+def tilt_projected(T, ap_index, N):
+    """T P [K, n_ap], P = I - t t' over the aperture's tip and tilt: t [n_ap, 2] the x and y coordinates of the aperture pixels, centred
+    and orthonormalised.  What a guide star that cannot see tip and tilt (a laser: the upward and downward paths cancel them) contributes:
+    every row of the result has zero inner product with any tilt of the front, so ``T P w`` does not move when a tilt is added to w."""
+    T = np.asarray(T, dtype=np.float64)
+    iy, ix = np.divmod(np.asarray(ap_index, dtype=np.int64), N)
+    t = np.stack([ix - ix.mean(), iy - iy.mean()], axis=1).astype(np.float64)
+    t, _ = np.linalg.qr(t)
+    return T - (T @ t) @ t.T
 
 
 def _regularised_inverse(H, alpha, who):
@@ -257,6 +298,15 @@ class TomographicController:
                                 ``R_g`` = ``modal_reconstructors``' block.
     gain, leak, stroke   ``u <- clip(leak u - gain sum_g R_g s_g, +-stroke)`` (``stroke <= 0``: no clip); alpha: the regularisation of H.
     pupil_mirror  False: only the altitude mirrors are unknowns; ``action()`` then returns the pupil mirror's actuators as they stand.
+    tilt_blind    names of guide stars that do not see tip and tilt (a laser guide star: the upward and downward paths cancel them).  The
+                  shapes uploaded for ``aog_wavefront_project`` on such a front and its rows of the normal matrix are ``T_g P``
+                  (``tilt_projected``): whatever tip and tilt its wavefront carries moves neither ``action()`` nor ``fit()``.  Host side
+                  only, and for ``measurement="truth"`` only: a ``"modal"`` measurement is the front's modal coefficients, tilt included,
+                  which the projected rows do not take out again (``ValueError``).  With every guide star blind nothing determines the
+                  unknowns' tip and tilt, and construction raises.
+
+    A guide front that looks at a source at finite range (``LayeredAOEnv(source_range=)``, ``add_sightline(range=)``) gets its ``T_g`` from the
+    cone read of the mirrors (``sightline_shapes(magnifications=)``), value for value what ``aog_install_layer_sum_cone`` installs.
 
     ``action(out=None)`` measures on every guide front, runs one ``aog_tomo_update``, sets every altitude mirror's command to its slice of u
     and returns the pupil mirror's [B, A] float64 actuators in ``ideal_action()``'s form (the action of an env built with
@@ -273,7 +323,8 @@ class TomographicController:
     screens from ``conjugate.install_layer_sum_conjugate``, ``AltitudeMirror`` objects and, per front, the mirrors' shifts [n_mirrors, 2];
     the caller installs, and hands the returned actuators to its fronts."""
 
-    def __init__(self, env, guide_stars=("self",), weights=None, measurement="truth", gain=0.5, leak=1.0, alpha=1e-6, stroke=0.0, pupil_mirror=True):
+    def __init__(self, env, guide_stars=("self",), weights=None, measurement="truth", gain=0.5, leak=1.0, alpha=1e-6, stroke=0.0, pupil_mirror=True,
+                 tilt_blind=()):
         mirrors = list(getattr(env, "altitude_mirrors", None) or ())
         if not mirrors:
             raise ValueError("TomographicController: the env has no altitude mirrors (LayeredAOEnv(altitude_mirrors=[...])); without them "
@@ -282,32 +333,34 @@ class TomographicController:
             raise ValueError("TomographicController: the env was built with altitude_action, which hands the altitude mirrors to the action; "
                              "build it without")
         guide_stars = (guide_stars,) if isinstance(guide_stars, str) else tuple(guide_stars)
-        fronts, shifts = [], []
+        fronts, shifts, mags = [], [], []
         n_layers = len(env.layers)
         for name in guide_stars:
-            if name == "self":
-                fronts.append(env), shifts.append(env._shifts[n_layers:])
-            elif name in env.sightlines:
-                sl = env.sightlines[name]
-                fronts.append(sl.env), shifts.append(sl._shifts[n_layers:])
+            if name == "self" or name in env.sightlines:
+                holder = env if name == "self" else env.sightlines[name]
+                fronts.append(env if name == "self" else holder.env), shifts.append(holder._shifts[n_layers:])
+                # (a front at finite range is installed through its cone geometry: T_g restates that read)
+                geometry = getattr(holder, "_geometry", None)
+                mags.append(None if geometry is None else geometry[n_layers:, :, 2])
             else:
                 raise ValueError(f"TomographicController: unknown guide star {name!r} (\"self\" or one of the env's sightlines {sorted(env.sightlines)})")
         self.env = env
-        self._build(fronts, mirrors, shifts, guide_stars, weights, measurement, gain, leak, alpha, stroke, pupil_mirror)
+        self._build(fronts, mirrors, shifts, guide_stars, weights, measurement, gain, leak, alpha, stroke, pupil_mirror, mags, tilt_blind)
         # the geometry is read once: T_g, H^-1 and the uploaded shapes belong to these shifts (_check_geometry)
         self._looked = [(env if name == "self" else env.sightlines[name], np.array(s, copy=True)) for name, s in zip(guide_stars, shifts)]
 
     @classmethod
-    def from_parts(cls, fronts, mirrors, shifts, weights=None, measurement="truth", gain=0.5, leak=1.0, alpha=1e-6, stroke=0.0, pupil_mirror=True):
+    def from_parts(cls, fronts, mirrors, shifts, weights=None, measurement="truth", gain=0.5, leak=1.0, alpha=1e-6, stroke=0.0, pupil_mirror=True,
+                   magnifications=None, tilt_blind=()):
         self = cls.__new__(cls)
         self.env = None
         if not mirrors:
             raise ValueError("TomographicController: no altitude mirrors")
         self._build(list(fronts), list(mirrors), list(shifts), tuple(f"front{g}" for g in range(len(fronts))), weights, measurement, gain, leak,
-                    alpha, stroke, pupil_mirror)
+                    alpha, stroke, pupil_mirror, magnifications, tilt_blind)
         return self
 
-    def _build(self, fronts, mirrors, shifts, names, weights, measurement, gain, leak, alpha, stroke, pupil_mirror):
+    def _build(self, fronts, mirrors, shifts, names, weights, measurement, gain, leak, alpha, stroke, pupil_mirror, magnifications=None, tilt_blind=()):
         if measurement not in MEASUREMENTS:
             raise ValueError(f"measurement must be 'truth' or 'modal' (got {measurement!r})")
         if not 1 <= len(fronts) <= _lib.TOMO_MAX_INPUTS:
@@ -326,7 +379,19 @@ class TomographicController:
         first = fronts[0]
         self.num_envs, self.num_modes, self.device = int(first.num_envs), int(first.num_modes), first.device
         # the geometry, on the host
-        self.T = [sightline_shapes(first, mirrors, s, self.pupil_mirror) for s in shifts]
+        tilt_blind = (tilt_blind,) if isinstance(tilt_blind, str) else tuple(tilt_blind)
+        for name in tilt_blind:
+            if name not in names:
+                raise ValueError(f"TomographicController: tilt_blind names {name!r}, which is no guide star of {names!r}")
+        if tilt_blind and measurement != "truth":
+            raise ValueError("TomographicController: tilt_blind needs measurement='truth' (a 'modal' measurement carries the front's tip and tilt "
+                             "in its coefficients, which the projected shapes do not remove)")
+        self.tilt_blind = tilt_blind
+        magnifications = [None] * len(fronts) if magnifications is None else list(magnifications)
+        if len(magnifications) != len(fronts):
+            raise ValueError(f"TomographicController: {len(fronts)} guide stars, {len(magnifications)} sets of magnifications")
+        self.T = [sightline_shapes(first, mirrors, s, self.pupil_mirror, magnifications=m) for s, m in zip(shifts, magnifications)]
+        self.T = [tilt_projected(T, first.tables.ap_index, int(first.num_pupil_pixels)) if name in tilt_blind else T for T, name in zip(self.T, names)]
         self.n_unknowns = int(self.T[0].shape[0])
         if self.n_unknowns > _lib.WAVEFRONT_MAX_SHAPES:
             raise ValueError(f"TomographicController: {self.n_unknowns} unknowns, aog_wavefront_project takes {_lib.WAVEFRONT_MAX_SHAPES} shapes")
@@ -335,7 +400,13 @@ class TomographicController:
         for m in mirrors:
             self.slices.append(slice(lo, lo + int(m.n_modes)))
             lo += int(m.n_modes)
-        self.H_inv = reconstructor(self.T, self.weights, self.alpha)
+        try:
+            self.H_inv = reconstructor(self.T, self.weights, self.alpha)
+        except ValueError as err:
+            if set(names) <= set(tilt_blind):
+                raise ValueError(f"{err}.  Every guide star is in tilt_blind: no front measures tip and tilt, so the unknowns' own tip and tilt are "
+                                 "undetermined — add a guide star that sees them (a natural star: leave it out of tilt_blind)") from None
+            raise
         R_truth = [np.ascontiguousarray(w * self.H_inv) for w in self.weights]
         if measurement == "truth":
             self.R = R_truth
