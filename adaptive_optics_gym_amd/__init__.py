@@ -9,6 +9,7 @@
     from adaptive_optics_gym_amd import ModalDisturbance  # vibration and static aberrations for LayeredAOEnv(disturbance=...)
     from adaptive_optics_gym_amd import MirrorServo       # loop latency and mirror dynamics for BatchedAOEnv(servo=...)
     from adaptive_optics_gym_amd.tomography import TomographicController   # the MCAO baseline of LayeredAOEnv(altitude_mirrors=...)
+    from adaptive_optics_gym_amd.scintillation import rytov_variance       # the regime check of LayeredAOEnv(scintillation=...)
     import gym_AO                                         # registers 'AO-v0' like the reference (needs gymnasium)
 """
 from .batched_env import BatchedAOEnv  # noqa: F401

@@ -134,6 +134,13 @@ class AogLqgConfig(C.Structure):  # mirrors aog_lqg_config (include/aogym_lqg.h;
     _fields_ = [(n, C.c_int32) for n in ("abi_version", "num_envs", "act_dim", "n_models", "reserved")]
 
 
+class AogScintConfig(C.Structure):  # mirrors aog_scint_config (include/aogym_scintillation.h; its size query is aog_scint_config_size)
+    _fields_ = [(n, C.c_int32) for n in ("abi_version", "num_envs", "n_pixels", "n_layers", "n_fiber", "reserved")] + [("scratch_bytes", C.c_int64)]
+
+
+SCINT_MAX_LAYERS, SCINT_MAX_FIBER = 8, 4   # AOG_SCINT_MAX_LAYERS, AOG_SCINT_MAX_FIBER
+
+
 LQG_MAX_ACT, LQG_MAX_MODELS, LQG_MAX_DELAY, LQG_MAX_ITERATIONS = 128, 4, 4, 4096   # AOG_LQG_MAX_*
 
 
@@ -319,6 +326,22 @@ CONE_SYMBOLS = {
     "aog_cone_check_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
 }
 
+# every symbol include/aogym_scintillation.h declares, the handle's lifecycle calls written out (aog_scint is no entry of STANDALONE below, and has no state)
+SCINTILLATION_SYMBOLS = {
+    "aog_scint_config_size": (C.c_int64, []),
+    "aog_scint_create": (C.c_int, [C.POINTER(AogScintConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "aog_scint_destroy": (None, [C.c_void_p]),
+    "aog_scint_upload": (C.c_int, [C.c_void_p] * 3),
+    "aog_scint_upload_modes": (C.c_int, [C.c_void_p] * 3),
+    "aog_scint_filter": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "aog_scint_correction": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "aog_scint_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aog_scint_tile_floats": (C.c_int64, [C.c_void_p]),
+    "aog_scint_scratch_bytes": (C.c_int64, [C.c_void_p]),
+    "aog_scint_install": (C.c_int, [C.c_void_p] * 6),
+    "aog_scint_receive": (C.c_int, [C.c_void_p] * 8),
+}
+
 
 def _lifecycle(prefix, config):
     """The five calls every stand-alone handle has (csrc/standalone_handle.h)."""
@@ -353,7 +376,7 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SYMBOLS, **DISTURBANCE_SYMBOLS, **SIGHTLINE_SYMBOLS, **SERVO_SYMBOLS, **CONJUGATE_SYMBOLS, **TOMOGRAPHY_SYMBOLS,
-                              **SHACK_GRADIENT_SYMBOLS, **LQG_SYMBOLS, **CONE_SYMBOLS}.items():
+                              **SHACK_GRADIENT_SYMBOLS, **LQG_SYMBOLS, **CONE_SYMBOLS, **SCINTILLATION_SYMBOLS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -371,7 +394,7 @@ def load():
         (AogConfig, AogTables, AogLayerTables, AogShTables, AogActor, AogInfo, AogLayerComposite, AogObsMft, AogActionNoise))]
     sized += [(AogDisturbanceConfig, lib.aog_disturbance_config_size()), (AogServoConfig, lib.aog_servo_config_size()),
               (AogAltMirrorConfig, lib.aog_altmirror_config_size()), (AogTomoConfig, lib.aog_tomo_config_size()),
-              (AogLqgConfig, lib.aog_lqg_config_size())]
+              (AogLqgConfig, lib.aog_lqg_config_size()), (AogScintConfig, lib.aog_scint_config_size())]
     for cls, size in sized:
         if size != C.sizeof(cls):
             raise RuntimeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, the library's struct {size}")

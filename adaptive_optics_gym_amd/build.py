@@ -2,7 +2,7 @@
 
 One translation unit per kernel family, compiled in parallel: ``aogym.hip`` (C-ABI core: handle, tables, step / reset), ``atmosphere.hip``
 (dynamic atmosphere), ``screens.hip`` (screen synthesis), ``shack.hip`` (Shack-Hartmann chain), ``focal.hip`` (K4 and the separable observation K11), ``actor.hip`` (policy query),
-``wavefront.hip`` (wavefront fit K12), ``science.hip`` (science camera K13), ``gradient.hip`` (output gradient K14), ``gradient_obs.hip`` (its observation part on the separable route), ``layers.hip`` (layered atmosphere: sum of several dynamic handles, along sightlines and from finite-range sources), ``pyramid.hip`` (pyramid wavefront sensor), ``pyramid_grad.hip`` (its gradient), ``shack_gradient.hip`` (the Shack-Hartmann chain's gradient), ``predictor.hip`` (predictive controller K17), ``telemetry.hip`` (modal telemetry K18), ``spgd.hip`` (SPGD controller K19), ``link.hip`` (link telemetry K20), ``disturbance.hip`` (modal disturbance generator K21), ``servo.hip`` (mirror servo K22), ``conjugate.hip`` (altitude mirror K23), ``tomography.hip`` (wavefront projection and tomographic reconstructor K24), ``lqg.hip`` (LQG controller K25) and ``fused_inst.hip`` once per padded mode count (the fused-kernel template instantiations).
+``wavefront.hip`` (wavefront fit K12), ``science.hip`` (science camera K13), ``gradient.hip`` (output gradient K14), ``gradient_obs.hip`` (its observation part on the separable route), ``layers.hip`` (layered atmosphere: sum of several dynamic handles, along sightlines and from finite-range sources), ``pyramid.hip`` (pyramid wavefront sensor), ``pyramid_grad.hip`` (its gradient), ``shack_gradient.hip`` (the Shack-Hartmann chain's gradient), ``predictor.hip`` (predictive controller K17), ``telemetry.hip`` (modal telemetry K18), ``spgd.hip`` (SPGD controller K19), ``link.hip`` (link telemetry K20), ``disturbance.hip`` (modal disturbance generator K21), ``servo.hip`` (mirror servo K22), ``conjugate.hip`` (altitude mirror K23), ``tomography.hip`` (wavefront projection and tomographic reconstructor K24), ``lqg.hip`` (LQG controller K25), ``scintillation.hip`` (Fresnel-filtered layers and the amplitude-aware receiver K26) and ``fused_inst.hip`` once per padded mode count (the fused-kernel template instantiations).
 
 The library is tied to its sources: ``source_id()`` is a SHA-256 over ``csrc/*.{h,hip}`` + ``include/aogym.h`` + the headers of ``EXTRA_HEADERS``; it is compiled into the core
 unit (``aog_build_id()``), ``needs_build()`` compares it with the id the existing library reports (not file times), every object carries the
@@ -24,18 +24,18 @@ OBJ = os.path.join(CSRC, "build")
 INCLUDE = os.path.join(HERE, "..", "include")
 ABI_HEADER = os.path.join(INCLUDE, "aogym.h")
 # the public headers beside aogym.h -> the units that include them (a new header is one entry here; source_files() and _unit_deps() read it)
-EXTRA_HEADERS = {"aogym_disturbance.h": ("layers", "disturbance"), "aogym_sightline.h": ("layers",), "aogym_servo.h": ("servo",), "aogym_conjugate.h": ("layers", "conjugate"), "aogym_tomography.h": ("tomography",), "aogym_shack_gradient.h": ("shack_gradient",), "aogym_lqg.h": ("lqg",), "aogym_cone.h": ("layers",)}
+EXTRA_HEADERS = {"aogym_disturbance.h": ("layers", "disturbance"), "aogym_sightline.h": ("layers",), "aogym_servo.h": ("servo",), "aogym_conjugate.h": ("layers", "conjugate"), "aogym_tomography.h": ("tomography",), "aogym_shack_gradient.h": ("shack_gradient",), "aogym_lqg.h": ("lqg",), "aogym_cone.h": ("layers",), "aogym_scintillation.h": ("scintillation",)}
 OUT = os.path.join(HERE, "libaogym.so")
 APADS = (16, 32, 64, 128)
 # one translation unit each; the last nine are the handles that are no aog_env (csrc/standalone_handle.h)
-UNITS = ("aogym", "atmosphere", "screens", "shack", "focal", "actor", "wavefront", "science", "gradient", "gradient_obs", "layers", "pyramid", "pyramid_grad", "shack_gradient", "predictor", "telemetry", "spgd", "link", "disturbance", "servo", "conjugate", "tomography", "lqg")
+UNITS = ("aogym", "atmosphere", "screens", "shack", "focal", "actor", "wavefront", "science", "gradient", "gradient_obs", "layers", "pyramid", "pyramid_grad", "shack_gradient", "predictor", "telemetry", "spgd", "link", "disturbance", "servo", "conjugate", "tomography", "lqg", "scintillation")
 # -fno-slp-vectorize: no kernel gets scalar fp32 pairs re-packed into v_pk_* behind its back (packed-FMA trap)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-fno-slp-vectorize"]
 # headers each unit includes besides the shared ones (an edit of a family header recompiles that family only)
 SHARED = ("aogym_internal.h", "host_common.h", "standalone_handle.h", "k_common.h", "fused_layout.h")
 DETECTOR = ("k_poisson.h", "k_detector.h")
 FAMILY = {"aogym": ("mft_host.h", "k_pack.h", "k_step.h", "k_actor.h", "k_step_act.h", "k_spgd.h", "k_step_spgd.h", "spgd_host.h") + DETECTOR, "atmosphere": ("k_pack.h", "k_extrude.h", "k_extrude_i8.h"), "screens": ("k_fft.h", "k_screens.h"),
-          "shack": ("k_fft.h", "k_shack.h", "k_poisson.h"), "focal": ("mft_host.h", "k_focal.h", "k_mft_mma.h", "k_obs.h") + DETECTOR, "actor": ("k_actor.h",), "wavefront": ("k_wavefront.h", "k_pupil_tile.h"), "science": ("mft_host.h", "k_science.h", "k_mft_mma.h"), "gradient": ("k_gradient.h", "k_pupil_tile.h"), "gradient_obs": ("mft_host.h", "k_gradient_obs.h", "k_pupil_tile.h", "k_mft_mma.h"), "layers": ("k_layers.h", "k_cone.h", "conjugate_host.h"), "pyramid": ("mft_host.h", "k_pyramid.h", "k_mft_mma.h", "k_poisson.h"), "pyramid_grad": ("mft_host.h", "k_pyramid_grad.h", "k_pupil_tile.h"), "shack_gradient": ("mft_host.h", "k_fft.h", "k_shack.h", "k_poisson.h", "k_shack_back.h", "k_pupil_tile.h"), "predictor": ("k_predictor.h",), "telemetry": ("k_telemetry.h",), "spgd": ("k_spgd.h", "spgd_host.h"), "link": ("k_link.h",), "disturbance": ("k_disturbance.h",), "servo": ("k_servo.h",), "conjugate": ("k_conjugate.h", "k_layers.h", "conjugate_host.h"), "tomography": ("k_tomography.h", "k_pupil_tile.h"), "lqg": ("k_lqg.h",), "fused_inst": ("k_fused.h",)}
+          "shack": ("k_fft.h", "k_shack.h", "k_poisson.h"), "focal": ("mft_host.h", "k_focal.h", "k_mft_mma.h", "k_obs.h") + DETECTOR, "actor": ("k_actor.h",), "wavefront": ("k_wavefront.h", "k_pupil_tile.h"), "science": ("mft_host.h", "k_science.h", "k_mft_mma.h"), "gradient": ("k_gradient.h", "k_pupil_tile.h"), "gradient_obs": ("mft_host.h", "k_gradient_obs.h", "k_pupil_tile.h", "k_mft_mma.h"), "layers": ("k_layers.h", "k_cone.h", "conjugate_host.h"), "pyramid": ("mft_host.h", "k_pyramid.h", "k_mft_mma.h", "k_poisson.h"), "pyramid_grad": ("mft_host.h", "k_pyramid_grad.h", "k_pupil_tile.h"), "shack_gradient": ("mft_host.h", "k_fft.h", "k_shack.h", "k_poisson.h", "k_shack_back.h", "k_pupil_tile.h"), "predictor": ("k_predictor.h",), "telemetry": ("k_telemetry.h",), "spgd": ("k_spgd.h", "spgd_host.h"), "link": ("k_link.h",), "disturbance": ("k_disturbance.h",), "servo": ("k_servo.h",), "conjugate": ("k_conjugate.h", "k_layers.h", "conjugate_host.h"), "tomography": ("k_tomography.h", "k_pupil_tile.h"), "lqg": ("k_lqg.h",), "scintillation": ("k_scintillation.h", "k_layers.h", "k_pupil_tile.h", "conjugate_host.h"), "fused_inst": ("k_fused.h",)}
 
 
 def hipcc_path() -> str:

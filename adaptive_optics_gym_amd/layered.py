@@ -107,14 +107,15 @@ def sightline_shifts(altitudes, angle, pupil_pixel):
     return np.ascontiguousarray((h[:, None, None] * a[None, :, :]) / float(pupil_pixel))
 
 
-def required_margin(altitudes, angles, pupil_pixel):
+def required_margin(altitudes, angles, pupil_pixel, guard=0):
     """The margin c (pixels on every side) a meta-pupil needs for the sightlines ``angles`` (a list of [B, 2] arrays):
-    ceil(max |h_l theta| / pupil_pixel) + 1 — the integer part of the shift and the bilinear read's second sample."""
+    ceil(max |h_l theta| / pupil_pixel) + 1 — the integer part of the shift and the bilinear read's second sample — plus ``guard``, the
+    band a ``scintillation`` keeps between every footprint and the meta-pupil's edge (``scintillation.default_guard``)."""
     worst = 0.0
     for a in angles:
         s = sightline_shifts(altitudes, a, pupil_pixel)
         worst = max(worst, float(np.abs(s).max()) if s.size else 0.0)
-    return int(np.ceil(worst)) + 1
+    return int(np.ceil(worst)) + 1 + int(guard)
 
 
 def default_meta_pupil_pixels(num_pupil_pixels, margin):
@@ -340,6 +341,20 @@ class LayeredAOEnv(_InstalledFront):
                  advance and steps with the head; ``info["altitude_commands"]`` is the list of what was set.  With it ``step_with_policy``,
                  ``step_with_spgd`` and ``step(next_actions=...)`` raise ``RuntimeError`` (the fused forms form or hold the action inside
                  a launch, where there is nothing to split); ``rollout()`` runs its unfused loop.
+    scintillation   None (the env constructs and launches exactly what it did before), True or dict(guard=, scratch_bytes=): every layer
+                 above the ground is propagated to the pupil by the weak-turbulence (Rytov) filter (``scintillation.py``,
+                 ``aog_scint_filter``) after the layers evolve: every front's phase becomes the sum of the DIFFRACTED phases S_l (the
+                 corrections S_l - phi_l are installed beside the layers like altitude mirrors' surfaces) and gets a log-amplitude map
+                 chi = sum chi_l (``log_amplitude()``).  After every ``step`` the amplitude-aware receiver (``aog_scint_receive``) adds
+                 ``info["scintillation"] = dict(power, irradiance, strehl, sigma_chi2)`` ([B] float64), and the same dict under
+                 ``info["sightlines"][name]``.  ``info["power"]``, ``obs`` and ``reward`` stay the step's: the diffracted phase at unit
+                 amplitude.  Needs ``layer_altitudes``; plane waves only (``source_range`` or a sightline ``range`` raise ``ValueError``);
+                 layers plus mirrors plus filtered layers are at most 8 sources; the meta-pupil's margin grows by the guard band (default
+                 ``scintillation.default_guard``: one Fresnel zone of the highest layer) and a too-small ``meta_pupil_pixels`` raises.
+                 ``rytov_variance()`` is the theoretical sigma_chi^2 of the profile; <~ 0.3 is the filter's regime.  The fused and
+                 pipelined step forms raise ``RuntimeError``; ``get_state`` / ``set_state`` carry nothing new (chi is a function of the
+                 layers' screens).  An env whose layers all sit at h = 0 filters nothing: its step is bit for bit the step without the
+                 option, and the receiver reports irradiance 1.
     servo        as ``BatchedAOEnv``'s (through ``**kw``): one mirror, one servo — the env's own front steps with ``servo.apply(actions)`` and
                  every sightline's front with the same applied action; the sightline fronts get no servo of their own.
 
@@ -371,8 +386,11 @@ class LayeredAOEnv(_InstalledFront):
                  rew_type="strehl_ratio", rew_threshold=None, timesteps_per_episode=20, flat_mirror_start_per_episode=True, SH_operation=False, *,
                  atm_type="dynamic", seed=None, screen_source="device", rng=None, global_env_offset=0, total_envs=None, extrusion="auto",
                  verbose=True, disturbance=None, layer_altitudes=None, field_angle=None, meta_pupil_pixels=None, sightlines=None, altitude_mirrors=None,
-                 altitude_action=None, source_range=None, **kw):
+                 altitude_action=None, source_range=None, scintillation=None, **kw):
         self._layers = []
+        self.scintillation = None
+        self.scintillation_on = False
+        self._scint_cache = {}
         self._mirrors = []
         self._altitude_scale = None
         self._handle = None
@@ -395,6 +413,11 @@ class LayeredAOEnv(_InstalledFront):
             raise ValueError("LayeredAOEnv: source_range needs layer_altitudes (a source's range only shows through layers above the ground)")
         if altitudes is None and altitude_mirrors:
             raise ValueError("LayeredAOEnv: altitude_mirrors need layer_altitudes (a mirror conjugated to an altitude is drawn on the layers' meta-pupil)")
+        from .scintillation import resolve_scintillation
+
+        scint = resolve_scintillation(scintillation)
+        if scint is not None and altitudes is None:
+            raise ValueError("LayeredAOEnv: scintillation needs layer_altitudes (a layer in the pupil plane does not diffract)")
         if altitude_action is not None and not altitude_mirrors:
             raise ValueError("LayeredAOEnv: altitude_action needs altitude_mirrors")
         if altitude_action is not None and not np.isfinite(float(altitude_action)):
@@ -425,17 +448,33 @@ class LayeredAOEnv(_InstalledFront):
             # depend on which envs this instance holds.  (With every source at infinity the margin is the plane wave's own, as it was.)
             stated = [declared_range(source_range)] + [declared_range(v.get("range") if isinstance(v, dict) else None) for v in (sightlines or {}).values()]
             finite = any(np.any(np.isfinite(H)) for H in stated)
+            guard = 0
+            if scint is not None:
+                from .scintillation import default_guard
+
+                if finite:
+                    raise ValueError("LayeredAOEnv: scintillation models plane waves only; source_range or a sightline's range does not go with it "
+                                     "(the spherical wave's scaling of the Fresnel filter is not built)")
+                filtered = int(np.count_nonzero(altitudes > 0))
+                if len(plan) + len(mirror_specs) + filtered > MAX_SOURCES:
+                    raise ValueError(f"LayeredAOEnv: {len(plan)} layers, {len(mirror_specs)} altitude mirrors and the diffraction corrections of {filtered} "
+                                     f"layers above the ground: an installation reads at most {MAX_SOURCES} sources")
+                guard = default_guard(altitudes, params.wavelength_wfs, params.pupil_pixel) if scint["guard"] is None else (scint["guard"] if filtered else 0)
             if finite:
                 for (what, _, _), H in zip(every, stated):   # (a layer or mirror at or above a source, before anything else)
                     cone_geometry(seen_at, np.zeros((H.size, 2)), H, params.pupil_pixel, first_mirror=len(plan), what=what)
             if meta_pupil_pixels is None:
                 n_meta = default_meta_pupil_pixels(N, required_margin_cone(seen_at, [(a, H) for (_, a, _), H in zip(every, stated)], params.pupil_pixel, N)
-                                                   if finite else required_margin(seen_at, [angle] + list(declared.values()), params.pupil_pixel))
+                                                   if finite else required_margin(seen_at, [angle] + list(declared.values()), params.pupil_pixel, guard))
             else:
                 n_meta = int(meta_pupil_pixels)
                 if n_meta != meta_pupil_pixels or n_meta < N or (n_meta - N) % 2:
                     raise ValueError(f"meta_pupil_pixels: expected an integer >= num_pupil_pixels ({N}) with an even difference, got {meta_pupil_pixels!r}")
             margins = np.where(seen_at > 0, (n_meta - N) // 2, 0)
+            if guard and (n_meta - N) // 2 < guard + 1:
+                raise ValueError(f"meta_pupil_pixels: {n_meta} leaves a margin of {(n_meta - N) // 2} pixels, the scintillation's guard band alone takes "
+                                 f"{guard} (and a sightline at least 1 more)")
+            true_margins, margins = margins, np.where(seen_at > 0, (n_meta - N) // 2 - guard, 0)   # (what a shift may use: the guard stays clear)
             for what, a, H in every:
                 if np.any(np.isfinite(H)):
                     check_margin_cone(cone_geometry(seen_at, a, H, params.pupil_pixel, first_mirror=len(plan), what=what), margins, N, what,
@@ -444,8 +483,8 @@ class LayeredAOEnv(_InstalledFront):
                     check_margin(sightline_shifts(seen_at, a, params.pupil_pixel), margins, what, first_mirror=len(plan))
             for m in mirror_specs:
                 resolve_mirror(m, N, n_meta)   # (actuators, coupling and a given basis's shape)
-            geometry = dict(angle=angle, declared=looks, n_meta=n_meta, margins=margins[:len(plan)], seen_at=seen_at, seen_margins=margins,
-                            mirrors=mirror_specs, range=own_range)
+            geometry = dict(angle=angle, declared=looks, n_meta=n_meta, margins=true_margins[:len(plan)], seen_at=seen_at, seen_margins=margins,
+                            mirrors=mirror_specs, range=own_range, guard=guard)
         self._front_args = dict(args=(act_type, act_dim, obs_dim, rew_type, rew_threshold, timesteps_per_episode, flat_mirror_start_per_episode,
                                       SH_operation), seed=seed, extrusion=extrusion, kw={k: v for k, v in kw.items() if k != "servo"})   # (one mirror, one servo: the env's)
         # The front: a quasi-static handle whose screens are installed, never drawn (_InstalledFront); it consumes no
@@ -497,6 +536,16 @@ class LayeredAOEnv(_InstalledFront):
                         self._altitude_scale = float(altitude_action)
                         width = self.num_modes + sum(m.n_modes for m in self._mirrors)
                         self.action_space = self.single_action_space = make_box(-1, 1, (width,), np.float16)
+            if scint is not None:
+                from .scintillation import Scintillation
+
+                if kw.get("precision", "fast") != "fast":
+                    raise ValueError("LayeredAOEnv: scintillation needs a fast front (its log-amplitude map and receiver are built on the screen tiles)")
+                self.scintillation_guard = geometry["guard"]
+                self.scintillation = Scintillation(self, [i for i, h in enumerate(altitudes) if h > 0], scint["scratch_bytes"])
+                self.scintillation_on = True
+                self._chi_tile = self.scintillation.tile(self)
+                self._filter()
             self._install()   # the first reset sees t = 0
             if geometry is not None:
                 for name, (angle, rng) in geometry["declared"].items():
@@ -540,12 +589,63 @@ class LayeredAOEnv(_InstalledFront):
         before there were ranges."""
         if geometry is not None:
             install_layer_sum_cone(front, self._layers, self._mirrors, geometry, coeff)
+        elif self.scintillation is not None and self.scintillation.corrections:
+            # the diffraction corrections S_l - phi_l as further sources behind the layers and mirrors, each at its layer's shift: the
+            # front's phase is sum S_l; then the front's log-amplitude map from the chi_l at the same shifts
+            from .conjugate import install_layer_sum_conjugate
+
+            extended, own, own_dev = self._scint_shifts(shifts)
+            install_layer_sum_conjugate(front, self._layers, self._mirrors + self.scintillation.corrections, extended, coeff)
+            self.scintillation.install(front, own, own_dev, front._chi_tile)
         elif self._mirrors:
             from .conjugate import install_layer_sum_conjugate
 
             install_layer_sum_conjugate(front, self._layers, self._mirrors, shifts, coeff)
         else:
             install_layer_sum_sightline(front, self._layers, shifts, coeff)
+
+    def _scint_shifts(self, shifts):
+        """(``shifts`` with the filtered layers' rows appended, those rows alone, the same on the device), kept per shifts array so that
+        a step builds and copies nothing."""
+        hit = self._scint_cache.get(id(shifts))
+        if hit is None or hit[0] is not shifts:
+            if len(self._scint_cache) >= 16:
+                self._scint_cache.clear()
+            own = np.ascontiguousarray(shifts[self.scintillation.layer_index])
+            hit = (shifts, np.ascontiguousarray(np.concatenate([shifts, own])), own, self._torch.from_numpy(own).to(self.device))
+            self._scint_cache[id(shifts)] = hit
+        return hit[1:]
+
+    def _filter(self):
+        """The Fresnel filter of the layers' current screens: after they evolve or are redrawn, before an installation."""
+        if self.scintillation is not None:
+            self.scintillation.filter()
+
+    def _refuse_with_scintillation(self, who):
+        if self.scintillation_on:
+            raise RuntimeError(f"{who}: this env has scintillation on; its receiver reads the mirror after every step, where {who} already holds the "
+                               "next action — use step(), or rollout(fused_policy=False)")
+
+    def _receive(self, front):
+        """The amplitude-aware receiver's dict for ``front`` in its current state."""
+        return self.scintillation.receive(front, front._chi_tile if self.scintillation.corrections else None)
+
+    def log_amplitude(self, first=0, count=None):
+        """[count, N, N] float32: the log-amplitude chi (nepers) on the env's own pupil as last installed, zeros outside the aperture."""
+        if not self.scintillation_on:
+            raise RuntimeError("log_amplitude: this env was built without scintillation")
+        return self.scintillation.unpack_tile(self, self._chi_tile, first, count)
+
+    def rytov_variance(self):
+        """[B] float64: the theoretical log-amplitude variance sigma_chi^2 of the configured profile per env (``scintillation.rytov_variance``
+        on the filter's own grid, with ``atm_fried`` taken at the science wavelength as the screens take it); <~ 0.3 is the regime of the
+        weak-turbulence filter."""
+        from .scintillation import rytov_variance
+
+        if not self.scintillation_on:
+            raise RuntimeError("rytov_variance: this env was built without scintillation")
+        return rytov_variance(self._altitudes, self.layer_fractions, self._fried, self.params.wavelength_wfs, self.params.pupil_pixel,
+                              (self.meta_pupil_pixels,) * 2, 0, self.params.outer_scale, fried_wavelength=self.params.wavelength_sci)
 
     def _install(self):
         coeff = None if self.disturbance is None else self._coeff
@@ -588,6 +688,8 @@ class LayeredAOEnv(_InstalledFront):
         if name in self._sightlines:
             raise ValueError(f"add_sightline: there is a sightline {name!r} already")
         rng = resolve_range(range, self.num_envs, self.total_envs, self.global_env_offset, f"sightline {name!r}: range")
+        if self.scintillation_on and np.any(np.isfinite(rng)):
+            raise ValueError(f"sightline {name!r}: scintillation models plane waves only; a range does not go with it")
         angle, shifts, geometry = self._shifts_for(angle, f"sightline {name!r}", rng)
         fa = self._front_args
         front = _InstalledFront(self.num_envs, self.device, "quasi_static", 0, self.fried_parameter, *fa["args"], seed=fa["seed"], screen_source="device",
@@ -596,6 +698,8 @@ class LayeredAOEnv(_InstalledFront):
         try:
             if self.disturbance is not None:
                 self.disturbance.upload_basis(front)
+            if self.scintillation_on:
+                front._chi_tile = self.scintillation.tile(front)
             sl = Sightline(self, name, front, angle, rng)
             sl._look(angle, shifts, geometry)
             self._install_front(front, shifts, None if self.disturbance is None else self._coeff, geometry)
@@ -641,10 +745,12 @@ class LayeredAOEnv(_InstalledFront):
             lay.evolve_atmosphere()
         if self.disturbance is not None:
             self._coeff = self.disturbance.advance()
+        self._filter()
         self._install()
 
     def step(self, actions, out=None, next_actions=BatchedAOEnv._PIPELINE_END):
         if next_actions is not BatchedAOEnv._PIPELINE_END:
+            self._refuse_with_scintillation("step(next_actions=...)")
             self._refuse_with_altitude_action("step(next_actions=...)")
             self._refuse_with_servo("step(next_actions=...)", "step(actions), one call per step")   # (before the layers move)
         commands = None
@@ -671,7 +777,11 @@ class LayeredAOEnv(_InstalledFront):
             for name, sl in self._sightlines.items():
                 obs, reward, _, _, info = sl.env.step(applied)
                 sl.last = seen[name] = {"obs": obs, "reward": reward, "power": info["power"], "strehl": info["strehl"]}
+                if self.scintillation_on:
+                    seen[name]["scintillation"] = self._receive(sl.env)
             ret[4]["sightlines"] = seen
+        if self.scintillation_on:
+            ret[4]["scintillation"] = self._receive(self)
         return ret
 
     def reset(self, mask=None, seed=None, options=None):
@@ -698,6 +808,7 @@ class LayeredAOEnv(_InstalledFront):
         return ret
 
     def step_with_policy(self, policy, cov_var=0.5, out=None, policy_out=None, action=None, ou_noise=None, action_mode="sample"):
+        self._refuse_with_scintillation("step_with_policy")
         self._refuse_with_altitude_action("step_with_policy")
         self._refuse_with_sightlines("step_with_policy")
         self._refuse_with_servo("step_with_policy", "step(policy(obs)), or rollout(fused_policy=False)")
@@ -705,6 +816,7 @@ class LayeredAOEnv(_InstalledFront):
         return super().step_with_policy(policy, cov_var, out=out, policy_out=policy_out, action=action, ou_noise=ou_noise, action_mode=action_mode)
 
     def step_with_spgd(self, ctrl, out=None, action=None, action_out=None):
+        self._refuse_with_scintillation("step_with_spgd")
         self._refuse_with_altitude_action("step_with_spgd")
         self._refuse_with_sightlines("step_with_spgd")
         self._refuse_with_servo("step_with_spgd", "step(ctrl.action()), or rollout(fused_policy=False)")
@@ -755,6 +867,7 @@ class LayeredAOEnv(_InstalledFront):
         self._apply_fried(new)   # (raises before any layer changed when r0 is below what the extrusion tables were made for)
         for lay, f in zip(self._layers, self.layer_fractions):
             lay.set_turbulence(new * f ** (-3.0 / 5.0), mask)
+        self._filter()   # (the redrawn screens)
         self._install()
 
     def get_state(self):
@@ -816,6 +929,7 @@ class LayeredAOEnv(_InstalledFront):
         for m, blob in zip(self._mirrors, state.get("altitude_mirrors", ())):
             m.set_state(blob)
         super().set_state(state)
+        self._filter()   # (chi and the diffracted phases are functions of the layers' screens: nothing of them is in the state)
         self._install()   # (the front's blob holds the same tiles; installing again keeps one path)
 
     def close(self):
@@ -828,6 +942,9 @@ class LayeredAOEnv(_InstalledFront):
         for m in self.__dict__.get("_mirrors", ()):
             m.close()
         self._mirrors = []
+        if self.__dict__.get("scintillation") is not None:
+            self.scintillation.close()
+            self.scintillation = None
         if self.__dict__.get("disturbance") is not None:
             self.disturbance.close()
             self.disturbance = None

@@ -438,7 +438,8 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
 
     ``link`` (a ``link.LinkTelemetry`` built for the env's ``num_envs`` and device): ``link.push(info["power"])`` after every step of every
     policy, the fused and look-ahead forms included; never reset here — read ``link.statistics()`` afterwards.  The transitions are those
-    of ``link=None`` bit for bit."""
+    of ``link=None`` bit for bit.  An env with ``scintillation`` pushes ``info["scintillation"]["power"]`` instead (the power with the
+    log-amplitude on the pupil) and runs the unfused loop only."""
     import inspect
 
     import numpy as np
@@ -453,6 +454,9 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
     if fused_policy and getattr(env, "servo", None) is not None:
         raise ValueError("fused_policy=True: this env has a mirror servo attached, and the fused forms load the action inside the step's launch, "
                          "where the servo has no place — the unfused loop (fused_policy=False) steps through it")
+    if fused_policy and getattr(env, "scintillation_on", False):
+        raise ValueError("fused_policy=True: this env has scintillation on, and its receiver reads the mirror between two steps, where a fused step "
+                         "already holds the next action — the unfused loop (fused_policy=False) steps through it")
     if policy not in _POLICIES:
         raise ValueError("policy must be 'actor', 'shack', 'ideal', 'pyramid', 'predictive', 'modal', 'lqg', 'spgd' or 'tomographic'")
     if action_mode not in ("sample", "mean"):
@@ -519,6 +523,7 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
 
         check_link(link, env)
     step_takes_out = "out" in inspect.signature(env.step).parameters
+    scintillating = bool(getattr(env, "scintillation_on", False))
     looking_ahead = bool(env.lookahead(True)) if (lookahead and callable(getattr(env, "lookahead", None))) else False
     n = T * episodes
     out = spare = None
@@ -589,7 +594,9 @@ def rollout(env, actor, episodes: int = 1, cov_var: float = 0.5, gatherer=None, 
                     dst.copy_(src)
             if science:
                 env.science_integrate()
-            if link is not None:
+            if link is not None and scintillating:   # (behind the option: the power the amplitude-aware receiver couples)
+                link.push(info["scintillation"]["power"].to(torch.float32))
+            elif link is not None:
                 link.push(info["power"])
             return next_obs
 
